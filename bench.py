@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py - denoised frames/s of the Emote-hack diffusion hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--mode weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--mode weak|strong] [--dump-outputs DIR] [--full]
+        A plain run sets up, warms up, times the K steps and prints the JSON line; --dump-outputs DIR also writes what the
+        timed path returned in its last step as DIR/<name>.npy (float32); --full adds everything else listed below.
         N>1: one rank per GPU over RCCL - either launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or,
         when WORLD_SIZE is not set, bench.py re-executes ITSELF under `python -m torch.distributed.run --nnodes=1
         --nproc-per-node N --master-addr 127.0.0.1` (the reference spawns one process per GPU the same way,
@@ -25,7 +27,7 @@ Weak scaling: an N-GPU run denoises a 12*N-frame clip as N windows = 2N (window 
 branches of window r (U[r::N] of the branch-major unit list), one all_gather of the eps slices per step, a group's
 ReferenceNet timesteps dealt over the ranks + one all_gather of the banks per group.
 
-Adds to the JSON line:  "roofline" for the dominant kernel (live HIP-event timing of every launch of that
+With --full, adds to the JSON line:  "roofline" for the dominant kernel (live HIP-event timing of every launch of that
 kernel family in an eager pass right after the timed region; algorithmic FLOPs per launch = 2*M*N*K for the GEMM/conv
 kernel) and "cpu_baseline" (the CPU oracle timed on the host cores on a bounded sample, rank 0, N=1 only); "parity": the full-size oracle
 forward that leg computes, used as the CHECKER of the HIP output in the benchmarked dtype and in f32 mode (max / mean abs error, north_star's
@@ -35,6 +37,7 @@ config.whole_clips_after_timed_region: --clips whole 50-step clips run back to b
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -49,6 +52,7 @@ MFMA_PEAK_BF16_TFLOPS = 2500.0   # dense bf16, /opt/skills/guides/MI355X_MICROAR
 HBM_PEAK_GBS = 8000.0
 NUM_INFERENCE_STEPS = 50
 REF_GROUP = 10
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: every array of the timed path's result fits under this in float32
 # algorithmic TFLOP per UNet forward at cfg2 (cond with ReferenceNet K/V, uncond, ReferenceNet image)
 TFLOP_COND, TFLOP_UNCOND, TFLOP_REFNET = 14.319, 13.251, 0.803
 # BASELINE.json configs (SURVEY.md 8d for the FLOP figures): latent size, frames per window, compute dtype, per-frame audio context,
@@ -314,6 +318,19 @@ def spawn_check(rank, world):
     td.destroy_process_group()
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: the arrays the timed path returned in its last step, each as DIR/<name>.npy in float32, so that two
+    builds run with the same arguments (same seeded inputs) can be compared output for output."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of output exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def bench_vae(a, dev, dtype):
     """--stage vae: decode_latents (EMOAnimationPipeline.py:291-307) of one denoised 12-frame 512x512 clip on the HIP AutoencoderKL
     (SD-1.x geometry, 83.7 M parameters, name-keyed random weights): latents / 0.18215 -> per-frame decoder -> (x / 2 + 0.5).clamp
@@ -326,22 +343,25 @@ def bench_vae(a, dev, dtype):
     vae.to(dev, dtype)
     F = 12
     lat = (0.18215 * seeded_randn((1, 4, F, 64, 64), 9)).to(dev)
-    for _ in range(max(1, a.warmup if a.warmup < 3 else 2)):
+    warmup = max(1, min(a.warmup, 2))
+    for _ in range(warmup):
         out = vae.decode_video(lat)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    steps = max(1, min(a.steps, 10))
+    steps = a.steps
     for _ in range(steps):
         out = vae.decode_video(lat)
     torch.cuda.synchronize()
     dt_s = (time.perf_counter() - t0) / steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"video": out})
     res = {"metric": "VAE-decoded frames/s (512x512, decode_latents)", "value": F / dt_s, "unit": "frames/s", "n_gpus": 1, "steps": steps,
-           "warmup": 2, "ms_per_step": dt_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
+           "warmup": warmup, "ms_per_step": dt_s * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
            "data": "synthetic",
            "config": {"workload": "SURVEY 8(f) row 2: AutoencoderKL.decode_video of a (1,4,12,64,64) latent clip -> (1,3,12,512,512), "
                                   "4 frames per decoder call, eager launches", "ms_per_frame": dt_s * 1e3 / F,
                       "output_finite": bool(torch.isfinite(out).all())}}
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         prof = ops.KernelProfiler()
         ops.PROFILER = prof
         vae.decode_video(lat)
@@ -399,6 +419,8 @@ def bench_call(a, pipe, ref, dev, rank, world, dist, F_WIN, f_tot):
     cold, warm = times[0], times[1:]
     dt_s = sum(warm) / len(warm)
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"latents": out})
         print(json.dumps({
             "metric": "denoised frames/s (512x512, 50-step DDPM)", "value": f_tot / dt_s, "unit": "frames/s", "n_gpus": world,
             "steps": NUM_INFERENCE_STEPS * len(warm), "warmup": NUM_INFERENCE_STEPS, "ms_per_step": dt_s / NUM_INFERENCE_STEPS * 1e3,
@@ -442,7 +464,7 @@ def main():
                          "cold call (plan + graph capture), then --calls timed calls that reuse the prepared plan")
     ap.add_argument("--calls", type=int, default=2, help="--entry call: timed calls after the cold one")
     ap.add_argument("--clips", type=int, default=None, help="whole 50-step clips run back to back BEHIND the timed region and reported as "
-                    "config.whole_clips_after_timed_region (default 3; cfg5: 1; 0 = skip)")
+                    "config.whole_clips_after_timed_region (default with --full 3, cfg5: 1; without --full 0; 0 = skip)")
     ap.add_argument("--stage", default="loop", choices=["loop", "vae"],
                     help="loop: the sampling loop (the headline metric); vae: the step right behind it - decode_latents of the 12-frame "
                          "512x512 clip (EMOAnimationPipeline.py:291-307) on the HIP AutoencoderKL, ms per frame (SURVEY 8f row 2)")
@@ -458,7 +480,15 @@ def main():
                          "exchanges were free.  e.g. --mode strong --emulate-rank 4/8 = one cond unit of BASELINE configs[3].  NOT a multi-GPU number")
     ap.add_argument("--share-gpu", action="store_true", help="validation on a 1-GPU box: every rank on cuda:0, exchange through gloo "
                                                              "(RCCL takes one device per rank) - the number is NOT a multi-GPU measurement")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (the denoised latents; --stage vae: "
+                         "the decoded video) as DIR/<name>.npy in float32")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: clocks sampled during the timed region, --clips whole clips behind it, "
+                         "the per-kernel roofline pass and the CPU baseline + parity leg (each still off with its --no-* / --clips 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the N ranks ourselves (replaces this process; the ranks inherit stdout, rank 0 prints the JSON line)
@@ -495,7 +525,7 @@ def main():
     cfg = CONFIGS[a.config]
     a.dtype = a.dtype or cfg["dtype"]
     if a.clips is None:
-        a.clips = 1 if a.config == "cfg5" else 3
+        a.clips = 0 if not a.full else 1 if a.config == "cfg5" else 3
     dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}[a.dtype]
     T_COND, T_UNCOND, T_REF = cfg["tflop"]
     if a.no_ln_fold:
@@ -572,8 +602,8 @@ def main():
         pipe.denoise_step(st, si % NUM_INFERENCE_STEPS)
         si += 1
     sync()
-    clk_idle = gpu_clocks(local_rank)
-    with ClockSampler(local_rank) as clk_timed:
+    clk_idle = gpu_clocks(local_rank) if a.full else None
+    with ClockSampler(local_rank) if a.full else contextlib.nullcontext() as clk_timed:
         t0 = time.perf_counter()
         groups_before = st.groups_launched
         for _ in range(a.steps):
@@ -583,6 +613,8 @@ def main():
         sync()
         dt_s = time.perf_counter() - t0
     ref_passes = st.groups_launched - groups_before
+    if a.dump_outputs and rank == 0:   # before anything behind the timed region moves the latents on
+        dump_outputs(a.dump_outputs, {"latents": st.latents})
     # WHOLE CLIPS right behind the timed region (not `value`): --clips x 50 loop iterations back to back, every ReferenceNet group
     # of a clip included - the per-step figure of a complete 50-step clip, long enough (seconds) for an external utilisation
     # sampler to see the GPU busy
@@ -610,7 +642,7 @@ def main():
     # stream (a graph replay cannot host per-launch events); kernels and shapes are identical to the timed region.  The
     # ReferenceNet group pass (one per REF_GROUP steps) is profiled separately and enters per step with weight 1/REF_GROUP.
     prof = prof_ref = None
-    if not a.no_profile:
+    if a.full and not a.no_profile:
         prof = ops.KernelProfiler()
         ops.PROFILER = prof
         prof_steps = min(a.steps, 2)
@@ -660,8 +692,9 @@ def main():
                            "devices_visible": torch.cuda.device_count(), "one_device_per_rank": not a.share_gpu,
                            "collectives_per_step": "1 all_gather_into_tensor of the eps slices (main stream, default group)",
                            "collectives_per_reference_group": f"{len(st.bank_variants)} all_gather_into_tensor of the fp16-rounded banks (main stream, default group)"},
-                       "clocks": {"idle_before": clk_idle, "timed_region": clk_timed.summary(),
-                                  "source": "amdgpu sysfs pp_dpm_sclk / pp_dpm_mclk, sampled every 50 ms on a host thread"},
+                       "clocks": None if not a.full else {
+                           "idle_before": clk_idle, "timed_region": clk_timed.summary(),
+                           "source": "amdgpu sysfs pp_dpm_sclk / pp_dpm_mclk, sampled every 50 ms on a host thread"},
                        "whole_clips_after_timed_region": whole},
         }
         # algorithmic work per step: cond + uncond Backbone per window + the ReferenceNet pass.  The reference
@@ -719,7 +752,7 @@ def main():
                     tf = v["flops"] / (v["ms"] * 1e-3) / 1e12 if v["flops"] else 0.0
                     f.write(f"| {name} | {tag} | {v['launches']:.1f} | {v['ms']:.3f} | {tf:.0f} | "
                             f"{v['bytes'] / (v['ms'] * 1e-3) / 1e9:.0f} |\n")
-        if world == 1 and not a.no_cpu_baseline and a.config == "cfg2":   # (the baseline leg times the cfg2 forward)
+        if a.full and world == 1 and not a.no_cpu_baseline and a.config == "cfg2":   # (the baseline leg times the cfg2 forward)
             try:
                 out["parity"], out["cpu_baseline"] = cpu_baseline(unet, ref, full=not a.cpu_baseline_sample)
             except Exception as ex:   # the baseline leg must never cost the measurement

@@ -6,6 +6,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -43,3 +47,21 @@ def test_spawn_command_shape():
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=8" in cmd and "--nnodes=1" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-6:] == ["--gpus", "8", "--steps", "5", "--mode", "strong"]
     assert cmd[cmd.index("--master-port") + 2].endswith("bench.py")
+
+
+def test_dump_outputs_writes_float32_and_refuses_oversized_output(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.arange(24, dtype=torch.float32).reshape(2, 3, 4).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "d"), {"latents": x})
+    y = np.load(tmp_path / "d" / "latents.npy")
+    assert y.dtype == np.float32 and y.shape == (2, 3, 4) and (y == x.float().numpy()).all()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_bench_refuses_zero_steps():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--spawn-check"], capture_output=True,
+                       text=True, env=_env(), timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr

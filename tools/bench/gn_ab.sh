@@ -5,8 +5,8 @@ for i in 1 2; do
 python bench.py --no-cpu-baseline --no-profile --gn-two-launch > $O/b_two_$i.json 2>/dev/null
 python bench.py --no-cpu-baseline --no-profile > $O/b_one_$i.json 2>/dev/null
 done
-EMO_BENCH_SHAPES=$O/shapes.md python bench.py --no-cpu-baseline > $O/bench.json 2>$O/bench.err
-EMO_BENCH_SHAPES=$O/shapes_two.md python bench.py --no-cpu-baseline --gn-two-launch > $O/bench_two.json 2>>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes.md python bench.py --full --no-cpu-baseline > $O/bench.json 2>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes_two.md python bench.py --full --no-cpu-baseline --gn-two-launch > $O/bench_two.json 2>>$O/bench.err
 python - $O <<'PY'
 import json,glob,sys
 O=sys.argv[1]

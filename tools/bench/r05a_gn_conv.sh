@@ -13,8 +13,8 @@ python bench.py --no-cpu-baseline --no-profile --gn-conv-min-hw 0 > $O/b_unfused
 python bench.py --no-cpu-baseline --no-profile --gn-conv-min-hw 1024 > $O/b_fused1024_$i.json 2>$O/err_f1024_$i.txt
 
 done
-EMO_BENCH_SHAPES=$O/shapes.md python bench.py --no-cpu-baseline > $O/bench.json 2>$O/bench.err
-EMO_BENCH_SHAPES=$O/shapes_unfused.md python bench.py --no-cpu-baseline --gn-conv-min-hw 0 > $O/bench_unfused.json 2>>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes.md python bench.py --full --no-cpu-baseline > $O/bench.json 2>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes_unfused.md python bench.py --full --no-cpu-baseline --gn-conv-min-hw 0 > $O/bench_unfused.json 2>>$O/bench.err
 
 python - $O <<'PY'
 import json,glob,sys

@@ -14,7 +14,7 @@ for i in 1 2; do
 python bench.py --no-cpu-baseline --no-profile > $O/b_streamed_$i.json 2>$O/err_s_$i.txt
 python bench.py --no-cpu-baseline --no-profile --gn-pair > $O/b_pair_$i.json 2>$O/err_p_$i.txt
 done
-EMO_BENCH_SHAPES=$O/shapes.md python bench.py --no-cpu-baseline > $O/bench.json 2>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes.md python bench.py --full --no-cpu-baseline > $O/bench.json 2>$O/bench.err
 python - $O <<'PY'
 import json,glob,sys
 O=sys.argv[1]

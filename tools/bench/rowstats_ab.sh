@@ -6,8 +6,8 @@ for i in 1 2; do
 python bench.py --no-cpu-baseline --no-profile --ln-stats-kernel > $O/b_ker_$i.json 2>/dev/null
 python bench.py --no-cpu-baseline --no-profile > $O/b_epi_$i.json 2>/dev/null
 done
-EMO_BENCH_SHAPES=$O/shapes.md python bench.py --no-cpu-baseline > $O/bench.json 2>$O/bench.err
-EMO_BENCH_SHAPES=$O/shapes_ker.md python bench.py --no-cpu-baseline --ln-stats-kernel > $O/bench_ker.json 2>>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes.md python bench.py --full --no-cpu-baseline > $O/bench.json 2>$O/bench.err
+EMO_BENCH_SHAPES=$O/shapes_ker.md python bench.py --full --no-cpu-baseline --ln-stats-kernel > $O/bench_ker.json 2>>$O/bench.err
 python - $O <<'PY'
 import json,glob,sys
 O=sys.argv[1]
