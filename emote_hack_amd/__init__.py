@@ -6,7 +6,8 @@ gfx950 HIP kernels reached through the C ABI in include/emo_hip.h.  No CPU fallb
 """
 from .config import normalize_unet_config, unet_config_from_yaml  # noqa: F401
 from .context import get_context_scheduler, ordered_halving, uniform  # noqa: F401
-from .scheduler import DDIMScheduler, DDPMScheduler  # noqa: F401
+from .scheduler import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                        EulerDiscreteScheduler, LMSDiscreteScheduler)
 
 
 def __getattr__(name):  # heavy modules on demand

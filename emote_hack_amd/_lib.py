@@ -58,6 +58,20 @@ class AttentionParams(C.Structure):
     ]
 
 
+class SchedStepParams(C.Structure):
+    _fields_ = [
+        ("guidance_scale", C.c_float),
+        ("a", C.c_float), ("b", C.c_float),
+        ("c_x", C.c_float),
+        ("c", C.c_float * 4),
+        ("slot", C.c_int * 4),
+        ("c_noise", C.c_float),
+        ("s_next", C.c_float),
+        ("seed", C.c_uint32), ("step", C.c_uint32),
+        ("scale_only", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/emo_hip.h declares
 _i, _i64, _f, _p, _u32 = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_uint32
 SIGNATURES = {
@@ -70,6 +84,7 @@ SIGNATURES = {
     "emo_convert": (_i, [_p, _i, _p, _i, _i64, _i, _p]),
     "emo_silu": (_i, [_p, _p, _i64, _i, _p]),
     "emo_timestep_embedding": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "emo_timestep_embedding_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_groupnorm_workspace_bytes": (C.c_size_t, [_i, _i64, _i, _i]),
     "emo_groupnorm_stats": (_i, [_p, _i, _p, _i, _i64, _i, _i, _i, _p]),
     "emo_groupnorm_apply": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
@@ -87,6 +102,7 @@ SIGNATURES = {
     "emo_attention": (_i, [C.POINTER(AttentionParams), _p]),
     "emo_temporal_attention": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _f, _i, _p]),
     "emo_cfg_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _u32, _u32, _p]),
+    "emo_sched_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, C.POINTER(SchedStepParams), _p]),
     "emo_accumulate_window": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "emo_act": (_i, [_p, _p, _i64, _i, _i, _p]),
     "emo_speed_encode": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

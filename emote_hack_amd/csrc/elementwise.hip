@@ -198,8 +198,10 @@ extern "C" int emo_silu(const void* x, void* y, int64_t n, int dtype, void* stre
 // flip_sin_to_cos.  `freqs` = exp(-ln(max_period) * arange(half) / (half - shift)) is a constant f32
 // table built once on the host exactly as the reference builds it, so the angle t*freq is the same
 // f32 product (an on-device expf would move the k=0 angle of t=981 by ~1e-4 rad).
-template <typename T>
-__global__ void timestep_kernel(const int64_t* __restrict__ ts, const float* __restrict__ freqs, T* __restrict__ out, int B,
+// TS = int64_t (the integer tables) or float (the fractional timesteps of the sigma-space samplers): for an integral value both
+// round to the same f32, so the two entries give the same bits.
+template <typename T, typename TS>
+__global__ void timestep_kernel(const TS* __restrict__ ts, const float* __restrict__ freqs, T* __restrict__ out, int B,
                                 int dim, int flip) {
   const int half = dim / 2;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * dim; i += gridDim.x * blockDim.x) {
@@ -220,7 +222,16 @@ extern "C" int emo_timestep_embedding(const int64_t* ts, const float* freqs, voi
   EMO_CHECK(ts && out && freqs, EMO_ERR_NULL, "emo_timestep_embedding: null pointer");
   EMO_CHECK(B > 0 && dim > 1, EMO_ERR_BAD_SHAPE, "emo_timestep_embedding: B=%d dim=%d", B, dim);
   int grid = grid_for((int64_t)B * dim, 256);
-  EMO_DISPATCH(dtype, "emo_timestep_embedding", (timestep_kernel<T><<<grid, 256, 0, as_stream(stream)>>>(ts, freqs, (T*)out, B, dim, flip)));
+  EMO_DISPATCH(dtype, "emo_timestep_embedding", (timestep_kernel<T, int64_t><<<grid, 256, 0, as_stream(stream)>>>(ts, freqs, (T*)out, B, dim, flip)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+extern "C" int emo_timestep_embedding_f32(const float* ts, const float* freqs, void* out, int B, int dim, int flip, int dtype,
+                                          void* stream) {
+  EMO_CHECK(ts && out && freqs, EMO_ERR_NULL, "emo_timestep_embedding_f32: null pointer");
+  EMO_CHECK(B > 0 && dim > 1, EMO_ERR_BAD_SHAPE, "emo_timestep_embedding_f32: B=%d dim=%d", B, dim);
+  int grid = grid_for((int64_t)B * dim, 256);
+  EMO_DISPATCH(dtype, "emo_timestep_embedding_f32", (timestep_kernel<T, float><<<grid, 256, 0, as_stream(stream)>>>(ts, freqs, (T*)out, B, dim, flip)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
@@ -262,6 +273,127 @@ extern "C" int emo_cfg_step(const float* np, const float* counter, float* lat, f
   EMO_CHECK(C > 0 && F > 0 && HW > 0, EMO_ERR_BAD_SHAPE, "emo_cfg_step: bad shape");
   cfg_step_kernel<<<grid_for((int64_t)C * F * HW, 256), 256, 0, as_stream(stream)>>>(np, counter, lat, eps_out, C, F, HW, gs, c_x,
                                                                                    c_eps, c_n, seed, step);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ---------------------------------------------------------------- sampler: CFG + window average + linear multistep step
+// The sigma-space samplers (DPM-Solver++ 2M, Euler, Euler-ancestral, LMS) as one linear form over the f32 latents, see
+// include/emo_hip.h.  One element: read x and the ring entries before writing anything of element i, so x' may overwrite x in
+// place.  The noise term is emo_cfg_step's expression line for line: same (seed, step, i) -> same z bits.
+// npu / npc: noise_pred of element i in the uncond / cond plane (npc unused without guidance); x0: its latent; cnt: the counter
+// of its frame.
+__device__ __forceinline__ float sched_elem(float npu, float npc, float x0, float cnt, float* __restrict__ hist,
+                                            float* __restrict__ eps_out, int i, int n, const emo_sched_step_params& p,
+                                            uint32_t key) {
+  const float inv = 1.0f / cnt;
+  float eps = npu * inv;
+  if (p.guidance_scale > 1.0f) {
+    const float cc = npc * inv;
+    eps = eps + p.guidance_scale * (cc - eps);
+  }
+  const float d = p.a * x0 + p.b * eps;
+  float x = p.c_x * x0 + p.c[0] * d;
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (p.slot[k] >= 0) x += p.c[k] * hist[(size_t)p.slot[k] * n + i];
+  if (p.slot[0] >= 0) hist[(size_t)p.slot[0] * n + i] = d;
+  if (p.c_noise != 0.f) {
+    const float c_n = p.c_noise;
+    uint32_t h1 = mix32(((uint32_t)i * 2u + 0u) ^ key), h2 = mix32(((uint32_t)i * 2u + 1u) ^ key);
+    float u1 = ((float)h1 + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
+    float u2 = (float)h2 * 2.3283064365386963e-10f;
+    x += c_n * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+  }
+  if (eps_out) eps_out[i] = eps;
+  return x;
+}
+
+// x_in = s * x: the model input of the first step that runs (emo_sched_step with scale_only)
+template <bool VEC>
+__global__ __launch_bounds__(256) void sched_scale_kernel(const float* __restrict__ lat, float* __restrict__ lat_in, int n, float s) {
+  const int stride = gridDim.x * blockDim.x;
+  if (VEC) {
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n / 4; g += stride) {
+      float4 v = reinterpret_cast<const float4*>(lat)[g];
+      v.x *= s; v.y *= s; v.z *= s; v.w *= s;
+      reinterpret_cast<float4*>(lat_in)[g] = v;
+    }
+  } else {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) lat_in[i] = s * lat[i];
+  }
+}
+
+// VEC: n % 4 == 0 and every base 16-byte aligned -> float4 accesses of the eps planes, x, x' and x_in (the ring entries stay per
+// element; the frame of each lane is its own when HW is not a multiple of 4); otherwise one element per iteration.
+template <bool VEC>
+__global__ __launch_bounds__(256) void sched_step_kernel(const float* __restrict__ np, const float* __restrict__ counter,
+                                                         float* __restrict__ lat, float* __restrict__ hist, float* __restrict__ lat_in,
+                                                         float* __restrict__ eps_out, int C, int F, int HW, emo_sched_step_params p) {
+  const int n = C * F * HW;   // < 2^31 (checked by the entry)
+  const int stride = gridDim.x * blockDim.x;
+  const uint32_t key = mix32(p.seed ^ mix32(p.step + 0x9E3779B9u));
+  if (VEC) {
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n / 4; g += stride) {
+      const int i = g * 4;
+      const float4 u = reinterpret_cast<const float4*>(np)[g];
+      const float4 c = p.guidance_scale > 1.0f ? reinterpret_cast<const float4*>(np + n)[g] : u;
+      const float4 x = reinterpret_cast<const float4*>(lat)[g];
+      // frame of each lane: one division for the group, then step the pixel (HW may be < 4 or not a multiple of 4)
+      const int q = (int)((unsigned)i / (unsigned)HW);
+      int px = i - q * HW, f = (int)((unsigned)q % (unsigned)F);
+      float cnt[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        cnt[j] = counter[f];
+        if (++px == HW) { px = 0; f = (f + 1 == F) ? 0 : f + 1; }
+      }
+      float4 o;
+      o.x = sched_elem(u.x, c.x, x.x, cnt[0], hist, eps_out, i + 0, n, p, key);
+      o.y = sched_elem(u.y, c.y, x.y, cnt[1], hist, eps_out, i + 1, n, p, key);
+      o.z = sched_elem(u.z, c.z, x.z, cnt[2], hist, eps_out, i + 2, n, p, key);
+      o.w = sched_elem(u.w, c.w, x.w, cnt[3], hist, eps_out, i + 3, n, p, key);
+      reinterpret_cast<float4*>(lat)[g] = o;
+      if (lat_in) reinterpret_cast<float4*>(lat_in)[g] = make_float4(p.s_next * o.x, p.s_next * o.y, p.s_next * o.z, p.s_next * o.w);
+    }
+  } else {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      const float x = sched_elem(np[i], p.guidance_scale > 1.0f ? np[n + i] : 0.f, lat[i], counter[((unsigned)i / (unsigned)HW) % (unsigned)F],
+                                 hist, eps_out, i, n, p, key);
+      lat[i] = x;
+      if (lat_in) lat_in[i] = p.s_next * x;
+    }
+  }
+}
+static inline bool aligned16(const void* q) { return q == nullptr || ((uintptr_t)q & 15u) == 0; }
+extern "C" int emo_sched_step(const float* np, const float* counter, float* lat, float* hist, float* lat_in, float* eps_out, int C, int F,
+                              int HW, const emo_sched_step_params* p, void* stream) {
+  EMO_CHECK(p && lat, EMO_ERR_NULL, "emo_sched_step: null pointer");
+  EMO_CHECK(C > 0 && F > 0 && HW > 0, EMO_ERR_BAD_SHAPE, "emo_sched_step: bad shape");
+  const int64_t n = (int64_t)C * F * HW;
+  EMO_CHECK(n < ((int64_t)1 << 31), EMO_ERR_BAD_SHAPE, "emo_sched_step: %lld elements (at most 2^31 - 1)", (long long)n);
+  if (p->scale_only) {
+    EMO_CHECK(lat_in != nullptr, EMO_ERR_NULL, "emo_sched_step: scale_only needs lat_in");
+  } else {
+    EMO_CHECK(np && counter, EMO_ERR_NULL, "emo_sched_step: null pointer");
+    for (int k = 0; k < 4; ++k) {
+      EMO_CHECK(p->slot[k] >= -1 && p->slot[k] < EMO_SCHED_RING, EMO_ERR_BAD_SHAPE, "emo_sched_step: slot[%d]=%d", k, p->slot[k]);
+      EMO_CHECK(p->slot[k] < 0 || hist != nullptr, EMO_ERR_NULL, "emo_sched_step: slot[%d] set without a history ring", k);
+    }
+    for (int k = 1; k < 4; ++k)   // the entry written this step is never one read this step
+      EMO_CHECK(p->slot[k] < 0 || p->slot[k] != p->slot[0], EMO_ERR_BAD_SHAPE, "emo_sched_step: slot[%d] == slot[0]", k);
+  }
+  const bool vec = (n % 4 == 0) && aligned16(np) && aligned16(lat) && aligned16(lat_in);
+  const int grid = grid_for(vec ? n / 4 : n, 256);
+  hipStream_t st = as_stream(stream);
+  if (p->scale_only) {
+    if (vec) sched_scale_kernel<true><<<grid, 256, 0, st>>>(lat, lat_in, (int)n, p->s_next);
+    else sched_scale_kernel<false><<<grid, 256, 0, st>>>(lat, lat_in, (int)n, p->s_next);
+  } else if (vec) {
+    sched_step_kernel<true><<<grid, 256, 0, st>>>(np, counter, lat, hist, lat_in, eps_out, C, F, HW, *p);
+  } else {
+    sched_step_kernel<false><<<grid, 256, 0, st>>>(np, counter, lat, hist, lat_in, eps_out, C, F, HW, *p);
+  }
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }

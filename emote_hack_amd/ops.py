@@ -157,12 +157,13 @@ def silu(x: torch.Tensor) -> torch.Tensor:
 
 
 def timestep_embedding(timesteps: torch.Tensor, freqs: torch.Tensor, dim: int, flip: bool, dtype) -> torch.Tensor:
+    """int64 timesteps -> emo_timestep_embedding; float32 ones (fractional tables) -> emo_timestep_embedding_f32"""
     _need_cuda(timesteps, freqs)
-    assert timesteps.dtype == torch.int64 and freqs.dtype == torch.float32
+    assert timesteps.dtype in (torch.int64, torch.float32) and freqs.dtype == torch.float32
     B = timesteps.shape[0]
     out = torch.empty(B, dim, device=timesteps.device, dtype=dtype)
-    check(_lib.load().emo_timestep_embedding(_ptr(timesteps), _ptr(freqs), _ptr(out), B, dim, int(flip), dt(dtype), _stream()),
-          "emo_timestep_embedding")
+    name = "emo_timestep_embedding" if timesteps.dtype == torch.int64 else "emo_timestep_embedding_f32"
+    check(getattr(_lib.load(), name)(_ptr(timesteps), _ptr(freqs), _ptr(out), B, dim, int(flip), dt(dtype), _stream()), name)
     return out
 
 
@@ -444,6 +445,30 @@ def cfg_step(noise_pred, counter, latents, *, C_, F, HW, guidance_scale, c_x, c_
     check(_lib.load().emo_cfg_step(_ptr(noise_pred), _ptr(counter), _ptr(latents), _ptr(eps_out), C_, F, HW, float(guidance_scale),
                                    float(c_x), float(c_eps), float(c_noise), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF,
                                    _stream()), "emo_cfg_step")
+
+
+def sched_step(noise_pred, counter, latents, history, lat_in, *, C_, F, HW, guidance_scale, a, b, c_x, c, slot, c_noise, s_next,
+               seed, step, eps_out=None):
+    """One step of a sigma-space sampler (emo_sched_step): c / slot are 4-tuples (slot -1 = no ring entry)."""
+    _need_cuda(noise_pred, counter, latents, history, lat_in, eps_out)
+    assert noise_pred.dtype == counter.dtype == latents.dtype == torch.float32
+    n = C_ * F * HW
+    assert latents.numel() == n and noise_pred.numel() >= n and (lat_in is None or lat_in.numel() == n)
+    assert all(s_ < 0 for s_ in slot) or (history is not None and history.numel() >= (max(slot) + 1) * n)
+    p = _lib.SchedStepParams(guidance_scale=float(guidance_scale), a=float(a), b=float(b), c_x=float(c_x),
+                             c=(C.c_float * 4)(*map(float, c)), slot=(C.c_int * 4)(*map(int, slot)), c_noise=float(c_noise),
+                             s_next=float(s_next), seed=int(seed) & 0xFFFFFFFF, step=int(step) & 0xFFFFFFFF, scale_only=0)
+    check(_lib.load().emo_sched_step(_ptr(noise_pred), _ptr(counter), _ptr(latents), _ptr(history), _ptr(lat_in), _ptr(eps_out),
+                                     C_, F, HW, C.byref(p), _stream()), "emo_sched_step")
+
+
+def sched_scale(latents, lat_in, *, C_, F, HW, s):
+    """lat_in = s * latents (emo_sched_step, scale_only): the model input of the first step that runs"""
+    _need_cuda(latents, lat_in)
+    assert latents.numel() == lat_in.numel() == C_ * F * HW
+    p = _lib.SchedStepParams(s_next=float(s), slot=(C.c_int * 4)(-1, -1, -1, -1), scale_only=1)
+    check(_lib.load().emo_sched_step(None, None, _ptr(latents), None, _ptr(lat_in), None, C_, F, HW, C.byref(p), _stream()),
+          "emo_sched_step")
 
 
 def accumulate_window(pred_rows, noise_pred_branch, counter, frames_i32, *, C_, F, HW, add_counter):

@@ -77,6 +77,12 @@ class EMOAnimationPipeline:
         scheduler it is given, like the reference."""
         if unet is None or scheduler is None:
             raise ValueError("unet and scheduler are required")
+        if not (hasattr(scheduler, "coefficients") or hasattr(scheduler, "step_plan")):
+            # PNDM (51 UNet evaluations for 50 steps, a repeated timestep restarting from an earlier sample) among others: the
+            # loop's step / window / ReferenceNet-group bookkeeping assumes one UNet evaluation per step
+            raise TypeError(f"{type(scheduler).__name__} is not served: the loop runs DDIMScheduler, DDPMScheduler, "
+                            "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler "
+                            "(or an object with their `coefficients(t, eta)` / `step_plan(si, first)` interface)")
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
         self.unet, self.controlnet, self.scheduler = unet, controlnet, scheduler
         # EMOAnimationPipeline.py:105-117: ANY scheduler whose config has the key, not DDIM only - a DDPMScheduler handed to the
@@ -157,6 +163,19 @@ class EMOAnimationPipeline:
         st.num_inference_steps = num_inference_steps
         st.scheduler = sch
         st.timesteps = list(sch.set_timesteps(num_inference_steps))
+        # sigma-space samplers (DPM-Solver++, Euler, Euler-a, LMS): emo_sched_step with a per-step plan.  The state keeps its own
+        # copy of the scheduler's tables (the object is shared: another set_timesteps must not move a state still being stepped), a
+        # ring of earlier model outputs and the model input of the next step, `lat_in`, which the step kernel writes - the UNet /
+        # ControlNet passes gather from it, so no step-dependent input scale is baked into a captured graph
+        st.plan_sched = hasattr(sch, "step_plan")
+        st.t_dtype = torch.float32 if getattr(sch, "float_timesteps", False) else torch.int64
+        if st.plan_sched:
+            import copy
+            st.sched_frozen = copy.deepcopy(sch)
+            st.lat_in = torch.empty_like(st.latents)
+            st.ring = int(sch.history)
+            st.history = torch.empty(st.ring, st.latents.numel(), device=dev, dtype=torch.float32) if st.ring else None
+            st.plans = {}
         n_steps = len(st.timesteps)
         # ReferenceNet images = [reference, motion frames] (Net.py:56-72 intent; junk/EMo-write-up.txt:104-110)
         st.n_ref_images = 1 + (0 if motion_latents is None else self._motion_rows(motion_latents).shape[0])
@@ -240,8 +259,8 @@ class EMOAnimationPipeline:
                 st.calls.append(call)
         if st.emulate:          # no exchange: the accumulators see this rank's units only
             st.units = mine
-        st.t_table = torch.tensor(st.timesteps, dtype=torch.int64, device=dev)   # INT timestep table, bit-exact
-        st.t_buf = torch.zeros(1, dtype=torch.int64, device=dev)
+        st.t_table = torch.tensor(st.timesteps, dtype=st.t_dtype, device=dev)   # INT timestep table, bit-exact (f32: Euler / LMS)
+        st.t_buf = torch.zeros(1, dtype=st.t_dtype, device=dev)
         if use_graphs is None:      # the measured path is the default one on a HIP device
             use_graphs = dev.type == "cuda"
         st.use_graphs, st.graphs = bool(use_graphs) and dev.type == "cuda", {}
@@ -267,7 +286,7 @@ class EMOAnimationPipeline:
         # ---- ReferenceNet groups: the banks depend on the timestep only (never on the latents): T timesteps per pass
         st.T = T = self.reference_group_size(reference_group, n_steps, st.world_size if (st.dist or st.emulate) else 1)
         st.groups = [list(range(i, min(i + T, n_steps))) for i in range(0, n_steps, T)]
-        st.ref_t = torch.zeros(T, dtype=torch.int64, device=dev)
+        st.ref_t = torch.zeros(T, dtype=st.t_dtype, device=dev)
         st.row_table = torch.tensor([((s_ // T) % 2) * T + s_ % T for s_ in range(n_steps)], dtype=torch.int32, device=dev)
         st.bank_idx = torch.zeros(1, dtype=torch.int32, device=dev)
         st.kv_all, st.group_ready, st.group_pending, st.groups_launched = {}, -1, -1, 0
@@ -432,6 +451,7 @@ class EMOAnimationPipeline:
                 raise ValueError("controlnet_conditioning_scale is baked into the captured ControlNet pass (prepare again)")
             st.cn_scale = scale
         st.group_ready, st.group_pending, st.eps_trace = -1, -1, []
+        st.sched_first = None      # sigma-space samplers: the multistep warm-up and lat_in restart at the next step that runs
 
     @staticmethod
     def _put_kv(store, key, kv):
@@ -472,21 +492,22 @@ class EMOAnimationPipeline:
         st.bank_L = [k * st.writer.bank[p][0].shape[1] for p in st.writer.order]
         banks = [ops.convert(st.writer.bank[p][0], tgt, fp16_round=True).reshape(n, -1) for p in st.writer.order]
         st.writer.clear()                                                                      # :823
-        st.bank_pack[tv] = banks if st.world_size == 1 else torch.cat(banks, dim=1)            # (n, total) plumbing copy
+        # (keyed by the group size as well: a replayed graph of another group size writes ITS tensors, not the last ones bound here)
+        st.bank_pack[(Tg, tv)] = banks if st.world_size == 1 else torch.cat(banks, dim=1)      # (n, total) plumbing copy
 
     def _part_reference_project(self, st, Tg, tv):
         """K / V^T projections of the group's banks with the BACKBONE's attn1.to_k / to_v (the read side of
         mutual_self_attention.py:238-241), once per group instead of once per step."""
-        st.stage[tv] = {}
+        st.stage[(Tg, tv)] = {}
         off = 0
         for i, (pr, L, C_) in enumerate(zip(st.reader.order, st.bank_L, st.bank_C)):
             if st.world_size == 1:
-                rows = st.bank_pack[tv][i]
+                rows = st.bank_pack[(Tg, tv)][i]
             else:   # bank i occupies columns [off, off + L*C) of every gathered row (rows in group order)
                 rows = st.ref_gath[(Tg, tv)][:Tg, off:off + L * C_].contiguous()
                 off += L * C_
             k, vt = self.unet.bank_kv(pr, rows.reshape(-1, C_), L)
-            st.stage[tv][pr] = (k, vt, L)
+            st.stage[(Tg, tv)][pr] = (k, vt, L)
 
     def _reference_write(self, st, g):
         """Phase 1 of group g: this rank's share of the group's ReferenceNet write passes (no communication) on the CURRENT stream."""
@@ -509,7 +530,7 @@ class EMOAnimationPipeline:
                 # stream as the per-step eps all_gather: every rank issues its collectives in ONE program order (eps of the group's
                 # last step, banks of the next group, eps of its first step, ...), so no start-order hazard exists by construction
                 import torch.distributed as td
-                send = st.bank_pack[tv]
+                send = st.bank_pack[(Tg, tv)]
                 n = send.shape[0]
                 if (Tg, tv) not in st.ref_gath:
                     st.ref_recv[(Tg, tv)] = torch.empty(st.world_size * n, send.shape[1], device=send.device, dtype=send.dtype)
@@ -523,11 +544,11 @@ class EMOAnimationPipeline:
             self._run(st, ("ref_project", Tg, tv), lambda tv=tv: self._part_reference_project(st, Tg, tv), pool=st.writer_pool)
             if tv not in st.kv_all:   # resident cache: two groups of T timesteps per block
                 st.kv_all[tv] = {}
-                for pr, (k, vt, L) in st.stage[tv].items():
+                for pr, (k, vt, L) in st.stage[(Tg, tv)].items():
                     st.kv_all[tv][pr] = (torch.zeros(2 * T * L, k.shape[1], device=k.device, dtype=k.dtype),
                                          torch.zeros(2 * T, vt.shape[1], vt.shape[2], device=vt.device, dtype=vt.dtype), L)
             dsts, srcs = [], []
-            for pr, (k, vt, L) in st.stage[tv].items():
+            for pr, (k, vt, L) in st.stage[(Tg, tv)].items():
                 ka, va, _ = st.kv_all[tv][pr]
                 dsts += [ka[slot * T * L:slot * T * L + Tg * L], va[slot * T:slot * T + Tg]]
                 srcs += [k[:Tg * L], vt[:Tg]]
@@ -572,7 +593,10 @@ class EMOAnimationPipeline:
     def _part_controlnet(self, st):
         downs, mids = [], []
         for i, idx in enumerate(st.cn_chunks):
-            x = self.scheduler.scale_model_input(st.latents.index_select(2, idx), None)[0].permute(1, 0, 2, 3).contiguous()
+            if st.plan_sched:   # the scaled model input, written by the step kernel
+                x = st.lat_in.index_select(2, idx)[0].permute(1, 0, 2, 3).contiguous()
+            else:
+                x = self.scheduler.scale_model_input(st.latents.index_select(2, idx), None)[0].permute(1, 0, 2, 3).contiguous()
             d, m = st.controlnet(x, st.t_buf, encoder_hidden_states=st.cn_text.repeat(idx.numel(), 1, 1), controlnet_cond=None,
                                  conditioning_scale=st.cn_scale, return_dict=False, _cond_rows=st.cn_embed[i])
             downs.append(d)
@@ -596,8 +620,11 @@ class EMOAnimationPipeline:
     #      from st.bank_idx, so it is captured once into a HIP graph and replayed for the other steps
     def _part_unet(self, st, ci):
         call = st.calls[ci]
-        x = torch.cat([st.latents.index_select(2, ix) for ix in call.idx])                     # :759-763 (index/copy only)
-        x = self.scheduler.scale_model_input(x, None)
+        if st.plan_sched:   # the scaled model input, written by the step kernel
+            x = torch.cat([st.lat_in.index_select(2, ix) for ix in call.idx])
+        else:
+            x = torch.cat([st.latents.index_select(2, ix) for ix in call.idx])                 # :759-763 (index/copy only)
+            x = self.scheduler.scale_model_input(x, None)
         # (a call of uncond units only names any resident cache: every one of its batches skips the bank segment)
         bank_tv = call.bank_tv if call.bank_tv is not None else st.bank_variants[0]
         self.unet._reference_control = st.reader
@@ -643,6 +670,9 @@ class EMOAnimationPipeline:
         sch = self.scheduler
         dev = self.unet.device
         t = st.timesteps[si]
+        if st.plan_sched and st.sched_first is None:    # the first step that runs: its model input, one scale-only launch
+            st.sched_first = si
+            ops.sched_scale(st.latents, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW, s=st.sched_frozen.input_scale(si))
         self._ensure_group(st, si)                                     # :711-716, hoisted: banks of T timesteps per pass
         st.t_buf.copy_(st.t_table[si:si + 1], non_blocking=True)       # device-to-device: the INT timestep of this step
         st.bank_idx.copy_(st.row_table[si:si + 1], non_blocking=True)  # ... and its row in the resident bank cache
@@ -658,14 +688,39 @@ class EMOAnimationPipeline:
             import torch.distributed as td
             td.all_gather_into_tensor(st.recv.view(-1), st.send.view(-1))
         self._accumulate_all(st)
-        # (the state's own scheduler object and step count: `self.scheduler` may have been replaced or re-timed since the plan was made)
-        sch = st.scheduler
-        c_x, c_eps, c_n = self._coefficients(sch, t, st.eta if isinstance(sch, DDIMScheduler) else None, st.num_inference_steps)
         eps_out = torch.empty(st.C4 * st.f_tot * st.HW, device=dev, dtype=torch.float32) if st.return_eps else None
-        ops.cfg_step(st.noise_pred, st.counter, st.latents, C_=st.C4, F=st.f_tot, HW=st.HW, guidance_scale=st.guidance_scale,
-                     c_x=c_x, c_eps=c_eps, c_noise=c_n, seed=st.seed, step=si, eps_out=eps_out)  # :812-817 fused
+        if st.plan_sched:
+            p, slot = self._step_plan(st, si)
+            ops.sched_step(st.noise_pred, st.counter, st.latents, st.history, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW,
+                           guidance_scale=st.guidance_scale, a=p.a, b=p.b, c_x=p.c_x, c=p.c, slot=slot, c_noise=p.c_noise,
+                           s_next=p.s_next, seed=st.seed, step=si, eps_out=eps_out)
+        else:
+            # (the state's own scheduler object and step count: `self.scheduler` may have been replaced or re-timed since the plan was made)
+            sch = st.scheduler
+            c_x, c_eps, c_n = self._coefficients(sch, t, st.eta if isinstance(sch, DDIMScheduler) else None, st.num_inference_steps)
+            ops.cfg_step(st.noise_pred, st.counter, st.latents, C_=st.C4, F=st.f_tot, HW=st.HW, guidance_scale=st.guidance_scale,
+                         c_x=c_x, c_eps=c_eps, c_noise=c_n, seed=st.seed, step=si, eps_out=eps_out)  # :812-817 fused
         if st.return_eps:
             st.eps_trace.append(eps_out.view(1, st.C4, st.f_tot, st.h, st.w))
+
+    @staticmethod
+    def _step_plan(st, si):
+        """(StepPlan, ring slots) of step si of a sigma-space sampler: d_n goes to slot (si - first) % ring, d_{n-k} is read from
+        slot (si - first - k) % ring - the ring restarts with the first step that runs."""
+        key = (st.sched_first, si)
+        if key not in st.plans:
+            p = st.sched_frozen.step_plan(si, st.sched_first)
+            j = si - st.sched_first
+            slot = [j % st.ring if st.ring else -1]
+            for k in range(1, 4):
+                if p.c[k] != 0.0:
+                    if k > j or k >= st.ring:
+                        raise RuntimeError(f"step plan of step {si} reads d_(n-{k}), which the ring does not hold")
+                    slot.append((j - k) % st.ring)
+                else:
+                    slot.append(-1)
+            st.plans[key] = (p, tuple(slot))
+        return st.plans[key]
 
     @staticmethod
     def _coefficients(sch, t, eta, num_inference_steps):
@@ -733,7 +788,9 @@ class EMOAnimationPipeline:
         def sched_id(s):   # the scheduler OBJECT the state steps with and everything its tables depend on
             c = s.config   # (a user-supplied scheduler may carry a leaner config: absent fields key as None)
             return (id(s), type(s).__name__) + tuple(getattr(c, f, None) for f in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule",
-                                                                                   "steps_offset", "set_alpha_to_one", "timestep_spacing"))
+                                                                                   "steps_offset", "set_alpha_to_one", "timestep_spacing",
+                                                                                   "solver_order", "use_karras_sigmas", "final_sigmas_type",
+                                                                                   "lower_order_final", "lms_order"))
 
         def pg_id():       # a state prepared with dist=True holds communicators of the default group it was made under
             if not kw.get("dist"):

@@ -624,10 +624,14 @@ class UNet3DConditionModel:
         s.forward_upsample_size, s.skip_hw = forward_upsample_size, []
         sample = sample.to(dev)
         # time (unet_controlnet.py:376-398)
+        # integer timesteps take the int64 embedding, floating ones (Python float or a float tensor: the fractional tables of the
+        # sigma-space samplers) the f32 one, unrounded - an integral value gives the same bits either way
+        is_float = timestep.is_floating_point() if torch.is_tensor(timestep) else isinstance(timestep, float)
+        t_dtype = torch.float32 if is_float else torch.int64
         if not torch.is_tensor(timestep):
-            timesteps = torch.tensor([timestep], dtype=torch.int64, device=dev)
+            timesteps = torch.tensor([timestep], dtype=t_dtype, device=dev)
         else:
-            timesteps = timestep.reshape(-1).to(device=dev, dtype=torch.int64)
+            timesteps = timestep.reshape(-1).to(device=dev, dtype=t_dtype)
         timesteps = timesteps.expand(B).contiguous()
         t_emb = ops.timestep_embedding(timesteps, w["time_freqs"], cfg["block_out_channels"][0], cfg["flip_sin_to_cos"], dtp)
         e = ops.gemm(t_emb, w["time_embedding.linear_1.w"], w["time_embedding.linear_1.b"])

@@ -72,6 +72,11 @@ int emo_silu(const void* x, void* y, int64_t n, int dtype, void* stream);
 int emo_timestep_embedding(const int64_t* timesteps, const float* freqs, void* out, int B, int dim,
                            int flip_sin_to_cos, int dtype, void* stream);
 
+/* emo_timestep_embedding over f32 timesteps (the fractional tables of Euler / Euler-ancestral / LMS); an integral value gives
+ * the bits of the int64 entry. */
+int emo_timestep_embedding_f32(const float* timesteps, const float* freqs, void* out, int B, int dim,
+                               int flip_sin_to_cos, int dtype, void* stream);
+
 /* ---- normalisation ---------------------------------------------------------------------------
  * GroupNorm over NHWC rows.  An "instance" is a contiguous run of S rows normalised together:
  *   5-D joint statistics (resnet.py:180,191; unet_controlnet.py:476): N=B,   S=F*H*W
@@ -244,6 +249,29 @@ int emo_temporal_attention(const void* qkv, int64_t ldqkv, void* out, int64_t ld
 int emo_cfg_step(const float* noise_pred, const float* counter, float* latents, float* eps_out, int C, int F,
                  int HW, float guidance_scale, float c_x, float c_eps, float c_noise, uint32_t seed, uint32_t step,
                  void* stream);
+/* Fused window-average + classifier-free guidance + one step of a sigma-space sampler (DPM-Solver++ 2M, Euler,
+ * Euler-ancestral, LMS) as a linear form with up to three earlier model outputs, all f32 over n = C*F*HW elements:
+ *   eps   = CFG(noise_pred / counter)                (exactly as emo_cfg_step)
+ *   d     = a*x + b*eps                              (the solver's model output: eps, or x0)
+ *   x'    = c_x*x + c[0]*d + sum_{k=1..3, slot[k] >= 0} c[k]*history[slot[k]] + c_noise*z
+ *   history[slot[0]] = d  (slot[0] >= 0);  latents = x';  lat_in = s_next*x' (lat_in non-null);  eps_out = eps (non-null)
+ * history: ring of EMO_SCHED_RING planes of n floats; slot[0] must differ from every slot read.  z is emo_cfg_step's
+ * counter-based N(0,1) of (seed, step, element), bit for bit.  scale_only != 0: lat_in = s_next*latents, nothing else is
+ * read or written (the model input of the first step that runs). */
+#define EMO_SCHED_RING 4
+typedef struct {
+  float guidance_scale;
+  float a, b;
+  float c_x;
+  float c[4];
+  int slot[4];
+  float c_noise;
+  float s_next;
+  uint32_t seed, step;
+  int scale_only;
+} emo_sched_step_params;
+int emo_sched_step(const float* noise_pred, const float* counter, float* latents, float* history, float* lat_in, float* eps_out,
+                   int C, int F, int HW, const emo_sched_step_params* p, void* stream);
 /* noise_pred[branch, :, frames[j]] += pred rows; counter[frames[j]] += 1 (EMOAnimationPipeline.py:790-794).
  * pred: rows ((j) h w, ld) in dtype for ONE branch of ONE window; frames: device int32 [nf].  The frames of a
  * window must be distinct; a position with frames[j] < 0 is skipped (a wrapped window of the uniform scheduler with
