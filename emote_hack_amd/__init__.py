@@ -23,6 +23,9 @@ def __getattr__(name):  # heavy modules on demand
     if name in ("ControlNetModel", "ControlNetOutput"):
         from . import controlnet
         return getattr(controlnet, name)
+    if name in ("CLIPTextModel", "clip_text_param_shapes", "clip_text_synth_state_dict"):
+        from . import clip_text
+        return getattr(clip_text, name)
     if name == "AppearanceEncoderModel":
         from .appearance_encoder import AppearanceEncoderModel
         return AppearanceEncoderModel

@@ -55,6 +55,7 @@ class AttentionParams(C.Structure):
         ("scale", C.c_float),
         ("dtype", C.c_int),
         ("seg1_row", C.c_void_p),
+        ("causal", C.c_int),
     ]
 
 
@@ -109,6 +110,7 @@ SIGNATURES = {
     "emo_speed_bucket": (_i, [_p, _p, _p, _i, _i, _p]),
     "emo_gather_rows": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_add_rowbias": (_i, [_p, _i, _p, _i, _p, _i, _i64, _i, _i, _i, _p]),
+    "emo_text_embed": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "emo_softmax_rows": (_i, [_p, _i64, _p, _i64, _i64, _i, _f, _i, _p]),
     "emo_audio_windows": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_rows_to_video": (_i, [_p, _i64, _p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _p]),

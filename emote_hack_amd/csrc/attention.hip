@@ -20,7 +20,9 @@
 // Two KV segments: [self / context keys of the batch row] ++ [a bank shared by seg1_div consecutive
 // batch rows] = the ReferenceNet read path (mutual_self_attention.py:238-241) without materialising the
 // F-times-repeated bank or the concatenated K/V.  Head dims 40/80/160 are zero-padded to 48/80/160 (bf16).
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 #include "common.h"
 
 static constexpr int ATT_THREADS = 256, BQ = 128, TK = 64;
@@ -79,14 +81,41 @@ __device__ __forceinline__ float max2f(float a, float b) {
   return r;
 }
 typedef float v2f __attribute__((ext_vector_type(2)));
+
+// The kernels' by-value argument: emo_attention_params WITHOUT its trailing `causal` word, which the kernels see as the CAUSAL
+// template parameter.  The same fields at the same offsets (asserted below), so the kernarg layout - and with it the ISA - of the
+// non-causal instantiations is what it was before the ABI field existed.
+struct AttKernelParams {
+  const void* q; int64_t ldq;
+  const void* k0; int64_t ldk0; const void* v0t; int64_t ldv0t; int Lk0;
+  const void* k1; int64_t ldk1; const void* v1t; int64_t ldv1t; int Lk1;
+  int seg0_div;
+  int seg1_div; int seg1_first_batch; int seg1_skip;
+  void* out; int64_t ldo;
+  int B; int Lq; int heads; int d;
+  float scale;
+  int dtype;
+  const int32_t* seg1_row;
+};
+static_assert(sizeof(AttKernelParams) == offsetof(emo_attention_params, causal) && offsetof(AttKernelParams, seg1_row) == offsetof(emo_attention_params, seg1_row) &&
+              offsetof(AttKernelParams, scale) == offsetof(emo_attention_params, scale) && offsetof(AttKernelParams, out) == offsetof(emo_attention_params, out) &&
+              offsetof(AttKernelParams, seg0_div) == offsetof(emo_attention_params, seg0_div), "AttKernelParams mirrors emo_attention_params");
 __device__ __forceinline__ int swap23(int i) { return (i & ~12) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
 // G = glds per wave per tile, NSR = ring depth, QT = 32-query tiles per wave (2 halves the LDS fragment traffic per MFMA)
 // RES = the resident-context variant (below): its own instantiation - the walk over q tiles costs ~20 registers, which the
 // self-attention launches (3 waves per SIMD at d = 40) do not have
 // (four blocks per CU at d <= 48 - 128 registers, 2-deep ring - spills 32-130 bytes per lane: not offered)
-template <typename T, int DCH, int G, int NSR, int QT, bool RES>
-__global__ __launch_bounds__(ATT_THREADS, (QT == 2 ? 2 : (DCH <= 6 ? 3 : (DCH <= 10 ? 2 : 1)))) void attention_kernel(const emo_attention_params p, int stage_bytes, int order_mode, int q_rep_arg) {
+// CAUSAL = the causal self-attention of the CLIP text encoder (query row i sees keys j <= i of segment 0; Lq == Lk0, no segment 1:
+// checked on the host).  A template parameter, not a runtime flag: the non-causal instantiations compile to the ISA they had before.
+//   * the block's tile walk ends at the tile holding its last query row - tiles wholly above the diagonal are never requested;
+//   * tiles that straddle a wave's diagonal run the masked (!fast) body, which sets the scores of keys > query to -1e30;
+//   * INVARIANT (thresholded online softmax, ATT_TAU below): a row must never see a tile of all-masked scores before it has seen
+//     key 0 - with m_run still at its -1e30 start such a tile would not move m_run and would contribute exp2(0) = 1 per key.  Tile 0
+//     holds key 0 and every row sees it, so the walk always starts at tile 0 (also per q tile of the resident walk); after it,
+//     an all-masked tile has p = exp2(-1e30 * c - m_sc) = 0 exactly.
+template <typename T, int DCH, int G, int NSR, int QT, bool RES, bool CAUSAL>
+__global__ __launch_bounds__(ATT_THREADS, (QT == 2 ? 2 : (DCH <= 6 ? 3 : (DCH <= 10 ? 2 : 1)))) void attention_kernel(const AttKernelParams p, int stage_bytes, int order_mode, int q_rep_arg) {
   const int q_rep = RES ? q_rep_arg : 1;
   using Cfg = AttCfg<T, DCH>;
   constexpr int V = Cfg::V, NT = Cfg::NT, KROW = Cfg::KROW, VROW = Cfg::VROW, STEPS = Cfg::STEPS;
@@ -167,7 +196,8 @@ __global__ __launch_bounds__(ATT_THREADS, (QT == 2 ? 2 : (DCH <= 6 ? 3 : (DCH <=
   const int nseg = (p.k1 != nullptr && b >= p.seg1_first_batch) ? 2 : 1;
   const int tiles0 = (p.Lk0 + TK - 1) / TK;
   const int tiles1 = nseg == 2 ? (p.Lk1 + TK - 1) / TK : 0;
-  const int ntiles = tiles0 + tiles1;
+  // causal: up to the tile holding the last query row of the block (of its last q tile in the resident walk; Lq == Lk0)
+  const int ntiles = CAUSAL ? min(tiles0, (min(p.Lq, (qt + 1) * q_rep * (BQ * QT)) - 1) / TK + 1) : tiles0 + tiles1;
   const int kb0 = b / p.seg0_div, kb1 = nseg == 2 ? (p.seg1_row ? p.seg1_row[0] : b / p.seg1_div - p.seg1_skip) : 0;
   const T* kbase0 = (const T*)p.k0 + (int64_t)kb0 * p.Lk0 * p.ldk0 + head * d;
   const T* vbase0 = (const T*)p.v0t + ((int64_t)kb0 * p.heads * d + (int64_t)head * d) * p.ldv0t;
@@ -384,6 +414,18 @@ __global__ __launch_bounds__(ATT_THREADS, (QT == 2 ? 2 : (DCH <= 6 ? 3 : (DCH <=
           __builtin_amdgcn_sched_barrier(0);
         }
       }
+      if constexpr (CAUSAL && !fast) {
+        const int qbase = qt * (4 * BQW) + wave * BQW + t * 32;   // the wave's first query row of q tile t (wave-uniform)
+        if (k0 + TK - 1 > qbase) {   // the tile reaches above this wave's diagonal: keys > query row (S^T: query = lane column)
+          const int qrow = qbase + l31;
+#pragma unroll
+          for (int r = 0; r < 16; r++) {
+            const int key = k0 + 16 * (r >> 3) + 8 * half + (r & 7);
+            if (key > qrow) s0[r] = -1e30f;
+            if (key + 32 > qrow) s1[r] = -1e30f;
+          }
+        }
+      }
       if constexpr (!fast) {
         if (ragged) {   // keys >= Lk
 #pragma unroll
@@ -506,6 +548,10 @@ __global__ __launch_bounds__(ATT_THREADS, (QT == 2 ? 2 : (DCH <= 6 ? 3 : (DCH <=
     const int cand[3] = {tiles0 - 1 - AHEAD, tiles0 - AHEAD, tiles0 - 1};
 #pragma unroll
     for (int i = 0; i < 3; i++) if (cand[i] >= t && cand[i] < c) c = cand[i];
+    if constexpr (CAUSAL) {   // tiles from the block's first query row on straddle some wave's diagonal: masked body
+      const int diag0 = (qt * (4 * BQW)) / TK;
+      if (diag0 < c) c = diag0;
+    }
     return c > t ? c : t;
   };
   for (int t = 0; t < ntiles;) {
@@ -602,11 +648,11 @@ struct AttLaunch {
   static_assert(NSR * STAGE_BYTES <= 160 * 1024, "attention stage does not fit LDS");
 };
 
-template <typename T, int DCH, int G, int QT>
+template <typename T, int DCH, int G, int QT, bool CAUSAL>
 static int launch_attention3(const emo_attention_params& p, hipStream_t st) {
   using L = AttLaunch<T, DCH, G>;
-  auto kern = attention_kernel<T, DCH, G, L::NSR, QT, false>;
-  auto kern_res = attention_kernel<T, DCH, G, L::NSR, QT, true>;
+  auto kern = attention_kernel<T, DCH, G, L::NSR, QT, false, CAUSAL>;
+  auto kern_res = attention_kernel<T, DCH, G, L::NSR, QT, true, CAUSAL>;
   constexpr int lds = L::NSR * L::STAGE_BYTES;
   if (lds > 64 * 1024) {
     static bool once = false;  // idempotent attribute; benign race
@@ -641,8 +687,10 @@ static int launch_attention3(const emo_attention_params& p, hipStream_t st) {
   // rows (second half of the batch) carry the bank segment and run twice as long as the uncond rows: started first, the short rows
   // fill the tail (1443 -> 1429 us at the 64x64 level, 143 -> 138.5 at 32x32; equal without a bank segment)
   const int order_mode = (p.k1 != nullptr && p.seg1_first_batch > 0) ? 3 : 2;
-  if (q_rep > 1) kern_res<<<grid, ATT_THREADS, lds, st>>>(p, L::STAGE_BYTES, order_mode, q_rep);
-  else kern<<<grid, ATT_THREADS, lds, st>>>(p, L::STAGE_BYTES, order_mode, 1);
+  AttKernelParams kp;
+  memcpy(&kp, &p, sizeof(kp));
+  if (q_rep > 1) kern_res<<<grid, ATT_THREADS, lds, st>>>(kp, L::STAGE_BYTES, order_mode, q_rep);
+  else kern<<<grid, ATT_THREADS, lds, st>>>(kp, L::STAGE_BYTES, order_mode, 1);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
@@ -653,7 +701,8 @@ static int launch_attention2(const emo_attention_params& p, hipStream_t st) {
   // ~170 instructions per query tile and KV tile) needs 256 registers at d = 40 (+ 20 bytes of scratch) = two waves per SIMD:
   // round 3 measured it 1.7x slower on the old instruction stream, round 4 on the lean one 1.5-3.5 % FASTER (1294 -> 1275 us,
   // 775 -> 748 us, profiles/r04m_attention_qt2.txt) - inside the run-to-run spread of a whole step, with a spill; not enabled.
-  return launch_attention3<T, DCH, G, 1>(p, st);
+  if (p.causal) return launch_attention3<T, DCH, G, 1, true>(p, st);
+  return launch_attention3<T, DCH, G, 1, false>(p, st);
 }
 
 // DPREV = chunk count of the next smaller head-dim class: this class serves dch in (DPREV, DCH]
@@ -709,6 +758,8 @@ extern "C" int emo_attention(const emo_attention_params* pp, void* stream) {
     EMO_CHECK(p.seg1_skip >= 0 && p.seg1_first_batch / (p.seg1_div > 0 ? p.seg1_div : 1) >= p.seg1_skip, EMO_ERR_BAD_SHAPE,
               "emo_attention: seg1_skip %d exceeds the bank rows skipped by seg1_first_batch %d", p.seg1_skip, p.seg1_first_batch);
   }
+  EMO_CHECK(!p.causal || (!p.k1 && !p.seg1_row && p.Lq == p.Lk0), EMO_ERR_UNSUPPORTED,
+            "emo_attention: causal needs one KV segment (no k1 / seg1_row) and Lq == Lk0 (Lq %d, Lk0 %d)", p.Lq, p.Lk0);
   if (p.k1) {
     EMO_CHECK(p.v1t && p.Lk1 > 0 && (p.seg1_div > 0 || p.seg1_row) && p.ldk1 % V == 0 && p.ldv1t % V == 0 && p.ldv1t >= p.Lk1, EMO_ERR_BAD_SHAPE,
               "emo_attention: segment-1 geometry");

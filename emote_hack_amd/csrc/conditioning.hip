@@ -4,18 +4,19 @@
 
 static inline int cgrid(int64_t n) { int64_t g = (n + 255) / 256; return (int)(g > 2048 ? 2048 : (g < 1 ? 1 : g)); }
 
-// act: 0 = SiLU, 1 = ReLU, 2 = tanh, 3 = erf-GELU (the wav2vec2 front-end's activation)
+// act: 0 = SiLU, 1 = ReLU, 2 = tanh, 3 = erf-GELU (the wav2vec2 front-end's activation), 4 = quick_gelu x * sigmoid(1.702 x)
+// (the CLIP text encoder's MLP activation; IEEE expf and division, not the approximate SiLU path: one f32 result, rounded once)
 template <typename T>
 __global__ void act_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, int kind) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float v = TT<T>::ld(x + i);
-    v = kind == 0 ? silu_f(v) : (kind == 1 ? fmaxf(v, 0.f) : (kind == 2 ? tanhf(v) : gelu_for<T>(v)));
+    v = kind == 0 ? silu_f(v) : (kind == 1 ? fmaxf(v, 0.f) : (kind == 2 ? tanhf(v) : (kind == 3 ? gelu_for<T>(v) : v / (1.0f + expf(-1.702f * v)))));
     TT<T>::st(y + i, v);
   }
 }
 extern "C" int emo_act(const void* x, void* y, int64_t n, int kind, int dtype, void* stream) {
   EMO_CHECK(x && y, EMO_ERR_NULL, "emo_act: null pointer");
-  EMO_CHECK(n > 0 && kind >= 0 && kind <= 3, EMO_ERR_BAD_SHAPE, "emo_act: n=%lld kind=%d", (long long)n, kind);
+  EMO_CHECK(n > 0 && kind >= 0 && kind <= 4, EMO_ERR_BAD_SHAPE, "emo_act: n=%lld kind=%d", (long long)n, kind);
   EMO_DISPATCH(dtype, "emo_act", (act_kernel<T><<<cgrid(n), 256, 0, as_stream(stream)>>>((const T*)x, (T*)y, n, kind)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
@@ -93,6 +94,29 @@ extern "C" int emo_add_rowbias(const void* x, int ldx, const void* rb, int ldr, 
   EMO_CHECK(x && rb && y, EMO_ERR_NULL, "emo_add_rowbias: null pointer");
   EMO_CHECK(M > 0 && C > 0 && rows_per_batch > 0, EMO_ERR_BAD_SHAPE, "emo_add_rowbias: bad shape");
   EMO_DISPATCH(dtype, "emo_add_rowbias", (add_rowbias_kernel<T><<<cgrid(M * C), 256, 0, as_stream(stream)>>>((const T*)x, ldx, (const T*)rb, ldr, (T*)y, ldy, M, C, rows_per_batch)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// CLIPTextEmbeddings.forward: out[b*L + l, :] = tok[ids[b*L + l], :] + pos[l, :], the sum in f32.  Ids are range-checked on the host
+// (IndexError, like nn.Embedding); the clamp only keeps a bad id from reading outside the table.
+template <typename T>
+__global__ void text_embed_kernel(const int32_t* __restrict__ ids, const T* __restrict__ tok, const T* __restrict__ pos, T* __restrict__ out,
+                                  int BL, int L, int D, int V) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < (int64_t)BL * D; i += (int64_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / D), c = (int)(i % D);
+    int id = ids[row];
+    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
+    TT<T>::st(out + i, TT<T>::ld(tok + (int64_t)id * D + c) + TT<T>::ld(pos + (int64_t)(row % L) * D + c));
+  }
+}
+extern "C" int emo_text_embed(const int32_t* ids, const void* tok_table, const void* pos_table, void* out, int B, int L, int D, int V, int P,
+                              int dtype, void* stream) {
+  EMO_CHECK(ids && tok_table && pos_table && out, EMO_ERR_NULL, "emo_text_embed: null pointer");
+  EMO_CHECK(B > 0 && L > 0 && D > 0 && V > 0 && L <= P, EMO_ERR_BAD_SHAPE, "emo_text_embed: B=%d L=%d D=%d V=%d P=%d", B, L, D, V, P);
+  EMO_CHECK((int64_t)B * L <= 0x7fffffff, EMO_ERR_BAD_SHAPE, "emo_text_embed: too many rows");
+  EMO_DISPATCH(dtype, "emo_text_embed", (text_embed_kernel<T><<<cgrid((int64_t)B * L * D), 256, 0, as_stream(stream)>>>(
+                                             ids, (const T*)tok_table, (const T*)pos_table, (T*)out, B * L, L, D, V)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }

@@ -396,9 +396,10 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias, n_img: int, H: int, W: int, 
 
 # ----------------------------------------------------------------------------- attention
 def attention(q, k0, v0t, Lk0, *, B, Lq, heads, d, scale, seg0_div=1, k1=None, v1t=None, Lk1=0, seg1_div=1,
-              seg1_first_batch=0, seg1_skip=0, seg1_row=None) -> torch.Tensor:
+              seg1_first_batch=0, seg1_skip=0, seg1_row=None, causal=False) -> torch.Tensor:
     """q (B*Lq, >=heads*d) rows view; k0 rows view; v0t (Bk, heads*d, ld) V^T tensors.
-    seg1_row: device int32 tensor holding the bank row every batch >= seg1_first_batch reads (see emo_hip.h)."""
+    seg1_row: device int32 tensor holding the bank row every batch >= seg1_first_batch reads (see emo_hip.h).
+    causal: query row i sees keys j <= i only (one KV segment, Lq == Lk0 - emo_hip.h emo_attention_params.causal)."""
     _need_cuda(q, k0, v0t)
     p = AttentionParams()
     pq, ldq = _rows(q)
@@ -418,12 +419,13 @@ def attention(q, k0, v0t, Lk0, *, B, Lq, heads, d, scale, seg0_div=1, k1=None, v
         p.seg1_div = 1
     p.out, p.ldo = out.data_ptr(), out.stride(0)
     p.B, p.Lq, p.heads, p.d, p.scale, p.dtype = B, Lq, heads, d, float(scale), dt(q)
+    p.causal = int(bool(causal))
     esz = q.element_size()
     # (only the batch rows from seg1_first_batch on read the second segment - under CFG the uncond half does not)
     b1 = max(B - seg1_first_batch, 0) if k1 is not None else 0
     _launch("attention", 4.0 * heads * Lq * d * (B * Lk0 + b1 * Lk1), esz * heads * d * (2.0 * B * Lq + 2.0 * (B * Lk0 + b1 * Lk1)),
             lambda: check(_lib.load().emo_attention(C.byref(p), _stream()), "emo_attention"),
-            tag=f"B={B} Lq={Lq} Lk={Lk0}+{Lk1} h={heads} d={d}")
+            tag=f"B={B} Lq={Lq} Lk={Lk0}+{Lk1} h={heads} d={d}" + (" causal" if causal else ""))
     return out
 
 
@@ -478,7 +480,7 @@ def accumulate_window(pred_rows, noise_pred_branch, counter, frames_i32, *, C_, 
 
 
 # ----------------------------------------------------------------------------- EMO conditioning ops (A17/A18)
-_ACT = {"silu": 0, "relu": 1, "tanh": 2, "gelu": 3}
+_ACT = {"silu": 0, "relu": 1, "tanh": 2, "gelu": 3, "quick_gelu": 4}
 
 
 def act(x: torch.Tensor, kind: str) -> torch.Tensor:
@@ -507,6 +509,25 @@ def gather_rows(table: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     out = torch.empty(idx.shape[0], table.shape[1], device=table.device, dtype=table.dtype)
     check(_lib.load().emo_gather_rows(_ptr(table), _ptr(idx), _ptr(out), idx.shape[0], table.shape[1], table.shape[0], dt(table),
                                       _stream()), "emo_gather_rows")
+    return out
+
+
+def text_embed(ids: torch.Tensor, tok_table: torch.Tensor, pos_table: torch.Tensor) -> torch.Tensor:
+    """ids (B, L) integer ids -> (B*L, D) rows tok_table[ids] + pos_table[:L] in the tables' dtype (emo_text_embed).  The ids are
+    checked against the vocabulary on the host, before upload: an id outside [0, V) raises IndexError, as nn.Embedding does."""
+    _need_cuda(tok_table, pos_table)
+    B, L = ids.shape
+    V, D = tok_table.shape
+    ids_cpu = ids.detach().to("cpu", torch.int64)
+    if ids_cpu.numel() and (int(ids_cpu.min()) < 0 or int(ids_cpu.max()) >= V):
+        raise IndexError(f"index out of range in self: token ids must lie in [0, {V}), got [{int(ids_cpu.min())}, {int(ids_cpu.max())}]")
+    if L > pos_table.shape[0]:
+        raise IndexError(f"sequence length {L} exceeds the {pos_table.shape[0]} position embeddings")
+    assert tok_table.is_contiguous() and pos_table.is_contiguous() and pos_table.dtype == tok_table.dtype
+    idx = ids_cpu.to(torch.int32).reshape(-1).to(tok_table.device)
+    out = torch.empty(B * L, D, device=tok_table.device, dtype=tok_table.dtype)
+    check(_lib.load().emo_text_embed(_ptr(idx), _ptr(tok_table), _ptr(pos_table), _ptr(out), B, L, D, V, pos_table.shape[0],
+                                     dt(tok_table), _stream()), "emo_text_embed")
     return out
 
 

@@ -17,12 +17,14 @@ MI355X.  Same `__call__` signature; the hot loop (`:698-823`) is re-designed:
     no broadcast, bit-identical latents on all ranks;
   * the attn2 K / V^T projections of the text / audio context are computed once per clip, not per step.
 
-Caller-supplied where out of scope: CLIP text encoder (`text_embeddings=`), VAE (`vae=` object with
-encode / decode_video, see emote_hack_amd/vae.py), wav2vec (`audio_features=`, windowed by
-emote_hack_amd.conditioning.audio_windows), `speed_embeddings=`.
+Prompts are encoded by `_encode_prompt` (:202-289) with the caller's tokenizer and a text encoder on the pipeline - on these kernels
+emote_hack_amd.clip_text.CLIPTextModel; `text_embeddings=` still takes precedence.
+Caller-supplied where out of scope: VAE (`vae=` object with encode / decode_video, see emote_hack_amd/vae.py),
+wav2vec (`audio_features=`, windowed by emote_hack_amd.conditioning.audio_windows), `speed_embeddings=`.
 """
 from __future__ import annotations
 
+import logging
 import math
 from dataclasses import dataclass
 from types import SimpleNamespace
@@ -34,6 +36,8 @@ from . import ops
 from .context import get_context_scheduler
 from .reference_control import ReferenceAttentionControl
 from .scheduler import DDIMScheduler, DDPMScheduler
+
+logger = logging.getLogger(__name__)
 
 
 @dataclass
@@ -106,6 +110,47 @@ class EMOAnimationPipeline:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
         if (callback_steps is None) or (not isinstance(callback_steps, int) or callback_steps <= 0):
             raise ValueError(f"`callback_steps` has to be a positive integer but is {callback_steps} of type {type(callback_steps)}.")
+
+    @torch.no_grad()
+    def _encode_prompt(self, prompt, device, num_videos_per_prompt, do_classifier_free_guidance, negative_prompt):
+        """EMOAnimationPipeline.py:202-289: tokenize (max_length padding, truncation with a warning), encode, [uncond, cond] under
+        classifier-free guidance.  The two halves go through ONE text-encoder call (the ids are stacked; every sequence is encoded
+        on its own, so this equals the reference's two calls) - the tokenizer is the caller's (transformers' CLIPTokenizer or
+        anything with its call interface), the encoder normally emote_hack_amd.clip_text.CLIPTextModel."""
+        batch_size = len(prompt) if isinstance(prompt, list) else 1
+        tok, enc = self.tokenizer, self.text_encoder
+        text_inputs = tok(prompt, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt")
+        text_input_ids = text_inputs.input_ids
+        untruncated_ids = tok(prompt, padding="longest", return_tensors="pt").input_ids
+        if untruncated_ids.shape[-1] >= text_input_ids.shape[-1] and not torch.equal(text_input_ids, untruncated_ids):
+            removed_text = tok.batch_decode(untruncated_ids[:, tok.model_max_length - 1:-1])
+            logger.warning("The following part of your input was truncated because CLIP can only handle sequences up to"
+                           f" {tok.model_max_length} tokens: {removed_text}")
+        use_mask = bool(getattr(getattr(enc, "config", None), "use_attention_mask", False))
+        ids, masks = [text_input_ids], [text_inputs.attention_mask] if use_mask else None
+        if do_classifier_free_guidance:
+            if negative_prompt is None:
+                uncond_tokens = [""] * batch_size
+            elif type(prompt) is not type(negative_prompt):
+                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} !="
+                                f" {type(prompt)}.")
+            elif isinstance(negative_prompt, str):
+                uncond_tokens = [negative_prompt]
+            elif batch_size != len(negative_prompt):
+                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`:"
+                                 f" {prompt} has batch size {batch_size}. Please make sure that passed `negative_prompt` matches"
+                                 " the batch size of `prompt`.")
+            else:
+                uncond_tokens = negative_prompt
+            uncond_input = tok(uncond_tokens, padding="max_length", max_length=text_input_ids.shape[-1], truncation=True, return_tensors="pt")
+            ids.insert(0, uncond_input.input_ids)
+            if use_mask:
+                masks.insert(0, uncond_input.attention_mask)
+        emb = enc(torch.cat(ids).to(device), attention_mask=torch.cat(masks).to(device) if use_mask else None)[0]
+        # duplicate the embeddings for each generation per prompt (:231-234, :276-279), uncond half first
+        halves = emb.split(batch_size) if do_classifier_free_guidance else (emb,)
+        halves = [e.repeat(1, num_videos_per_prompt, 1).view(e.shape[0] * num_videos_per_prompt, e.shape[1], -1) for e in halves]
+        return torch.cat(halves) if do_classifier_free_guidance else halves[0]
 
     # ------------------------------------------------------------------ the hot loop
     @torch.no_grad()
@@ -965,13 +1010,13 @@ class EMOAnimationPipeline:
     def invert(self, image, prompt=None, num_inference_steps=20, num_actual_inference_steps=10, eta=0.0, return_intermediates=False, **kwargs):
         """:417-477 - deterministic DDIM inversion of real frames into a noise map: frames -> latents (`images2latents`, or pass
         latents=(f, 4, h, w)), then for the ascending timesteps x <- next_step(unet(x as one (1, c, f, h, w) clip, t, text), t, x), stopping after
-        `num_actual_inference_steps`.  The CLIP text encoder is outside this build: pass text_embeddings=(1, L, D) (or a text_encoder +
-        tokenizer pair on the pipeline, called like upstream)."""
+        `num_actual_inference_steps`.  The prompt goes through the tokenizer + text encoder on the pipeline, called like upstream
+        (emote_hack_amd.clip_text.CLIPTextModel runs it on these kernels); or pass text_embeddings=(1, L, D)."""
         text_embeddings = kwargs.get("text_embeddings")
         if text_embeddings is None:
             if self.text_encoder is None or self.tokenizer is None:
-                raise ValueError("invert: pass text_embeddings=(1, L, D) (no CLIP text encoder in this build)")
-            text_input = self.tokenizer(prompt, padding="max_length", max_length=77, return_tensors="pt")
+                raise ValueError("invert: pass text_embeddings=(1, L, D), or put a tokenizer + text_encoder on the pipeline")
+            text_input = self.tokenizer(prompt, padding="max_length", max_length=self.tokenizer.model_max_length, return_tensors="pt")
             text_embeddings = self.text_encoder(text_input.input_ids.to(self._execution_device))[0]
         latents = kwargs.get("latents")
         if latents is None:
@@ -1028,8 +1073,9 @@ class EMOAnimationPipeline:
                  init_latents=None, num_actual_inference_steps: Optional[int] = None, appearance_encoder=None,
                  reference_control_writer=None, reference_control_reader=None, source_image=None,
                  decoder_consistency=None, audio=None, head_rotation_speeds=None, **kwargs):
-        """Signature = EMOAnimationPipeline.py:544-578.  Extra keyword inputs for the parts that are out of
-        scope here: text_embeddings=(2,L,D), ref_image_latents=(1,4,h,w), audio_features=(F,L_a,D),
+        """Signature = EMOAnimationPipeline.py:544-578.  `prompt` / `negative_prompt` are encoded by `_encode_prompt` when the
+        pipeline has a tokenizer (and a text encoder, e.g. emote_hack_amd.clip_text.CLIPTextModel); text_embeddings=(2,L,D) takes precedence.
+        Extra keyword inputs for the parts that are out of scope here: ref_image_latents=(1,4,h,w), audio_features=(F,L_a,D),
         speed_embeddings=(1,4*C0), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
         optional): use_graphs (default: HIP-graph replay on a HIP device - the path bench.py measures), reference_group
         (ReferenceNet timesteps per batched pass; default 10, the configuration bench.py measures - 25 would make two passes per 50-step clip,
@@ -1057,8 +1103,13 @@ class EMOAnimationPipeline:
         text_embeddings = kwargs.get("text_embeddings")
         if text_embeddings is None:
             if self.text_encoder is None:
-                raise ValueError("pass text_embeddings=(2,L,D) [uncond, cond] (no CLIP text encoder in this build)")
-            text_embeddings = self.text_encoder(prompt, negative_prompt)
+                raise ValueError("pass text_embeddings=(2,L,D) [uncond, cond], or put a tokenizer + text_encoder "
+                                 "(emote_hack_amd.clip_text.CLIPTextModel) on the pipeline")
+            if self.tokenizer is not None:     # :628-630
+                text_embeddings = self._encode_prompt(prompt, self._execution_device, num_videos_per_prompt, guidance_scale > 1.0,
+                                                      negative_prompt)
+            else:
+                text_embeddings = self.text_encoder(prompt, negative_prompt)
         ref_lat = kwargs.get("ref_image_latents")
         if ref_lat is None:
             if self.vae is None or source_image is None:

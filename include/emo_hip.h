@@ -229,6 +229,10 @@ typedef struct {
                                 seg1_row[0] (seg1_div / seg1_skip unused).  A sampling loop keeps the projected banks of a
                                 whole group of timesteps resident and selects the current one by writing this word - the
                                 launch parameters (hence a captured hipGraph) stay the same from step to step. */
+  int causal;   /* 1: causal self-attention - query row i of each batch row attends to keys j <= i of segment 0 only (the
+                   CLIP text encoder's causal mask, transformers CLIPAttention behind CLIPTextTransformer._build_causal_attention_mask;
+                   the CLIPTextModel that magicanimate/pipelines/animation.py:75-76 loads).  Needs Lq == Lk0 and no segment 1
+                   (k1 and seg1_row NULL), else EMO_ERR_UNSUPPORTED.  0 (a zeroed struct): no mask, as before. */
 } emo_attention_params;
 int emo_attention(const emo_attention_params* p, void* stream);
 
@@ -281,9 +285,10 @@ int emo_accumulate_window(const void* pred, int ld, float* noise_pred_branch, fl
                           int nf, int C, int F, int HW, int add_counter, int dtype, void* stream);
 
 /* ---- EMO conditioning ----------------------------------------------
- * emo_act: y = act(x), kind 0 SiLU | 1 ReLU | 2 tanh | 3 erf-GELU over n contiguous elements (the ReLU / tanh of
- *   Net.py:214-218,246 and train_stage_3_speedlayers.py:36-40,66-73; GELU: the activation of the wav2vec2 encoder
- *   Net.py:611-612 loads - transformers Wav2Vec2FeedForward / conv layers).
+ * emo_act: y = act(x), kind 0 SiLU | 1 ReLU | 2 tanh | 3 erf-GELU | 4 quick_gelu x * sigmoid(1.702 x) over n contiguous elements
+ *   (the ReLU / tanh of Net.py:214-218,246 and train_stage_3_speedlayers.py:36-40,66-73; GELU: the activation of the wav2vec2 encoder
+ *   Net.py:611-612 loads - transformers Wav2Vec2FeedForward / conv layers; quick_gelu: transformers QuickGELUActivation, the MLP
+ *   activation of the SD-1.x CLIP text encoder, CLIPMLP behind EMOAnimationPipeline.py:226-229).  f32 math, rounded once.
  * emo_speed_encode: SpeedEncoder.encode_speed (Net.py:231-247): out[b,i] = tanh((v[b]-centers[i])/radii[i]*3).
  * emo_speed_bucket: SpeedController.map_speed_to_bucket (train_stage_3_speedlayers.py:42-47), INT bit-exact:
  *   idx[b] = argmin_i |v[b] - centers[i]| (first minimum on ties).
@@ -295,6 +300,12 @@ int emo_speed_bucket(const float* v, const float* centers, int32_t* idx, int B, 
 int emo_gather_rows(const void* table, const int32_t* idx, void* out, int B, int D, int rows, int dtype, void* stream);
 int emo_add_rowbias(const void* x, int ldx, const void* rb, int ldr, void* y, int ldy, int64_t M, int C, int rows_per_batch,
                     int dtype, void* stream);
+/* emo_text_embed: CLIPTextEmbeddings.forward (transformers; the text encoder of EMOAnimationPipeline.py:226-229) in one launch:
+ *   out[b*L + l, :] = tok_table[ids[b*L + l], :] + pos_table[l, :]   (inputs_embeds + position_embedding(arange(L))).
+ *   ids: device int32 [B*L], each in [0, V) - checked by the caller before upload (an out-of-range id is clamped here, never read
+ *   out of bounds); tok_table [V][D], pos_table [P][D] with L <= P, out [B*L][D], all in dtype; the sum in f32, rounded once. */
+int emo_text_embed(const int32_t* ids, const void* tok_table, const void* pos_table, void* out, int B, int L, int D, int V, int P,
+                   int dtype, void* stream);
 
 /* ---- either side of the loop ----------------------------------------------------
  * emo_softmax_rows: y[m, :] = softmax(scale * x[m, :]) over N columns - the VAE mid-block attention (one head of 512
