@@ -74,7 +74,7 @@ class SchedStepParams(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/emo_hip.h declares
-_i, _i64, _f, _p, _u32 = C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_uint32
+_i, _i64, _f, _p = C.c_int, C.c_int64, C.c_float, C.c_void_p
 SIGNATURES = {
     "emo_version": (_i, []),
     "emo_last_error_string": (C.c_char_p, []),
@@ -102,7 +102,6 @@ SIGNATURES = {
     "emo_gemm_workspace_bytes": (C.c_size_t, [_i64, _i, _i]),
     "emo_attention": (_i, [C.POINTER(AttentionParams), _p]),
     "emo_temporal_attention": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "emo_cfg_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _u32, _u32, _p]),
     "emo_sched_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, C.POINTER(SchedStepParams), _p]),
     "emo_accumulate_window": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "emo_act": (_i, [_p, _p, _i64, _i, _i, _p]),

@@ -236,51 +236,17 @@ extern "C" int emo_timestep_embedding_f32(const float* ts, const float* freqs, v
   return EMO_OK;
 }
 
-// ---------------------------------------------------------------- sampler: CFG + window average + step
+// ---------------------------------------------------------------- sampler: CFG + window average + linear multistep step
+// Every scheduler of the loop (DDIM, DDPM, DPM-Solver++ 2M, Euler, Euler-ancestral, LMS) as one linear form over the f32 latents,
+// see include/emo_hip.h.  One element: read x and the ring entries before writing anything of element i, so x' may overwrite x in
+// place.  z is a pure function of (seed, step, i): every rank draws the same bits without communication.
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
   x = (x ^ (x >> 16)) * 0x7FEB352Du;
   x = (x ^ (x >> 15)) * 0x846CA68Bu;
   x = x ^ (x >> 16);
   return x;
 }
-__global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ np, const float* __restrict__ counter,
-                                                       float* __restrict__ lat, float* __restrict__ eps_out, int C, int F, int HW,
-                                                       float gs, float c_x, float c_eps, float c_n, uint32_t seed, uint32_t step) {
-  const int64_t n = (int64_t)C * F * HW;
-  const uint32_t key = mix32(seed ^ mix32(step + 0x9E3779B9u));
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int f = (int)((i / HW) % F);
-    float inv = 1.0f / counter[f];
-    float eps = np[i] * inv;                        // noise_pred / counter (EMOAnimationPipeline.py:813)
-    if (gs > 1.0f) {                                // do_classifier_free_guidance = guidance_scale > 1.0 (:622); else np is [1][n]
-      const float cc = np[n + i] * inv;
-      eps = eps + gs * (cc - eps);                  // :814
-    }
-    float x = c_x * lat[i] + c_eps * eps;
-    if (c_n != 0.f) {
-      uint32_t h1 = mix32(((uint32_t)i * 2u + 0u) ^ key), h2 = mix32(((uint32_t)i * 2u + 1u) ^ key);
-      float u1 = ((float)h1 + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
-      float u2 = (float)h2 * 2.3283064365386963e-10f;
-      x += c_n * sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-    }
-    lat[i] = x;
-    if (eps_out) eps_out[i] = eps;
-  }
-}
-extern "C" int emo_cfg_step(const float* np, const float* counter, float* lat, float* eps_out, int C, int F, int HW,
-                            float gs, float c_x, float c_eps, float c_n, uint32_t seed, uint32_t step, void* stream) {
-  EMO_CHECK(np && counter && lat, EMO_ERR_NULL, "emo_cfg_step: null pointer");
-  EMO_CHECK(C > 0 && F > 0 && HW > 0, EMO_ERR_BAD_SHAPE, "emo_cfg_step: bad shape");
-  cfg_step_kernel<<<grid_for((int64_t)C * F * HW, 256), 256, 0, as_stream(stream)>>>(np, counter, lat, eps_out, C, F, HW, gs, c_x,
-                                                                                   c_eps, c_n, seed, step);
-  EMO_LAUNCH_CHECK();
-  return EMO_OK;
-}
 
-// ---------------------------------------------------------------- sampler: CFG + window average + linear multistep step
-// The sigma-space samplers (DPM-Solver++ 2M, Euler, Euler-ancestral, LMS) as one linear form over the f32 latents, see
-// include/emo_hip.h.  One element: read x and the ring entries before writing anything of element i, so x' may overwrite x in
-// place.  The noise term is emo_cfg_step's expression line for line: same (seed, step, i) -> same z bits.
 // npu / npc: noise_pred of element i in the uncond / cond plane (npc unused without guidance); x0: its latent; cnt: the counter
 // of its frame.
 __device__ __forceinline__ float sched_elem(float npu, float npc, float x0, float cnt, float* __restrict__ hist,
@@ -288,10 +254,9 @@ __device__ __forceinline__ float sched_elem(float npu, float npc, float x0, floa
                                             uint32_t key) {
   const float inv = 1.0f / cnt;
   float eps = npu * inv;
-  if (p.guidance_scale > 1.0f) {
-    const float cc = npc * inv;
-    eps = eps + p.guidance_scale * (cc - eps);
-  }
+  // CFG with c*inv - uc in one rounding, written out so that the bits do not depend on the compiler: left to it, u*inv and c*inv
+  // were paired into one packed multiply, which rounds c*inv first (tests/golden/sched_ddim_ddpm.safetensors pins the bits)
+  if (p.guidance_scale > 1.0f) eps = fmaf(p.guidance_scale, fmaf(npc, inv, -eps), eps);
   const float d = p.a * x0 + p.b * eps;
   float x = p.c_x * x0 + p.c[0] * d;
 #pragma unroll

@@ -441,17 +441,9 @@ def temporal_attention(qkv: torch.Tensor, B, F, HW, heads, d, scale) -> torch.Te
 
 
 # ----------------------------------------------------------------------------- sampler
-def cfg_step(noise_pred, counter, latents, *, C_, F, HW, guidance_scale, c_x, c_eps, c_noise, seed, step, eps_out=None):
-    _need_cuda(noise_pred, counter, latents)
-    assert noise_pred.dtype == counter.dtype == latents.dtype == torch.float32
-    check(_lib.load().emo_cfg_step(_ptr(noise_pred), _ptr(counter), _ptr(latents), _ptr(eps_out), C_, F, HW, float(guidance_scale),
-                                   float(c_x), float(c_eps), float(c_noise), int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF,
-                                   _stream()), "emo_cfg_step")
-
-
 def sched_step(noise_pred, counter, latents, history, lat_in, *, C_, F, HW, guidance_scale, a, b, c_x, c, slot, c_noise, s_next,
                seed, step, eps_out=None):
-    """One step of a sigma-space sampler (emo_sched_step): c / slot are 4-tuples (slot -1 = no ring entry)."""
+    """One scheduler step (emo_sched_step): c / slot are 4-tuples (slot -1 = no ring entry)."""
     _need_cuda(noise_pred, counter, latents, history, lat_in, eps_out)
     assert noise_pred.dtype == counter.dtype == latents.dtype == torch.float32
     n = C_ * F * HW

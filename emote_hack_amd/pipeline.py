@@ -2,7 +2,7 @@
 MI355X.  Same `__call__` signature; the hot loop (`:698-823`) is re-designed:
 
   * per step: Backbone read passes over this rank's work units -> (all_gather of the eps slices) -> window average + CFG +
-    scheduler step fused in ONE HIP kernel (emo_cfg_step) on f32 master latents;
+    scheduler step fused in ONE HIP kernel (emo_sched_step) on f32 master latents;
   * the ReferenceNet banks depend on the timestep only (never on the latents), so the write pass is hoisted out of the
     step: T timesteps (reference_group, default 10) go through ONE batched pass (M is T times larger: the batch-1 pass of
     the reference is a small-M, launch-bound workload), their K / V^T projections with the Backbone's attn1 weights are
@@ -24,6 +24,7 @@ wav2vec (`audio_features=`, windowed by emote_hack_amd.conditioning.audio_window
 """
 from __future__ import annotations
 
+import copy
 import logging
 import math
 from dataclasses import dataclass
@@ -35,7 +36,6 @@ import torch
 from . import ops
 from .context import get_context_scheduler
 from .reference_control import ReferenceAttentionControl
-from .scheduler import DDIMScheduler, DDPMScheduler
 
 logger = logging.getLogger(__name__)
 
@@ -81,12 +81,12 @@ class EMOAnimationPipeline:
         scheduler it is given, like the reference."""
         if unet is None or scheduler is None:
             raise ValueError("unet and scheduler are required")
-        if not (hasattr(scheduler, "coefficients") or hasattr(scheduler, "step_plan")):
+        if not hasattr(scheduler, "step_plan"):
             # PNDM (51 UNet evaluations for 50 steps, a repeated timestep restarting from an earlier sample) among others: the
             # loop's step / window / ReferenceNet-group bookkeeping assumes one UNet evaluation per step
             raise TypeError(f"{type(scheduler).__name__} is not served: the loop runs DDIMScheduler, DDPMScheduler, "
                             "DPMSolverMultistepScheduler, EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler "
-                            "(or an object with their `coefficients(t, eta)` / `step_plan(si, first)` interface)")
+                            "(or an object with their `step_plan(si, first)` interface)")
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
         self.unet, self.controlnet, self.scheduler = unet, controlnet, scheduler
         # EMOAnimationPipeline.py:105-117: ANY scheduler whose config has the key, not DDIM only - a DDPMScheduler handed to the
@@ -206,21 +206,17 @@ class EMOAnimationPipeline:
         st.reader = ReferenceAttentionControl(unet, do_classifier_free_guidance=cfg, mode="read", batch_size=cbs,
                                               fusion_blocks=fusion_blocks)                        # :634
         st.num_inference_steps = num_inference_steps
-        st.scheduler = sch
         st.timesteps = list(sch.set_timesteps(num_inference_steps))
-        # sigma-space samplers (DPM-Solver++, Euler, Euler-a, LMS): emo_sched_step with a per-step plan.  The state keeps its own
-        # copy of the scheduler's tables (the object is shared: another set_timesteps must not move a state still being stepped), a
-        # ring of earlier model outputs and the model input of the next step, `lat_in`, which the step kernel writes - the UNet /
-        # ControlNet passes gather from it, so no step-dependent input scale is baked into a captured graph
-        st.plan_sched = hasattr(sch, "step_plan")
+        # every step is emo_sched_step with a per-step plan.  The state keeps its own copy of the scheduler's tables (the object is
+        # shared: another set_timesteps must not move a state still being stepped), a ring of earlier model outputs and the model
+        # input of the next step, `lat_in`, which the step kernel writes - the UNet / ControlNet passes gather from it, so no
+        # step-dependent input scale is baked into a captured graph
         st.t_dtype = torch.float32 if getattr(sch, "float_timesteps", False) else torch.int64
-        if st.plan_sched:
-            import copy
-            st.sched_frozen = copy.deepcopy(sch)
-            st.lat_in = torch.empty_like(st.latents)
-            st.ring = int(sch.history)
-            st.history = torch.empty(st.ring, st.latents.numel(), device=dev, dtype=torch.float32) if st.ring else None
-            st.plans = {}
+        st.sched_frozen = copy.deepcopy(sch)
+        st.lat_in = torch.empty_like(st.latents)
+        st.ring = int(sch.history)
+        st.history = torch.empty(st.ring, st.latents.numel(), device=dev, dtype=torch.float32) if st.ring else None
+        st.plans = {}
         n_steps = len(st.timesteps)
         # ReferenceNet images = [reference, motion frames] (Net.py:56-72 intent; junk/EMo-write-up.txt:104-110)
         st.n_ref_images = 1 + (0 if motion_latents is None else self._motion_rows(motion_latents).shape[0])
@@ -383,7 +379,7 @@ class EMOAnimationPipeline:
     # ---- the INPUTS of a prepared loop state, copied into its buffers in place (the captured graphs keep reading them)
     @staticmethod
     def _do_cfg(guidance_scale):
-        """`do_classifier_free_guidance = guidance_scale > 1.0` (:622), decided on the f32 value emo_cfg_step receives: a scale
+        """`do_classifier_free_guidance = guidance_scale > 1.0` (:622), decided on the f32 value emo_sched_step receives: a scale
         in (1, 1 + 2^-24] would otherwise allocate two noise_pred planes for a kernel that reads one."""
         import numpy as np
         return bool(np.float32(guidance_scale) > np.float32(1.0))
@@ -435,6 +431,9 @@ class EMOAnimationPipeline:
             st.guidance_scale = float(guidance_scale)
         if eta is not None:
             st.eta = eta
+            if hasattr(st.sched_frozen, "eta"):   # DDIM: the plans read it, so none of the previous clip's may be kept
+                st.sched_frozen.eta = eta
+                st.plans = {}
         if seed is not None:
             st.seed = seed
         ctx_stale = False
@@ -496,7 +495,7 @@ class EMOAnimationPipeline:
                 raise ValueError("controlnet_conditioning_scale is baked into the captured ControlNet pass (prepare again)")
             st.cn_scale = scale
         st.group_ready, st.group_pending, st.eps_trace = -1, -1, []
-        st.sched_first = None      # sigma-space samplers: the multistep warm-up and lat_in restart at the next step that runs
+        st.sched_first = None      # the multistep warm-up and lat_in restart at the next step that runs
 
     @staticmethod
     def _put_kv(store, key, kv):
@@ -638,10 +637,7 @@ class EMOAnimationPipeline:
     def _part_controlnet(self, st):
         downs, mids = [], []
         for i, idx in enumerate(st.cn_chunks):
-            if st.plan_sched:   # the scaled model input, written by the step kernel
-                x = st.lat_in.index_select(2, idx)[0].permute(1, 0, 2, 3).contiguous()
-            else:
-                x = self.scheduler.scale_model_input(st.latents.index_select(2, idx), None)[0].permute(1, 0, 2, 3).contiguous()
+            x = st.lat_in.index_select(2, idx)[0].permute(1, 0, 2, 3).contiguous()     # the scaled model input, written by the step kernel
             d, m = st.controlnet(x, st.t_buf, encoder_hidden_states=st.cn_text.repeat(idx.numel(), 1, 1), controlnet_cond=None,
                                  conditioning_scale=st.cn_scale, return_dict=False, _cond_rows=st.cn_embed[i])
             downs.append(d)
@@ -665,11 +661,7 @@ class EMOAnimationPipeline:
     #      from st.bank_idx, so it is captured once into a HIP graph and replayed for the other steps
     def _part_unet(self, st, ci):
         call = st.calls[ci]
-        if st.plan_sched:   # the scaled model input, written by the step kernel
-            x = torch.cat([st.lat_in.index_select(2, ix) for ix in call.idx])
-        else:
-            x = torch.cat([st.latents.index_select(2, ix) for ix in call.idx])                 # :759-763 (index/copy only)
-            x = self.scheduler.scale_model_input(x, None)
+        x = torch.cat([st.lat_in.index_select(2, ix) for ix in call.idx])   # :759-763; the scaled model input, written by the step kernel
         # (a call of uncond units only names any resident cache: every one of its batches skips the bank segment)
         bank_tv = call.bank_tv if call.bank_tv is not None else st.bank_variants[0]
         self.unet._reference_control = st.reader
@@ -712,10 +704,8 @@ class EMOAnimationPipeline:
     @torch.no_grad()
     def denoise_step(self, st, si):
         """One iteration of the hot loop (EMOAnimationPipeline.py:698-823)."""
-        sch = self.scheduler
         dev = self.unet.device
-        t = st.timesteps[si]
-        if st.plan_sched and st.sched_first is None:    # the first step that runs: its model input, one scale-only launch
+        if st.sched_first is None:    # the first step that runs: its model input, one scale-only launch
             st.sched_first = si
             ops.sched_scale(st.latents, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW, s=st.sched_frozen.input_scale(si))
         self._ensure_group(st, si)                                     # :711-716, hoisted: banks of T timesteps per pass
@@ -734,24 +724,17 @@ class EMOAnimationPipeline:
             td.all_gather_into_tensor(st.recv.view(-1), st.send.view(-1))
         self._accumulate_all(st)
         eps_out = torch.empty(st.C4 * st.f_tot * st.HW, device=dev, dtype=torch.float32) if st.return_eps else None
-        if st.plan_sched:
-            p, slot = self._step_plan(st, si)
-            ops.sched_step(st.noise_pred, st.counter, st.latents, st.history, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW,
-                           guidance_scale=st.guidance_scale, a=p.a, b=p.b, c_x=p.c_x, c=p.c, slot=slot, c_noise=p.c_noise,
-                           s_next=p.s_next, seed=st.seed, step=si, eps_out=eps_out)
-        else:
-            # (the state's own scheduler object and step count: `self.scheduler` may have been replaced or re-timed since the plan was made)
-            sch = st.scheduler
-            c_x, c_eps, c_n = self._coefficients(sch, t, st.eta if isinstance(sch, DDIMScheduler) else None, st.num_inference_steps)
-            ops.cfg_step(st.noise_pred, st.counter, st.latents, C_=st.C4, F=st.f_tot, HW=st.HW, guidance_scale=st.guidance_scale,
-                         c_x=c_x, c_eps=c_eps, c_noise=c_n, seed=st.seed, step=si, eps_out=eps_out)  # :812-817 fused
+        p, slot = self._step_plan(st, si)   # :812-817 fused
+        ops.sched_step(st.noise_pred, st.counter, st.latents, st.history, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW,
+                       guidance_scale=st.guidance_scale, a=p.a, b=p.b, c_x=p.c_x, c=p.c, slot=slot, c_noise=p.c_noise,
+                       s_next=p.s_next, seed=st.seed, step=si, eps_out=eps_out)
         if st.return_eps:
             st.eps_trace.append(eps_out.view(1, st.C4, st.f_tot, st.h, st.w))
 
     @staticmethod
     def _step_plan(st, si):
-        """(StepPlan, ring slots) of step si of a sigma-space sampler: d_n goes to slot (si - first) % ring, d_{n-k} is read from
-        slot (si - first - k) % ring - the ring restarts with the first step that runs."""
+        """(StepPlan, ring slots) of step si: d_n goes to slot (si - first) % ring, d_{n-k} is read from slot (si - first - k) % ring
+        - the ring restarts with the first step that runs."""
         key = (st.sched_first, si)
         if key not in st.plans:
             p = st.sched_frozen.step_plan(si, st.sched_first)
@@ -766,17 +749,6 @@ class EMOAnimationPipeline:
                     slot.append(-1)
             st.plans[key] = (p, tuple(slot))
         return st.plans[key]
-
-    @staticmethod
-    def _coefficients(sch, t, eta, num_inference_steps):
-        """(c_x, c_eps, c_noise) of step t from the scheduler object.  The step count goes by KEYWORD, and a user-supplied scheduler
-        with the leaner `coefficients(t[, eta])` signature is still served - as long as it has been timed for this many steps."""
-        try:
-            return sch.coefficients(t, eta, num_inference_steps=num_inference_steps)
-        except TypeError:
-            if getattr(sch, "num_inference_steps", num_inference_steps) != num_inference_steps:
-                raise
-            return sch.coefficients(t, eta) if eta is not None else sch.coefficients(t)
 
     def _run_loop(self, st, num_actual_inference_steps=None, callback=None, callback_steps=1):
         n = st.num_inference_steps

@@ -1,10 +1,17 @@
-"""DDPM / DDIM schedulers for the sampling loop (call sites EMOAnimationPipeline.py:653-654,764,817).
+"""Schedulers of the sampling loop (call sites EMOAnimationPipeline.py:653-654,764,817): DDPM / DDIM, and the sigma-space
+samplers below (DPM-Solver++ 2M, Euler, Euler-ancestral, LMS).
 
 The reference uses `diffusers` schedulers (not in its tree, version unpinned) - restated here from
 the papers (DDPM: Ho et al. 2020 Eq. 7/11, "fixed_small" variance; DDIM: Song et al. 2021 Eq. 12).
-Host side only computes the INTEGER timestep table (bit-exact) and three scalars per step; the
-per-element update x <- c_x*x + c_eps*eps + c_noise*z runs in the fused HIP sampler kernel
-(emo_cfg_step) with counter-based noise, so every rank draws identical z without communication.
+Every scheduler serves one protocol: per step the host computes, in float64, a PLAN `step_plan(si, first)` of the linear form
+the fused HIP step kernel (emo_sched_step) evaluates per element, with counter-based noise, so every rank draws identical z
+without communication:
+  d_n   = a*x + b*eps                       (the solver's model output: eps, or x0 = (x - sigma_t*eps) / alpha_t)
+  x'    = c_x*x + sum_k c[k]*d_{n-k} + c_noise*z   (k = 0..3; d_{n-k} from a ring of `history` earlier model outputs)
+  x_in  = s_next*x'                         (scale_model_input of the NEXT step, `input_scale(si + 1)`)
+A multistep warm-up counts from the first step that RUNS (`first`), so a loop started late begins at order 1.
+DDPM / DDIM compute the INTEGER timestep table (bit-exact) and three scalars per step, `coefficients(t)`:
+x' = c_x*x + c_eps*eps + c_noise*z, the plan a = 0, b = 1, c = (c_eps,), no ring, an unscaled model input.
 
 Pipeline-enforced config (EMOAnimationPipeline.py:105-130): steps_offset=1 on every scheduler whose config carries the key
 (both classes here do, like diffusers' since `timestep_spacing` exists), clip_sample=False.  A scheduler built on its own keeps
@@ -19,6 +26,30 @@ from types import SimpleNamespace
 import torch
 
 
+class StepPlan(SimpleNamespace):
+    """a, b, c_x, c (4 floats: d_n, d_{n-1}, d_{n-2}, d_{n-3}), c_noise, s_next - see the module docstring"""
+
+
+class _PlanBase:
+    """The step-plan protocol every scheduler of the loop serves.  Subclasses set `float_timesteps`, `history` (model-output
+    ring slots the plan needs) and implement `_plan`; `input_scale` when the model input is scaled."""
+    order = 1
+    history = 0
+
+    def input_scale(self, si):
+        """scale_model_input factor of step si"""
+        return 1.0
+
+    def step_plan(self, si, first=0):
+        """StepPlan of step si for a loop whose first executed step is `first` (the multistep warm-up counts from there)"""
+        if not first <= si < len(self.timesteps):
+            raise IndexError(f"step {si} outside [{first}, {len(self.timesteps)})")
+        p = self._plan(si, first)
+        p.c = tuple(float(v) for v in p.c) + (0.0,) * (4 - len(p.c))
+        p.s_next = self.input_scale(si + 1) if si + 1 < len(self.timesteps) else 1.0
+        return p
+
+
 def _betas(T, beta_start, beta_end, schedule):
     if schedule == "linear":
         return torch.linspace(beta_start, beta_end, T, dtype=torch.float32)
@@ -27,9 +58,9 @@ def _betas(T, beta_start, beta_end, schedule):
     raise NotImplementedError(f"{schedule} is not implemented")
 
 
-class _SchedulerBase:
-    order = 1
+class _SchedulerBase(_PlanBase):
     init_noise_sigma = 1.0
+    float_timesteps = False
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear",
                  steps_offset=0, clip_sample=False, set_alpha_to_one=True, timestep_spacing="leading", **_ignored):
@@ -58,14 +89,15 @@ class _SchedulerBase:
     def scale_model_input(self, sample, timestep=None):
         return sample
 
-    def _alphas(self, t, num_inference_steps=None):
-        # (a prepared loop state passes ITS step count: the scheduler object is shared, and another prepare_denoise /
-        # set_timesteps in between must not change the coefficients of a state that is still being stepped)
-        n = self.num_inference_steps if num_inference_steps is None else num_inference_steps
-        prev_t = t - self.config.num_train_timesteps // n
+    def _alphas(self, t):
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
         a_t = float(self.alphas_cumprod[t])
         a_prev = float(self.alphas_cumprod[prev_t]) if prev_t >= 0 else self._final_alpha()
         return a_t, a_prev
+
+    def _plan(self, si, first):
+        c_x, c_eps, c_n = self.coefficients(self.timesteps[si])
+        return StepPlan(a=0.0, b=1.0, c_x=c_x, c=(c_eps,), c_noise=c_n)
 
 
 class DDIMScheduler(_SchedulerBase):
@@ -78,9 +110,9 @@ class DDIMScheduler(_SchedulerBase):
     def _final_alpha(self):
         return self.final_alpha_cumprod
 
-    def coefficients(self, t, eta=None, num_inference_steps=None):
+    def coefficients(self, t, eta=None):
         eta = self.eta if eta is None else eta
-        a_t, a_prev = self._alphas(t, num_inference_steps)
+        a_t, a_prev = self._alphas(t)
         var = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
         std = eta * math.sqrt(max(var, 0.0))
         c_x = math.sqrt(a_prev / a_t)
@@ -92,8 +124,8 @@ class DDPMScheduler(_SchedulerBase):
     def _final_alpha(self):
         return 1.0
 
-    def coefficients(self, t, eta=None, num_inference_steps=None):
-        a_t, a_prev = self._alphas(t, num_inference_steps)
+    def coefficients(self, t, eta=None):
+        a_t, a_prev = self._alphas(t)
         cur_alpha = a_t / a_prev
         cur_beta = 1 - cur_alpha
         k0 = math.sqrt(a_prev) * cur_beta / (1 - a_t)       # coefficient of x0 (Eq. 7)
@@ -111,15 +143,6 @@ class DDPMScheduler(_SchedulerBase):
 # and linear multistep (LMS, the k-diffusion sampler after Karras et al.'s sigma-space ODE dx/dsigma = eps).  Behaviour restated
 # from the papers in the form diffusers ~0.26-0.27 (the release the reference's import sites imply) gives them: VP
 # alphas_cumprod, sigma = sqrt((1 - alpha_bar) / alpha_bar), the same timestep spacings, init_noise_sigma and model-input scale.
-#
-# The host computes, in float64, a per-step PLAN of the linear form the fused HIP step kernel (emo_sched_step) evaluates:
-#   d_n   = a*x + b*eps                       (the solver's model output: eps, or x0 = (x - sigma_t*eps) / alpha_t)
-#   x'    = c_x*x + sum_k c[k]*d_{n-k} + c_noise*z   (k = 0..3; d_{n-k} from a ring of earlier model outputs)
-#   x_in  = s_next*x'                         (scale_model_input of the NEXT step)
-# A multistep warm-up counts from the first step that RUNS (`first`), so a loop started late begins at order 1.
-
-class StepPlan(SimpleNamespace):
-    """a, b, c_x, c (4 floats: d_n, d_{n-1}, d_{n-2}, d_{n-3}), c_noise, s_next - see the block comment above"""
 
 
 def _spaced(T, n, spacing, steps_offset, plus_one=False):
@@ -156,12 +179,10 @@ def _sigma_to_t(sigma, log_sigmas):
     return np.interp(np.log(np.maximum(sigma, 1e-10)), log_sigmas, np.arange(len(log_sigmas), dtype=np.float64))
 
 
-class _SigmaSchedulerBase:
-    """Shared table handling of the sigma-space samplers (see the block comment above).  Subclasses set `float_timesteps`,
-    `history` (model-output ring slots the plan needs) and implement `_tables` and `_plan`."""
-    order = 1
+class _SigmaSchedulerBase(_PlanBase):
+    """Shared table handling of the sigma-space samplers (see the block comment above).  Subclasses implement `_tables`, and the
+    plan protocol's `_plan`; input_scale is 1 (the VP-form DPM-Solver) unless overridden."""
     float_timesteps = True
-    history = 0
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="linear", steps_offset=0,
                  clip_sample=False, timestep_spacing="linspace", use_karras_sigmas=False, prediction_type="epsilon", **_ignored):
@@ -201,23 +222,10 @@ class _SigmaSchedulerBase:
         t = float(timestep.reshape(-1)[0]) if torch.is_tensor(timestep) else float(timestep)
         return min(range(len(self.timesteps)), key=lambda i: abs(self.timesteps[i] - t))
 
-    def input_scale(self, si):
-        """scale_model_input factor of step si (1 for the VP-form DPM-Solver)"""
-        return 1.0
-
     def scale_model_input(self, sample, timestep=None):
         if timestep is None:
             raise ValueError(f"{type(self).__name__}.scale_model_input needs the timestep: the scale depends on the step")
         return sample * self.input_scale(self.step_index(timestep))
-
-    def step_plan(self, si, first=0):
-        """StepPlan of step si for a loop whose first executed step is `first` (the multistep warm-up counts from there)"""
-        if not first <= si < len(self.timesteps):
-            raise IndexError(f"step {si} outside [{first}, {len(self.timesteps)})")
-        p = self._plan(si, first)
-        p.c = tuple(float(v) for v in p.c) + (0.0,) * (4 - len(p.c))
-        p.s_next = self.input_scale(si + 1) if si + 1 < len(self.timesteps) else 1.0
-        return p
 
 
 class _KarrasSigmaScheduler(_SigmaSchedulerBase):

@@ -243,25 +243,19 @@ int emo_temporal_attention(const void* qkv, int64_t ldqkv, void* out, int64_t ld
                            int heads, int d, float scale, int dtype, void* stream);
 
 /* ---- sampler -------------------------------------------------------------------------------
- * Fused window-average + classifier-free guidance + scheduler step
- * (EMOAnimationPipeline.py:812-817):  eps = uc + s*(c - uc) on noise_pred/counter;
- * x <- c_x*x + c_eps*eps + c_noise*z,  z = counter-based N(0,1) keyed by (seed, step, element).
- * noise_pred f32 [2][n] (uc, c), counter f32 per frame [F] broadcast over (C, H*W): element
- * (c, f, p) has index (c*F + f)*HW + p.  latents f32 [n], updated in place; eps_out optional.
- * guidance_scale <= 1 is the reference's "no classifier-free guidance" (:622 `do_classifier_free_guidance =
- * guidance_scale > 1.0`): noise_pred is then [1][n] and eps = noise_pred / counter. */
-int emo_cfg_step(const float* noise_pred, const float* counter, float* latents, float* eps_out, int C, int F,
-                 int HW, float guidance_scale, float c_x, float c_eps, float c_noise, uint32_t seed, uint32_t step,
-                 void* stream);
-/* Fused window-average + classifier-free guidance + one step of a sigma-space sampler (DPM-Solver++ 2M, Euler,
- * Euler-ancestral, LMS) as a linear form with up to three earlier model outputs, all f32 over n = C*F*HW elements:
- *   eps   = CFG(noise_pred / counter)                (exactly as emo_cfg_step)
+ * Fused window-average + classifier-free guidance + one scheduler step (EMOAnimationPipeline.py:812-817) - DDIM, DDPM,
+ * DPM-Solver++ 2M, Euler, Euler-ancestral, LMS - as a linear form with up to three earlier model outputs, all f32 over
+ * n = C*F*HW elements.  Element (c, f, p) has index (c*F + f)*HW + p; counter holds one f32 per frame [F], broadcast over
+ * (C, H*W):
+ *   eps   = uc + guidance_scale*(c - uc) on noise_pred / counter   (noise_pred f32 [2][n] = (uc, c))
  *   d     = a*x + b*eps                              (the solver's model output: eps, or x0)
  *   x'    = c_x*x + c[0]*d + sum_{k=1..3, slot[k] >= 0} c[k]*history[slot[k]] + c_noise*z
  *   history[slot[0]] = d  (slot[0] >= 0);  latents = x';  lat_in = s_next*x' (lat_in non-null);  eps_out = eps (non-null)
- * history: ring of EMO_SCHED_RING planes of n floats; slot[0] must differ from every slot read.  z is emo_cfg_step's
- * counter-based N(0,1) of (seed, step, element), bit for bit.  scale_only != 0: lat_in = s_next*latents, nothing else is
- * read or written (the model input of the first step that runs). */
+ * guidance_scale <= 1 is the reference's "no classifier-free guidance" (:622 `do_classifier_free_guidance =
+ * guidance_scale > 1.0`): noise_pred is then [1][n] and eps = noise_pred / counter.
+ * history: ring of EMO_SCHED_RING planes of n floats; slot[0] must differ from every slot read.  z = counter-based N(0,1)
+ * keyed by (seed, step, element): every rank draws the same bits.  scale_only != 0: lat_in = s_next*latents, nothing else
+ * is read or written (the model input of the first step that runs). */
 #define EMO_SCHED_RING 4
 typedef struct {
   float guidance_scale;

@@ -79,7 +79,7 @@ class SchedulerRef:
 
     def coefficients(self, t):
         """Per-step scalars (c_x, c_eps, c_noise) such that x_prev = c_x*x + c_eps*eps + c_noise*z.
-        This is the form the fused HIP cfg_step kernel consumes."""
+        This is the form of the DDIM / DDPM step plans the fused HIP sched_step kernel consumes."""
         prev_t = t - self.T // self.n
         a_t = float(self.alphas_cumprod[t].double())
         if prev_t >= 0:
@@ -145,7 +145,7 @@ def _mix32(x):
 def counter_normal(seed: int, step: int, n: int) -> torch.Tensor:
     """Counter-based N(0,1): element i of step s draws two 32-bit hashes of (seed, s, i) and
     applies Box-Muller.  Identical on every rank without communication (SURVEY.md 8e
-    'Determinism').  The integer hash is bit-exact with emo_cfg_step's device code; the float
+    'Determinism').  The integer hash is bit-exact with emo_sched_step's device code; the float
     transform agrees to ~1e-6."""
     idx = np.arange(n, dtype=np.uint64)
     m = np.uint64(0xFFFFFFFF)

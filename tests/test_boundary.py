@@ -38,13 +38,18 @@ def test_library_exports_every_declared_symbol():
 
 def test_ctypes_struct_layout_matches_header():
     """Field order of the params structs must match the header (a stale .so once silently mis-read a field)."""
-    from emote_hack_amd._lib import AttentionParams, GemmParams
+    from emote_hack_amd._lib import AttentionParams, GemmParams, SchedStepParams
     src = open(os.path.join(ROOT, "include", "emo_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    for cname, struct in (("emo_gemm_params", GemmParams), ("emo_attention_params", AttentionParams)):
+    for cname, struct in (("emo_gemm_params", GemmParams), ("emo_attention_params", AttentionParams),
+                          ("emo_sched_step_params", SchedStepParams)):
         body = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\} " + cname, src, flags=re.S).group(1)
-        fields = re.findall(r"(?:const\s+)?(?:void|float|int64_t|uint32_t|int32_t|int)\s*\*?\s*([A-Za-z_0-9]+)\s*;", body)
-        assert fields == [f[0] for f in struct._fields_], (cname, fields)
+        fields = []   # (name, array length or None); one declaration may list several names (`float a, b;`)
+        for decl in re.findall(r"(?:const\s+)?(?:void|float|int64_t|uint32_t|int32_t|int)\b\s*\*?\s*([^;]+);", body):
+            for d in decl.split(","):
+                name, n = re.fullmatch(r"\s*([A-Za-z_0-9]+)\s*(?:\[\s*(\d+)\s*\])?\s*", d).groups()
+                fields.append((name, None if n is None else int(n)))
+        assert fields == [(f[0], getattr(f[1], "_length_", None)) for f in struct._fields_], (cname, fields)
 
 
 def test_product_never_imports_the_oracle():
@@ -261,7 +266,7 @@ def test_ddim_step_inverts_the_in_tree_next_step():
         x_t = a_t ** 0.5 * x0 + (1 - a_t) ** 0.5 * eps
         c_x, c_eps, c_n = sch.coefficients(t, 0.0)
         assert c_n == 0.0
-        x_prev = c_x * x_t + c_eps * eps                             # what emo_cfg_step applies (:817)
+        x_prev = c_x * x_t + c_eps * eps                             # what the DDIM step plan applies (:817)
         back, pred_x0 = next_step(eps, t, x_prev)
         torch.testing.assert_close(back, x_t, rtol=1e-9, atol=1e-9)
         torch.testing.assert_close(pred_x0, x0, rtol=1e-8, atol=1e-8)

@@ -98,17 +98,30 @@ def _patch_ops():
         if add_counter:
             counter[frames.long()] += 1
 
-    def cfg_step(noise_pred, counter, latents, *, C_, F, HW, guidance_scale, c_x, c_eps, c_noise, seed, step, eps_out=None):
-        avg = noise_pred / counter.view(1, 1, F, 1)
-        eps = avg[0] + guidance_scale * (avg[1] - avg[0]) if guidance_scale > 1.0 else avg[0]
-        x = c_x * latents.view(C_, F, HW) + c_eps * eps
+    def sched_step(noise_pred, counter, latents, history, lat_in, *, C_, F, HW, guidance_scale, a, b, c_x, c, slot, c_noise, s_next,
+                   seed, step, eps_out=None):   # include/emo_hip.h emo_sched_step
+        avg = noise_pred.view(-1, C_, F, HW) / counter.view(1, 1, F, 1)
+        eps = (avg[0] + guidance_scale * (avg[1] - avg[0]) if guidance_scale > 1.0 else avg[0]).reshape(-1)
+        x = latents.view(-1)
+        d = a * x + b * eps
+        out = c_x * x + c[0] * d
+        for k in range(1, 4):      # the ring is read before d_n is written into it
+            if slot[k] >= 0:
+                out = out + c[k] * history[slot[k]]
+        if slot[0] >= 0:
+            history[slot[0]] = d
         if c_noise != 0.0:
-            x = x + c_noise * counter_normal(seed, step, latents.numel()).view(C_, F, HW)
-        latents.view(C_, F, HW).copy_(x)
+            out = out + c_noise * counter_normal(seed, step, x.numel())
+        x.copy_(out)
+        if lat_in is not None:
+            lat_in.view(-1).copy_(s_next * out)
         if eps_out is not None:
-            eps_out.copy_(eps.reshape(-1))
+            eps_out.copy_(eps)
 
-    ops.convert, ops.accumulate_window, ops.cfg_step = convert, accumulate_window, cfg_step
+    def sched_scale(latents, lat_in, *, C_, F, HW, s):
+        lat_in.copy_(s * latents)
+
+    ops.convert, ops.accumulate_window, ops.sched_step, ops.sched_scale = convert, accumulate_window, sched_step, sched_scale
 
 
 def _models():

@@ -880,7 +880,9 @@ def test_temporal_attention(dtype, B, Fr, HW, heads, d):
 
 
 def test_cfg_step_and_accumulate():
+    """DDIM / DDPM steps: emo_sched_step with the product schedulers' step plans against the oracle's update."""
     o = ops()
+    from emote_hack_amd.scheduler import DDIMScheduler, DDPMScheduler
     from oracle.scheduler_ref import SchedulerRef, counter_normal
     C4, Ft, HW = 4, 6, 20
     npred = seeded_randn((2, C4, Ft, HW), 38)
@@ -894,9 +896,12 @@ def test_cfg_step_and_accumulate():
         eps = avg[0] + 7.5 * (avg[1] - avg[0])
         z = counter_normal(3, 7, lat.numel())
         ref = cx * lat + ce * eps.reshape(-1) + cn * z
+        mine = DDIMScheduler() if kind == "ddim" else DDPMScheduler()   # (their own offsets, 1 and 0: t is on the table)
+        mine.set_timesteps(50)
+        p = mine.step_plan(mine.timesteps.index(t))
         l_dev, e_dev = lat.clone().to(DEV), torch.empty(lat.numel(), device=DEV)
-        o.cfg_step(npred.to(DEV), counter.to(DEV), l_dev, C_=C4, F=Ft, HW=HW, guidance_scale=7.5, c_x=cx, c_eps=ce, c_noise=cn,
-                   seed=3, step=7, eps_out=e_dev)
+        o.sched_step(npred.to(DEV), counter.to(DEV), l_dev, None, None, C_=C4, F=Ft, HW=HW, guidance_scale=7.5, a=p.a, b=p.b,
+                     c_x=p.c_x, c=p.c, slot=(-1, -1, -1, -1), c_noise=p.c_noise, s_next=p.s_next, seed=3, step=7, eps_out=e_dev)
         torch.testing.assert_close(e_dev.cpu(), eps.reshape(-1), rtol=1e-5, atol=1e-5)
         torch.testing.assert_close(l_dev.cpu(), ref, rtol=1e-4, atol=1e-4)
     # window accumulate

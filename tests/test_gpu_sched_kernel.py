@@ -1,6 +1,8 @@
-"""emo_sched_step (the fused CFG + sigma-space sampler step) against a float64 torch evaluation of its linear form, and the f32
-timestep embedding against the int64 entry and the oracle."""
+"""emo_sched_step (the fused CFG + scheduler step) against a float64 torch evaluation of its linear form and, for DDIM / DDPM, against
+the bits of the kernel it replaced; the f32 timestep embedding against the int64 entry and the oracle."""
 from __future__ import annotations
+
+import os
 
 import pytest
 import torch
@@ -83,20 +85,38 @@ def test_sched_scale_only():
 
 
 @pytest.mark.parametrize("C,F,HW", [(4, 3, 64), (3, 3, 5)])
-def test_noise_is_cfg_step_noise_bit_for_bit(C, F, HW):
-    """c_x = 1, c = 0, c_noise != 0 against emo_cfg_step with c_eps = 0: the same z of (seed, step, element)."""
+def test_ddim_ddpm_plans_give_the_retired_cfg_step_bits(C, F, HW):
+    """DDIM (eta 0 and 0.5) and DDPM (t > 0 and t = 0) at guidance 7.5 and 1.0, through emo_sched_step with the plans of
+    DDIMScheduler / DDPMScheduler.step_plan: latents and eps_out equal, bit for bit, what emo_cfg_step (cfg_step_kernel, the
+    DDIM / DDPM step before every scheduler ran on emo_sched_step) returned for the same inputs at commit cae0c69 on an MI355X
+    (tests/golden/sched_ddim_ddpm.safetensors).  (4, 3, 64) takes the float4 path, (3, 3, 5) the per-element one."""
+    import json
+    from safetensors import safe_open
     from emote_hack_amd import ops
-    n = C * F * HW
-    np_ = seeded_randn((2, n), 5).to(DEV)
-    counter = torch.ones(F, device=DEV)
-    lat = seeded_randn((n,), 6).to(DEV)
-    a_lat, b_lat = lat.clone(), lat.clone()
-    ops.sched_step(np_, counter, a_lat, None, None, C_=C, F=F, HW=HW, guidance_scale=7.5, a=0.0, b=1.0, c_x=1.0, c=(0, 0, 0, 0),
-                   slot=(-1, -1, -1, -1), c_noise=0.83, s_next=1.0, seed=1234, step=17)
-    ops.cfg_step(np_, counter, b_lat, C_=C, F=F, HW=HW, guidance_scale=7.5, c_x=1.0, c_eps=0.0, c_noise=0.83, seed=1234, step=17)
-    torch.cuda.synchronize()
-    assert torch.equal(a_lat, b_lat)
-    assert not torch.equal(a_lat, lat)
+    from emote_hack_amd.scheduler import DDIMScheduler, DDPMScheduler
+    from tests import cases
+    key, n = f"{C}x{F}x{HW}", C * F * HW
+    with safe_open(os.path.join(cases.GOLDEN_DIR, "sched_ddim_ddpm.safetensors"), "pt") as f:
+        meta = f.metadata()
+        g = {k: f.get_tensor(k) for k in f.keys() if k.startswith(key + "/")}
+    np_, counter = g[f"{key}/noise_pred"].to(DEV), g[f"{key}/counter"].to(DEV)
+    for name, case in json.loads(meta["cases"]).items():
+        sch = DDIMScheduler(eta=case["eta"]) if name.startswith("ddim") else DDPMScheduler()
+        sch.set_timesteps(case["steps"])
+        si = case["si"]
+        assert sch.timesteps[si] == case["t"] and sch.history == 0
+        p = sch.step_plan(si)
+        assert (p.c_x, p.c[0], p.c_noise) == (case["c_x"], case["c_eps"], case["c_noise"])   # the recorded coefficients
+        for gs in json.loads(meta["guidance_scales"]):
+            lat = g[f"{key}/latents"].to(DEV, copy=True)
+            lat_in = torch.full((n,), float("nan"), device=DEV)
+            eps = torch.full((n,), float("nan"), device=DEV)
+            ops.sched_step(np_, counter, lat, None, lat_in, C_=C, F=F, HW=HW, guidance_scale=gs, a=p.a, b=p.b, c_x=p.c_x, c=p.c,
+                           slot=(-1, -1, -1, -1), c_noise=p.c_noise, s_next=p.s_next, seed=int(meta["seed"]), step=si, eps_out=eps)
+            torch.cuda.synchronize()
+            assert torch.equal(lat.cpu(), g[f"{key}/gs{gs}/{name}/latents"]), (name, gs)
+            assert torch.equal(eps.cpu(), g[f"{key}/gs{gs}/eps"]), (name, gs)
+            assert torch.equal(lat_in, lat), (name, gs)          # s_next = 1: the next model input is x' itself
 
 
 def test_sched_step_refuses_bad_slots():

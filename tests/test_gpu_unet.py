@@ -178,7 +178,7 @@ def test_denoise_loop_context_batch_size_and_no_cfg_vs_golden(prefix, cbs, gs, g
         cbs > 1: `torch.cat([text] * cbs)` (:631) puts window 0's cond row under the UNCOND text and the bank written under it, so
         the ReferenceNet runs under both texts and the UNet calls are split per bank variant;
     ddim_nocfg - guidance_scale 1.0 (`do_classifier_free_guidance = guidance_scale > 1.0`, :622): cond units only, every row
-        reads the bank, eps = noise_pred / counter (emo_cfg_step with guidance_scale <= 1)."""
+        reads the bank, eps = noise_pred / counter (emo_sched_step with guidance_scale <= 1)."""
     from emote_hack_amd import DDIMScheduler
     from emote_hack_amd.appearance_encoder import AppearanceEncoderModel
     from emote_hack_amd.pipeline import EMOAnimationPipeline

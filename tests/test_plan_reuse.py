@@ -62,7 +62,7 @@ def test_bind_inputs_refuses_what_the_plan_cannot_hold():
 
 
 def test_cfg_decision_is_made_on_the_f32_value_the_kernel_sees():
-    """emo_cfg_step takes guidance_scale as f32: a scale in (1, 1 + 2^-24] is 1.0f there - the host must not plan two planes."""
+    """emo_sched_step takes guidance_scale as f32: a scale in (1, 1 + 2^-24] is 1.0f there - the host must not plan two planes."""
     from emote_hack_amd.pipeline import EMOAnimationPipeline
     assert EMOAnimationPipeline._do_cfg(7.5) and EMOAnimationPipeline._do_cfg(1.0 + 2.0 ** -20)
     assert not EMOAnimationPipeline._do_cfg(1.0) and not EMOAnimationPipeline._do_cfg(1.0 + 2.0 ** -30) and not EMOAnimationPipeline._do_cfg(0.0)

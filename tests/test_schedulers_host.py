@@ -255,5 +255,12 @@ def test_unserved_scheduler_is_refused():
 
     class PNDMScheduler:
         config = type("C", (), {})()
-    with pytest.raises(TypeError, match="PNDMScheduler is not served"):
-        EMOAnimationPipeline(unet=type("U", (), {"device": "cpu"})(), scheduler=PNDMScheduler())
+
+    class CoefficientsOnlyScheduler:   # the DDIM / DDPM `coefficients(t, eta)` without the step-plan protocol
+        config = type("C", (), {})()
+
+        def coefficients(self, t, eta=None):
+            return 1.0, 0.0, 0.0
+    for sch in (PNDMScheduler(), CoefficientsOnlyScheduler()):
+        with pytest.raises(TypeError, match=f"{type(sch).__name__} is not served"):
+            EMOAnimationPipeline(unet=type("U", (), {"device": "cpu"})(), scheduler=sch)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Idle-gap analysis of a rocprofv3 --kernel-trace database: for the last loop iterations (delimited by the
-cfg_step kernel) report wall time, the union of kernel-busy intervals, the number of dispatches, the largest gaps between
+sched_step kernel) report wall time, the union of kernel-busy intervals, the number of dispatches, the largest gaps between
 consecutive kernels and the time spent in kernels that are NOT this library's (torch index / copy plumbing, rocBLAS)."""
 import re
 import sqlite3
@@ -9,7 +9,7 @@ import sys
 FOREIGN = re.compile(r"at::|c10::|rocblas|Cijk_|hipblas|nccl|rccl|thrust|cub::")   # everything else is a libemo_hip.so kernel
 db = sqlite3.connect(sys.argv[1])
 rows = db.execute("select name, start, end from kernels order by start").fetchall()
-marks = [i for i, r in enumerate(rows) if "cfg_step_kernel" in r[0]]
+marks = [i for i, r in enumerate(rows) if "sched_step_kernel" in r[0]]
 if len(marks) < 3:
     raise SystemExit("need >= 3 steps in the trace")
 for a, b in zip(marks[-3:-1], marks[-2:]):
