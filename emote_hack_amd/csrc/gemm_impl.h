@@ -569,7 +569,11 @@ __global__ __launch_bounds__(64 * WVM * WVN, (GemmTile<WTM, WTN, WVM, WVN, NS>::
       const T* src = zero;
       if (a_ok[i] && k0 < p.K && iy >= 0 && iy < Hin && ix >= 0 && ix < Win) {
         if (p.upsample2x) { iy >>= 1; ix >>= 1; }
-        else if (p.up_h) { iy = iy * p.H / p.up_h; ix = ix * p.W_ / p.up_w; }   // nearest to an explicit size (rare path)
+        else if (p.up_h) {   // nearest to an explicit size (rare path): torch's index - f32 scale in / out, floorf, clamp to in - 1
+          // (the integer dst * H / up_h differs from it where the f32 product rounds below an integer: H = 14 -> 46 at dst 23 reads 6, not 7)
+          iy = min((int)floorf((float)iy * ((float)p.H / (float)p.up_h)), p.H - 1);
+          ix = min((int)floorf((float)ix * ((float)p.W_ / (float)p.up_w)), p.W_ - 1);
+        }
         src = A + (((int64_t)a_cr[i].img * p.H + iy) * p.W_ + ix) * p.lda + ci;
       }
       EMO_GLDS16(src, sa + (i * NW + wave) * 1024);

@@ -170,7 +170,9 @@ typedef struct {
                       conv of the VAE encoder's Downsample2D (diffusers AutoencoderKL; Ho = (H + 1 - 3) / stride + 1) */
   int up_h; int up_w;  /* conv only: nearest upsampling to an EXPLICIT size folded into the loader (F.interpolate(size=...),
                       resnet.py:74-82 with `output_size`: inputs that are not a multiple of 2^num_upsamplers,
-                      unet_controlnet.py:357-365,456-459); source pixel = floor(dst * H / up_h).  0 = off (upsample2x covers x2) */
+                      unet_controlnet.py:357-365,456-459); source pixel = min((int)floorf(dst * ((float)H / up_h)), H - 1), torch's
+                      nearest index with its f32 scale (not the integer dst * H / up_h, which differs from it e.g. at H = 14,
+                      up_h = 46, dst = 23: 6 against 7).  0 = off (upsample2x covers x2) */
   int w_slab_rows; int64_t w_slab_stride;  /* dense only: per-instance weights - rows [i * w_slab_rows, (i+1) * w_slab_rows) of A
                       multiply the weight slab W + i * w_slab_stride (elements); w_slab_rows must be a multiple of 256 (a tile never
                       straddles two slabs).  `bias` is then per instance as well: f32 [M / w_slab_rows][N].  0 = one W (and one bias)

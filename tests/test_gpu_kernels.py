@@ -946,3 +946,133 @@ def test_gemm_split_k_matches_single_pass(dtype, sk):
     gotc, _, _ = o.conv3x3(dv(x.permute(0, 2, 3, 1).reshape(-1, 64).contiguous()), dv(wt.permute(0, 2, 3, 1).reshape(96, 576)).contiguous(),
                            None, 2, 8, 8, split_k=sk)
     close(gotc, refc, dtype)
+
+
+# ---- statistics under a common offset -----------------------------------------------------------------------------------------
+# Every GroupNorm flavour forms the variance as E[x^2] - mean^2 from f32 partial sums.  In the inputs below EVERY normalised unit (a
+# group of an instance, a row, a channel) has a mean of 16 times its own standard deviation, mean^2 = 256 var: each unit is
+# standardised in f64 first, then scaled and shifted (`_offset_rows` asserts the ratio on the quantised rows it returns).  A CPU
+# emulation of the f32 sum / sum-of-squares formulation, accumulated sequentially (the worst order) over groups of 640 .. 327,680
+# elements, stays below 1.3e-4 relative variance error there (it passes 1e-3 at 64x), so the tolerances of the tests above are a
+# condition the algorithm meets - against F.group_norm / F.layer_norm in f64.
+OFFSET_SPREADS = 16.0
+
+
+def _offset_rows(N, S, C, G, seed, dtype, spread=2.0):
+    """(N * S, C) rows, quantised to dtype, whose N x G normalised units (S rows x C / G channels each) all have standard deviation
+    `spread` and mean OFFSET_SPREADS * spread.  GroupNorm: (instances, rows per instance, C, groups); LayerNorm: (M, 1, C, 1);
+    per-channel norm over S rows: (1, S, C, C)."""
+    z = seeded_randn((N * S, C), seed).double().reshape(N, S, G, C // G)
+    z = (z - z.mean((1, 3), keepdim=True)) / z.std((1, 3), unbiased=False, keepdim=True)
+    x = q((z * spread + OFFSET_SPREADS * spread).float().reshape(N * S, C), dtype)
+    u = x.double().reshape(N, S, G, C // G)
+    ratio = u.mean((1, 3)) / u.std((1, 3), unbiased=False)
+    assert 0.98 * OFFSET_SPREADS < float(ratio.min()) and float(ratio.max()) < 1.02 * OFFSET_SPREADS, (float(ratio.min()), float(ratio.max()))   # (exact before q(); bf16 steps of 0.25 at 32 move a small unit by ~1 %)
+    return x
+
+
+def _gn_ref64(x, N, S, C, G, g, b, eps, silu):
+    ref = F.group_norm(x.double().reshape(N, S, C).permute(0, 2, 1), G, g.double(), b.double(), eps).permute(0, 2, 1).reshape(N * S, C)
+    return (F.silu(ref) if silu else ref).float()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("N,S,C,G,silu", [(2, 4 * 64, 320, 32, True), (6, 100, 64, 8, False), (1, 12 * 16 * 16, 2560, 32, True), (2, 64 * 64, 640, 32, False)])
+def test_groupnorm_two_launch_common_offset(dtype, N, S, C, G, silu):
+    """emo_groupnorm_stats + emo_groupnorm_apply (called directly: ops.group_norm would take the one-launch kernel where it fits) on
+    rows with a common offset of 16 spreads; groups of 800 .. 245,760 elements."""
+    from emote_hack_amd import _lib
+    o = ops()
+    lib = _lib.load()
+    dti = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[dtype]
+    x = _offset_rows(N, S, C, G, 601, dtype)
+    g, b = 1 + 0.1 * seeded_randn((C,), 602), 0.1 * seeded_randn((C,), 603)
+    ref = _gn_ref64(x, N, S, C, G, g, b, 1e-5, silu)
+    xd, gd, bd = x.to(DEV).to(dtype), g.to(DEV), b.to(DEV)
+    part = torch.empty(lib.emo_groupnorm_workspace_bytes(N, S, C, G) // 4, device=DEV, dtype=torch.float32)
+    two = torch.empty_like(xd)
+    st = torch.cuda.current_stream().cuda_stream
+    assert lib.emo_groupnorm_stats(xd.data_ptr(), C, part.data_ptr(), N, S, C, G, dti, st) == 0
+    assert lib.emo_groupnorm_apply(xd.data_ptr(), C, part.data_ptr(), gd.data_ptr(), bd.data_ptr(), two.data_ptr(), C, N, S, C, G, 1e-5,
+                                   int(silu), dti, st) == 0
+    close(two, ref, dtype)
+    close(o.group_norm(xd, gd, bd, N, G, 1e-5, silu), ref, dtype)       # whichever kernel the wrapper picks
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("N,S,C,G,silu", [(2, 12 * 8 * 8, 1280, 32, True), (24, 8 * 8, 1280, 32, True), (5, 37, 320, 32, True), (40, 1000, 64, 8, False)])
+def test_groupnorm_one_launch_common_offset(dtype, N, S, C, G, silu):
+    """emo_groupnorm (statistics and normalisation in one block) on rows with a common offset of 16 spreads."""
+    from emote_hack_amd import _lib
+    o = ops()
+    dti = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[dtype]
+    assert _lib.load().emo_groupnorm_one_launch_ok(N, S, C, G, dti) == 1
+    x = _offset_rows(N, S, C, G, 611, dtype)
+    g, b = 1 + 0.1 * seeded_randn((C,), 612), 0.1 * seeded_randn((C,), 613)
+    got = o.group_norm(x.to(DEV).to(dtype), g.to(DEV), b.to(DEV), N, G, 1e-5, silu)
+    close(got, _gn_ref64(x, N, S, C, G, g, b, 1e-5, silu), dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B,Fr,H,W,Cin,Cout", [(2, 3, 16, 32, 128, 320), (1, 2, 16, 16, 320, 128)])
+def test_conv3x3_groupnorm_inside_the_conv_common_offset(dtype, B, Fr, H, W, Cin, Cout):
+    """emo_groupnorm_coeffs + the normalisation inside the halo-reuse conv (gn_coef) on an input with a common offset of 16 spreads:
+    against F.group_norm (f64, joint over the Fr frames) -> silu -> conv2d, at the tolerance of the fused-conv test above."""
+    o = ops()
+    n, G = B * Fr, 32
+    x = _offset_rows(B, Fr * H * W, Cin, G, 621, dtype).reshape(n, H, W, Cin).permute(0, 3, 1, 2).contiguous()
+    g, b = 1 + 0.1 * seeded_randn((Cin,), 622), 0.1 * seeded_randn((Cin,), 623)
+    wt, bias = q(seeded_randn((Cout, Cin, 3, 3), 624) / math.sqrt(9 * Cin), dtype), 0.1 * seeded_randn((Cout,), 625)
+    xn = F.silu(F.group_norm(x.double().reshape(B, Fr, Cin, H, W).permute(0, 2, 1, 3, 4), G, g.double(), b.double(), 1e-5)).permute(0, 2, 1, 3, 4).reshape(n, Cin, H, W)
+    ref = F.conv2d(xn, wt.double(), bias.double(), padding=1).float().permute(0, 2, 3, 1).reshape(-1, Cout)
+    rows = x.permute(0, 2, 3, 1).reshape(-1, Cin).contiguous().to(DEV).to(dtype)
+    wp = wt.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).to(DEV).to(dtype).contiguous()
+    assert o.conv_gn_fusable(rows, wp, n, H, W)
+    coef = o.group_norm_coeffs(rows, g.to(DEV), b.to(DEV), B, G, 1e-5)
+    got, _, _ = o.conv3x3(rows, wp, bias.to(DEV), n, H, W, gn=(coef, Fr, True), split_k=1)
+    close(got, ref, dtype, scale=2.0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("N,S,C,G,Cout", [(6, 1024, 320, 32, 320), (3, 256, 64, 8, 96), (2, 4096, 640, 32, 640)])
+def test_groupnorm_folded_into_linear_common_offset(dtype, N, S, C, G, Cout):
+    """emo_groupnorm_fold_linear + emo_gemm(w_slab_rows) on rows with a common offset of 16 spreads: the mean term, 16 times the
+    normalised signal, rides in the per-instance bias and must cancel against the product of the raw rows with the ROUNDED folded
+    weights - against group_norm (f64) -> linear, at the tolerance of the fold test above."""
+    o = ops()
+    x = _offset_rows(N, S, C, G, 631, dtype)
+    g, b = 1 + 0.1 * seeded_randn((C,), 632), 0.1 * seeded_randn((C,), 633)
+    w, bias = q(seeded_randn((Cout, C), 634) / C ** 0.5, dtype), 0.1 * seeded_randn((Cout,), 635)
+    xn = F.group_norm(x.double().reshape(N, S, C).permute(0, 2, 1), G, g.double(), b.double(), 1e-6).permute(0, 2, 1).reshape(N * S, C)
+    ref = F.linear(xn, w.double(), bias.double()).float()
+    xd = x.to(DEV).to(dtype)
+    wn, rb = o.group_norm_fold_linear(xd, g.to(DEV), b.to(DEV), N, G, 1e-6, w.to(DEV).to(dtype), bias.to(DEV))
+    close(o.gemm(xd, wn, rb, w_slab_rows=S), ref, dtype, scale=2.0)
+
+
+@pytest.mark.parametrize("gelu", [False, True])
+@pytest.mark.parametrize("S,C", [(799, 96), (20000, 64)])
+def test_channelnorm_common_offset(S, C, gelu):
+    """emo_channelnorm (per-channel statistics over the S rows) with a common offset of 16 spreads, at the tolerance of its test in
+    tests/test_gpu_wav2vec2.py (f32 rtol 1e-3 / atol 1e-4), against nn.GroupNorm(C, C) in f64."""
+    o = ops()
+    x = _offset_rows(1, S, C, C, 641, torch.float32)
+    g, b = 1 + 0.1 * seeded_randn((C,), 642), 0.1 * seeded_randn((C,), 643)
+    ref = F.group_norm(x.double().t()[None], C, g.double(), b.double(), 1e-5)[0].t()
+    ref = (F.gelu(ref) if gelu else ref).float()
+    close(o.channel_norm(x.to(DEV), g.to(DEV), b.to(DEV), 1e-5, gelu=gelu), ref, torch.float32)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("M,C", [(100, 320), (77, 1280), (333, 64)])
+def test_layernorm_common_offset(dtype, M, C):
+    """emo_layernorm and emo_layernorm_stats on rows with a common offset of 16 spreads, against F.layer_norm in f64; the statistics at
+    the tolerance test_gemm_layernorm_fold holds them to."""
+    o = ops()
+    x = _offset_rows(M, 1, C, 1, 651, dtype)
+    g, b = 1 + 0.1 * seeded_randn((C,), 652), 0.1 * seeded_randn((C,), 653)
+    ref = F.layer_norm(x.double(), (C,), g.double(), b.double()).float()
+    xd = x.to(DEV).to(dtype)
+    close(o.layer_norm(xd, g.to(DEV), b.to(DEV)), ref, dtype)
+    mu, var = x.double().mean(1), x.double().var(1, unbiased=False)
+    torch.testing.assert_close(o.layer_norm_stats(xd, 1e-5).cpu(), torch.stack([mu, (var + 1e-5).rsqrt()], 1).float(), rtol=1e-4, atol=1e-5)

@@ -212,3 +212,25 @@ def test_pipeline_helper_methods_equal_the_reference_method_bodies():
     cache = {i: ([seeded_randn((1, 8, 4, 4), 600 + 10 * i + k) for k in range(3)], seeded_randn((1, 8, 2, 2), 700 + i)) for i in range(6)}
     down, mid = pipe.select_controlnet_res_samples(cache, [[0, 1], [4, 5]], True, 4, 2)
     assert all(torch.equal(d, g[f"select/down{k}"]) for k, d in enumerate(down)) and torch.equal(mid, g["select/mid"])
+
+
+def test_nearest_index_helper_is_torchs_nearest_resize():
+    """tests/test_gpu_conv_loader.py builds the reference of the explicit-size upsampling (emo_gemm_params.up_h / up_w) with
+    `nearest_index`: it must be F.interpolate(size=..., mode="nearest") itself - on an index ramp, so that the output IS the source
+    index - for every in < 130 and in <= out <= 4 in.  The integer dst * in / out, which the conv loader used to compute, is not: it
+    agrees for out = 2 in and 2 in - 1 (the sizes the UNet asks for) and differs at hundreds of other pairs, e.g. 14 -> 46 at dst 23."""
+    import torch.nn.functional as F
+    from tests.test_gpu_conv_loader import nearest_index
+    differs = 0
+    for n_in in range(1, 130):
+        ramp = torch.arange(n_in, dtype=torch.float32).reshape(1, 1, n_in, 1)
+        for n_out in range(n_in, 4 * n_in + 1):
+            want = F.interpolate(ramp, size=(n_out, 1), mode="nearest").reshape(-1).to(torch.int64)
+            got = nearest_index(n_in, n_out)
+            assert torch.equal(got, want), (n_in, n_out)
+            integer = torch.arange(n_out) * n_in // n_out
+            if n_out in (2 * n_in, 2 * n_in - 1):
+                assert torch.equal(integer, want), (n_in, n_out)
+            differs += int(not torch.equal(integer, want))
+    assert differs == 625
+    assert nearest_index(14, 46)[23] == 6 and nearest_index(26, 44)[22] == 12 and nearest_index(21, 69)[[23, 46]].tolist() == [6, 13]
