@@ -101,6 +101,7 @@ SIGNATURES = {
     "emo_gemm_suggest_split_k": (_i, [_i64, _i, _i, _i, _i, _i]),
     "emo_gemm_workspace_bytes": (C.c_size_t, [_i64, _i, _i]),
     "emo_attention": (_i, [C.POINTER(AttentionParams), _p]),
+    "emo_attention_plan": (_i, [C.POINTER(AttentionParams), C.POINTER(C.c_int)]),
     "emo_temporal_attention": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _f, _i, _p]),
     "emo_sched_step": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, C.POINTER(SchedStepParams), _p]),
     "emo_accumulate_window": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

@@ -648,26 +648,17 @@ struct AttLaunch {
   static_assert(NSR * STAGE_BYTES <= 160 * 1024, "attention stage does not fit LDS");
 };
 
-template <typename T, int DCH, int G, int QT, bool CAUSAL>
-static int launch_attention3(const emo_attention_params& p, hipStream_t st) {
-  using L = AttLaunch<T, DCH, G>;
-  auto kern = attention_kernel<T, DCH, G, L::NSR, QT, false, CAUSAL>;
-  auto kern_res = attention_kernel<T, DCH, G, L::NSR, QT, true, CAUSAL>;
-  constexpr int lds = L::NSR * L::STAGE_BYTES;
-  if (lds > 64 * 1024) {
-    static bool once = false;  // idempotent attribute; benign race
-    if (!once) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern_res, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      once = true;
-    }
-  }
-  // resident mode (kernel comment): every KV tile of every batch row fits the ring - the text / audio context
+// What emo_attention launches for a parameter block: (DCH class, loader rounds G, ring depth NSR, q tiles per block, causal) -
+// emo_attention_plan's answer.  The launch chain below carries an optional AttPlan*: with one it takes every decision of a launch
+// and returns in front of the first HIP call.
+struct AttPlan { int dch, g, nsr, q_rep, causal; };
+
+// resident mode (kernel comment): every KV tile of every batch row fits the ring - the text / audio context
+static int att_q_rep(const emo_attention_params& p, int nsr, int QT) {
   const int nqt_all = (p.Lq + BQ * QT - 1) / (BQ * QT);
   const int tiles_max = (p.Lk0 + TK - 1) / TK + (p.k1 ? (p.Lk1 + TK - 1) / TK : 0);
   int q_rep = 1;
-  if (tiles_max <= L::NSR) {
+  if (tiles_max <= nsr) {
 #ifdef EMO_ATT_QREP_ENV   // tools/bench/xattn_bench.py sweep builds only (build_variant.sh -DEMO_ATT_QREP_ENV): never in the product
     static const int forced_env = getenv("EMO_ATT_QREP") ? atoi(getenv("EMO_ATT_QREP")) : 0;
     const int forced = forced_env > nqt_all ? nqt_all : forced_env;
@@ -680,8 +671,32 @@ static int launch_attention3(const emo_attention_params& p, hipStream_t st) {
     for (q_rep = 4; q_rep > 1 && (q_rep > nqt_all || ((nqt_all + q_rep - 1) / q_rep) * chunks < 160); q_rep >>= 1) {}
     if (forced > 0) q_rep = forced;
   }
+  return q_rep;
+}
+
+template <typename T, int DCH, int G, int QT, bool CAUSAL>
+static int launch_attention3(const emo_attention_params& p, hipStream_t st, AttPlan* plan) {
+  using L = AttLaunch<T, DCH, G>;
+  auto kern = attention_kernel<T, DCH, G, L::NSR, QT, false, CAUSAL>;
+  auto kern_res = attention_kernel<T, DCH, G, L::NSR, QT, true, CAUSAL>;
+  constexpr int lds = L::NSR * L::STAGE_BYTES;
+  const int nqt_all = (p.Lq + BQ * QT - 1) / (BQ * QT);
+  const int q_rep = att_q_rep(p, L::NSR, QT);
   const int64_t nblk = (int64_t)((nqt_all + q_rep - 1) / q_rep) * p.heads * p.B;
   if (nblk >= (1ll << 31)) return emo_fail(EMO_ERR_BAD_SHAPE, "emo_attention: too many blocks");
+  if (plan) {
+    *plan = AttPlan{DCH, G, L::NSR, q_rep, CAUSAL ? 1 : 0};
+    return EMO_OK;
+  }
+  if (lds > 64 * 1024) {
+    static bool once = false;  // idempotent attribute; benign race
+    if (!once) {
+      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern_res, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
+      once = true;
+    }
+  }
   dim3 grid((unsigned)nblk);
   // order_mode 2: (b, head) chunks round-robin over the XCDs; 3: the same from the LAST batch row backwards - under CFG the cond
   // rows (second half of the batch) carry the bank segment and run twice as long as the uncond rows: started first, the short rows
@@ -696,18 +711,18 @@ static int launch_attention3(const emo_attention_params& p, hipStream_t st) {
 }
 
 template <typename T, int DCH, int G>
-static int launch_attention2(const emo_attention_params& p, hipStream_t st) {
+static int launch_attention2(const emo_attention_params& p, hipStream_t st, AttPlan* plan) {
   // QT = 2 (two 32-query tiles per wave: K / V^T fragments, requests and loop overhead shared by 64 query rows - ~136 instead of
   // ~170 instructions per query tile and KV tile) needs 256 registers at d = 40 (+ 20 bytes of scratch) = two waves per SIMD:
   // round 3 measured it 1.7x slower on the old instruction stream, round 4 on the lean one 1.5-3.5 % FASTER (1294 -> 1275 us,
   // 775 -> 748 us, profiles/r04m_attention_qt2.txt) - inside the run-to-run spread of a whole step, with a spill; not enabled.
-  if (p.causal) return launch_attention3<T, DCH, G, 1, true>(p, st);
-  return launch_attention3<T, DCH, G, 1, false>(p, st);
+  if (p.causal) return launch_attention3<T, DCH, G, 1, true>(p, st, plan);
+  return launch_attention3<T, DCH, G, 1, false>(p, st, plan);
 }
 
 // DPREV = chunk count of the next smaller head-dim class: this class serves dch in (DPREV, DCH]
 template <typename T, int DCH, int DPREV>
-static int launch_attention(const emo_attention_params& p, hipStream_t st) {
+static int launch_attention(const emo_attention_params& p, hipStream_t st, AttPlan* plan) {
   using Cfg = AttCfg<T, DCH>;
   // chunks the loader must cover for THIS head dim (K rows + d V^T rows), rounded up to whole 256-lane rounds
   const int g = (Cfg::K_CHUNKS + p.d * Cfg::VCHP + 255) / 256;
@@ -715,7 +730,7 @@ static int launch_attention(const emo_attention_params& p, hipStream_t st) {
   constexpr int GMAX = (Cfg::K_CHUNKS + Cfg::DPAD * Cfg::VCHP + 255) / 256;
 #define EMO_ATT_G(GV)                                                            \
   case GV:                                                                       \
-    if constexpr (GV >= GMIN && GV <= GMAX) return launch_attention2<T, DCH, GV>(p, st); \
+    if constexpr (GV >= GMIN && GV <= GMAX) return launch_attention2<T, DCH, GV>(p, st, plan); \
     break;
   switch (g) {
     EMO_ATT_G(1) EMO_ATT_G(2) EMO_ATT_G(3) EMO_ATT_G(4) EMO_ATT_G(5) EMO_ATT_G(6) EMO_ATT_G(7) EMO_ATT_G(8)
@@ -728,21 +743,22 @@ static int launch_attention(const emo_attention_params& p, hipStream_t st) {
 }
 
 template <typename T>
-static int dispatch_attention(const emo_attention_params& p, hipStream_t st) {
+static int dispatch_attention(const emo_attention_params& p, hipStream_t st, AttPlan* plan) {
   constexpr int V = TT<T>::VEC;
   const int dch = p.d / V;
-  if (dch <= 2) return launch_attention<T, 2, 0>(p, st);
-  if (dch <= 4) return launch_attention<T, 4, 2>(p, st);
-  if (dch <= 6) return launch_attention<T, 6, 4>(p, st);
-  if (dch <= 10) return launch_attention<T, 10, 6>(p, st);
-  if (dch <= 20) return launch_attention<T, 20, 10>(p, st);
+  if (dch <= 2) return launch_attention<T, 2, 0>(p, st, plan);
+  if (dch <= 4) return launch_attention<T, 4, 2>(p, st, plan);
+  if (dch <= 6) return launch_attention<T, 6, 4>(p, st, plan);
+  if (dch <= 10) return launch_attention<T, 10, 6>(p, st, plan);
+  if (dch <= 20) return launch_attention<T, 20, 10>(p, st, plan);
   if constexpr (sizeof(T) == 4) {
-    if (dch <= 40) return launch_attention<T, 40, 20>(p, st);
+    if (dch <= 40) return launch_attention<T, 40, 20>(p, st, plan);
   }
   return emo_fail(EMO_ERR_UNSUPPORTED, "emo_attention: head dim %d too large", p.d);
 }
 
-extern "C" int emo_attention(const emo_attention_params* pp, void* stream) {
+// argument checks + the launch chain; plan != nullptr: decide only (emo_attention_plan)
+static int attention_entry(const emo_attention_params* pp, void* stream, AttPlan* plan) {
   EMO_CHECK(pp, EMO_ERR_NULL, "emo_attention: null params");
   const emo_attention_params& p = *pp;
   EMO_CHECK(p.q && p.k0 && p.v0t && p.out, EMO_ERR_NULL, "emo_attention: null pointer");
@@ -773,6 +789,17 @@ extern "C" int emo_attention(const emo_attention_params* pp, void* stream) {
                 "emo_attention: a K / V^T slab of segment 1 exceeds 1 GB (Lk1 %d, ldk1 %lld, ldv1t %lld)", p.Lk1, (long long)p.ldk1, (long long)p.ldv1t);
   }
   hipStream_t st = as_stream(stream);
-  EMO_DISPATCH(p.dtype, "emo_attention", return dispatch_attention<T>(p, st));
+  EMO_DISPATCH(p.dtype, "emo_attention", return dispatch_attention<T>(p, st, plan));
+  return EMO_OK;
+}
+
+extern "C" int emo_attention(const emo_attention_params* pp, void* stream) { return attention_entry(pp, stream, nullptr); }
+
+extern "C" int emo_attention_plan(const emo_attention_params* pp, int plan[5]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_attention_plan: null plan");
+  AttPlan pl = {0, 0, 0, 0, 0};
+  const int rc = attention_entry(pp, nullptr, &pl);
+  if (rc != EMO_OK) return rc;
+  plan[0] = pl.dch; plan[1] = pl.g; plan[2] = pl.nsr; plan[3] = pl.q_rep; plan[4] = pl.causal;
   return EMO_OK;
 }

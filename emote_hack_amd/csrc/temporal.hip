@@ -333,13 +333,29 @@ extern "C" int emo_temporal_attention(const void* qkv, int64_t ldqkv, void* out,
     return EMO_OK;
   }
   // choose heads-per-block / pixels-per-block so the Q,K,V stage stays under ~48 KB
-  const int budget = 48 * 1024;
+  const int budget = 48 * 1024, lds_plain = 64 * 1024, lds_max = 160 * 1024;
+  auto need = [&](int h, int pp) { return (size_t)3 * F * ((size_t)pp * h * d * esz + 16) + (size_t)pp * h * F * F * 4; };   // stage + score matrix
   int hpb = heads;
-  while (hpb > 1 && (hpb % 2 == 0) && 3 * F * (hpb * d * esz + 16) + hpb * F * F * 4 > budget) hpb /= 2;   // stage + score matrix
+  while (hpb > 1 && (hpb % 2 == 0) && need(hpb, 1) > (size_t)budget) hpb /= 2;
+  // halving stops at an odd count (heads = 5; 6 -> 3): where that block cannot launch at all, step down to the largest divisor of
+  // heads that fits the budget, ending at 1.  A choice that launches is kept as it is.
+  if (hpb > 1 && need(hpb, 1) > (size_t)lds_plain) {
+    do { hpb--; } while (hpb > 1 && (heads % hpb != 0 || need(hpb, 1) > (size_t)budget));
+  }
   int P = 1;
-  while (P < 8 && P * 2 <= HW && 3 * F * (2 * P * hpb * d * esz + 16) + 2 * P * hpb * F * F * 4 <= budget) P *= 2;
-  const size_t lds = (size_t)3 * F * (P * hpb * d * esz + 16) + (size_t)P * hpb * F * F * 4;
-  EMO_CHECK(lds <= 64 * 1024, EMO_ERR_UNSUPPORTED, "emo_temporal_attention: LDS %zu", lds);
+  while (P < 8 && P * 2 <= HW && need(hpb, 2 * P) <= (size_t)budget) P *= 2;
+  const size_t lds = need(hpb, P);
+  EMO_CHECK(lds <= (size_t)lds_max, EMO_ERR_UNSUPPORTED, "emo_temporal_attention: LDS %zu", lds);
+  if (lds > (size_t)lds_plain) {   // one head of one pixel above 64 KB (f32, d = 160, F = 32: 67072 B): opt in to the CU's 160 KB
+    static bool once[3] = {false, false, false};   // per dtype (0..2: checked above); idempotent attribute, benign race
+    if (!once[dtype]) {
+      hipError_t e = hipSuccess;
+      EMO_DISPATCH(dtype, "emo_temporal_attention",
+                   e = hipFuncSetAttribute((const void*)temporal_attention_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+      if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_temporal_attention: hipFuncSetAttribute: %s", hipGetErrorString(e));
+      once[dtype] = true;
+    }
+  }
   EMO_CHECK(B <= 65535 && heads / hpb <= 65535, EMO_ERR_BAD_SHAPE, "emo_temporal_attention: grid limits");
   dim3 grid((HW + P - 1) / P, heads / hpb, B);
   const int JW = P * hpb * d / V < TA_THREADS ? P * hpb * d / V : TA_THREADS;

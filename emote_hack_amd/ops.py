@@ -396,15 +396,19 @@ def conv3x3(x: torch.Tensor, w: torch.Tensor, bias, n_img: int, H: int, W: int, 
 
 # ----------------------------------------------------------------------------- attention
 def attention(q, k0, v0t, Lk0, *, B, Lq, heads, d, scale, seg0_div=1, k1=None, v1t=None, Lk1=0, seg1_div=1,
-              seg1_first_batch=0, seg1_skip=0, seg1_row=None, causal=False) -> torch.Tensor:
+              seg1_first_batch=0, seg1_skip=0, seg1_row=None, causal=False, out=None) -> torch.Tensor:
     """q (B*Lq, >=heads*d) rows view; k0 rows view; v0t (Bk, heads*d, ld) V^T tensors.
     seg1_row: device int32 tensor holding the bank row every batch >= seg1_first_batch reads (see emo_hip.h).
-    causal: query row i sees keys j <= i only (one KV segment, Lq == Lk0 - emo_hip.h emo_attention_params.causal)."""
-    _need_cuda(q, k0, v0t)
+    causal: query row i sees keys j <= i only (one KV segment, Lq == Lk0 - emo_hip.h emo_attention_params.causal).
+    out: optional (B*Lq, >=heads*d) rows view to write into (its stride(0) is ldo); allocated when None."""
+    _need_cuda(q, k0, v0t, out)
     p = AttentionParams()
     pq, ldq = _rows(q)
     pk, ldk = _rows(k0)
-    out = torch.empty(B * Lq, heads * d, device=q.device, dtype=q.dtype)
+    if out is None:
+        out = torch.empty(B * Lq, heads * d, device=q.device, dtype=q.dtype)
+    assert out.dtype == q.dtype and out.shape[0] == B * Lq and out.shape[1] >= heads * d, (out.shape, out.dtype)
+    po, ldo = _rows(out)
     p.q, p.ldq = pq.value, ldq
     p.k0, p.ldk0, p.v0t, p.ldv0t, p.Lk0 = pk.value, ldk, v0t.data_ptr(), v0t.stride(1), Lk0
     p.seg0_div = seg0_div
@@ -417,7 +421,7 @@ def attention(q, k0, v0t, Lk0, *, B, Lq, heads, d, scale, seg0_div=1, k1=None, v
             p.seg1_row = seg1_row.data_ptr()
     else:
         p.seg1_div = 1
-    p.out, p.ldo = out.data_ptr(), out.stride(0)
+    p.out, p.ldo = po.value, ldo
     p.B, p.Lq, p.heads, p.d, p.scale, p.dtype = B, Lq, heads, d, float(scale), dt(q)
     p.causal = int(bool(causal))
     esz = q.element_size()
@@ -429,12 +433,35 @@ def attention(q, k0, v0t, Lk0, *, B, Lq, heads, d, scale, seg0_div=1, k1=None, v
     return out
 
 
-def temporal_attention(qkv: torch.Tensor, B, F, HW, heads, d, scale) -> torch.Tensor:
-    _need_cuda(qkv)
+def attention_plan(*, dtype, B, Lq, Lk0, heads, d, Lk1=0, causal=False):
+    """What ops.attention launches for this shape, asked of the library on the host (emo_hip.h emo_attention_plan; no GPU needed):
+    (head-dim class in 16-byte chunks, loader rounds, ring depth, q tiles per block - > 1 = the resident walk -, causal).
+    Lk1 > 0 = a second KV segment is present.  Contiguous operands; raises EmoHipError where emo_attention would refuse the shape."""
+    p = AttentionParams()
+    fake, Cc = 256, heads * d   # non-NULL, never dereferenced
+    ld0, ld1 = (Lk0 + 7) // 8 * 8, (Lk1 + 7) // 8 * 8
+    p.q, p.ldq, p.k0, p.ldk0, p.v0t, p.ldv0t, p.Lk0 = fake, Cc, fake, Cc, fake, ld0, Lk0
+    p.seg0_div = p.seg1_div = 1
+    if Lk1:
+        p.k1, p.ldk1, p.v1t, p.ldv1t, p.Lk1 = fake, Cc, fake, ld1, Lk1
+    p.out, p.ldo = fake, Cc
+    p.B, p.Lq, p.heads, p.d, p.scale, p.dtype = B, Lq, heads, d, 1.0, dt(dtype)
+    p.causal = int(bool(causal))
+    plan = (C.c_int * 5)()
+    check(_lib.load().emo_attention_plan(C.byref(p), plan), "emo_attention_plan")
+    return tuple(plan)
+
+
+def temporal_attention(qkv: torch.Tensor, B, F, HW, heads, d, scale, out=None) -> torch.Tensor:
+    """out: optional (B*F*HW, >=heads*d) rows view to write into (its stride(0) is ldo); allocated when None."""
+    _need_cuda(qkv, out)
     pq, ld = _rows(qkv)
-    out = torch.empty(B * F * HW, heads * d, device=qkv.device, dtype=qkv.dtype)
+    if out is None:
+        out = torch.empty(B * F * HW, heads * d, device=qkv.device, dtype=qkv.dtype)
+    assert out.dtype == qkv.dtype and out.shape[0] == B * F * HW and out.shape[1] >= heads * d, (out.shape, out.dtype)
+    po, ldo = _rows(out)
     _launch("temporal_attention", 4.0 * B * HW * heads * F * F * d, qkv.element_size() * 4.0 * B * F * HW * heads * d,
-            lambda: check(_lib.load().emo_temporal_attention(pq, ld, _ptr(out), out.stride(0), B, F, HW, heads, d, float(scale),
+            lambda: check(_lib.load().emo_temporal_attention(pq, ld, po, ldo, B, F, HW, heads, d, float(scale),
                                                              dt(qkv), _stream()), "emo_temporal_attention"),
             tag=f"B={B} F={F} HW={HW} h={heads} d={d}")
     return out

@@ -237,6 +237,10 @@ typedef struct {
                    (k1 and seg1_row NULL), else EMO_ERR_UNSUPPORTED.  0 (a zeroed struct): no mask, as before. */
 } emo_attention_params;
 int emo_attention(const emo_attention_params* p, void* stream);
+/* Host-only: what emo_attention would launch for p - plan = (head-dim class in 16-byte chunks, loader rounds per tile, KV ring depth,
+ * q tiles walked per block (> 1 = the resident-context variant), causal).  Runs emo_attention's argument checks and returns their
+ * status; launches nothing and touches no device memory (the pointers of p only need to be non-NULL where emo_attention wants them). */
+int emo_attention_plan(const emo_attention_params* p, int plan[5]);
 
 /* Temporal self-attention of the AnimateDiff motion module (motion_module.py:275-334): tokens
  * "(b f) d c -> (b d) f c"; qkv rows are [(b*F+f)*HW + pix][3*C] (q|k|v), output [(b*F+f)*HW+pix][C].

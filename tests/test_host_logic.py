@@ -234,3 +234,69 @@ def test_nearest_index_helper_is_torchs_nearest_resize():
             differs += int(not torch.equal(integer, want))
     assert differs == 625
     assert nearest_index(14, 46)[23] == 6 and nearest_index(26, 44)[22] == 12 and nearest_index(21, 69)[[23, 46]].tolist() == [6, 13]
+
+
+def test_attention_sweeps_reach_every_instantiation():
+    """emo_attention_plan (csrc/attention.hip: the launch chain run without a launch) against the shapes that
+    tests/test_gpu_attention_sweeps.py launches: the sweep must reach every (head-dim class, loader rounds, ring depth) the library
+    can pick for an admissible head dim - taken from the library, so a later change to the classes cannot silently shrink the
+    coverage -, its "resident" shapes must take the resident walk (q tiles per block > 1) and its "streaming" shapes must not."""
+    from tests import attention_sweep_cases as S
+    counts = {}
+    for dtype in S.DTYPES:
+        dims = S.head_dims(dtype)
+        # every instantiation an admissible head dim can reach (class, rounds and ring depth follow from d and the dtype alone:
+        # asked on a one-tile and on a many-tile shape, with and without a second segment, causal or not)
+        reachable = set()
+        for d in dims:
+            for kw in (dict(B=1, Lq=1, Lk0=1, heads=1), dict(B=3, Lq=1000, Lk0=1000, heads=5, Lk1=300),
+                       dict(B=2, Lq=64, Lk0=64, heads=2, causal=True)):
+                reachable.add(S.plan(dtype, d, **kw)[:3])
+        swept = set()
+        for d in dims:
+            per_d = set()
+            for kw in S.streaming_shapes(d):
+                pl = S.plan(dtype, d, **kw)
+                assert pl[3] == 1, (dtype, d, kw, pl)
+                assert pl[4] == int(bool(kw.get("causal"))), (dtype, d, kw, pl)
+                per_d.add(pl[:3])
+            for kw in S.resident_shapes(d):
+                pl = S.plan(dtype, d, **kw)
+                assert pl[3] == S.RESIDENT_LQ[kw["Lq"]] > 1, (dtype, d, kw, pl)
+                per_d.add(pl[:3])
+            assert len(per_d) == 1, (dtype, d, per_d)      # one head dim = one instantiation, whatever the shape
+            swept |= per_d
+        assert swept == reachable, (dtype, swept ^ reachable)
+        counts[dtype] = len(swept)
+        # the ring-schedule matrix runs two ring depths per dtype, the shallowest one the dtype has among them
+        ring = {S.plan(dt_, d, B=4, Lq=130, Lk0=64, heads=2)[2] for dt_, d in S.RING if dt_ == dtype}
+        assert len(ring) == 2 and min(ring) == min(pl[2] for pl in reachable), (dtype, ring)
+        # the causal resident walk exists for some head dim (the sweep launches it wherever the plan reports it)
+        c = S.CAUSAL_RESIDENT
+        assert any(S.plan(dtype, d, B=c["B"], Lq=c["L"], Lk0=c["L"], heads=c["heads"], causal=True)[3] > 1 for d in dims)
+    # more than a handful each (2-byte: 12, f32: 18 when this test was written - not pinned: the library is the authority)
+    assert all(n >= 6 for n in counts.values()), counts
+    ring_all = {S.plan(dt_, d, B=4, Lq=130, Lk0=64, heads=2)[2] for dt_, d in S.RING}
+    assert ring_all == {1, 2, 3}
+
+
+def test_attention_plan_runs_the_argument_checks():
+    """emo_attention_plan returns what emo_attention's argument checks return, and writes nothing on a refusal."""
+    import ctypes as C
+    from emote_hack_amd import ops
+    from emote_hack_amd._lib import AttentionParams, EmoHipError
+    with pytest.raises(EmoHipError):
+        ops.attention_plan(dtype=torch.bfloat16, B=2, Lq=64, Lk0=64, heads=2, d=44)        # d % 8
+    with pytest.raises(EmoHipError):
+        ops.attention_plan(dtype=torch.float32, B=2, Lq=64, Lk0=64, heads=2, d=164)         # above 160
+    with pytest.raises(EmoHipError):
+        ops.attention_plan(dtype=torch.float16, B=2, Lq=64, Lk0=65, heads=2, d=64, causal=True)   # causal needs Lq == Lk0
+    with pytest.raises(EmoHipError):
+        ops.attention_plan(dtype=torch.float16, B=2, Lq=64, Lk0=64, heads=2, d=64, Lk1=8, causal=True)
+    lib = _lib.load()
+    plan = (C.c_int * 5)(-7, -7, -7, -7, -7)
+    assert lib.emo_attention_plan(C.byref(AttentionParams()), plan) != 0      # null pointers
+    assert lib.emo_attention_plan(None, plan) != 0
+    assert list(plan) == [-7] * 5
+    assert ops.attention_plan(dtype=torch.bfloat16, B=24, Lq=4096, Lk0=77, heads=8, d=40)[3] == 4   # the text cross-attention of the 64x64 level
+    assert ops.attention_plan(dtype=torch.bfloat16, B=24, Lq=4096, Lk0=4096, heads=8, d=40, Lk1=4096) == (6, 3, 3, 1, 0)
