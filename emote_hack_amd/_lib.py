@@ -92,6 +92,9 @@ SIGNATURES = {
     "emo_groupnorm_coeffs": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _f, _i, _p]),
     "emo_groupnorm_one_launch_ok": (_i, [_i, _i64, _i, _i, _i]),
     "emo_groupnorm": (_i, [_p, _i, _p, _p, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
+    "emo_groupnorm_apply_mod": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
+    "emo_groupnorm_mod": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
+    "emo_groupnorm_coeffs_mod": (_i, [_p, _p, _p, _p, _i, _p, _i, _i64, _i, _i, _f, _i, _p]),
     "emo_groupnorm_fold_linear": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _f, _i, _p]),
     "emo_layernorm": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _f, _p, _i, _i, _i, _p]),
     "emo_layernorm_stats": (_i, [_p, _i, _p, _i64, _i, _f, _i, _p]),

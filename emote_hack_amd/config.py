@@ -70,14 +70,12 @@ def normalize_unet_config(kwargs: dict, *, strict: bool = True) -> FrozenConfig:
         raise ValueError(f"unknown mid_block_type : {cfg['mid_block_type']}")
     if cfg["dual_cross_attention"]:
         raise NotImplementedError("dual_cross_attention")  # unet_3d_blocks.py:232
-    if cfg["resnet_time_scale_shift"] != "default":
-        raise NotImplementedError("resnet_time_scale_shift != 'default' is outside the hot path")
+    if cfg["resnet_time_scale_shift"] not in ("default", "scale_shift"):  # resnet.py:149-154
+        raise ValueError(f"unknown time_embedding_norm : {cfg['resnet_time_scale_shift']} ")
     if cfg["class_embed_type"] not in (None, "timestep", "identity"):      # unet_controlnet.py:120-127: anything else leaves class_embedding None
         cfg["class_embed_type"] = None
     if cfg["unet_use_cross_frame_attention"]:
         raise NotImplementedError("SparseCausalAttention2D is undefined in the reference (attention.py:190)")
-    if cfg["unet_use_temporal_attention"]:
-        raise NotImplementedError("attn_temp path (off in configs/inference.yaml:3)")
     if cfg["use_motion_module"] and cfg["motion_module_type"] != "Vanilla":
         raise ValueError("motion_module_type must be 'Vanilla'")  # motion_module.py:47-50
     mm = dict(MOTION_DEFAULTS)

@@ -9,7 +9,21 @@
 //   pass 2  gn_apply_kernel : prologue: every block combines the <= 256 chunk partials of its instance in f64, in the same
 //                             fixed order -> (mean, rstd) in LDS (no third launch, no inter-block fence: an agent-scope
 //                             release on this part writes back the whole L2);  y = (x-mean)*rstd*gamma+beta, optional SiLU
+// Every apply form (two-launch apply, one-launch kernel, coefficient table) has a MODULATED instantiation (MOD) for the scale-shift
+// resnets (resnet.py:149-156,191-197): y = act(GN(x) * (1 + s) + t) with (s, t) = mod[n][c], mod[n][C + c] per (instance, channel).
+// (xh gamma + beta)(1 + s) + t = xh gamma' + beta' with gamma' = gamma (1 + s), beta' = beta (1 + s) + t: the modulation is folded into
+// the thread's copy of the affine right where that is loaded - before the statistics, so nothing more is held across them - and
+// the plain arithmetic runs on (gamma', beta'): the same registers, the same streaming loop, the same traffic plus N * 2C floats.
 #include "common.h"
+
+// The scale-shift modulation of a channel's GroupNorm affine.  ONE statement of its three roundings (1 + s, gamma m, fma(beta, m, t))
+// shared by every kernel that applies or tabulates it, so that the table of emo_groupnorm_coeffs_mod is bit-identical to the factors
+// emo_groupnorm_apply_mod / emo_groupnorm_mod use.
+__device__ __forceinline__ void gn_modulate(float& gamma, float& beta, float s, float t) {
+  const float m = 1.0f + s;
+  beta = fmaf(beta, m, t);
+  gamma = gamma * m;
+}
 
 static constexpr int GN_THREADS = 256;
 static constexpr int GN_MAXJ = 3;  // column vectors per thread: C <= 256*3*VEC
@@ -152,16 +166,18 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
 
 static constexpr int GN_MAXG = 128;   // groups held in the apply pass's LDS statistics table
 
-template <typename T>
+template <typename T, bool MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ partials,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               T* __restrict__ y, int ldy, int64_t S, int C, int G, int G_all,
-                                                              int nsplit_stats, int nsplit, double count, float eps, int silu) {
+                                                              int nsplit_stats, int nsplit, double count, float eps, int silu,
+                                                              const float* __restrict__ mod, int ldmod, int C_all) {
   constexpr int V = TT<T>::VEC;
   __shared__ float s_stats[GN_MAXG * 2];
   const int n = blockIdx.x / nsplit, sp = blockIdx.x % nsplit;
   x += (int64_t)blockIdx.y * C; y += (int64_t)blockIdx.y * C;
   gamma += (int64_t)blockIdx.y * C; beta += (int64_t)blockIdx.y * C;
+  if constexpr (MOD) mod += (int64_t)(blockIdx.x / nsplit) * ldmod + (int64_t)blockIdx.y * C;   // (scale | shift) row of this instance, this column part
   const int CV = C / V, cpg = C / G;
   const int64_t rows_per = (S + nsplit - 1) / nsplit;
   const int64_t s0 = sp * rows_per;
@@ -185,6 +201,11 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
     for (int e = 0; e < V; e += 4) {
       *(float4*)(gm + e) = *(const float4*)(gamma + cv * V + e);
       *(float4*)(bt + e) = *(const float4*)(beta + cv * V + e);
+      if constexpr (MOD) {
+        const float4 ms = *(const float4*)(mod + cv * V + e), mt = *(const float4*)(mod + C_all + cv * V + e);
+        gn_modulate(gm[e], bt[e], ms.x, mt.x); gn_modulate(gm[e + 1], bt[e + 1], ms.y, mt.y);
+        gn_modulate(gm[e + 2], bt[e + 2], ms.z, mt.z); gn_modulate(gm[e + 3], bt[e + 3], ms.w, mt.w);
+      }
     }
   }
   if (have) {
@@ -261,7 +282,9 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
       for (int e = 0; e < V; e++) {
         int c = cv * V + e, g = c / cpg;
         float mean = s_stats[2 * g], rstd = s_stats[2 * g + 1];
-        a[e] = rstd * gamma[c]; b[e] = fmaf(-mean, a[e], beta[c]);
+        float gc = gamma[c], bc = beta[c];
+        if constexpr (MOD) gn_modulate(gc, bc, mod[c], mod[C_all + c]);
+        a[e] = rstd * gc; b[e] = fmaf(-mean, a[e], bc);
       }
       for (int64_t s = s0; s < s1; s++) {
         float f[V];
@@ -298,31 +321,60 @@ extern "C" int emo_groupnorm_stats(const void* x, int ldx, void* partials, int N
   return EMO_OK;
 }
 
-extern "C" int emo_groupnorm_apply(const void* x, int ldx, const void* partials, const float* gamma, const float* beta, void* y,
-                                   int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
-  EMO_CHECK(x && partials && gamma && beta && y, EMO_ERR_NULL, "emo_groupnorm_apply: null pointer");
-  int rc = gn_check("emo_groupnorm_apply", N, S, C, G, ldx, dtype);
+// the modulation operand of the *_mod entries: f32 rows [N][(scale | shift)] = C + C columns, row stride ldmod, 16-byte aligned vectors
+static int gn_mod_check(const char* who, const float* mod, int ldmod, int C) {
+  EMO_CHECK(mod, EMO_ERR_NULL, "%s: null mod", who);
+  EMO_CHECK(C % 4 == 0 && ldmod % 4 == 0 && ldmod >= 2 * C && ((uintptr_t)mod % 16) == 0, EMO_ERR_BAD_SHAPE,
+            "%s: mod must be 16-byte aligned [N][2 * C] rows (C=%d ldmod=%d)", who, C, ldmod);
+  return EMO_OK;
+}
+
+static int gn_apply_launch(const char* who, const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
+                           const float* mod, int ldmod, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype,
+                           void* stream) {
+  EMO_CHECK(x && partials && gamma && beta && y, EMO_ERR_NULL, "%s: null pointer", who);
+  int rc = gn_check(who, N, S, C, G, ldx, dtype);
   if (rc) return rc;
-  rc = gn_check("emo_groupnorm_apply", N, S, C, G, ldy, dtype);
+  rc = gn_check(who, N, S, C, G, ldy, dtype);
   if (rc) return rc;
-  EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "emo_groupnorm_apply: gamma/beta alignment");
+  EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "%s: gamma/beta alignment", who);
   const GnGeom gg = gn_geom(N, S, C, G, emo_dtype_vec(dtype));
   const double count = (double)S * (C / G);
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * gg.nsplit_apply), (unsigned)gg.NC);
-  EMO_DISPATCH(dtype, "emo_groupnorm_apply",
-               (gn_apply_kernel<T><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp, G,
-                                                                gg.nsplit_stats, gg.nsplit_apply, count, eps, silu)));
+  if (mod)
+    EMO_DISPATCH(dtype, who,
+                 (gn_apply_kernel<T, true><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
+                                                                        G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, mod, ldmod, C)));
+  else
+    EMO_DISPATCH(dtype, who,
+                 (gn_apply_kernel<T, false><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
+                                                                         G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, nullptr, 0, C)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
+}
+
+extern "C" int emo_groupnorm_apply(const void* x, int ldx, const void* partials, const float* gamma, const float* beta, void* y,
+                                   int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
+  return gn_apply_launch("emo_groupnorm_apply", x, ldx, partials, gamma, beta, nullptr, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_apply_mod(const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
+                                       const float* mod, int ldmod, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu,
+                                       int dtype, void* stream) {
+  int rc = gn_mod_check("emo_groupnorm_apply_mod", mod, ldmod, C);
+  if (rc) return rc;
+  return gn_apply_launch("emo_groupnorm_apply_mod", x, ldx, partials, gamma, beta, mod, ldmod, y, ldy, N, S, C, G, eps, silu, dtype, stream);
 }
 
 // The coefficient half of the apply pass for consumers that normalise on the fly (the halo conv, emo_gemm_params.gn_coef): one
 // block per instance runs the SAME statistics prologue as gn_apply_kernel - per column part, TPG lanes per group, strided f64
 // sums + shuffle tree - and writes scale = rstd * gamma, shift = beta - mean * scale, channel pairs interleaved (s, s, b, b).
+template <bool MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_coeffs_kernel(const float* __restrict__ partials, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ coef,
-                                                               int C, int G_all, int NC, int nsplit_stats, double count, float eps) {
+                                                               int C, int G_all, int NC, int nsplit_stats, double count, float eps,
+                                                               const float* __restrict__ mod, int ldmod) {
   __shared__ float s_stats[GN_MAXG * 2];
   const int n = blockIdx.x, tid = threadIdx.x;
   const int G = G_all / NC;
@@ -353,24 +405,42 @@ __global__ __launch_bounds__(GN_THREADS) void gn_coeffs_kernel(const float* __re
   for (int c = tid; c < C; c += GN_THREADS) {
     const int g = c / cpg;
     const float mean = s_stats[2 * g], rstd = s_stats[2 * g + 1];
-    const float a = rstd * gamma[c];
+    float gc = gamma[c], bc = beta[c];
+    if constexpr (MOD) gn_modulate(gc, bc, mod[(int64_t)n * ldmod + c], mod[(int64_t)n * ldmod + C + c]);
+    const float a = rstd * gc;
     float* dst = coef + (int64_t)n * 2 * C + (c >> 1) * 4 + (c & 1);
     dst[0] = a;
-    dst[2] = fmaf(-mean, a, beta[c]);   // (the very expression of the apply kernels: one fma, whatever the compiler would contract)
+    dst[2] = fmaf(-mean, a, bc);   // (the very expression of the apply kernels: one fma, whatever the compiler would contract)
   }
+}
+
+static int gn_coeffs_launch(const char* who, const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
+                            float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
+  EMO_CHECK(partials && gamma && beta && coef, EMO_ERR_NULL, "%s: null pointer", who);
+  int rc = gn_check(who, N, S, C, G, C, dtype);
+  if (rc) return rc;
+  const GnGeom gg = gn_geom(N, S, C, G, emo_dtype_vec(dtype));
+  const double count = (double)S * (C / G);
+  if (mod)
+    gn_coeffs_kernel<true><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
+                                                                              gg.nsplit_stats, count, eps, mod, ldmod);
+  else
+    gn_coeffs_kernel<false><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
+                                                                               gg.nsplit_stats, count, eps, nullptr, 0);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
 }
 
 extern "C" int emo_groupnorm_coeffs(const void* partials, const float* gamma, const float* beta, float* coef, int N,
                                     int64_t S, int C, int G, float eps, int dtype, void* stream) {
-  EMO_CHECK(partials && gamma && beta && coef, EMO_ERR_NULL, "emo_groupnorm_coeffs: null pointer");
-  int rc = gn_check("emo_groupnorm_coeffs", N, S, C, G, C, dtype);
+  return gn_coeffs_launch("emo_groupnorm_coeffs", partials, gamma, beta, nullptr, 0, coef, N, S, C, G, eps, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_coeffs_mod(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
+                                        float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
+  int rc = gn_mod_check("emo_groupnorm_coeffs_mod", mod, ldmod, C);
   if (rc) return rc;
-  const GnGeom gg = gn_geom(N, S, C, G, emo_dtype_vec(dtype));
-  const double count = (double)S * (C / G);
-  gn_coeffs_kernel<<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
-                                                                      gg.nsplit_stats, count, eps);
-  EMO_LAUNCH_CHECK();
-  return EMO_OK;
+  return gn_coeffs_launch("emo_groupnorm_coeffs_mod", partials, gamma, beta, mod, ldmod, coef, N, S, C, G, eps, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------ GroupNorm in one launch
@@ -409,10 +479,11 @@ static inline Gn1Geom gn1_geom(int N, int64_t S, int C, int G, int V) {
   return g;
 }
 
-template <typename T, int R>
+template <typename T, int R, bool MOD>
 __global__ __launch_bounds__(GN1_MAXT) void gn_one_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, T* __restrict__ y, int ldy, int S, int Wc,
-                                                          int GPB, int slabs, double count, float eps, int silu) {
+                                                          int GPB, int slabs, double count, float eps, int silu,
+                                                          const float* __restrict__ mod, int ldmod, int C_all) {
   constexpr int V = TT<T>::VEC;
   extern __shared__ float lds[];   // [RP][Wc][2]
   __shared__ float s_stats[GN1_MAXGPB * 2];
@@ -436,6 +507,11 @@ __global__ __launch_bounds__(GN1_MAXT) void gn_one_kernel(const T* __restrict__ 
     for (int e = 0; e < V; e += 4) {
       *(float4*)(gm + e) = *(const float4*)(gamma + c0 + e);
       *(float4*)(bt + e) = *(const float4*)(beta + c0 + e);
+      if constexpr (MOD) {
+        const float4 ms = *(const float4*)(mod + (int64_t)n * ldmod + c0 + e), mt = *(const float4*)(mod + (int64_t)n * ldmod + C_all + c0 + e);
+        gn_modulate(gm[e], bt[e], ms.x, mt.x); gn_modulate(gm[e + 1], bt[e + 1], ms.y, mt.y);
+        gn_modulate(gm[e + 2], bt[e + 2], ms.z, mt.z); gn_modulate(gm[e + 3], bt[e + 3], ms.w, mt.w);
+      }
     }
     float sum[V], sq[V];
 #pragma unroll
@@ -509,34 +585,53 @@ extern "C" int emo_groupnorm_one_launch_ok(int N, int64_t S, int C, int G, int d
   return gn1_geom(N, S, C, G, V).ok;
 }
 
-extern "C" int emo_groupnorm(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int N, int64_t S, int C,
-                             int G, float eps, int silu, int dtype, void* stream) {
-  EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "emo_groupnorm: null pointer");
-  int rc = gn_check("emo_groupnorm", N, S, C, G, ldx, dtype);
+static int gn_one_launch(const char* who, const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y,
+                         int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
+  EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "%s: null pointer", who);
+  int rc = gn_check(who, N, S, C, G, ldx, dtype);
   if (rc) return rc;
-  rc = gn_check("emo_groupnorm", N, S, C, G, ldy, dtype);
+  rc = gn_check(who, N, S, C, G, ldy, dtype);
   if (rc) return rc;
-  EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "emo_groupnorm: gamma/beta alignment");
+  EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "%s: gamma/beta alignment", who);
   const int V = emo_dtype_vec(dtype);
   const Gn1Geom gg = gn1_geom(N, S, C, G, V);
-  EMO_CHECK(gg.ok, EMO_ERR_UNSUPPORTED, "emo_groupnorm: N=%d S=%lld C=%d G=%d does not fit one block per (instance, group slab); "
-            "use emo_groupnorm_stats + emo_groupnorm_apply", N, (long long)S, C, G);
+  EMO_CHECK(gg.ok, EMO_ERR_UNSUPPORTED, "%s: N=%d S=%lld C=%d G=%d does not fit one block per (instance, group slab); "
+            "use emo_groupnorm_stats + emo_groupnorm_apply", who, N, (long long)S, C, G);
   const int RP = gg.NT / (gg.Wc / V);
   const size_t lds = (size_t)RP * gg.Wc * 2 * sizeof(float);
   const int slabs = G / gg.GPB;
   const double count = (double)S * (C / G);
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * slabs));
-#define GN1_LAUNCH(RR) \
-  EMO_DISPATCH(dtype, "emo_groupnorm", (gn_one_kernel<T, RR><<<grid, gg.NT, lds, st>>>((const T*)x, ldx, gamma, beta, (T*)y, ldy, (int)S, \
-                                                                                       gg.Wc, gg.GPB, slabs, count, eps, silu)))
-  if (gg.R == 2) { GN1_LAUNCH(2); }
-  else if (gg.R == 4) { GN1_LAUNCH(4); }
-  else if (gg.R == 8) { GN1_LAUNCH(8); }
-  else { GN1_LAUNCH(16); }
+#define GN1_LAUNCH(RR, MM) \
+  EMO_DISPATCH(dtype, who, (gn_one_kernel<T, RR, MM><<<grid, gg.NT, lds, st>>>((const T*)x, ldx, gamma, beta, (T*)y, ldy, (int)S, gg.Wc, gg.GPB, \
+                                                                               slabs, count, eps, silu, mod, ldmod, C)))
+  if (mod) {
+    if (gg.R == 2) { GN1_LAUNCH(2, true); }
+    else if (gg.R == 4) { GN1_LAUNCH(4, true); }
+    else if (gg.R == 8) { GN1_LAUNCH(8, true); }
+    else { GN1_LAUNCH(16, true); }
+  } else {
+    if (gg.R == 2) { GN1_LAUNCH(2, false); }
+    else if (gg.R == 4) { GN1_LAUNCH(4, false); }
+    else if (gg.R == 8) { GN1_LAUNCH(8, false); }
+    else { GN1_LAUNCH(16, false); }
+  }
 #undef GN1_LAUNCH
   EMO_LAUNCH_CHECK();
   return EMO_OK;
+}
+
+extern "C" int emo_groupnorm(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int N, int64_t S, int C,
+                             int G, float eps, int silu, int dtype, void* stream) {
+  return gn_one_launch("emo_groupnorm", x, ldx, gamma, beta, nullptr, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_mod(const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y, int ldy,
+                                 int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
+  int rc = gn_mod_check("emo_groupnorm_mod", mod, ldmod, C);
+  if (rc) return rc;
+  return gn_one_launch("emo_groupnorm_mod", x, ldx, gamma, beta, mod, ldmod, y, ldy, N, S, C, G, eps, silu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------ GroupNorm folded into a Linear

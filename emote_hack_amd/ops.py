@@ -171,16 +171,40 @@ def timestep_embedding(timesteps: torch.Tensor, freqs: torch.Tensor, dim: int, f
 GN_ONE_LAUNCH = True   # A/B hook (bench.py --gn-two-launch): False keeps every GroupNorm on the stats + apply pair
 
 
-def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, silu_: bool, out=None) -> torch.Tensor:
+def _mod_rows(mod, n_inst, Cc):
+    """(ptr, ld) of a scale-shift modulation operand: f32 (n_inst, 2C) = (scale | shift), possibly a column view of a wider buffer"""
+    assert mod.dtype == torch.float32 and tuple(mod.shape) == (n_inst, 2 * Cc) and mod.stride(1) == 1, (mod.shape, mod.dtype, mod.stride())
+    return _ptr(mod), mod.stride(0)
+
+
+def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, silu_: bool, out=None, mod=None) -> torch.Tensor:
     """GroupNorm over NHWC rows; x (n_inst*S, C).  n_inst=B -> joint 5-D statistics (resnet.py:180),
-    n_inst=B*F -> per frame (attention.py:124)."""
-    _need_cuda(x)
+    n_inst=B*F -> per frame (attention.py:124).
+    mod = f32 (n_inst, 2C) rows (scale | shift): the scale-shift form y = act(GN(x) * (1 + scale) + shift) (resnet.py:191-197) in the
+    same launches - emo_hip.h emo_groupnorm_apply_mod / emo_groupnorm_mod."""
+    _need_cuda(x, mod)
     lib = _lib.load()
     M, Cc = x.shape
     S = M // n_inst
     px, ldx = _rows(x)
     y = torch.empty(M, Cc, device=x.device, dtype=x.dtype) if out is None else out
     py, ldy = _rows(y)
+    if mod is not None:
+        pm, ldm = _mod_rows(mod, n_inst, Cc)
+        tag = f"M={M} C={Cc}{' silu' if silu_ else ''} mod"
+        if GN_ONE_LAUNCH and lib.emo_groupnorm_one_launch_ok(n_inst, S, Cc, groups, dt(x)):
+            _launch("groupnorm", 0.0, x.element_size() * 2.0 * M * Cc,
+                    lambda: check(lib.emo_groupnorm_mod(px, ldx, _ptr(gamma), _ptr(beta), pm, ldm, py, ldy, n_inst, S, Cc, groups, float(eps),
+                                                        int(silu_), dt(x), _stream()), "emo_groupnorm_mod"), tag=tag + " 1L")
+            return y
+        part = torch.empty(max(lib.emo_groupnorm_workspace_bytes(n_inst, S, Cc, groups) // 4, 1), device=x.device, dtype=torch.float32)
+
+        def run_mod():
+            check(lib.emo_groupnorm_stats(px, ldx, _ptr(part), n_inst, S, Cc, groups, dt(x), _stream()), "emo_groupnorm_stats")
+            check(lib.emo_groupnorm_apply_mod(px, ldx, _ptr(part), _ptr(gamma), _ptr(beta), pm, ldm, py, ldy, n_inst, S, Cc, groups,
+                                              float(eps), int(silu_), dt(x), _stream()), "emo_groupnorm_apply_mod")
+        _launch("groupnorm", 0.0, x.element_size() * 2.0 * M * Cc, run_mod, tag=tag)
+        return y
     if GN_ONE_LAUNCH and lib.emo_groupnorm_one_launch_ok(n_inst, S, Cc, groups, dt(x)):   # small instances: one launch, one read
         _launch("groupnorm", 0.0, x.element_size() * 2.0 * M * Cc,
                 lambda: check(lib.emo_groupnorm(px, ldx, _ptr(gamma), _ptr(beta), py, ldy, n_inst, S, Cc, groups, float(eps), int(silu_),
@@ -197,11 +221,12 @@ def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: floa
     return y
 
 
-def group_norm_coeffs(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float) -> torch.Tensor:
+def group_norm_coeffs(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, mod=None) -> torch.Tensor:
     """The statistics half of a GroupNorm whose normalisation runs inside its consumer (conv3x3(gn=...)): one read-only pass over x,
     then the per-(instance, channel) factors (n_inst, 2C) f32, channel pairs interleaved (scale, scale, shift, shift) - emo_hip.h
-    emo_groupnorm_coeffs.  The normalised tensor is never materialised."""
-    _need_cuda(x)
+    emo_groupnorm_coeffs.  The normalised tensor is never materialised.
+    mod = f32 (n_inst, 2C) rows (scale | shift): the factors carry the scale-shift modulation (emo_groupnorm_coeffs_mod)."""
+    _need_cuda(x, mod)
     lib = _lib.load()
     M, Cc = x.shape
     S = M // n_inst
@@ -211,6 +236,11 @@ def group_norm_coeffs(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, ep
 
     def run():
         check(lib.emo_groupnorm_stats(px, ldx, _ptr(part), n_inst, S, Cc, groups, dt(x), _stream()), "emo_groupnorm_stats")
+        if mod is not None:
+            pm, ldm = _mod_rows(mod, n_inst, Cc)
+            check(lib.emo_groupnorm_coeffs_mod(_ptr(part), _ptr(gamma), _ptr(beta), pm, ldm, _ptr(coef), n_inst, S, Cc, groups, float(eps), dt(x),
+                                               _stream()), "emo_groupnorm_coeffs_mod")
+            return
         check(lib.emo_groupnorm_coeffs(_ptr(part), _ptr(gamma), _ptr(beta), _ptr(coef), n_inst, S, Cc, groups, float(eps), dt(x), _stream()),
               "emo_groupnorm_coeffs")
     _launch("groupnorm_stats", 0.0, x.element_size() * 1.0 * M * Cc, run, tag=f"M={M} C={Cc}")   # algorithmic: one read

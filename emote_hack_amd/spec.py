@@ -20,6 +20,11 @@ class ResnetSpec:
     cin: int
     cout: int
     temb: int
+    scale_shift: bool = False   # time_embedding_norm="scale_shift" (resnet.py:149-156,191-195): time_emb_proj is 2 * cout wide
+
+    @property
+    def temb_cols(self):
+        return 2 * self.cout if self.scale_shift else self.cout
 
     @property
     def has_shortcut(self):
@@ -42,6 +47,8 @@ class TransformerSpec:
     # `tam` behind it (prefixes of the siblings; None in a plain UNet)
     sam: Optional[str] = None
     tam: Optional["MotionSpec"] = None
+    # unet_use_temporal_attention (attention.py:235-246,309-318): norm_temp + attn_temp over the frames, behind the feed-forward
+    temporal: bool = False
 
 
 @dataclass
@@ -97,7 +104,10 @@ def build_spec(cfg_kwargs, *, has_out=True, controlnet=None, gut_last_transforme
     def tfm(prefix, c, heads):
         if c % heads:
             raise ValueError("channels not divisible by heads")
-        return TransformerSpec(prefix, c, heads, cfg["cross_attention_dim"], cfg["use_linear_projection"])
+        return TransformerSpec(prefix, c, heads, cfg["cross_attention_dim"], cfg["use_linear_projection"],
+                               temporal=bool(cfg["unet_use_temporal_attention"]))
+
+    ss = cfg["resnet_time_scale_shift"] == "scale_shift"
 
     down = []
     out_c = boc[0]
@@ -107,7 +117,7 @@ def build_spec(cfg_kwargs, *, has_out=True, controlnet=None, gut_last_transforme
         use_mm = cfg["use_motion_module"] and (res in cfg["motion_module_resolutions"]) and not cfg["motion_module_decoder_only"]
         b = BlockSpec("down", f"down_blocks.{i}", channels=out_c)
         for j in range(cfg["layers_per_block"]):
-            b.resnets.append(ResnetSpec(f"{b.prefix}.resnets.{j}", in_c if j == 0 else out_c, out_c, temb))
+            b.resnets.append(ResnetSpec(f"{b.prefix}.resnets.{j}", in_c if j == 0 else out_c, out_c, temb, ss))
             b.attentions.append(tfm(f"{b.prefix}.attentions.{j}", out_c, hd[i]) if t.endswith("CrossAttnDownBlock3D") else None)
             b.motions.append(motion(f"{b.prefix}.motion_modules.{j}", out_c, use_mm))
         if i != n - 1:
@@ -116,7 +126,7 @@ def build_spec(cfg_kwargs, *, has_out=True, controlnet=None, gut_last_transforme
 
     c = boc[-1]
     mid = BlockSpec("mid", "mid_block", channels=c)
-    mid.resnets = [ResnetSpec("mid_block.resnets.0", c, c, temb), ResnetSpec("mid_block.resnets.1", c, c, temb)]
+    mid.resnets = [ResnetSpec("mid_block.resnets.0", c, c, temb, ss), ResnetSpec("mid_block.resnets.1", c, c, temb, ss)]
     mid.attentions = [tfm("mid_block.attentions.0", c, hd[-1])]
     mid.motions = [motion("mid_block.motion_modules.0", c, cfg["use_motion_module"] and cfg["motion_module_mid_block"])]
 
@@ -136,7 +146,7 @@ def build_spec(cfg_kwargs, *, has_out=True, controlnet=None, gut_last_transforme
         for j in range(L):
             skip_c = in_c if j == L - 1 else out_c
             r_in = prev_c if j == 0 else out_c
-            b.resnets.append(ResnetSpec(f"{b.prefix}.resnets.{j}", r_in + skip_c, out_c, temb))
+            b.resnets.append(ResnetSpec(f"{b.prefix}.resnets.{j}", r_in + skip_c, out_c, temb, ss))
             b.attentions.append(tfm(f"{b.prefix}.attentions.{j}", out_c, rhd[i]) if t.endswith("CrossAttnUpBlock3D") else None)
             b.motions.append(motion(f"{b.prefix}.motion_modules.{j}", out_c, use_mm))
         if i != n - 1:
@@ -155,8 +165,8 @@ def _resnet_shapes(r: ResnetSpec, d):
     d[f"{p}.norm1.bias"] = (r.cin,)
     d[f"{p}.conv1.weight"] = (r.cout, r.cin, 3, 3)
     d[f"{p}.conv1.bias"] = (r.cout,)
-    d[f"{p}.time_emb_proj.weight"] = (r.cout, r.temb)
-    d[f"{p}.time_emb_proj.bias"] = (r.cout,)
+    d[f"{p}.time_emb_proj.weight"] = (r.temb_cols, r.temb)
+    d[f"{p}.time_emb_proj.bias"] = (r.temb_cols,)
     d[f"{p}.norm2.weight"] = (r.cout,)
     d[f"{p}.norm2.bias"] = (r.cout,)
     d[f"{p}.conv2.weight"] = (r.cout, r.cout, 3, 3)
@@ -220,6 +230,10 @@ def _transformer_shapes(t: TransformerSpec, d):
     _ff_shapes(f"{tb}.ff", c, d)
     d[f"{tb}.norm3.weight"] = (c,)
     d[f"{tb}.norm3.bias"] = (c,)
+    if t.temporal:   # registered behind norm3 (attention.py:235-246)
+        _attn_shapes(f"{tb}.attn_temp", c, c, d)
+        d[f"{tb}.norm_temp.weight"] = (c,)
+        d[f"{tb}.norm_temp.bias"] = (c,)
     d[f"{p}.proj_out.weight"] = (c, c) if t.linear_proj else (c, c, 1, 1)
     d[f"{p}.proj_out.bias"] = (c,)
 

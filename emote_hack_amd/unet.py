@@ -12,6 +12,14 @@ Weights are re-laid once at load (SURVEY.md section 7 "hard parts"):
   conv 3x3  OIHW -> [Cout][ky][kx][Cin]      1x1 / Linear -> [N][K]
   GEGLU proj rows interleaved (32 value, 32 gate) so the gate is applied in the GEMM epilogue
   attn1 to_q|to_k fused; motion-module to_q|to_k|to_v fused; all 22 time_emb_proj fused into one GEMM.
+
+Two ctor switches no shipped config turns on run on the same kernels:
+  unet_use_temporal_attention=True   every transformer block carries norm_temp + attn_temp (attention.py:235-246,309-318): behind the
+      feed-forward, self-attention over the F frames of each pixel - the motion module's temporal kernel with the block's own heads and
+      no positional encoding.  (A freshly constructed reference model has attn_temp.to_out[0].weight zero-initialised, attention.py:245:
+      the branch is an identity until weights are loaded.)
+  resnet_time_scale_shift="scale_shift"   time_emb_proj is 2 * cout wide and modulates behind norm2, h = norm2(h) * (1 + scale) + shift
+      (resnet.py:149-156,191-195), inside the GroupNorm kernels (ops.group_norm(mod=)).
 """
 from __future__ import annotations
 
@@ -77,6 +85,18 @@ def ff_tail_weights(w_out, b_out, w2, b2):
     return torch.cat([wo @ w2.float(), wo], 1), wo @ b2.float() + b_out.float()
 
 
+def ln_fold_weights(wt, b, gamma, beta, dtp):
+    """(W, bias) of a Linear behind a LayerNorm with affine (gamma, beta) -> (W * gamma rounded to the compute dtype, its row sums,
+    bias + W . beta): LN(x) W^T + b = rstd (x W'^T - mean colsum) + b' (FOLD_LAYERNORM; ops.gemm(ln=...))."""
+    g_, be = gamma.float(), beta.float()
+    wt = wt.reshape(wt.shape[0], -1).float()
+    wp = (wt * g_[None, :]).to(dtp)
+    bp = wt.to(dtp).float() @ be
+    if b is not None:
+        bp = bp + b.float()
+    return wp.contiguous(), wp.float().sum(1).contiguous(), bp.contiguous()
+
+
 class _Ctx:
     """Per-forward geometry + reference-attention state."""
 
@@ -106,6 +126,13 @@ class UNet3DConditionModel:
         self._controlnet = kwargs.pop("_controlnet", None)   # ControlNetModel: conditioning-embedding channels
         self._gut_last = kwargs.pop("_gut_last_transformer", False)   # AppearanceEncoderModel (appearance_encoder.py:613-621)
         self.config: FrozenConfig = normalize_unet_config(kwargs)
+        if self._gut_last and self.config["unet_use_temporal_attention"]:
+            # the reference's ReferenceNet is a 2-D diffusers clone (appearance_encoder.py:217-633): its blocks have no attn_temp branch
+            raise NotImplementedError("AppearanceEncoderModel has no unet_use_temporal_attention branch in the reference")
+        if self._controlnet is not None and (self.config["resnet_time_scale_shift"] != "default" or self.config["unet_use_temporal_attention"]):
+            # the reference's ControlNet blocks are third-party 2-D diffusers blocks (controlnet.py:155-262): their scale-shift arithmetic
+            # is not in the tree, and they have no attn_temp branch
+            raise NotImplementedError("ControlNetModel: resnet_time_scale_shift='scale_shift' / unet_use_temporal_attention are not served")
         self.spec: UNetSpec = build_spec(self.config, has_out=self._has_out, controlnet=self._controlnet,
                                          gut_last_transformer=self._gut_last)
         self.sample_size = self.config["sample_size"]
@@ -237,15 +264,7 @@ class UNet3DConditionModel:
             return o.reshape(co, 9 * cip).to(dtp).contiguous()
 
         def ln_fold(wt, b, norm):
-            """(W, bias) of a Linear behind LayerNorm `norm` -> (W * gamma rounded to the compute dtype, its row sums, bias +
-            W . beta): LN(x) W^T + b = rstd (x W'^T - mean colsum) + b'."""
-            g_, be = m[norm + ".weight"].float(), m[norm + ".bias"].float()
-            wt = wt.reshape(wt.shape[0], -1).float()
-            wp = (wt * g_[None, :]).to(dtp)
-            bp = wt.to(dtp).float() @ be
-            if b is not None:
-                bp = bp + b.float()
-            return wp.contiguous(), wp.float().sum(1).contiguous(), bp.contiguous()
+            return ln_fold_weights(wt, b, m[norm + ".weight"], m[norm + ".bias"], dtp)
 
         def geglu_rows(t):  # interleave (32 value, 32 gate) rows / entries
             n = t.shape[0] // 2
@@ -300,7 +319,7 @@ class UNet3DConditionModel:
                 temb_w.append(m[p + ".time_emb_proj.weight"])
                 temb_b.append(m[p + ".time_emb_proj.bias"])
                 self._temb_off[p] = off
-                off += r.cout
+                off += r.temb_cols       # 2 * cout (scale | shift) under resnet_time_scale_shift="scale_shift"
             for a in blk.attentions:
                 if a is None:
                     continue
@@ -322,8 +341,17 @@ class UNet3DConditionModel:
                 w[tb + ".attn2.v"] = lin(tb + ".attn2.to_v.weight")
                 w[tb + ".attn2.o.w"], w[tb + ".attn2.o.b"] = lin(tb + ".attn2.to_out.0.weight"), f32(tb + ".attn2.to_out.0.bias")
                 w[tb + ".ff2.w"], w[tb + ".ff2.b"] = lin(tb + ".ff.net.2.weight"), f32(tb + ".ff.net.2.bias")
-                if self._fuse_tail:
+                if self._fuse_tail and not a.temporal:   # (attn_temp sits between ff.net.2 and proj_out: the two are not adjacent)
                     w[tb + ".tail.w"], w[tb + ".tail.b"] = ff_tail(tb + ".ff.net.2", p + ".proj_out")
+                if a.temporal:      # norm_temp -> attn_temp (attention.py:235-246,309-318): q | k | v as one projection, like the motion module's
+                    at = tb + ".attn_temp"
+                    wqkv = torch.cat([m[at + ".to_q.weight"], m[at + ".to_k.weight"], m[at + ".to_v.weight"]], 0)
+                    w[at + ".o.w"], w[at + ".o.b"] = lin(at + ".to_out.0.weight"), f32(at + ".to_out.0.bias")
+                    if fold:
+                        w[at + ".qkv_ln"] = ln_fold(wqkv, None, tb + ".norm_temp")
+                    else:
+                        w[at + ".qkv"] = wqkv.to(dtp).contiguous()
+                        w[tb + ".norm_temp.g"], w[tb + ".norm_temp.b"] = f32(tb + ".norm_temp.weight"), f32(tb + ".norm_temp.bias")
                 if fold:
                     w[tb + ".attn1.qk_ln"] = ln_fold(torch.cat([m[tb + ".attn1.to_q.weight"], m[tb + ".attn1.to_k.weight"]], 0), None, tb + ".norm1")
                     w[tb + ".attn1.v_ln"] = ln_fold(m[tb + ".attn1.to_v.weight"], None, tb + ".norm1")
@@ -402,20 +430,26 @@ class UNet3DConditionModel:
         G, eps = self.config["norm_num_groups"], self.config["norm_eps"]
         n_img = c.B * c.F
         off = self._temb_off[p]
-        temb = temb_all[:, off:off + r.cout]
-        h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps, rowbias=temb, rows_per_batch=c.F * H * W)
+        temb = temb_all[:, off:off + r.temb_cols]
+        if r.scale_shift:  # resnet.py:191-195: nothing is added in front of norm2; (scale | shift) = temb modulates behind it
+            h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps)
+        else:
+            h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps, rowbias=temb, rows_per_batch=c.F * H * W)
         sc = ops.gemm(x, w[p + ".sc.w"], w[p + ".sc.b"]) if r.has_shortcut else x
-        return self._norm_act_conv(h, p + ".norm2", p + ".conv2", c, H, W, G, eps, inplace=True, residual=sc, out_scale=1.0 / scale, out=out)
+        return self._norm_act_conv(h, p + ".norm2", p + ".conv2", c, H, W, G, eps, inplace=True, mod=temb if r.scale_shift else None,
+                                   residual=sc, out_scale=1.0 / scale, out=out)
 
-    def _norm_act_conv(self, x, norm, conv, c: _Ctx, H, W, G, eps, inplace=False, **kw):
+    def _norm_act_conv(self, x, norm, conv, c: _Ctx, H, W, G, eps, inplace=False, mod=None, **kw):
         """GroupNorm (joint over the F frames of a batch row) -> SiLU -> 3x3 conv (resnet.py:180-183,191-196; unet_controlnet.py:476-477)
-        with the normalisation inside the conv where the halo-reuse kernel serves it (GN_CONV_MIN_HW)."""
+        with the normalisation inside the conv where the halo-reuse kernel serves it (GN_CONV_MIN_HW).
+        mod: f32 (B, 2C) (scale | shift) of a scale-shift resnet's norm2 (resnet.py:193-195), applied by the same kernels."""
         w = self._w
         n_img = c.B * c.F
+        mkw = {} if mod is None else dict(mod=mod)      # (the default path calls exactly what it always called)
         if GN_CONV_MIN_HW and H * W >= GN_CONV_MIN_HW and ops.conv_gn_fusable(x, w[conv + ".w"], n_img, H, W, kw.get("rowbias"), kw.get("rows_per_batch", 0)):
-            coef = ops.group_norm_coeffs(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps)
+            coef = ops.group_norm_coeffs(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps, **mkw)
             return ops.conv3x3(x, w[conv + ".w"], w[conv + ".b"], n_img, H, W, gn=(coef, c.F, True), **kw)[0]
-        h = ops.group_norm(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps, True, out=x if inplace else None)
+        h = ops.group_norm(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps, True, out=x if inplace else None, **mkw)
         return ops.conv3x3(h, w[conv + ".w"], w[conv + ".b"], n_img, H, W, **kw)[0]
 
     def _kv(self, rows, wk, wv, L):
@@ -523,7 +557,7 @@ class UNet3DConditionModel:
         else:
             kc, vct = self._kv(ctx_rows, w[tb + ".attn2.k"], w[tb + ".attn2.v"], ctx_len)
         att = ops.attention(q2, kc, vct, ctx_len, B=nb, Lq=HW, heads=heads, d=d, scale=scale, seg0_div=ctx_div)
-        gh, g_out, h_out = self._tail_buffer(h, C_)
+        gh, g_out, h_out = (None, None, None) if a.temporal else self._tail_buffer(h, C_)
         h = ops.gemm(att, w[tb + ".attn2.o.w"], w[tb + ".attn2.o.b"], residual=h, out=h_out)
         # --- GEGLU feed-forward
         if self._fold_ln:
@@ -535,7 +569,23 @@ class UNet3DConditionModel:
         if gh is not None:      # ff.net.2 + residual + proj_out + residual in one pass over [g | h]
             return ops.gemm(gh, w[tb + ".tail.w"], w[tb + ".tail.b"], residual=x, out=out)
         h = ops.gemm(g, w[tb + ".ff2.w"], w[tb + ".ff2.b"], residual=h)
+        if a.temporal:
+            h = self._attn_temp(tb, h, c.B, c.F, HW, heads, d)
         return ops.gemm(h, w[p + ".proj_out.w"], w[p + ".proj_out.b"], residual=x, out=out)
+
+    def _attn_temp(self, tb, h, B, F, HW, heads, d):
+        """The Temp-Attn branch of BasicTransformerBlock (attention.py:309-318; the bank-reading forward runs the same lines,
+        mutual_self_attention.py:274-282) on the rows h (B*F*HW, C): "(b f) d c -> (b d) f c", norm_temp, self-attention over the F frames
+        of a pixel with the block's own heads and no positional encoding, to_out + residual, regrouped back.  The regrouping is the
+        temporal kernel's indexing - no transpose pass; its scores and softmax are f32 in every dtype, which is all upcast_attention asks."""
+        w, at = self._w, tb + ".attn_temp"
+        if self._fold_ln:   # norm_temp folded into the q | k | v projection, as _motion does
+            wq, cs, bq = w[at + ".qkv_ln"]
+            qkv = ops.gemm(h, wq, bq, ln=(cs, ops.layer_norm_stats(h, 1e-5)))
+        else:
+            qkv = ops.gemm(ops.layer_norm(h, w[tb + ".norm_temp.g"], w[tb + ".norm_temp.b"]), w[at + ".qkv"])
+        att = ops.temporal_attention(qkv, B, F, HW, heads, d, d ** -0.5)
+        return ops.gemm(att, w[at + ".o.w"], w[at + ".o.b"], residual=h)
 
     def _norm_proj_in(self, x, p, nb, HW, groups):
         """GroupNorm(eps 1e-6, per frame) + proj_in; folded into per-frame weights where a frame is large (GN_FOLD_MIN_HW)."""

@@ -99,6 +99,25 @@ int emo_groupnorm_apply(const void* x, int ldx, const void* partials, const floa
 int emo_groupnorm_coeffs(const void* partials, const float* gamma, const float* beta, float* coef, int N, int64_t S,
                          int C, int G, float eps, int dtype, void* stream);
 
+/* Scale-shift GroupNorm (resnet.py:149-156,191-197: ResnetBlock3D(time_embedding_norm="scale_shift")): behind norm2 the time
+ * embedding modulates instead of being added in front of it,  y = act(GN(x) * (1 + s) + t),  (s, t) = chunk(time_emb_proj(silu(temb)), 2)
+ * per (batch row, channel).  `mod` is f32 [N][(scale | shift)]: mod[n * ldmod + c] = s, mod[n * ldmod + C + c] = t (ldmod >= 2 * C, a
+ * multiple of 4; mod 16-byte aligned; C a multiple of 4) - a column view of the batched time-embedding GEMM's output.  A per-(instance,
+ * channel) affine of x like the plain norm: the modulation is folded into the thread's copy of the affine, gamma' = gamma (1 + s),
+ * beta' = beta (1 + s) + t, and the plain arithmetic runs on it - factors a' = rstd gamma (1 + s), b' = (beta - mean rstd gamma)(1 + s) + t
+ * - so the pass stays ONE read and ONE write of the activation (+ N * 2C floats).  Same partials, same fixed-order f64 combine, same limits:
+ *   emo_groupnorm_apply_mod   the second of the two launches (after emo_groupnorm_stats)       (resnet.py:191-197)
+ *   emo_groupnorm_mod         the one-launch kernel, where emo_groupnorm_one_launch_ok says 1  (resnet.py:191-197)
+ *   emo_groupnorm_coeffs_mod  the (a', b') table for emo_gemm_params.gn_coef, bit-identical to the factors the two above use
+ *                             (resnet.py:191-200: norm2 -> modulate -> SiLU inside conv2) */
+int emo_groupnorm_apply_mod(const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
+                            const float* mod, int ldmod, void* y, int ldy, int N, int64_t S, int C, int G, float eps,
+                            int silu, int dtype, void* stream);
+int emo_groupnorm_mod(const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y,
+                      int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream);
+int emo_groupnorm_coeffs_mod(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
+                             float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream);
+
 /* The same GroupNorm in ONE launch, for instances small enough that one workgroup holds (instance, slab of whole groups)
  * in registers (<= 32 K elements per workgroup: the 8x8 level and the per-frame 16x16 norms at the bench size): one read of x, statistics in the same fixed
  * order (f32 partials, f64 mean / variance), one write.  emo_groupnorm_one_launch_ok returns 1 when the geometry fits;
@@ -244,7 +263,11 @@ int emo_attention_plan(const emo_attention_params* p, int plan[5]);
 
 /* Temporal self-attention of the AnimateDiff motion module (motion_module.py:275-334): tokens
  * "(b f) d c -> (b d) f c"; qkv rows are [(b*F+f)*HW + pix][3*C] (q|k|v), output [(b*F+f)*HW+pix][C].
- * F <= 32.  The transposes are folded into the indexing. */
+ * F <= 32.  The transposes are folded into the indexing.
+ * Also the `attn_temp` branch of BasicTransformerBlock(unet_use_temporal_attention=True) (attention.py:235-246,309-318;
+ * mutual_self_attention.py:274-282): the same regrouping with the block's own heads / head dim and no positional encoding.  The scores
+ * accumulate and the softmax runs in f32 for every dtype (only the probabilities are rounded to the value dtype, orig_attention.py:677),
+ * so upcast_attention=True (orig_attention.py:656-658) asks nothing more of the kernel. */
 int emo_temporal_attention(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, int B, int F, int HW,
                            int heads, int d, float scale, int dtype, void* stream);
 
