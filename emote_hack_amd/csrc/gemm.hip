@@ -2,9 +2,9 @@
 // The kernels live in gemm_impl.h and are instantiated per element type in gemm_f32.hip / gemm_bf16.hip / gemm_f16.hip.
 #include "gemm_api.h"
 
-extern template int gemm_run<float>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t);
-extern template int gemm_run<bf16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t);
-extern template int gemm_run<f16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t);
+extern template int gemm_run<float>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
+extern template int gemm_run<bf16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
+extern template int gemm_run<f16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
 extern template int gemm_run_halo<float>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
 extern template int gemm_run_halo<bf16_t>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
 extern template int gemm_run_halo<f16_t>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
@@ -73,7 +73,9 @@ static bool gemm_vt_ok(const emo_gemm_params& p) {
 }
 extern "C" int emo_gemm_vt_ok(const emo_gemm_params* pp) { return pp && emo_dtype_ok(pp->dtype) && gemm_vt_ok(*pp) ? 1 : 0; }
 
-extern "C" int emo_gemm(const emo_gemm_params* pp, void* stream) {
+// argument checks + planning + the launch chain; lp != nullptr: decide only (emo_gemm_plan) - nothing below this line touches the
+// device or dereferences an operand pointer in front of the launch itself
+static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* lp) {
   EMO_CHECK(pp, EMO_ERR_NULL, "emo_gemm: null params");
   const emo_gemm_params& p = *pp;
   EMO_CHECK(p.A && p.W && p.C, EMO_ERR_NULL, "emo_gemm: null pointer");
@@ -124,6 +126,7 @@ extern "C" int emo_gemm(const emo_gemm_params* pp, void* stream) {
   {
     const int He = p.upsample2x ? 2 * p.H : p.H;
     if (conv && halo_conv_ok(p)) {
+      if (lp) { *lp = GemmLaunchPlan{1, 0, 0, 0, 0, 0, 0, 0}; return EMO_OK; }   // (the halo family: its id only)
       const int64_t nt = (p.N + HaloGeom::BN - 1) / HaloGeom::BN;
       // 16-row patches (8 waves, one block per CU) when they still give (nearly) every CU a block; p.tile 1 / 2 pins 8 / 16
       const int We = p.upsample2x ? 2 * p.W_ : p.W_;
@@ -162,6 +165,18 @@ extern "C" int emo_gemm(const emo_gemm_params* pp, void* stream) {
   }
   hipStream_t st = as_stream(stream);
   int rc = EMO_OK;
-  EMO_DISPATCH(p.dtype, "emo_gemm", rc = gemm_run<T>(p, pl, S, st));
+  EMO_DISPATCH(p.dtype, "emo_gemm", rc = gemm_run<T>(p, pl, S, st, lp));
   return rc;
+}
+
+extern "C" int emo_gemm(const emo_gemm_params* pp, void* stream) { return gemm_entry(pp, stream, nullptr); }
+
+extern "C" int emo_gemm_plan(const emo_gemm_params* pp, int plan[8]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_gemm_plan: null plan");
+  GemmLaunchPlan lp = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int rc = gemm_entry(pp, nullptr, &lp);
+  if (rc != EMO_OK) return rc;
+  plan[0] = lp.family; plan[1] = lp.tile; plan[2] = lp.phase_loop; plan[3] = lp.flags;
+  plan[4] = lp.split_k; plan[5] = lp.store; plan[6] = lp.bias_in_acc; plan[7] = lp.rb_in_acc;
+  return EMO_OK;
 }

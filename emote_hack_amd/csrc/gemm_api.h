@@ -101,6 +101,45 @@ static GemmPlan plan_gemm(int64_t M, int N, int K, int dtype, int geglu, int tra
   return pl;
 }
 
-// per-dtype entry points (defined in gemm_impl.h, explicitly instantiated in gemm_<dtype>.hip)
-template <typename T> int gemm_run(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st);        // tiles (+ split-K reduce)
+// ---- the epilogue's path predicates.  Each is ONE function that the kernels (gemm_impl.h) and emo_gemm_plan (the host side of the
+// same launch chain) both call, so the plan cannot drift from what the kernel does.  Compile-time facts of an instantiation (CONV,
+// TRANS, LN, the tile's height, element size, waves' width) are template arguments: a predicate that is false by construction folds in
+// the front end, as it did when these expressions stood in the kernel's body.
+#ifndef EMO_GEMM_RB_IN_ACC
+#define EMO_GEMM_RB_IN_ACC 1   // (0: tools/bench A/B build)
+#endif
+// epilogue_row: whole 4-column quads with 8 / 16-byte accesses (else the scalar path).  p is the kernel's epilogue view of the
+// parameters (rowbias nulled when it rides in the accumulators); R: the residual pointer (compared with NULL only)
+__host__ __device__ __forceinline__ bool gemm_vec_ok(const emo_gemm_params& p, const void* R) {
+  return (p.N & 3) == 0 && ((p.ldc | (R ? p.ldr : 0)) & 3) == 0 && (!p.rowbias || (p.ld_rowbias & 3) == 0);
+}
+// row-major single-pass outputs start their accumulators at the bias
+template <bool LN, bool TRANS> __host__ __device__ __forceinline__ bool gemm_bias_in_acc(const emo_gemm_params& p, int nsplit) {
+  return !LN && !TRANS && nsplit == 1 && p.bias != nullptr && (p.N & 3) == 0;
+}
+// ... and at the per-batch row bias, when a tile's rows lie inside one batch of rows_per_batch rows
+template <bool CONV, bool TRANS, int BM> __host__ __device__ __forceinline__ bool gemm_rb_in_acc(const emo_gemm_params& p, int nsplit) {
+  return EMO_GEMM_RB_IN_ACC && !CONV && !TRANS && nsplit == 1 && p.rowbias != nullptr && (p.N & 3) == 0 && (p.ld_rowbias & 3) == 0 &&
+         p.rows_per_batch > 0 && (p.rows_per_batch % BM) == 0;
+}
+// coalesced LDS-staged epilogue (2-byte types, row-major, single pass): needs whole 16-byte chunks everywhere
+template <bool TRANS, int ESZ, int WTN> __host__ __device__ __forceinline__ bool gemm_use_lds_epi(const emo_gemm_params& p, int nsplit, int nk, const void* R) {
+  const int n_out_all = p.geglu ? p.N / 2 : p.N;
+  return !TRANS && ESZ == 2 && nsplit == 1 && nk > 0 && (n_out_all & 7) == 0 && (p.N & 3) == 0 &&
+         (p.ldc & 7) == 0 && (!R || (p.ldr & 7) == 0) && (!p.rowbias || (p.ld_rowbias & 3) == 0) &&
+         (!p.geglu || (WTN % 2 == 0 && !p.rowbias)) && (!p.rowbias || p.rows_per_batch > 0);
+}
+// ... on the instantiations whose ring slot holds every wave's 32 x 32 staging tile
+__host__ __device__ constexpr bool gemm_lds_slot_ok(bool trans, int esz, int stage_bytes, int nw) { return !trans && esz == 2 && stage_bytes >= 80 * 32 * nw; }
+// V^T store: one 8 / 16-byte store per quad of 4 consecutive rows (t_rows % 4 == 0: a quad never straddles two batches)
+__host__ __device__ __forceinline__ bool gemm_vt_quad_ok(const emo_gemm_params& p) {
+  return (p.t_rows & 3) == 0 && (p.t_ld & 3) == 0 && (p.t_batch_stride & 3) == 0;
+}
+
+// emo_gemm_plan's answer (emo_hip.h): what the launch chain decided, filled by launch_gemm in front of its first HIP call
+enum { EMO_STORE_LDS = 0, EMO_STORE_VEC_ROW = 1, EMO_STORE_SCALAR_ROW = 2, EMO_STORE_VT_QUAD = 3, EMO_STORE_VT_SCALAR = 4, EMO_STORE_SPLITK_WS = 5 };
+struct GemmLaunchPlan { int family, tile, phase_loop, flags, split_k, store, bias_in_acc, rb_in_acc; };
+
+// per-dtype entry points (defined in gemm_impl.h, explicitly instantiated in gemm_<dtype>.hip); lp != nullptr: decide only
+template <typename T> int gemm_run(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st, GemmLaunchPlan* lp);        // tiles (+ split-K reduce)
 template <typename T> int gemm_run_halo(const emo_gemm_params& p, int ph, int bn, int64_t gx, hipStream_t st);                   // conv3x3_halo_kernel

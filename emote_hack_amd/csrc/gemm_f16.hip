@@ -1,4 +1,4 @@
 // gemm_f16.hip - the GEMM / conv kernels of gemm_impl.h instantiated for f16_t
 #include "gemm_impl.h"
 
-template int gemm_run<f16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t);
+template int gemm_run<f16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);

@@ -104,7 +104,7 @@ __device__ __forceinline__ void epilogue_row(const f32x16 (&acc)[WTN], const emo
                                              T* __restrict__ C, const T* __restrict__ R, bool ln = false, float ln_rstd = 1.f) {
   const float* rbias = (p.rowbias && m_ok) ? p.rowbias + (m / p.rows_per_batch) * p.ld_rowbias : nullptr;
   const int n_out = p.geglu ? p.N / 2 : p.N;
-  const bool vec_ok = (p.N & 3) == 0 && ((p.ldc | (R ? p.ldr : 0)) & 3) == 0 && (!p.rowbias || (p.ld_rowbias & 3) == 0);
+  const bool vec_ok = gemm_vec_ok(p, R);
 #pragma unroll
   for (int j = 0; j < WTN; j++) {
     if (p.geglu && (j & 1)) continue;   // gate tile is consumed with its value tile
@@ -123,6 +123,8 @@ __device__ __forceinline__ void epilogue_row(const f32x16 (&acc)[WTN], const emo
                          acc[(j + 1) % WTN][4 * g + 3]};
           if (ln) { gt[0] *= ln_rstd; gt[1] *= ln_rstd; gt[2] *= ln_rstd; gt[3] *= ln_rstd; }
           if (p.bias) { const float4 b4 = *(const float4*)(p.bias + nw0 + 32); gt[0] += b4.x; gt[1] += b4.y; gt[2] += b4.z; gt[3] += b4.w; }
+          // (the row bias covers all N columns of W-row space, the gate columns included: emo_hip.h orders + bias, + rowbias, GEGLU)
+          if (rbias) { const float4 b4 = *(const float4*)(rbias + nw0 + 32); gt[0] += b4.x; gt[1] += b4.y; gt[2] += b4.z; gt[3] += b4.w; }
           if constexpr (sizeof(T) == 2) {
             geglu_poly2(o[0], o[1], gt[0], gt[1], o[0], o[1]);
             geglu_poly2(o[2], o[3], gt[2], gt[3], o[2], o[3]);
@@ -159,6 +161,7 @@ __device__ __forceinline__ void epilogue_row(const f32x16 (&acc)[WTN], const emo
             float gt = acc[(j + 1) % WTN][4 * g + e];
             if (ln) gt *= ln_rstd;
             if (p.bias) gt += p.bias[nw + 32];
+            if (rbias) gt += rbias[nw + 32];
             v *= gelu_for<T>(gt);
           }
           if (no0 + e < n_out) {
@@ -615,23 +618,16 @@ __global__ __launch_bounds__(64 * WVM * WVN, (GemmTile<WTM, WTN, WVM, WVN, NS>::
   T* __restrict__ C = (T*)p.C;
   const T* __restrict__ R = (const T*)p.residual;
   // row-major single-pass outputs start their accumulators at the bias; the epilogues then see bias == nullptr
-  const bool bias_in_acc = !LN && !TRANS && nsplit == 1 && p.bias != nullptr && (p.N & 3) == 0;
+  const bool bias_in_acc = gemm_bias_in_acc<LN, TRANS>(p, nsplit);
   emo_gemm_params pe = p;
   if (bias_in_acc || LN) pe.bias = nullptr;   // (LN: the folded bias enters the accumulator init scaled by 1 / rstd)
   // the per-batch row bias (temb of a resnet, the positional-encoding term of a temporal q|k|v projection) is uniform over a tile
   // whose rows lie inside one batch of rows_per_batch rows: it then starts the accumulators as well (under the LayerNorm fold
   // divided by rstd_m like the bias) and the epilogue has no row-bias loads (per staged pass: one L2 round trip each)
-#ifndef EMO_GEMM_RB_IN_ACC
-#define EMO_GEMM_RB_IN_ACC 1   // (0: tools/bench A/B build)
-#endif
-  const bool rb_in_acc = EMO_GEMM_RB_IN_ACC && !CONV && !TRANS && nsplit == 1 && p.rowbias != nullptr && (p.N & 3) == 0 && (p.ld_rowbias & 3) == 0 &&
-                         p.rows_per_batch > 0 && (p.rows_per_batch % BM) == 0;
+  const bool rb_in_acc = gemm_rb_in_acc<CONV, TRANS, BM>(p, nsplit);   // (EMO_GEMM_RB_IN_ACC: gemm_api.h)
   if (rb_in_acc) pe.rowbias = nullptr;
   // coalesced LDS-staged epilogue (bf16, row-major, single pass): needs whole 16-byte chunks everywhere
-  const int n_out_all = p.geglu ? p.N / 2 : p.N;
-  const bool use_lds_epi = !TRANS && sizeof(T) == 2 && nsplit == 1 && nk > 0 && (n_out_all & 7) == 0 && (p.N & 3) == 0 &&
-                           (p.ldc & 7) == 0 && (!R || (p.ldr & 7) == 0) && (!p.rowbias || (p.ld_rowbias & 3) == 0) &&
-                           (!p.geglu || (WTN % 2 == 0 && !p.rowbias)) && (!p.rowbias || p.rows_per_batch > 0);
+  const bool use_lds_epi = gemm_use_lds_epi<TRANS, (int)sizeof(T), WTN>(p, nsplit, nk, R);
 
   // ---- ping-pong loader (PP): group g's waves load A rows [g*128, g*128+128) of the tile, group 1's also the whole W panel;
   // glds round i of wave wg covers LDS rows (i*4 + wg)*8 .. +8 of the (half-)panel.  Source pointers are formed per request
@@ -1009,7 +1005,7 @@ __global__ __launch_bounds__(64 * WVM * WVN, (GemmTile<WTM, WTN, WVM, WVN, NS>::
   // merged q | k | v projection (emo_gemm_params.vt): the waves whose columns are V columns store transposed, the others as usual
   bool vt_wave = false;
   if constexpr (!TRANS && !CONV && LN) vt_wave = p.vt != nullptr && wn0 >= p.vt_col0;
-  if constexpr (!TRANS && sizeof(T) == 2 && Tile::STAGE_BYTES >= 80 * 32 * NW) {   // (a ring slot must hold a wave's 32 x 32 staging tile)
+  if constexpr (gemm_lds_slot_ok(TRANS, (int)sizeof(T), Tile::STAGE_BYTES, NW)) {   // (a ring slot must hold a wave's 32 x 32 staging tile)
     lds_epilogue = use_lds_epi;
     if (lds_epilogue) {
       // the slot the last stage was read from is free once every wave has finished that stage (the other slot holds the
@@ -1060,7 +1056,7 @@ __global__ __launch_bounds__(64 * WVM * WVN, (GemmTile<WTM, WTN, WVM, WVN, NS>::
   } else {
     // TRANS: lane <-> column n; register quad g <-> rows 8*g + 4*half + {0..3} (4 CONSECUTIVE rows), which are 4
     // contiguous elements of V^T: Ct[m / t_rows][n][m % t_rows] -> one 8-byte (bf16) / 16-byte (f32) store per quad
-    const bool quad_ok = (p.t_rows & 3) == 0 && (p.t_ld & 3) == 0 && (p.t_batch_stride & 3) == 0;
+    const bool quad_ok = gemm_vt_quad_ok(p);
 #pragma unroll
     for (int i = 0; i < WTM; i++) {
       // LayerNorm fold: the statistics of row 8g + 4half + e live in lane (row) of this wave - fetched with EVERY lane active,
@@ -1146,7 +1142,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_kernel(const emo_gem
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       if (p.bias) { v[e] += p.bias[nw + e]; if (p.geglu) g[e] += p.bias[nw + 32 + e]; }
-      if (p.rowbias) v[e] += p.rowbias[(m / p.rows_per_batch) * p.ld_rowbias + nw + e];
+      if (p.rowbias) {   // (all N columns of W-row space carry it, the gate columns included)
+        const float* rb = p.rowbias + (m / p.rows_per_batch) * p.ld_rowbias + nw + e;
+        v[e] += rb[0];
+        if (p.geglu) g[e] += rb[32];
+      }
       if (p.geglu) v[e] = v[e] * gelu_erf_f(g[e]);
     }
     if (!p.transpose_out) {
@@ -1182,18 +1182,44 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_kernel(const emo_gem
 }
 
 // ------------------------------------------------------------------------------------------ host side
+// the id (gemm_api.h EMO_TILE_*) of an instantiation's tile geometry
+template <int WTM, int WTN, int WVM, int WVN, bool PP> constexpr int tile_id_of() {
+  if (PP) return EMO_TILE_256x256_PP;
+  if (WTM == 1 && WTN == 1 && WVM == 2 && WVN == 2) return EMO_TILE_64x64;
+  if (WTM == 2 && WTN == 2 && WVM == 2 && WVN == 2) return EMO_TILE_128x128;
+  if (WTM == 1 && WTN == 5 && WVM == 4 && WVN == 1) return EMO_TILE_128x160;
+  if (WTM == 4 && WTN == 2 && WVM == 2 && WVN == 4) return EMO_TILE_256x256;
+  if (WTM == 1 && WTN == 5 && WVM == 8 && WVN == 1) return EMO_TILE_256x160;
+  if (WTM == 2 && WTN == 5 && WVM == 4 && WVN == 2) return EMO_TILE_256x320;
+  return -1;
+}
+
+// What the kernel of this instantiation does with p: its own path predicates (gemm_api.h), evaluated the way gemm_kernel evaluates them
+template <typename T, bool CONV, bool TRANS, int WTM, int WTN, int WVM, int WVN, int NS, bool LN, bool PP>
+static void describe_launch(const emo_gemm_params& p, int S, GemmLaunchPlan& lp) {
+  using Tile = GemmTile<WTM, WTN, WVM, WVN, NS>;
+  constexpr int BK = KBYTES / (int)sizeof(T);
+  lp.family = 0;
+  lp.tile = PP ? EMO_TILE_256x256_PP : tile_id_of<WTM, WTN, WVM, WVN, false>();
+  lp.phase_loop = (PP && EMO_GEMM_PH) ? 1 : 0;
+  lp.flags = (CONV ? 1 : 0) | (TRANS ? 2 : 0) | (LN ? 4 : 0) | ((!TRANS && !CONV && LN && p.vt) ? 8 : 0);
+  lp.split_k = S;
+  lp.bias_in_acc = gemm_bias_in_acc<LN, TRANS>(p, S) ? 1 : 0;
+  lp.rb_in_acc = gemm_rb_in_acc<CONV, TRANS, Tile::BM>(p, S) ? 1 : 0;
+  emo_gemm_params pe = p;                         // the epilogue's view (gemm_kernel)
+  if (lp.bias_in_acc || LN) pe.bias = nullptr;
+  if (lp.rb_in_acc) pe.rowbias = nullptr;
+  const int nk = (p.K + BK - 1) / BK;             // (single pass: every block's slice is all of K)
+  if (gemm_lds_slot_ok(TRANS, (int)sizeof(T), Tile::STAGE_BYTES, Tile::NW) && gemm_use_lds_epi<TRANS, (int)sizeof(T), WTN>(p, S, nk, p.residual)) lp.store = EMO_STORE_LDS;
+  else if (S > 1) lp.store = EMO_STORE_SPLITK_WS;
+  else if (TRANS) lp.store = gemm_vt_quad_ok(p) ? EMO_STORE_VT_QUAD : EMO_STORE_VT_SCALAR;
+  else lp.store = gemm_vec_ok(pe, p.residual) ? EMO_STORE_VEC_ROW : EMO_STORE_SCALAR_ROW;
+}
+
 template <typename T, bool CONV, bool TRANS, int WTM, int WTN, int WVM, int WVN, int NS, bool LN, bool PP = false>
-static int launch_gemm(const emo_gemm_params& p, int S, hipStream_t st) {
+static int launch_gemm(const emo_gemm_params& p, int S, hipStream_t st, GemmLaunchPlan* lp) {
   using Tile = GemmTile<WTM, WTN, WVM, WVN, NS>;
   auto kern = gemm_kernel<T, CONV, TRANS, WTM, WTN, WVM, WVN, NS, LN, PP>;
-  if (Tile::LDS_BYTES > 64 * 1024) {
-    static bool once = false;
-    if (!once) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES);
-      if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      once = true;
-    }
-  }
   const int64_t tiles = ((p.M + Tile::BM - 1) / Tile::BM) * ((p.N + Tile::BN - 1) / Tile::BN);
   if (tiles >= (1ll << 31)) return emo_fail(EMO_ERR_BAD_SHAPE, "emo_gemm: too many tiles");
   // the split store of emo_gemm_params.vt switches per WAVE (epilogue_vt): whatever tile the dispatch (or one of its fallbacks) ended
@@ -1202,6 +1228,15 @@ static int launch_gemm(const emo_gemm_params& p, int S, hipStream_t st) {
   if (p.vt && (p.vt_col0 % (32 * WTN) != 0 || p.t_rows % (32 * WTM) != 0))
     return emo_fail(EMO_ERR_UNSUPPORTED, "emo_gemm: vt_col0=%d / t_rows=%d do not fall on the wave boundaries (%d columns, %d rows) of the launched tile",
                     p.vt_col0, p.t_rows, 32 * WTN, 32 * WTM);
+  if (lp) { describe_launch<T, CONV, TRANS, WTM, WTN, WVM, WVN, NS, LN, PP>(p, S, *lp); return EMO_OK; }
+  if (Tile::LDS_BYTES > 64 * 1024) {
+    static bool once = false;
+    if (!once) {
+      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Tile::LDS_BYTES);
+      if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
+      once = true;
+    }
+  }
   // persistent launch: as many blocks as the chip holds at once (by LDS, <= 4 per CU), each walking its tiles; a
   // multiple of 8 so that a block's tiles all map to its own XCD
   int64_t slots = (256 * Tile::BPC / S) & ~7;
@@ -1225,7 +1260,7 @@ static int launch_gemm(const emo_gemm_params& p, int S, hipStream_t st) {
 #define EMO_GEMM_NS 2   // LDS ring depth (tools/bench/build_variant.sh builds deeper-ring / shorter-stage variants for A/B runs)
 #endif
 template <typename T, bool CONV, bool TRANS, bool LN>
-static int dispatch_tile(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st) {
+static int dispatch_tile(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st, GemmLaunchPlan* lp) {
   constexpr int NS = EMO_GEMM_NS;
   constexpr int NS_BIG = (NS * 512 * KBYTES <= 160 * 1024) ? NS : 2;   // a 256x256 stage holds 512 rows of KBYTES
   switch (pl.tile) {
@@ -1233,35 +1268,35 @@ static int dispatch_tile(const emo_gemm_params& p, const GemmPlan& pl, int S, hi
       if constexpr (!CONV && !TRANS && sizeof(T) == 2) {
         // (the phase loader: >= 2 K-tiles, and a tile's 256 rows of A / W inside the 31-bit range of its buffer resources)
         const bool ph_ok = p.K >= 2 * (KBYTES / (int)sizeof(T)) && 256 * p.lda * (int64_t)sizeof(T) < (1ll << 31) && 256 * (int64_t)p.K * (int64_t)sizeof(T) < (1ll << 31);
-        if (S == 1 && p.K % (KBYTES / (int)sizeof(T)) == 0 && ph_ok && p.split_k <= 1) return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, 2, LN, true>(p, S, st);
+        if (S == 1 && p.K % (KBYTES / (int)sizeof(T)) == 0 && ph_ok && p.split_k <= 1) return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, 2, LN, true>(p, S, st, lp);
       }
-      return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, NS_BIG, LN>(p, S, st);
-    case EMO_TILE_256x256: return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, NS_BIG, LN>(p, S, st);
-    case EMO_TILE_64x64: return launch_gemm<T, CONV, TRANS, 1, 1, 2, 2, NS, LN>(p, S, st);
-    case EMO_TILE_128x160: return launch_gemm<T, CONV, TRANS, 1, 5, 4, 1, NS, LN>(p, S, st);
+      return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, NS_BIG, LN>(p, S, st, lp);
+    case EMO_TILE_256x256: return launch_gemm<T, CONV, TRANS, 4, 2, 2, 4, NS_BIG, LN>(p, S, st, lp);
+    case EMO_TILE_64x64: return launch_gemm<T, CONV, TRANS, 1, 1, 2, 2, NS, LN>(p, S, st, lp);
+    case EMO_TILE_128x160: return launch_gemm<T, CONV, TRANS, 1, 5, 4, 1, NS, LN>(p, S, st, lp);
     case EMO_TILE_256x160:
-      if constexpr (!CONV && !TRANS) return launch_gemm<T, CONV, TRANS, 1, 5, 8, 1, 2, LN>(p, S, st);
+      if constexpr (!CONV && !TRANS) return launch_gemm<T, CONV, TRANS, 1, 5, 8, 1, 2, LN>(p, S, st, lp);
       break;
     case EMO_TILE_256x320:
-      if constexpr (!CONV && !TRANS && sizeof(T) == 2) return launch_gemm<T, CONV, TRANS, 2, 5, 4, 2, 2, LN>(p, S, st);
+      if constexpr (!CONV && !TRANS && sizeof(T) == 2) return launch_gemm<T, CONV, TRANS, 2, 5, 4, 2, 2, LN>(p, S, st, lp);
       break;
     default: break;
   }
-  return launch_gemm<T, CONV, TRANS, 2, 2, 2, 2, NS, LN>(p, S, st);
+  return launch_gemm<T, CONV, TRANS, 2, 2, 2, 2, NS, LN>(p, S, st, lp);
 }
 
 template <typename T>
-static int dispatch_gemm(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st) {
+static int dispatch_gemm(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st, GemmLaunchPlan* lp) {
   const bool conv = p.conv_taps != 0;
-  if (p.ln_colsum) return p.transpose_out ? dispatch_tile<T, false, true, true>(p, pl, S, st) : dispatch_tile<T, false, false, true>(p, pl, S, st);
-  if (p.transpose_out) return conv ? dispatch_tile<T, true, true, false>(p, pl, S, st) : dispatch_tile<T, false, true, false>(p, pl, S, st);
-  return conv ? dispatch_tile<T, true, false, false>(p, pl, S, st) : dispatch_tile<T, false, false, false>(p, pl, S, st);
+  if (p.ln_colsum) return p.transpose_out ? dispatch_tile<T, false, true, true>(p, pl, S, st, lp) : dispatch_tile<T, false, false, true>(p, pl, S, st, lp);
+  if (p.transpose_out) return conv ? dispatch_tile<T, true, true, false>(p, pl, S, st, lp) : dispatch_tile<T, false, true, false>(p, pl, S, st, lp);
+  return conv ? dispatch_tile<T, true, false, false>(p, pl, S, st, lp) : dispatch_tile<T, false, false, false>(p, pl, S, st, lp);
 }
 
 
-template <typename T> int gemm_run(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st) {
-  int rc = dispatch_gemm<T>(p, pl, S, st);
-  if (rc) return rc;
+template <typename T> int gemm_run(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st, GemmLaunchPlan* lp) {
+  int rc = dispatch_gemm<T>(p, pl, S, st, lp);
+  if (rc || lp) return rc;
   if (S > 1) {
     const int64_t total = p.M * (p.geglu ? p.N / 2 : p.N) / 4;
     int64_t g = (total + 255) / 256; if (g > 4096) g = 4096;

@@ -299,7 +299,7 @@ GEMM_TILE = 0   # tuning hook for tools/bench: pins emo_gemm_params.tile of ever
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, *, rowbias=None, rows_per_batch=0, residual=None, geglu=False,
          out_scale=1.0, out=None, transpose_rows=0, transpose_ld=0, conv=None, split_k=None, ln=None, tile=None,
-         w_slab_rows=0, gn=None, vt_cols=0, vt_rows=0, vt_ld=0):
+         w_slab_rows=0, gn=None, vt_cols=0, vt_rows=0, vt_ld=0, workspace=None, vt_out=None):
     """out = epilogue(a @ w.T).  a (M, K) rows view; w (N, K) contiguous in the compute dtype.
     ln = (colsum f32 (N,), stats f32 (M, 2) from layer_norm_stats(a)): LayerNorm over K folded into the GEMM - a holds the RAW
     rows, w / bias carry the folded affine (emo_hip.h emo_gemm_params.ln_colsum).
@@ -310,7 +310,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, *, rowbias=None, rows_per_
     halo-reuse 3x3 conv - a holds the RAW rows (emo_hip.h emo_gemm_params.gn_coef; conv_gn_fusable says which convs qualify).
     vt_cols = n: the LAST n output columns are stored transposed per batch of vt_rows rows (V^T (M / vt_rows, n, vt_ld)), the first N - n
     row-major: returns (out (M, N - n), vt) - or None when this GEMM is not served that way (emo_hip.h emo_gemm_params.vt; the caller
-    then runs two launches)."""
+    then runs two launches).
+    vt_out = the (M / vt_rows, vt_cols, vt_ld) tensor to store V^T into instead of a fresh allocation.
+    workspace = an f32 tensor to hold the split-K partials (at least split_k * M * N elements) instead of a fresh allocation."""
     _need_cuda(a, w)
     if vt_cols and _VT_VERDICT.get((a.shape[0], tuple(w.shape), vt_cols, vt_rows, vt_ld, a.dtype, tile, GEMM_TILE)) is False:
         return None     # asked before (emo_gemm_vt_ok below): not served - no throw-away allocations, no ctypes call
@@ -359,7 +361,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, *, rowbias=None, rows_per_
     vt = None
     if vt_cols:
         assert conv is None and not geglu and residual is None and not transpose_rows and tuple(out.shape) == (M, N - vt_cols)
-        vt = torch.empty(M // vt_rows, vt_cols, vt_ld, device=a.device, dtype=a.dtype)
+        vt = vt_out if vt_out is not None else torch.empty(M // vt_rows, vt_cols, vt_ld, device=a.device, dtype=a.dtype)
+        assert tuple(vt.shape) == (M // vt_rows, vt_cols, vt_ld) and vt.is_contiguous() and vt.dtype == a.dtype
         p.vt, p.vt_col0, p.t_rows, p.t_ld, p.t_batch_stride = vt.data_ptr(), N - vt_cols, vt_rows, vt_ld, vt_cols * vt_ld
     if gn is not None:
         coef, imgs_per_inst, gn_silu = gn
@@ -384,7 +387,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, *, rowbias=None, rows_per_
     sk = lib.emo_gemm_suggest_split_k(M, N, K, p.dtype, int(bool(geglu)), int(bool(transpose_rows))) if split_k is None else split_k
     ws = None
     if sk > 1:
-        ws = torch.empty(lib.emo_gemm_workspace_bytes(M, N, sk) // 4, device=a.device, dtype=torch.float32)
+        if workspace is not None:
+            assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.numel() * 4 >= lib.emo_gemm_workspace_bytes(M, N, sk)
+        ws = workspace if workspace is not None else torch.empty(lib.emo_gemm_workspace_bytes(M, N, sk) // 4, device=a.device, dtype=torch.float32)
         p.split_k, p.workspace = sk, ws.data_ptr()
     esz = a.element_size()
     _launch("gemm_conv3x3" if conv is not None else "gemm_dense", 2.0 * M * N * K,
@@ -395,6 +400,61 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias=None, *, rowbias=None, rows_per_
                 (" ln" if ln is not None else "") + (" slab" if w_slab_rows else "") + (" rowbias" if rowbias is not None else "") +
                 (" gn" if gn is not None else "") + (f" vt{vt_cols}" if vt_cols else ""))
     return (out, vt) if vt_cols else out
+
+
+GEMM_STORE_PATHS = ("lds", "vec_row", "scalar_row", "vt_quad", "vt_scalar", "splitk_ws")   # emo_hip.h emo_gemm_plan, plan[5]
+
+
+def gemm_plan(*, dtype, M, N, K, lda=None, ldc=None, bias=False, rowbias=False, rows_per_batch=0, ld_rowbias=None, residual=False, ldr=None,
+              geglu=False, out_scale=1.0, transpose_rows=0, transpose_ld=0, t_batch_stride=None, conv=None, split_k=None, workspace=True,
+              ln=False, ln_colsum=None, ln_stats=None, tile=0, w_slab_rows=0, w_slab_stride=None, vt_cols=0, vt_rows=0, vt_ld=0,
+              misalign=None):
+    """What ops.gemm / emo_gemm launches for this parameter block, asked of the library on the host (emo_hip.h emo_gemm_plan; no GPU
+    needed): (family, tile after fallbacks, phase loop, flags [1 conv | 2 V^T kernel | 4 LayerNorm fold | 8 vt split store], split_k,
+    store path - an index into GEMM_STORE_PATHS -, bias in the accumulators, row bias in the accumulators).
+    Operands are described, not passed: bias / rowbias / residual / ln say whether the pointer is set; lda / ldc / ldr / ld_rowbias
+    default to the contiguous widths; split_k=None asks the planner as ops.gemm does, workspace=False withholds the split-K workspace;
+    ln_colsum / ln_stats override ln for one pointer each; misalign = dict(A= / W= / C= / residual= / bias= / ln_colsum= / ln_stats= /
+    vt= bytes) offsets that pointer from 256-byte alignment.  Raises EmoHipError where emo_gemm would refuse the call."""
+    mis = dict(misalign or {})
+    fake = lambda name, on=True: (256 + mis.get(name, 0)) if on else None    # non-NULL, never dereferenced
+    p = GemmParams()
+    n_out = N // 2 if geglu else N
+    p.A, p.lda, p.W = fake("A"), (K if conv is None else conv["Cin"]) if lda is None else lda, fake("W")
+    p.bias = fake("bias", bias)
+    if rowbias:
+        p.rowbias, p.rows_per_batch, p.ld_rowbias = fake("rowbias"), rows_per_batch, N if ld_rowbias is None else ld_rowbias
+    if residual:
+        p.residual, p.ldr = fake("residual"), n_out if ldr is None else ldr
+    p.C = fake("C")
+    if transpose_rows:
+        p.transpose_out, p.t_rows, p.t_ld = 1, transpose_rows, transpose_ld
+        p.t_batch_stride = n_out * transpose_ld if t_batch_stride is None else t_batch_stride
+    else:
+        p.ldc = (n_out - vt_cols) if ldc is None else ldc
+    p.M, p.N, p.K = M, N, K
+    p.geglu, p.out_scale = int(geglu), float(out_scale)
+    if conv is not None:
+        p.conv_taps, p.H, p.W_, p.Cin = 9, conv["H"], conv["W"], conv["Cin"]
+        p.stride, p.upsample2x, p.Ho, p.Wo = conv["stride"], int(conv.get("upsample2x", 0)), conv["Ho"], conv["Wo"]
+        p.conv_asym = int(conv.get("asym", 0))
+        p.up_h, p.up_w = conv.get("up", (0, 0))
+    p.dtype = dt(dtype)
+    if vt_cols:
+        p.vt, p.vt_col0, p.t_rows, p.t_ld, p.t_batch_stride = fake("vt"), N - vt_cols, vt_rows, vt_ld, vt_cols * vt_ld
+    if w_slab_rows:
+        p.w_slab_rows, p.w_slab_stride = w_slab_rows, N * K if w_slab_stride is None else w_slab_stride
+    p.tile = int(tile)
+    p.ln_colsum = fake("ln_colsum", ln if ln_colsum is None else ln_colsum)
+    p.ln_stats = fake("ln_stats", ln if ln_stats is None else ln_stats)
+    lib = _lib.load()
+    if split_k is None:     # what ops.gemm does
+        split_k = 1 if (ln or vt_cols or w_slab_rows) else lib.emo_gemm_suggest_split_k(M, N, K, p.dtype, int(bool(geglu)), int(bool(transpose_rows)))
+    if split_k > 1:
+        p.split_k, p.workspace = split_k, fake("workspace", workspace)
+    plan = (C.c_int * 8)()
+    check(lib.emo_gemm_plan(C.byref(p), plan), "emo_gemm_plan")
+    return tuple(plan)
 
 
 def conv_gn_fusable(x: torch.Tensor, w: torch.Tensor, n_img: int, H: int, W: int, rowbias=None, rows_per_batch=0) -> bool:

@@ -219,6 +219,18 @@ int emo_gemm(const emo_gemm_params* p, void* stream);
 int emo_conv3x3_gn_fusable(const emo_gemm_params* p);
 /* 1 when p (with vt / vt_col0 set) is a GEMM the split row-major | transposed store serves on the tile the planner picks for it */
 int emo_gemm_vt_ok(const emo_gemm_params* p);
+/* Host-only: what emo_gemm would launch for p.  Runs emo_gemm's argument checks and planning and returns their status; writes nothing
+ * on a refusal, launches nothing and touches no device memory (the pointers of p are only compared with NULL and checked for alignment).
+ *   plan[0] family      0 = the tile kernel, 1 = the halo-reuse 3x3 conv (the other fields are then 0)
+ *   plan[1] tile        the tile instantiated, after every fallback: 1 64x64, 2 128x128, 3 128x160, 4 256x256, 5 256x160, 6 256x320,
+ *                       7 256x256 with the phase main loop
+ *   plan[2] main loop   0 = lockstep, 1 = phase
+ *   plan[3] flags       bit 0 conv loader, bit 1 transposed (V^T) kernel, bit 2 LayerNorm fold, bit 3 split row-major | V^T store (vt)
+ *   plan[4] split_k     as launched (1 = single pass)
+ *   plan[5] store path  0 LDS-staged full lines, 1 vector row (8 / 16 bytes per quad), 2 scalar row, 3 V^T quad, 4 V^T scalar,
+ *                       5 split-K workspace (f32 partials; the reduce kernel stores the output)
+ *   plan[6], plan[7]    1 when the bias / the per-batch row bias starts the accumulators instead of being added in the epilogue */
+int emo_gemm_plan(const emo_gemm_params* p, int plan[8]);
 /* heuristic split factor for (M, N, K) and the workspace it needs */
 int emo_gemm_suggest_split_k(int64_t M, int N, int K, int dtype, int geglu, int transpose_out);
 size_t emo_gemm_workspace_bytes(int64_t M, int N, int split_k);

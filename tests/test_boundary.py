@@ -319,3 +319,68 @@ def test_attention_argument_checks_run_before_any_launch():
     assert rc == -1 and b"exceeds 1 GB" in lib.emo_last_error_string()
     rc = lib.emo_attention(C.byref(params(k1=fake, v1t=fake, Lk1=1 << 20, ldk1=640, ldv1t=1 << 20, seg1_div=2)), None)
     assert rc == -1 and b"segment 1" in lib.emo_last_error_string()
+
+
+def test_gemm_argument_checks_run_before_any_launch():
+    """emo_gemm's refusals, asked through emo_gemm_plan (the same entry with the launch cut off, so no GPU is needed): each returns
+    its status and an error string, and the plan array is not written.  tests/test_gpu_gemm_sweeps.py confirms on the device that
+    emo_gemm returns the same statuses with the output untouched."""
+    import ctypes as C
+    from emote_hack_amd import _lib, ops
+    from emote_hack_amd._lib import EmoHipError
+    lib = _lib.load()
+    BAD_SHAPE, UNSUPPORTED, NULL = -1, -3, -5
+    bf16, f32 = torch.bfloat16, torch.float32
+
+    def refused(code, word, **kw):
+        base = dict(dtype=bf16, M=256, N=128, K=128)
+        base.update(kw)
+        with pytest.raises(EmoHipError) as e:
+            ops.gemm_plan(**base)
+        assert f"(emo_status {code})" in str(e.value), (kw, str(e.value))
+        assert word in str(e.value), (kw, str(e.value))
+
+    refused(BAD_SHAPE, "multiples of 8", K=124)                                  # K % V
+    refused(BAD_SHAPE, "multiples of 4", dtype=f32, K=126)
+    refused(BAD_SHAPE, "multiples of 8", lda=132)                                # lda % V
+    refused(BAD_SHAPE, "multiples of 4", dtype=f32, lda=130)
+    refused(BAD_SHAPE, "16-byte aligned", misalign=dict(A=8))
+    refused(BAD_SHAPE, "16-byte aligned", misalign=dict(W=4))
+    refused(BAD_SHAPE, "alignment", misalign=dict(C=8))
+    refused(BAD_SHAPE, "alignment", residual=True, misalign=dict(residual=4))
+    refused(BAD_SHAPE, "GEGLU", geglu=True, N=96)
+    refused(BAD_SHAPE, "split-K needs N", N=126, split_k=2)
+    refused(NULL, "workspace", split_k=2, workspace=False)
+    refused(UNSUPPORTED, "LayerNorm fold", K=1280, ln=True, split_k=2)
+    refused(NULL, "both ln_colsum and ln_stats", ln_colsum=True, ln_stats=False)
+    refused(NULL, "both ln_colsum and ln_stats", ln_colsum=False, ln_stats=True)
+    refused(BAD_SHAPE, "aligned colsum", ln=True, misalign=dict(ln_colsum=8))
+    refused(BAD_SHAPE, "aligned colsum", ln=True, N=126)
+    refused(BAD_SHAPE, "w_slab_rows", w_slab_rows=128, bias=True)               # a slab is a multiple of 256 rows ...
+    refused(BAD_SHAPE, "w_slab_rows", M=384, w_slab_rows=256)                   # ... divides M ...
+    refused(BAD_SHAPE, "w_slab_rows", w_slab_rows=256, w_slab_stride=128 * 128 - 8)   # ... and slabs do not overlap
+    refused(UNSUPPORTED, "per-instance weights", w_slab_rows=256, N=126)
+    refused(UNSUPPORTED, "per-instance weights", w_slab_rows=256, transpose_rows=64, transpose_ld=64)
+    refused(BAD_SHAPE, "rowbias", rowbias=True, rows_per_batch=0)
+    refused(BAD_SHAPE, "rowbias", rowbias=True, rows_per_batch=64, ld_rowbias=120)
+    refused(BAD_SHAPE, "transpose", transpose_rows=64, transpose_ld=60)
+    # a vt that emo_gemm_vt_ok rejects: without the LayerNorm fold, a V block off the wave boundary, batches that are not whole tiles
+    refused(UNSUPPORTED, "vt", N=192, vt_cols=64, vt_rows=64, vt_ld=64)
+    refused(UNSUPPORTED, "vt", N=192, ln=True, vt_cols=56, vt_rows=64, vt_ld=64, tile=2)
+    refused(UNSUPPORTED, "vt", N=192, ln=True, vt_cols=64, vt_rows=96, vt_ld=96, tile=2)
+    refused(UNSUPPORTED, "vt", N=192, ln=True, vt_cols=64, vt_rows=64, vt_ld=64, tile=2, misalign=dict(vt=8))
+    assert ops.gemm_plan(dtype=bf16, M=256, N=192, K=128, ln=True, vt_cols=64, vt_rows=128, vt_ld=128, tile=2)[3] == 4 | 8
+    # nothing is written on a refusal; null arguments
+    plan = (C.c_int * 8)(*([-7] * 8))
+    assert lib.emo_gemm_plan(C.byref(_lib.GemmParams()), plan) == NULL and b"null" in lib.emo_last_error_string()
+    assert lib.emo_gemm_plan(None, plan) == NULL
+    p = _lib.GemmParams()
+    p.A = p.W = p.C = 256
+    p.M, p.N, p.K, p.lda, p.ldc, p.dtype, p.out_scale = 256, 128, 124, 124, 128, _lib.EMO_BF16, 1.0
+    assert lib.emo_gemm_plan(C.byref(p), plan) == BAD_SHAPE
+    assert list(plan) == [-7] * 8
+    assert lib.emo_gemm_plan(C.byref(p), None) == NULL
+    # and the same entry without a stream refuses alike (no GPU is touched in front of the checks)
+    assert lib.emo_gemm(C.byref(p), None) == BAD_SHAPE and b"multiples of 8" in lib.emo_last_error_string()
+    p.K = p.lda = 128
+    assert lib.emo_gemm_plan(C.byref(p), plan) == 0 and list(plan)[:2] == [0, 1] and plan[5] == 0      # 64x64 tiles, LDS-staged store

@@ -300,3 +300,83 @@ def test_attention_plan_runs_the_argument_checks():
     assert list(plan) == [-7] * 5
     assert ops.attention_plan(dtype=torch.bfloat16, B=24, Lq=4096, Lk0=77, heads=8, d=40)[3] == 4   # the text cross-attention of the 64x64 level
     assert ops.attention_plan(dtype=torch.bfloat16, B=24, Lq=4096, Lk0=4096, heads=8, d=40, Lk1=4096) == (6, 3, 3, 1, 0)
+
+
+def test_gemm_sweeps_reach_every_instantiation():
+    """emo_gemm_plan (csrc/gemm.hip: emo_gemm's checks, planner and launch chain run without a launch) against the case tables that
+    tests/test_gpu_gemm_sweeps.py launches: they must reach every dense instantiation dispatch_gemm / dispatch_tile can produce -
+    tile x {plain, V^T, LayerNorm fold, fold + V^T} x dtype minus what the `if constexpr` guards of dispatch_tile exclude -, both main
+    loops, every store path on every tile that can take it, and the bias / row bias both in and out of the accumulators.  The path
+    reported comes from the predicates the kernels themselves evaluate (csrc/gemm_api.h), so a table that shrinks fails here."""
+    from emote_hack_amd import ops
+    from tests import gemm_sweep_cases as S
+    paths = {n: i for i, n in enumerate(ops.GEMM_STORE_PATHS)}
+    seen, stores, loops, in_acc, vt_split = set(), set(), set(), set(), set()
+    n_cases = 0
+    for _name, cases in S.all_tables():
+        for c in cases:
+            fam, tile, phase, flags, split, store, b_acc, rb_acc = S.plan(c)
+            n_cases += 1
+            assert fam == 0 and not flags & 1, c                  # dense, the tile kernel
+            assert phase == int(tile == 7), (c, tile, phase)
+            assert split == (c.get("split_k", 1) or split), c
+            two = c["dtype"] != torch.float32
+            seen.add((c["dtype"], tile, flags & 6))
+            stores.add((two, tile, flags & 2, store))
+            loops.add(phase)
+            in_acc.add((b_acc, rb_acc))
+            if flags & 8:
+                vt_split.add((c["dtype"], tile))
+    # every instantiation: the guards of dispatch_tile leave 256x160 to the row-major kernels, 256x320 and the phase loop to the
+    # row-major 2-byte ones (plan_gemm and dispatch_tile send the other hints to 128x160 / 128x128 / 256x256)
+    excluded = {(dt_, t, f) for dt_ in S.DTYPES for t in (5, 6, 7) for f in (2, 6)} | {(torch.float32, t, f) for t in (6, 7) for f in (0, 4)}
+    want = {(dt_, t, f) for dt_ in S.DTYPES for t in range(1, 8) for f in (0, 2, 4, 6)} - excluded
+    assert len(excluded) == 22 and seen == want, (want - seen, seen - want)
+    assert loops == {0, 1}
+    want_stores = set()
+    for two in (False, True):
+        row_tiles = range(1, 8) if two else range(1, 6)
+        for t in row_tiles:
+            want_stores |= {(two, t, 0, paths[s]) for s in (("lds",) if two else ()) + ("vec_row", "scalar_row")}
+            if t != 7:      # (split-K takes the lockstep loop)
+                want_stores.add((two, t, 0, paths["splitk_ws"]))
+        want_stores |= {(two, t, 2, paths[s]) for t in (1, 2, 3, 4) for s in ("vt_quad", "vt_scalar", "splitk_ws")}
+    assert stores == want_stores, (want_stores - stores, stores - want_stores)
+    assert in_acc == {(0, 0), (0, 1), (1, 0), (1, 1)}
+    assert {t for _, t in vt_split} >= {1, 2} and {d for d, _ in vt_split} == set(S.DTYPES)
+    assert n_cases >= 14000       # (14472 when this test was written: the tables are the sweep)
+    # the fallbacks of a pinned tile
+    pl = lambda **kw: ops.gemm_plan(M=512, N=320, **kw)
+    for dt_ in (torch.bfloat16, torch.float16):
+        assert pl(dtype=dt_, K=128, tile=7)[1:3] == (7, 1)
+        assert pl(dtype=dt_, K=128 + 8, tile=7)[1:3] == (4, 0)          # ragged K
+        assert pl(dtype=dt_, K=64, tile=7)[1:3] == (4, 0)               # one stage: the phase loop needs two
+        assert pl(dtype=dt_, K=640, tile=7, split_k=2)[1:3] == (4, 0)
+        assert pl(dtype=dt_, K=128, tile=6)[1] == 6 and pl(dtype=dt_, K=128, tile=5)[1] == 5
+        assert pl(dtype=dt_, K=128, tile=5, transpose_rows=64, transpose_ld=64)[1] == 3
+    assert pl(dtype=torch.float32, K=128, tile=7)[1:3] == (4, 0)
+    assert pl(dtype=torch.float32, K=128, tile=6)[1] == 3                # 256x320 is 2-byte only: 128x160
+    for hint in (8, 9, 15):
+        assert pl(dtype=torch.bfloat16, K=128, tile=hint)[1] == 2        # above the table: 128x128
+    # GEGLU pairs value and gate tiles inside a wave: even wave widths only
+    assert {ops.gemm_plan(dtype=torch.bfloat16, M=512, N=320 * 2, K=128, geglu=True, tile=t)[1] for t in (1, 3, 5, 6)} == {2}
+    # the conv loader: the halo family where it serves, else the tile kernel with the conv flag (hints 5 / 6 fall back to 128x128)
+    conv = dict(H=16, W=16, Cin=64, stride=1, Ho=16, Wo=16)
+    assert ops.gemm_plan(dtype=torch.bfloat16, M=512, N=128, K=576, conv=conv, split_k=1) == (1, 0, 0, 0, 0, 0, 0, 0)
+    conv2 = dict(H=16, W=16, Cin=64, stride=2, Ho=8, Wo=8)
+    assert ops.gemm_plan(dtype=torch.bfloat16, M=128, N=128, K=576, conv=conv2, tile=5, split_k=1)[:4] == (0, 2, 0, 1)
+
+
+def test_planner_can_pick_a_split_with_an_empty_slice():
+    """plan_gemm caps the split at nk / 4 slices but cuts K into slices of ceil(nk / s) stages: (s - 1) * ceil(nk / s) >= nk leaves the
+    last slice without a stage (nk = 25 split 6 ways: 5 slices of 5).  The kernel must then write zeros to that slab
+    (tests/test_gpu_gemm_sweeps.py runs what this search finds).  The search covers the planner's splitting domain - few-tile dense
+    shapes, nk = 8 .. 400 stages, every dtype - and must keep finding the short-K hit and report the long-K ones."""
+    from tests import gemm_sweep_cases as S
+    hits = S.planned_empty_slices()
+    assert any(h["_nk"] == 25 and h["_S"] == 6 for h in hits)
+    assert all(S.split_empty(h["_nk"], h["_S"]) and h["_S"] <= h["_nk"] // 4 for h in hits)
+    for h in hits[:50]:
+        assert S.plan({k: v for k, v in h.items() if not k.startswith("_")})[4] == h["_S"]
+    long_k = sorted({(h["_nk"], h["_S"]) for h in hits if h["_nk"] >= 41})
+    print(f"planned splits with an empty slice: {len(hits)} of the searched shapes; nk >= 41: {long_k[:12]}")
