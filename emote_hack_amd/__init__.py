@@ -26,6 +26,10 @@ def __getattr__(name):  # heavy modules on demand
     if name in ("CLIPTextModel", "clip_text_param_shapes", "clip_text_synth_state_dict"):
         from . import clip_text
         return getattr(clip_text, name)
+    if name in ("CLIPVisionModel", "CLIPVisionModelWithProjection", "CLIPImageProcessor", "clip_vision_param_shapes",
+                "clip_vision_synth_state_dict"):
+        from . import clip_vision
+        return getattr(clip_vision, name)
     if name == "AppearanceEncoderModel":
         from .appearance_encoder import AppearanceEncoderModel
         return AppearanceEncoderModel

@@ -122,6 +122,9 @@ SIGNATURES = {
     "emo_channelnorm": (_i, [_p, _i64, _p, _p, _p, _i64, _i64, _i, _f, _i, _p, _i, _p]),
     "emo_maxpool2x2": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _p]),
     "emo_bilinear_to_nchw": (_i, [_p, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "emo_image_preprocess": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),
+    "emo_patch_rows": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "emo_vision_embed": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _f, _i, _p]),
 }
 
 _lib = None

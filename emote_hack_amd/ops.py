@@ -710,3 +710,55 @@ def bilinear_to_nchw(x: torch.Tensor, n_img: int, Cc: int, h: int, w: int, Ho: i
     y = torch.empty(n_img, Cc, Ho, Wo, device=x.device, dtype=torch.float32)
     check(_lib.load().emo_bilinear_to_nchw(px, ld, _ptr(y), n_img, Cc, h, w, Ho, Wo, dt(x), _stream()), "emo_bilinear_to_nchw")
     return y
+
+
+# ----------------------------------------------------------------------------- CLIP vision encoder front
+def image_preprocess(frames: torch.Tensor, S: int, ytap, yw, xtap, xw, span_max: int, rescale, mean, std) -> torch.Tensor:
+    """uint8 RGB frames (n, H, W, 3) -> f32 pixel_values (n, 3, S, S): transformers' CLIPImageProcessor as one launch
+    (emo_image_preprocess).  ytap / xtap int32 (S, 2) and yw / xw f32 (S, k) are the per-axis tap tables of the crop window
+    (emote_hack_amd.clip_vision.resize_crop_taps builds them on the host); rescale, mean[3], std[3] are host scalars."""
+    _need_cuda(frames, ytap, yw, xtap, xw)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    n, H, W, _ = frames.shape
+    for tap, wt in ((ytap, yw), (xtap, xw)):
+        assert tap.dtype == torch.int32 and tuple(tap.shape) == (S, 2) and tap.is_contiguous(), (tap.dtype, tap.shape)
+        assert wt.dtype == torch.float32 and wt.dim() == 2 and wt.shape[0] == S and wt.is_contiguous(), (wt.dtype, wt.shape)
+    out = torch.empty(n, 3, S, S, device=frames.device, dtype=torch.float32)
+    m3, s3 = (C.c_float * 3)(*map(float, mean)), (C.c_float * 3)(*map(float, std))
+    _launch("image_preprocess", 0.0, float(frames.numel()) + 4.0 * out.numel(),
+            lambda: check(_lib.load().emo_image_preprocess(_ptr(frames), _ptr(out), n, H, W, S, _ptr(ytap), _ptr(yw), yw.shape[1], _ptr(xtap),
+                                                           _ptr(xw), xw.shape[1], int(span_max), float(rescale), m3, s3, _stream()),
+                          "emo_image_preprocess"), tag=f"n={n} {H}x{W}->{S}")
+    return out
+
+
+def patch_rows(pixel_values: torch.Tensor, patch: int, dtype) -> torch.Tensor:
+    """pixel_values (B, 3, S, S) f32 -> (B * (S / patch)^2, ld) GEMM A rows in `dtype`, columns (c, py, px), ld = 3 * patch^2 rounded up
+    to 8 with zero pad columns (emo_patch_rows)."""
+    _need_cuda(pixel_values)
+    assert pixel_values.dtype == torch.float32 and pixel_values.dim() == 4 and pixel_values.shape[1] == 3, (pixel_values.dtype, pixel_values.shape)
+    pixel_values = pixel_values.contiguous()
+    B, _, S, S2 = pixel_values.shape
+    assert S == S2 and S % patch == 0, (S, S2, patch)
+    ld = (3 * patch * patch + 7) // 8 * 8
+    out = torch.empty(B * (S // patch) ** 2, ld, device=pixel_values.device, dtype=dtype)
+    _launch("patch_rows", 0.0, 4.0 * pixel_values.numel() + out.element_size() * float(out.numel()),
+            lambda: check(_lib.load().emo_patch_rows(_ptr(pixel_values), _ptr(out), B, S, patch, ld, dt(dtype), _stream()), "emo_patch_rows"))
+    return out
+
+
+def vision_embed(patch_out: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma, beta, B: int, eps=1e-5) -> torch.Tensor:
+    """patch_out (B * Np, C) rows, cls (C,), pos (Np + 1, C) in the compute dtype, gamma / beta f32 -> (B * (Np + 1), C) rows
+    LayerNorm([cls | patch rows] + pos): token assembly and pre_layrnorm in one launch (emo_vision_embed)."""
+    _need_cuda(patch_out, cls, pos, gamma, beta)
+    pp, ldp = _rows(patch_out)
+    Cc = patch_out.shape[1]
+    Np = patch_out.shape[0] // B
+    assert patch_out.shape[0] == B * Np and tuple(pos.shape) == (Np + 1, Cc) and tuple(cls.shape) == (Cc,), (patch_out.shape, pos.shape, cls.shape)
+    assert pos.is_contiguous() and cls.is_contiguous() and pos.dtype == cls.dtype == patch_out.dtype
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == Cc
+    y = torch.empty(B * (Np + 1), Cc, device=patch_out.device, dtype=patch_out.dtype)
+    _launch("vision_embed", 0.0, patch_out.element_size() * (2.0 * B * (Np + 1) * Cc + (Np + 1) * Cc),
+            lambda: check(_lib.load().emo_vision_embed(pp, ldp, _ptr(cls), _ptr(pos), _ptr(gamma), _ptr(beta), _ptr(y), Cc, B, Np, Cc, float(eps),
+                                                       dt(patch_out), _stream()), "emo_vision_embed"))
+    return y

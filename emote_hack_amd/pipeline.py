@@ -76,9 +76,12 @@ def slerp(v0: torch.Tensor, v1: torch.Tensor, t: float, DOT_THRESHOLD: float = 0
 
 
 class EMOAnimationPipeline:
-    def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None):
+    def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None, image_encoder=None,
+                 image_processor=None):
         """EMOAnimationPipeline.py:87-130.  The ctor forces steps_offset=1 / clip_sample=False on the
-        scheduler it is given, like the reference."""
+        scheduler it is given, like the reference.  image_encoder= (the reference's ctor call, :909-917) is a
+        CLIPVisionModelWithProjection - on these kernels emote_hack_amd.clip_vision's; image_processor= defaults to that module's
+        CLIPImageProcessor at the encoder's image_size."""
         if unet is None or scheduler is None:
             raise ValueError("unet and scheduler are required")
         if not hasattr(scheduler, "step_plan"):
@@ -89,6 +92,12 @@ class EMOAnimationPipeline:
                             "(or an object with their `step_plan(si, first)` interface)")
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
         self.unet, self.controlnet, self.scheduler = unet, controlnet, scheduler
+        if image_encoder is not None and image_processor is None:
+            from .clip_vision import CLIPImageProcessor
+            S = image_encoder.config.image_size
+            image_processor = CLIPImageProcessor(size={"shortest_edge": S}, crop_size={"height": S, "width": S},
+                                                 device=getattr(image_encoder, "device", unet.device))
+        self.image_encoder, self.image_processor = image_encoder, image_processor
         # EMOAnimationPipeline.py:105-117: ANY scheduler whose config has the key, not DDIM only - a DDPMScheduler handed to the
         # pipeline runs [981, ..., 1] on 50 of 1000 steps, like a diffusers DDPMScheduler would under the reference ctor
         if getattr(scheduler.config, "steps_offset", 1) != 1:
@@ -151,6 +160,23 @@ class EMOAnimationPipeline:
         halves = emb.split(batch_size) if do_classifier_free_guidance else (emb,)
         halves = [e.repeat(1, num_videos_per_prompt, 1).view(e.shape[0] * num_videos_per_prompt, e.shape[1], -1) for e in halves]
         return torch.cat(halves) if do_classifier_free_guidance else halves[0]
+
+    @torch.no_grad()
+    def _encode_image(self, image, device, num_videos_per_prompt, do_classifier_free_guidance):
+        """The image counterpart of _encode_prompt: the cross-attention context from `image_encoder` (:909-917), ONE token per image.
+        Nothing in the reference defines the pairing; this is the convention of the image-variation pipeline whose ctor call those lines
+        copy: cond = image_embeds.unsqueeze(1), uncond = zeros of the same shape, order [uncond, cond] as with text.
+        image: anything the image processor takes (a PIL image, an (H, W, 3) uint8 array / tensor), or pixel_values (1, 3, S, S) already.
+        -> (2, 1, D) = [uncond, cond] under classifier-free guidance, (1, 1, D) without."""
+        enc = self.image_encoder
+        S = enc.config.image_size
+        if torch.is_tensor(image) and image.is_floating_point() and image.dim() == 4 and tuple(image.shape[1:]) == (3, S, S):
+            pixel_values = image
+        else:
+            pixel_values = self.image_processor(image, return_tensors="pt").pixel_values
+        cond = enc(pixel_values.to(device)).image_embeds.unsqueeze(1)                          # (b, 1, D)
+        cond = cond.repeat(1, num_videos_per_prompt, 1).view(cond.shape[0] * num_videos_per_prompt, 1, -1)
+        return torch.cat([torch.zeros_like(cond), cond]) if do_classifier_free_guidance else cond
 
     # ------------------------------------------------------------------ the hot loop
     @torch.no_grad()
@@ -1047,6 +1073,7 @@ class EMOAnimationPipeline:
                  decoder_consistency=None, audio=None, head_rotation_speeds=None, **kwargs):
         """Signature = EMOAnimationPipeline.py:544-578.  `prompt` / `negative_prompt` are encoded by `_encode_prompt` when the
         pipeline has a tokenizer (and a text encoder, e.g. emote_hack_amd.clip_text.CLIPTextModel); text_embeddings=(2,L,D) takes precedence.
+        clip_image= (with prompt "") conditions on an image instead: `_encode_image` runs the pipeline's image_encoder on it.
         Extra keyword inputs for the parts that are out of scope here: ref_image_latents=(1,4,h,w), audio_features=(F,L_a,D),
         speed_embeddings=(1,4*C0), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
         optional): use_graphs (default: HIP-graph replay on a HIP device - the path bench.py measures), reference_group
@@ -1073,6 +1100,15 @@ class EMOAnimationPipeline:
         if appearance_encoder is None:
             raise ValueError("appearance_encoder (ReferenceNet) is required")
         text_embeddings = kwargs.get("text_embeddings")
+        clip_image = kwargs.get("clip_image")
+        if clip_image is not None:      # image conditioning: the context is the image encoder's one token (_encode_image)
+            if getattr(self, "image_encoder", None) is None:
+                raise ValueError("clip_image= needs an image_encoder on the pipeline (emote_hack_amd.clip_vision.CLIPVisionModelWithProjection)")
+            if text_embeddings is not None:
+                raise ValueError("clip_image= and text_embeddings= both name the cross-attention context: pass one")
+            if prompt not in ("", [""]):
+                raise ValueError("clip_image= replaces the prompt as the cross-attention context: call with prompt \"\"")
+            text_embeddings = self._encode_image(clip_image, self._execution_device, num_videos_per_prompt, guidance_scale > 1.0)
         if text_embeddings is None:
             if self.text_encoder is None:
                 raise ValueError("pass text_embeddings=(2,L,D) [uncond, cond], or put a tokenizer + text_encoder "

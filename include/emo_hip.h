@@ -364,6 +364,33 @@ int emo_channelnorm(const void* x, int64_t ldx, const float* gamma, const float*
 int emo_maxpool2x2(const void* x, int64_t ldx, void* y, int64_t ldy, int n_img, int H, int W, int C, int dtype, void* stream);
 int emo_bilinear_to_nchw(const void* x, int64_t ld, float* y, int n_img, int C, int h, int w, int Ho, int Wo, int dtype, void* stream);
 
+/* ---- CLIP vision encoder front (transformers CLIPVisionModelWithProjection: the `image_encoder` EMOAnimationPipeline.py:867 loads and
+ * :909-917 hands to the pipeline; its image_embeds are the `clip_condition_embeddings` of models/videonet.py:255) -----------------------
+ * emo_image_preprocess: transformers CLIPImageProcessor (resize to the shortest edge, centre crop, rescale, normalise) in one launch.
+ *   img uint8 [n][H][W][3] RGB -> out f32 [n][3][S][S].  Replaces
+ *     torch.nn.functional.interpolate(x.float(), size, mode="bicubic", antialias=True, align_corners=False), the crop,
+ *     .clamp(0, 255) * rescale, (x - mean[c]) / std[c]
+ *   in f32 with no intermediate rounding to uint8 (Keys kernel a = -0.5, support widened by the scale when shrinking, weights
+ *   renormalised to sum 1, half-pixel centres).  The resize is separable; the host hands over one tap table per axis FOR THE CROP WINDOW
+ *   (so only the window is computed, and the resize size / crop offsets live in the tables): ytap / xtap device int32 [S][2] = (first
+ *   input row / column, tap count <= ky / kx), yw / xw device f32 [S][ky] / [S][kx].  span_max = the most input columns any tile of 64
+ *   output columns touches (it sizes the LDS buffer; <= 5461).  mean / stddev: HOST float[3]; rescale: 1/255 for CLIP.  Table entries
+ *   are clamped to the frame, so a bad table reads wrong pixels, never out of bounds.
+ * emo_patch_rows: the im2col of CLIPVisionEmbeddings.patch_embedding (nn.Conv2d(3, hidden, kernel_size=P, stride=P, bias=False)):
+ *   pix f32 [B][3][S][S] -> out [B * (S/P)^2][ld] in dtype, column (c * P + py) * P + px = pix[b][c][gy * P + py][gx * P + px], so the
+ *   rows multiply patch_embedding.weight.reshape(hidden, 3 * P * P) (padded to ld with zeros); columns [3 P P, ld) are written as zero.
+ * emo_vision_embed: CLIPVisionEmbeddings.forward + CLIPVisionTransformer.pre_layrnorm in one read and one write:
+ *   row b * (Np + 1) = cls + pos[0], row b * (Np + 1) + 1 + p = patch[b * Np + p] + pos[1 + p]  (torch.cat([class_embeds, patch_embeds], 1)
+ *   + position_embedding(position_ids)), then nn.LayerNorm(C, eps) over the row with gamma / beta f32.  patch [B * Np][ldp], cls [C],
+ *   pos [Np + 1][C], y [B * (Np + 1)][ldy] in dtype; sums and statistics in f32 (mean, then centred squares - emo_layernorm's
+ *   convention), rounded once. */
+int emo_image_preprocess(const uint8_t* img, float* out, int n, int H, int W, int S, const int32_t* ytap, const float* yw, int ky,
+                         const int32_t* xtap, const float* xw, int kx, int span_max, float rescale, const float* mean,
+                         const float* stddev, void* stream);
+int emo_patch_rows(const float* pix, void* out, int B, int S, int P, int ld, int dtype, void* stream);
+int emo_vision_embed(const void* patch, int64_t ldp, const void* cls, const void* pos, const float* gamma, const float* beta, void* y,
+                     int64_t ldy, int B, int Np, int C, float eps, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
