@@ -102,6 +102,7 @@ SIGNATURES = {
     "emo_conv3x3_gn_fusable": (_i, [C.POINTER(GemmParams)]),
     "emo_gemm_vt_ok": (_i, [C.POINTER(GemmParams)]),
     "emo_gemm_plan": (_i, [C.POINTER(GemmParams), C.POINTER(C.c_int)]),
+    "emo_conv3x3_halo_plan": (_i, [C.POINTER(GemmParams), C.POINTER(C.c_int)]),
     "emo_gemm_suggest_split_k": (_i, [_i64, _i, _i, _i, _i, _i]),
     "emo_gemm_workspace_bytes": (C.c_size_t, [_i64, _i, _i]),
     "emo_attention": (_i, [C.POINTER(AttentionParams), _p]),

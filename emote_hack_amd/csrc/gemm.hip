@@ -73,9 +73,46 @@ static bool gemm_vt_ok(const emo_gemm_params& p) {
 }
 extern "C" int emo_gemm_vt_ok(const emo_gemm_params* pp) { return pp && emo_dtype_ok(pp->dtype) && gemm_vt_ok(*pp) ? 1 : 0; }
 
-// argument checks + planning + the launch chain; lp != nullptr: decide only (emo_gemm_plan) - nothing below this line touches the
-// device or dereferences an operand pointer in front of the launch itself
-static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* lp) {
+// The launch decisions of the halo family (halo_conv_ok(p) holds): patch height, and per launch the block width, the output columns
+// [n0, n0 + n) it covers, its tiles and its grid.  ONE function for the launch path and emo_conv3x3_halo_plan.
+struct HaloLaunch { int bn, n0, n; int64_t tiles, grid; };   // bn == 0: no such launch
+struct HaloPlan { int served, ph; HaloLaunch main, tail; };
+static HaloPlan plan_halo(const emo_gemm_params& p) {
+  const int He = p.upsample2x ? 2 * p.H : p.H, We = p.upsample2x ? 2 * p.W_ : p.W_;
+  const int64_t nt = (p.N + HaloGeom::BN - 1) / HaloGeom::BN;
+  // 16-row patches (8 waves, one block per CU) when they still give (nearly) every CU a block; p.tile 1 / 2 pins 8 / 16
+  const int64_t n_img = p.M / ((int64_t)He * We), tpx = (We + HaloGeom::PW - 1) / HaloGeom::PW;
+  const int64_t tiles16 = n_img * tpx * ((He + 15) / 16) * nt;
+  const bool ph16 = He % 16 == 0 && ((p.tile & 3) == 2 || ((p.tile & 3) != 1 && tiles16 >= 200));
+  // A width that is an odd multiple of 64 (N = 320 = 128 + 128 + 64): the last 128-column tile would multiply 64 columns of
+  // zeros - 17 % of the launch at N = 320.  The 64 remainder columns get their own launch of 64-channel blocks instead
+  // (same patches, half the weight tile, half the MFMAs per stage); p.tile bit 2 (4) keeps the single launch (tools/bench A/B).
+  const int n_rem = (p.N > HaloGeom::BN && p.N % HaloGeom::BN == 64 && !(p.tile & 4)) ? 64 : 0;
+  // ... and with 16-row patches the LAST 192 columns may go to 192-channel blocks (N = 320 = 128 + 192: two launches of full-width
+  // blocks instead of 128 + 128 + a half-width 64) - when a launch of one block per patch still fits the chip in ONE round: at
+  // M = 49152 (192 patches: the shared-prefix half batch) +15 %, N = 192 +23 %; at M = 98304 (384 patches) each of the two
+  // launches would run a second, half-empty round: 0.4-4.5 % SLOWER than 768 + 384 blocks (profiles/r06k_conv_bn192.txt).
+  // p.tile bit 3 (8) keeps the 64-column remainder launch, bit 4 (16) forces the 192-column blocks (tools/bench A/B)
+  const bool wide = n_rem && ph16 && !p.gn_coef && !(p.tile & 8) && (n_img * tpx * (He / 16) <= 256 || p.N == 192 || (p.tile & 16));   // (N = 192: ONE launch instead of two)
+  auto launch = [&](int n0, int n, int bn) {
+    const int64_t ntq = (n + bn - 1) / bn;
+    const int64_t tiles = n_img * tpx * (ph16 ? He / 16 : (He + 7) / 8) * ntq, slots = ph16 ? 256 : 512;
+    return HaloLaunch{bn, n0, n, tiles, tiles > slots ? slots : tiles};
+  };
+  HaloPlan h = {1, ph16 ? 16 : 8, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+  if (!n_rem) {
+    h.main = launch(0, p.N, p.N == 64 ? 64 : ((p.N == 192 && ph16 && !p.gn_coef && !(p.tile & 8)) ? 192 : HaloGeom::BN));
+    return h;
+  }
+  const int n_a = p.N - (wide ? 192 : n_rem);
+  if (n_a > 0) h.main = launch(0, n_a, HaloGeom::BN);
+  h.tail = launch(n_a, p.N - n_a, wide ? 192 : 64);
+  return h;
+}
+
+// argument checks + planning + the launch chain; lp / hp != nullptr: decide only (emo_gemm_plan / emo_conv3x3_halo_plan) - nothing
+// below this line touches the device or dereferences an operand pointer in front of the launch itself
+static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* lp, HaloPlan* hp = nullptr) {
   EMO_CHECK(pp, EMO_ERR_NULL, "emo_gemm: null params");
   const emo_gemm_params& p = *pp;
   EMO_CHECK(p.A && p.W && p.C, EMO_ERR_NULL, "emo_gemm: null pointer");
@@ -123,46 +160,25 @@ static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* l
     EMO_CHECK(p.gn_imgs_per_inst > 0 && (p.M / ((int64_t)p.H * p.W_)) % p.gn_imgs_per_inst == 0 && ((uintptr_t)p.gn_coef % 16) == 0,
               EMO_ERR_BAD_SHAPE, "emo_gemm: gn_imgs_per_inst=%d must divide the image count; gn_coef 16-byte aligned", p.gn_imgs_per_inst);
   }
-  {
-    const int He = p.upsample2x ? 2 * p.H : p.H;
-    if (conv && halo_conv_ok(p)) {
-      if (lp) { *lp = GemmLaunchPlan{1, 0, 0, 0, 0, 0, 0, 0}; return EMO_OK; }   // (the halo family: its id only)
-      const int64_t nt = (p.N + HaloGeom::BN - 1) / HaloGeom::BN;
-      // 16-row patches (8 waves, one block per CU) when they still give (nearly) every CU a block; p.tile 1 / 2 pins 8 / 16
-      const int We = p.upsample2x ? 2 * p.W_ : p.W_;
-      const int64_t n_img = p.M / ((int64_t)He * We), tpx = (We + HaloGeom::PW - 1) / HaloGeom::PW;
-      const int64_t tiles16 = n_img * tpx * ((He + 15) / 16) * nt;
-      const bool ph16 = He % 16 == 0 && ((p.tile & 3) == 2 || ((p.tile & 3) != 1 && tiles16 >= 200));
-      // A width that is an odd multiple of 64 (N = 320 = 128 + 128 + 64): the last 128-column tile would multiply 64 columns of
-      // zeros - 17 % of the launch at N = 320.  The 64 remainder columns get their own launch of 64-channel blocks instead
-      // (same patches, half the weight tile, half the MFMAs per stage); p.tile bit 2 (4) keeps the single launch (tools/bench A/B).
-      const int n_rem = (p.N > HaloGeom::BN && p.N % HaloGeom::BN == 64 && !(p.tile & 4)) ? 64 : 0;
-      // ... and with 16-row patches the LAST 192 columns may go to 192-channel blocks (N = 320 = 128 + 192: two launches of full-width
-      // blocks instead of 128 + 128 + a half-width 64) - when a launch of one block per patch still fits the chip in ONE round: at
-      // M = 49152 (192 patches: the shared-prefix half batch) +15 %, N = 192 +23 %; at M = 98304 (384 patches) each of the two
-      // launches would run a second, half-empty round: 0.4-4.5 % SLOWER than 768 + 384 blocks (profiles/r06k_conv_bn192.txt).
-      // p.tile bit 3 (8) keeps the 64-column remainder launch, bit 4 (16) forces the 192-column blocks (tools/bench A/B)
-      const bool wide = n_rem && ph16 && !p.gn_coef && !(p.tile & 8) && (n_img * tpx * (He / 16) <= 256 || p.N == 192 || (p.tile & 16));   // (N = 192: ONE launch instead of two)
-      auto launch = [&](const emo_gemm_params& q, int bn) {
-        const int64_t ntq = (q.N + bn - 1) / bn;
-        const int64_t tiles = n_img * tpx * (ph16 ? He / 16 : (He + 7) / 8) * ntq, slots = ph16 ? 256 : 512;
-        const int64_t gx = tiles > slots ? slots : tiles;
-        int rc_h = EMO_OK;
-        EMO_DISPATCH(q.dtype, "emo_gemm", rc_h = gemm_run_halo<T>(q, ph16 ? 16 : 8, bn, gx, as_stream(stream)));
-        return rc_h;
-      };
-      if (!n_rem) return launch(p, p.N == 64 ? 64 : ((p.N == 192 && ph16 && !p.gn_coef && !(p.tile & 8)) ? 192 : HaloGeom::BN));
-      emo_gemm_params a = p;
-      a.N = p.N - (wide ? 192 : n_rem);
-      const int rc_a = a.N > 0 ? launch(a, HaloGeom::BN) : EMO_OK;
-      return rc_a ? rc_a : launch(output_columns(p, a.N, p.N - a.N), wide ? 192 : 64);
-    }
+  if (conv && halo_conv_ok(p)) {
+    const HaloPlan h = plan_halo(p);
+    if (hp) { *hp = h; return EMO_OK; }
+    if (lp) { *lp = GemmLaunchPlan{1, 0, 0, 0, 0, 0, 0, 0}; return EMO_OK; }   // (the halo family: its id only)
+    auto launch = [&](const HaloLaunch& l) {
+      const emo_gemm_params q = output_columns(p, l.n0, l.n);
+      int rc_h = EMO_OK;
+      EMO_DISPATCH(q.dtype, "emo_gemm", rc_h = gemm_run_halo<T>(q, h.ph, l.bn, l.grid, as_stream(stream)));
+      return rc_h;
+    };
+    const int rc_a = h.main.bn ? launch(h.main) : EMO_OK;
+    return rc_a || !h.tail.bn ? rc_a : launch(h.tail);
   }
   GemmPlan pl = plan_gemm(p.M, p.N, p.K, p.dtype, p.geglu, p.transpose_out, p.tile & 15, p.ln_colsum != nullptr);   // (tile >> 4: tile-order override, gemm_impl.h)
   if (S > 1) {
     EMO_CHECK(p.workspace != nullptr && S <= 65535, EMO_ERR_NULL, "emo_gemm: split_k=%d needs a workspace", S);
     EMO_CHECK(p.N % 4 == 0, EMO_ERR_BAD_SHAPE, "emo_gemm: split-K needs N %% 4 == 0");
   }
+  if (hp) { *hp = HaloPlan{}; return EMO_OK; }   // (not the halo family's: served = 0)
   hipStream_t st = as_stream(stream);
   int rc = EMO_OK;
   EMO_DISPATCH(p.dtype, "emo_gemm", rc = gemm_run<T>(p, pl, S, st, lp));
@@ -178,5 +194,16 @@ extern "C" int emo_gemm_plan(const emo_gemm_params* pp, int plan[8]) {
   if (rc != EMO_OK) return rc;
   plan[0] = lp.family; plan[1] = lp.tile; plan[2] = lp.phase_loop; plan[3] = lp.flags;
   plan[4] = lp.split_k; plan[5] = lp.store; plan[6] = lp.bias_in_acc; plan[7] = lp.rb_in_acc;
+  return EMO_OK;
+}
+
+extern "C" int emo_conv3x3_halo_plan(const emo_gemm_params* pp, int plan[8]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_conv3x3_halo_plan: null plan");
+  HaloPlan h = {};
+  const int rc = gemm_entry(pp, nullptr, nullptr, &h);
+  if (rc != EMO_OK) return rc;
+  plan[0] = h.served; plan[1] = h.ph;
+  plan[2] = h.main.bn; plan[3] = (int)h.main.tiles; plan[4] = (int)h.main.grid;
+  plan[5] = h.tail.bn; plan[6] = (int)h.tail.tiles; plan[7] = (int)h.tail.grid;
   return EMO_OK;
 }

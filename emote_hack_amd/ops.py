@@ -457,6 +457,32 @@ def gemm_plan(*, dtype, M, N, K, lda=None, ldc=None, bias=False, rowbias=False, 
     return tuple(plan)
 
 
+def conv_halo_plan(*, dtype, n_img, H, W, Cin, N, upsample2x=False, lda=None, ldc=None, bias=False, rowbias=False, rows_per_batch=0,
+                   ld_rowbias=None, residual=False, ldr=None, inplace=False, out_scale=1.0, gn=False, imgs_per_inst=1, silu=True, tile=0):
+    """What the stride-1 3x3 conv of n_img frames of H x W (x Cin) to N channels launches on the halo-reuse kernel, asked of the library
+    on the host (emo_hip.h emo_conv3x3_halo_plan; no GPU needed): (served, patch height, block width / tiles / grid of the main launch,
+    block width / tiles / grid of the tail launch; 0s for a launch that does not exist or a conv the kernel does not serve).
+    Operands are described, not passed, as in gemm_plan; the output and the residual get DISJOINT fake address ranges unless
+    inplace=True says the residual is the output (then ldr = ldc).  Raises EmoHipError where emo_gemm would refuse the call."""
+    He, We = (2 * H, 2 * W) if upsample2x else (H, W)
+    p = GemmParams()
+    p.A, p.lda, p.W = 256, Cin if lda is None else lda, 256
+    p.bias = 256 if bias else None
+    if rowbias:
+        p.rowbias, p.rows_per_batch, p.ld_rowbias = 256, rows_per_batch, N if ld_rowbias is None else ld_rowbias
+    p.C, p.ldc = 1 << 40, N if ldc is None else ldc
+    if residual or inplace:
+        p.residual, p.ldr = (p.C, p.ldc) if inplace else (1 << 41, N if ldr is None else ldr)
+    p.M, p.N, p.K, p.out_scale = n_img * He * We, N, 9 * Cin, float(out_scale)
+    p.conv_taps, p.H, p.W_, p.Cin, p.stride, p.upsample2x, p.Ho, p.Wo = 9, H, W, Cin, 1, int(upsample2x), He, We
+    p.dtype, p.tile, p.split_k = dt(dtype), int(tile), 1
+    if gn:
+        p.gn_coef, p.gn_imgs_per_inst, p.gn_silu = 256, int(imgs_per_inst), int(bool(silu))
+    plan = (C.c_int * 8)()
+    check(_lib.load().emo_conv3x3_halo_plan(C.byref(p), plan), "emo_conv3x3_halo_plan")
+    return tuple(plan)
+
+
 def conv_gn_fusable(x: torch.Tensor, w: torch.Tensor, n_img: int, H: int, W: int, rowbias=None, rows_per_batch=0) -> bool:
     """Whether the stride-1 3x3 conv of x (n_img*H*W, >= Cin) with the re-laid weight w runs on the halo-reuse kernel, i.e. may take
     its GroupNorm (+ SiLU) along as conv3x3(gn=...) (emo_hip.h emo_conv3x3_gn_fusable)."""

@@ -231,6 +231,16 @@ int emo_gemm_vt_ok(const emo_gemm_params* p);
  *                       5 split-K workspace (f32 partials; the reduce kernel stores the output)
  *   plan[6], plan[7]    1 when the bias / the per-batch row bias starts the accumulators instead of being added in the epilogue */
 int emo_gemm_plan(const emo_gemm_params* p, int plan[8]);
+/* Host-only: the launch decisions of the halo-reuse 3x3 conv for p - the ones emo_gemm launches by (one function makes both).  Runs
+ * emo_gemm's argument checks and returns their status; writes nothing on a refusal, launches nothing, touches no operand (C and
+ * residual are compared as address ranges: a residual that overlaps the output is an in-place epilogue).
+ *   plan[0] served      1 = the halo-reuse kernel runs this conv; 0 = the tile kernel does (the other fields are then 0)
+ *   plan[1] patch height 8 or 16 rows
+ *   plan[2..4] the main launch: output channels per block (128; 64 at N = 64; 192 at N = 192 under emo_gemm_params.tile bit 2), tiles, grid - 0s when
+ *              there is none (N = 192 on 192-column blocks: the tail launch is the only one)
+ *   plan[5..7] the tail launch over the last 64 or 192 columns of a width that is an odd multiple of 64: block width, tiles, grid - 0s
+ *              when there is none */
+int emo_conv3x3_halo_plan(const emo_gemm_params* p, int plan[8]);
 /* heuristic split factor for (M, N, K) and the workspace it needs */
 int emo_gemm_suggest_split_k(int64_t M, int N, int K, int dtype, int geglu, int transpose_out);
 size_t emo_gemm_workspace_bytes(int64_t M, int N, int split_k);

@@ -380,3 +380,66 @@ def test_planner_can_pick_a_split_with_an_empty_slice():
         assert S.plan({k: v for k, v in h.items() if not k.startswith("_")})[4] == h["_S"]
     long_k = sorted({(h["_nk"], h["_S"]) for h in hits if h["_nk"] >= 41})
     print(f"planned splits with an empty slice: {len(hits)} of the searched shapes; nk >= 41: {long_k[:12]}")
+
+
+def test_halo_sweeps_reach_every_instantiation():
+    """emo_conv3x3_halo_plan (csrc/gemm.hip plan_halo: the function the launch path decides by, asked without a launch) against the
+    case tables that tests/test_gpu_conv_halo_sweeps.py launches.  Every case must be served by the halo-reuse kernel with the patch
+    height and the block widths it names; every "many tiles" launch must give every block two tiles and some three
+    (tiles >= 2 * grid + 1); together the cases must reach all 27 instantiations of gemm_run_halo and, in the many-tile launches,
+    both branches of the kernel's tile_of (tiles % 8 zero and not) and both halo-buffer parities from tile to tile (odd and even
+    chunk counts).  A table that shrinks, or a planner change that moves a case to another kernel, fails here."""
+    from emote_hack_amd import ops
+    from tests import halo_sweep_cases as H
+    seen, many_mod8, many_chunks = set(), set(), set()
+    for name, cases in H.all_tables():
+        assert cases, name
+        for case in cases:
+            c = H.full(case)
+            for dtype in H.DTYPES:
+                served, ph, bn_a, tiles_a, grid_a, bn_b, tiles_b, grid_b = H.plan(case, dtype)
+                assert served == 1, (name, case, dtype)                                                     # (a)
+                assert (ph, bn_a, bn_b) == (c["ph"], c["main"], c["tail"]), (name, case, dtype, ph, bn_a, bn_b)   # (b)
+                for which, bn, tiles, grid in (("main", bn_a, tiles_a, grid_a), ("tail", bn_b, tiles_b, grid_b)):
+                    if not bn:
+                        assert (tiles, grid) == (0, 0) and which not in c["many"], (name, case)
+                        continue
+                    assert grid == min(tiles, H.GRID[ph]), (name, case, tiles, grid)
+                    seen.add((dtype, ph, bn, c["gn"]))
+                    if which in c["many"]:
+                        assert tiles >= 2 * grid + 1, (name, case, dtype, which, tiles, grid)              # (c)
+                        many_mod8.add(tiles % 8 == 0)
+                        many_chunks.add(c["chunks"] % 2)
+                        # the walk of the table's tile_of covers every tile once, and the first block walks three
+                        walk = sorted(H.tile_of(i, tiles) for i in range(tiles))
+                        assert walk == list(range(tiles)) and len(range(0, tiles, grid)) >= 3
+            if name in ("many", "gn_many"):
+                assert c["many"], (name, case)
+    want = {(dtype, ph, bn, gn) for dtype in H.DTYPES for ph in (8, 16) for bn in (128, 64) for gn in (False, True)}
+    want |= {(dtype, 16, 192, False) for dtype in H.DTYPES}
+    assert len(want) == 27 and seen == want, (want - seen, seen - want)                                     # (d)
+    assert many_mod8 == {True, False} and many_chunks == {0, 1}                                             # (e)
+    # the in-place residual on a ragged frame is NOT the halo kernel's (two blocks store the overlapped pixels): the conv loader's
+    for case in H.INPLACE_RAGGED:
+        for dtype in H.DTYPES:
+            assert H.plan(case, dtype) == (0,) * 8, (case, dtype)
+            assert H.plan(dict(case, residual=1), dtype)[0] == 1         # ... the alias is the only reason
+            g = H.geometry(case, dtype)
+            conv = dict(H=case["H"], W=case["W"], Cin=g["Cin"], stride=1, Ho=case["H"], Wo=case["W"])
+            fam, _tile, _phase, flags = ops.gemm_plan(dtype=dtype, M=case["n"] * case["H"] * case["W"], N=case["N"], K=9 * g["Cin"], conv=conv,
+                                                      bias=True, residual=True, split_k=1)[:4]       # (gemm_plan's residual aliases C)
+            assert fam == 0 and flags & 1, (case, dtype)
+    # emo_gemm_plan keeps its answer for the family, and the new entry runs emo_gemm's checks
+    assert ops.gemm_plan(dtype=torch.bfloat16, M=512, N=128, K=576, conv=dict(H=16, W=16, Cin=64, stride=1, Ho=16, Wo=16), split_k=1) == (1, 0, 0, 0, 0, 0, 0, 0)
+    assert ops.conv_halo_plan(dtype=torch.bfloat16, n_img=2, H=16, W=16, Cin=64, N=128) == (1, 8, 128, 4, 4, 0, 0, 0)
+    assert ops.conv_halo_plan(dtype=torch.bfloat16, n_img=2, H=16, W=16, Cin=64, N=320, tile=2) == (1, 16, 128, 2, 2, 192, 2, 2)
+    assert ops.conv_halo_plan(dtype=torch.bfloat16, n_img=2, H=16, W=8, Cin=64, N=128) == (0,) * 8          # 8-pixel rows: the im2col loader
+    assert ops.conv_halo_plan(dtype=torch.bfloat16, n_img=200, H=16, W=16, Cin=64, N=128)[1] == 16          # 200 tiles of 16 rows: planned
+    with pytest.raises(_lib.EmoHipError):
+        ops.conv_halo_plan(dtype=torch.bfloat16, n_img=2, H=16, W=16, Cin=60, N=128)                        # Cin % 8
+    with pytest.raises(_lib.EmoHipError):
+        ops.conv_halo_plan(dtype=torch.bfloat16, n_img=2, H=16, W=8, Cin=64, N=128, gn=True)                # the fold needs the halo kernel
+    import ctypes as C
+    plan = (C.c_int * 8)(*([-7] * 8))
+    assert _lib.load().emo_conv3x3_halo_plan(C.byref(_lib.GemmParams()), plan) != 0 and list(plan) == [-7] * 8
+    assert _lib.load().emo_conv3x3_halo_plan(None, plan) != 0
