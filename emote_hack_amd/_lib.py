@@ -121,6 +121,10 @@ SIGNATURES = {
     "emo_rows_to_video": (_i, [_p, _i64, _p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _p]),
     "emo_channelnorm_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "emo_channelnorm": (_i, [_p, _i64, _p, _p, _p, _i64, _i64, _i, _f, _i, _p, _i, _p]),
+    "emo_audio_resample_taps_per_phase": (_i, [_i, _i]),
+    "emo_audio_resample": (_i, [_p, _i64, _i64, _i, _p, _i64, _i, _i, _i, _p, _i64, _i64, _p]),
+    "emo_waveform_normalize_workspace_bytes": (C.c_size_t, [_i64]),
+    "emo_waveform_normalize": (_i, [_p, _p, _i64, _f, _p, C.c_size_t, _p]),
     "emo_maxpool2x2": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _p]),
     "emo_bilinear_to_nchw": (_i, [_p, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "emo_image_preprocess": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),

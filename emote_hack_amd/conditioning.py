@@ -428,10 +428,40 @@ def audio_windows(hidden_states: torch.Tensor, m: int = 2, n: int = 2) -> torch.
     return ops.audio_windows(hs, m, n).reshape(hs.shape[0], -1)
 
 
-def audio_context_tokens(windows: torch.Tensor, num_video_frames: int, feature_dim: int = 768) -> torch.Tensor:
+def _as_fraction(v, what):
+    from fractions import Fraction
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"{what}: a pair is (numerator, denominator), got {v!r}")
+        return Fraction(int(v[0]), int(v[1]))
+    return Fraction(v)         # an int, a Fraction, a decimal string, or a float taken at its exact binary value
+
+
+def audio_frame_indices(num_video_frames: int, fps, audio_start=0, num_audio_frames: int = None, audio_frame_rate=(16000, 320)):
+    """The wav2vec2 frame under every video frame of a clip: video frame i starts at audio_start + i / fps seconds and takes audio frame
+    floor((audio_start + i / fps) * audio_frame_rate), audio_frame_rate = 16000 / prod(conv_stride) = 50 Hz for wav2vec2-base.  Exact
+    rational arithmetic (fps: an int, a Fraction or a (num, den) pair such as (30000, 1001)); returns a list of ints.  With
+    num_audio_frames given, a clip whose last frame starts at or after the end of the audio is a ValueError."""
+    fps, t0, rate = _as_fraction(fps, "fps"), _as_fraction(audio_start, "audio_start"), _as_fraction(audio_frame_rate, "audio_frame_rate")
+    if fps <= 0 or t0 < 0 or rate <= 0:
+        raise ValueError(f"fps and audio_frame_rate must be positive and audio_start >= 0, got fps={fps} audio_start={t0}")
+    idx = [math.floor((t0 + i / fps) * rate) for i in range(num_video_frames)]
+    if num_audio_frames is not None and idx and idx[-1] >= num_audio_frames:
+        raise ValueError(f"the audio ends before the clip does: video frame {num_video_frames - 1} starts at "
+                         f"{float(t0 + (num_video_frames - 1) / fps):.3f} s = audio frame {idx[-1]}, the audio has {num_audio_frames} frames "
+                         f"({float(num_audio_frames / rate):.3f} s) - pass a shorter video_length, a smaller audio_start or more audio")
+    return idx
+
+
+def audio_context_tokens(windows: torch.Tensor, num_video_frames: int, feature_dim: int = 768, fps=None, audio_start=0,
+                         audio_frame_rate=(16000, 320)) -> torch.Tensor:
     """Per-video-frame attn2 context for the UNet (`audio_features=`): windows (T_a, W * D) -> (F, W, D).  The reference never
-    aligns the 50 Hz wav2vec frames with the video frames (the audio path is unwired); this picks audio frame
-    floor(i * T_a / F) for video frame i (index arithmetic only - a documented design choice, not reference behaviour)."""
+    aligns the 50 Hz wav2vec frames with the video frames (the audio path is unwired).  Without `fps` this STRETCHES the
+    audio over the clip: audio frame floor(i * T_a / F) for video frame i.  With `fps` (and `audio_start` seconds) it keeps time:
+    audio_frame_indices.  Index arithmetic only - a documented design choice, not reference behaviour."""
     Ta = windows.shape[0]
-    idx = torch.div(torch.arange(num_video_frames, device=windows.device) * Ta, num_video_frames, rounding_mode="floor").clamp_(max=Ta - 1)
+    if fps is not None:
+        idx = torch.tensor(audio_frame_indices(num_video_frames, fps, audio_start, Ta, audio_frame_rate), dtype=torch.long, device=windows.device)
+    else:
+        idx = torch.div(torch.arange(num_video_frames, device=windows.device) * Ta, num_video_frames, rounding_mode="floor").clamp_(max=Ta - 1)
     return windows.index_select(0, idx).reshape(num_video_frames, -1, feature_dim)

@@ -10,6 +10,10 @@
 //   emo_channelnorm    : per-CHANNEL normalisation over the rows of a sequence (nn.GroupNorm(C, C) on (1, C, T): the first conv
 //                        layer of the wav2vec2 feature extractor, transformers Wav2Vec2GroupNormConvLayer) + affine + optional
 //                        erf-GELU; chunk partials in f32, re-reduced in f64 in a fixed order by every apply block (deterministic)
+//   emo_audio_resample : channel downmix + rational polyphase resampling of an utterance to the processor's rate (the sf.read /
+//                        librosa.resample / mean(axis=1) of Net.py:627-640), f32, one output sample per lane, 64-bit sample indices
+//   emo_waveform_normalize : the processor's utterance normalisation (Net.py:639), two passes (mean, then centred squares), block
+//                        partials combined in f64 in index order by every block (deterministic)
 // All HBM-bound and tiny; 16-byte accesses where the geometry allows.
 #include "common.h"
 
@@ -272,6 +276,138 @@ extern "C" int emo_channelnorm(const void* x, int64_t ldx, const float* gamma, c
   EMO_LAUNCH_CHECK();
   EMO_DISPATCH(dtype, "emo_channelnorm", (channelnorm_apply_kernel<T><<<g2, 256, 0, st>>>((const T*)x, ldx, (const float*)workspace, gamma, beta, (T*)y, ldy, S, C,
                                                                                                (int)n, eps, act)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+
+// -------------------------------------------------------------------------------------------------------------- audio resampling
+// y[n] = sum_j h[n*down - j*up] * x[j] over |n*down - j*up| <= half, x[j] = mean over channels of frame j (0 outside the utterance).
+// With t = n*down = T0*up + p the taps of output n are h[p + up*i] at j = T0 - i: row p of the phase table, column c = i + i0
+// (i0 = ceil(half / up) rounded so that every i fits; entries past +-half are 0).  Ascending j = descending c.
+__global__ __launch_bounds__(256) void audio_resample_kernel(const float* __restrict__ in, int64_t in_start, int64_t n_in, int channels,
+                                                             const float* __restrict__ tab, int tpp, int i0, int64_t up, int64_t down,
+                                                             float* __restrict__ out, int64_t out_start, int64_t n_out) {
+  for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < n_out; o += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t t = (out_start + o) * down, T0 = t / up, p = t - T0 * up;
+    const float* w = tab + p * tpp;
+    float acc = 0.f;
+    for (int c = tpp - 1; c >= 0; c--) {
+      const int64_t j = T0 - (c - i0) - in_start;          // index into the slice; global frame T0 - (c - i0)
+      float x = 0.f;
+      if (j >= 0 && j < n_in) {
+        const float* f = in + j * channels;
+        float s = f[0];
+        for (int ch = 1; ch < channels; ch++) s += f[ch];
+        x = s / (float)channels;
+      }
+      acc = fmaf(w[c], x, acc);
+    }
+    out[o] = acc;
+  }
+}
+
+extern "C" int emo_audio_resample_taps_per_phase(int up, int half) {
+  if (up < 1 || half < 0) return 0;
+  return (int)(((int64_t)half + up - 1) / up + (int64_t)half / up + 1);
+}
+extern "C" int emo_audio_resample(const float* in, int64_t in_start, int64_t n_in, int channels, const float* taps, int64_t n_taps, int up,
+                                  int down, int half, float* out, int64_t out_start, int64_t n_out, void* stream) {
+  EMO_CHECK(in && taps && out, EMO_ERR_NULL, "emo_audio_resample: null pointer");
+  EMO_CHECK(up >= 1 && down >= 1 && up <= 65536 && down <= 65536 && half >= 0 && half <= 10 * 65536, EMO_ERR_BAD_SHAPE,
+            "emo_audio_resample: up=%d down=%d half=%d", up, down, half);
+  const int tpp = emo_audio_resample_taps_per_phase(up, half);
+  EMO_CHECK(n_taps == (int64_t)up * tpp, EMO_ERR_BAD_SHAPE, "emo_audio_resample: the phase table has %lld entries, up * taps_per_phase = %lld",
+            (long long)n_taps, (long long)up * tpp);
+  EMO_CHECK(n_in > 0 && channels >= 1 && channels <= 64 && n_out > 0 && in_start >= 0 && out_start >= 0, EMO_ERR_BAD_SHAPE,
+            "emo_audio_resample: n_in=%lld channels=%d n_out=%lld in_start=%lld out_start=%lld", (long long)n_in, channels, (long long)n_out,
+            (long long)in_start, (long long)out_start);
+  const int64_t lim = (int64_t)1 << 44;      // (out_start + n_out) * down and in_start + n_in stay far inside int64
+  EMO_CHECK(n_in < lim && in_start < lim && n_out < lim && out_start < lim, EMO_ERR_BAD_SHAPE, "emo_audio_resample: index range");
+  audio_resample_kernel<<<fgrid(n_out, 256), 256, 0, as_stream(stream)>>>(in, in_start, n_in, channels, taps, tpp, (half + up - 1) / up, up, down,
+                                                                         out, out_start, n_out);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- waveform normalisation
+// y = (x - mean) / sqrt(var + eps), population variance.  Block b owns the contiguous chunk [b*per, (b+1)*per).  Pass 1: chunk sums ->
+// part[b].  Pass 2: every block combines part[0..nb) in index order (f64) into the mean, then sums the squared deviations of its
+// chunk -> part[nb + b].  Pass 3: every block combines both lists the same way and normalises.  No atomics: the same bits every run.
+static constexpr int WN_T = 256, WN_MAXB = 512;
+
+static inline int wn_blocks(int64_t n) {
+  int64_t b = (n + WN_T - 1) / WN_T;
+  return (int)(b > WN_MAXB ? WN_MAXB : (b < 1 ? 1 : b));
+}
+
+__device__ __forceinline__ float wn_block_sum(float v, float* sh) {      // fixed-order tree over the 256 lanes
+  sh[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int s = WN_T / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+
+__device__ __forceinline__ double wn_combine(const float* part, int nb, double* bc) {   // every thread gets sum(part[0..nb)) in index order
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int k = 0; k < nb; k++) a += (double)part[k];
+    *bc = a;
+  }
+  __syncthreads();
+  return *bc;
+}
+
+__global__ __launch_bounds__(WN_T) void wavenorm_sum_kernel(const float* __restrict__ x, float* __restrict__ part, int64_t n, int64_t per) {
+  __shared__ float sh[WN_T];
+  const int64_t s0 = blockIdx.x * per, s1 = s0 + per < n ? s0 + per : n;
+  float a = 0.f;
+  for (int64_t i = s0 + threadIdx.x; i < s1; i += WN_T) a += x[i];
+  a = wn_block_sum(a, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+__global__ __launch_bounds__(WN_T) void wavenorm_dev_kernel(const float* __restrict__ x, float* __restrict__ part, int64_t n, int64_t per, int nb) {
+  __shared__ float sh[WN_T];
+  __shared__ double bc;
+  const float mean = (float)(wn_combine(part, nb, &bc) / (double)n);
+  const int64_t s0 = blockIdx.x * per, s1 = s0 + per < n ? s0 + per : n;
+  float a = 0.f;
+  for (int64_t i = s0 + threadIdx.x; i < s1; i += WN_T) {
+    const float d = x[i] - mean;
+    a = fmaf(d, d, a);
+  }
+  a = wn_block_sum(a, sh);
+  if (threadIdx.x == 0) part[nb + blockIdx.x] = a;
+}
+
+__global__ __launch_bounds__(WN_T) void wavenorm_apply_kernel(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ y,
+                                                              int64_t n, int nb, float eps) {
+  __shared__ double bc[2];
+  const float mean = (float)(wn_combine(part, nb, &bc[0]) / (double)n);
+  const float rstd = (float)(1.0 / sqrt(wn_combine(part + nb, nb, &bc[1]) / (double)n + (double)eps));
+  for (int64_t i = blockIdx.x * (int64_t)WN_T + threadIdx.x; i < n; i += (int64_t)gridDim.x * WN_T) y[i] = (x[i] - mean) * rstd;
+}
+
+extern "C" size_t emo_waveform_normalize_workspace_bytes(int64_t n) { return (size_t)wn_blocks(n) * 2 * sizeof(float); }
+extern "C" int emo_waveform_normalize(const float* x, float* y, int64_t n, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+  EMO_CHECK(x && y && workspace, EMO_ERR_NULL, "emo_waveform_normalize: null pointer");
+  EMO_CHECK(n > 0 && eps >= 0.f, EMO_ERR_BAD_SHAPE, "emo_waveform_normalize: n=%lld eps=%g", (long long)n, (double)eps);
+  EMO_CHECK(workspace_bytes >= emo_waveform_normalize_workspace_bytes(n), EMO_ERR_BAD_SHAPE,
+            "emo_waveform_normalize: workspace of %llu bytes, emo_waveform_normalize_workspace_bytes(%lld) = %llu",
+            (unsigned long long)workspace_bytes, (long long)n, (unsigned long long)emo_waveform_normalize_workspace_bytes(n));
+  const int nb = wn_blocks(n);
+  const int64_t per = (n + nb - 1) / nb;
+  hipStream_t st = as_stream(stream);
+  wavenorm_sum_kernel<<<nb, WN_T, 0, st>>>(x, (float*)workspace, n, per);
+  EMO_LAUNCH_CHECK();
+  wavenorm_dev_kernel<<<nb, WN_T, 0, st>>>(x, (float*)workspace, n, per, nb);
+  EMO_LAUNCH_CHECK();
+  wavenorm_apply_kernel<<<nb, WN_T, 0, st>>>(x, (const float*)workspace, y, n, nb, eps);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }

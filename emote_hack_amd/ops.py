@@ -720,6 +720,42 @@ def channel_norm(x: torch.Tensor, gamma, beta, eps=1e-5, gelu=False) -> torch.Te
     return y
 
 
+def audio_resample(frames: torch.Tensor, taps: torch.Tensor, up: int, down: int, half: int, in_start: int = 0, out_start: int = 0,
+                   n_out: int = None) -> torch.Tensor:
+    """Interleaved f32 frames (n_in, channels) holding global frames in_start .. -> the n_out mono samples from global output index
+    out_start on, resampled by up / down: y[n] = sum_j h[n * down - j * up] * mean_c frames[j, c] (emo_audio_resample; Net.py:627-640).
+    taps: the f32 phase table (up, taps_per_phase) of emote_hack_amd.audio_io.phase_table.  n_out defaults to the whole utterance,
+    ceil(n_in * up / down) (with in_start = out_start = 0)."""
+    _need_cuda(frames, taps)
+    assert frames.dtype == torch.float32 and frames.dim() == 2 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    assert taps.dtype == torch.float32 and taps.dim() == 2 and taps.is_contiguous(), (taps.dtype, taps.shape)
+    n_in, ch = frames.shape
+    if n_out is None:
+        n_out = -(-n_in * up // down)
+    out = torch.empty(n_out, device=frames.device, dtype=torch.float32)
+    _launch("audio_resample", 2.0 * n_out * taps.shape[1], 4.0 * (frames.numel() + n_out),
+            lambda: check(_lib.load().emo_audio_resample(_ptr(frames), int(in_start), n_in, ch, _ptr(taps), taps.numel(), int(up), int(down), int(half),
+                                                         _ptr(out), int(out_start), int(n_out), _stream()), "emo_audio_resample"),
+            tag=f"{up}/{down}")
+    return out
+
+
+def waveform_normalize(x: torch.Tensor, eps: float = 1e-7, workspace: torch.Tensor = None) -> torch.Tensor:
+    """(x - mean) / sqrt(var + eps) over the n f32 samples of one utterance, population variance, two passes in a fixed order
+    (emo_waveform_normalize; Net.py:639).  workspace: optional device buffer of >= emo_waveform_normalize_workspace_bytes(n) bytes."""
+    _need_cuda(x, workspace)
+    assert x.dtype == torch.float32 and x.is_contiguous(), (x.dtype, x.shape)
+    lib = _lib.load()
+    n = x.numel()
+    if workspace is None:
+        workspace = torch.empty(max(lib.emo_waveform_normalize_workspace_bytes(n) // 4, 1), device=x.device, dtype=torch.float32)
+    y = torch.empty_like(x)
+    _launch("waveform_normalize", 0.0, 16.0 * n,
+            lambda: check(lib.emo_waveform_normalize(_ptr(x), _ptr(y), n, float(eps), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                                     _stream()), "emo_waveform_normalize"))
+    return y
+
+
 def maxpool2x2(x: torch.Tensor, n_img: int, H: int, W: int) -> torch.Tensor:
     """nn.MaxPool2d(2, 2) over NHWC rows (Net.py:828)."""
     _need_cuda(x)

@@ -27,6 +27,8 @@ from __future__ import annotations
 import copy
 import logging
 import math
+import numbers
+import os
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Callable, List, Optional, Union
@@ -77,11 +79,12 @@ def slerp(v0: torch.Tensor, v1: torch.Tensor, t: float, DOT_THRESHOLD: float = 0
 
 class EMOAnimationPipeline:
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None, image_encoder=None,
-                 image_processor=None):
+                 image_processor=None, speed_encoder=None):
         """EMOAnimationPipeline.py:87-130.  The ctor forces steps_offset=1 / clip_sample=False on the
         scheduler it is given, like the reference.  image_encoder= (the reference's ctor call, :909-917) is a
         CLIPVisionModelWithProjection - on these kernels emote_hack_amd.clip_vision's; image_processor= defaults to that module's
-        CLIPImageProcessor at the encoder's image_size."""
+        CLIPImageProcessor at the encoder's image_size.  speed_encoder= is an emote_hack_amd.conditioning.SpeedEncoder for
+        `__call__(head_rotation_speeds=)`; the attribute may also be assigned afterwards."""
         if unet is None or scheduler is None:
             raise ValueError("unet and scheduler are required")
         if not hasattr(scheduler, "step_plan"):
@@ -98,6 +101,7 @@ class EMOAnimationPipeline:
             image_processor = CLIPImageProcessor(size={"shortest_edge": S}, crop_size={"height": S, "width": S},
                                                  device=getattr(image_encoder, "device", unet.device))
         self.image_encoder, self.image_processor = image_encoder, image_processor
+        self.speed_encoder = speed_encoder
         # EMOAnimationPipeline.py:105-117: ANY scheduler whose config has the key, not DDIM only - a DDPMScheduler handed to the
         # pipeline runs [981, ..., 1] on 50 of 1000 steps, like a diffusers DDPMScheduler would under the reference ctor
         if getattr(scheduler.config, "steps_offset", 1) != 1:
@@ -1074,8 +1078,15 @@ class EMOAnimationPipeline:
         """Signature = EMOAnimationPipeline.py:544-578.  `prompt` / `negative_prompt` are encoded by `_encode_prompt` when the
         pipeline has a tokenizer (and a text encoder, e.g. emote_hack_amd.clip_text.CLIPTextModel); text_embeddings=(2,L,D) takes precedence.
         clip_image= (with prompt "") conditions on an image instead: `_encode_image` runs the pipeline's image_encoder on it.
+        audio= is a .wav path (any sample rate, any channel count: read, downmixed, resampled to 16 kHz and normalised by
+        emote_hack_amd.audio_io, then wav2vec2 through feature_extractor=), a (samples, sample_rate) pair, or a bare waveform at 16 kHz
+        (audio_sample_rate= names another rate).  fps= (an int, a Fraction or a (num, den) pair) with audio_start= seconds keeps time:
+        video frame i takes the wav2vec2 frame at audio_start + i / fps (ValueError when the audio ends before the clip); without fps
+        the audio is stretched over the clip.  head_rotation_speeds= is ONE speed per clip (a float or a one-element f32 tensor) encoded by
+        the pipeline's speed_encoder into `speed_embeddings` (one shared row); the reference's own `SpeedEncoder(10, 64)` asserts at
+        Net.py:212 (9 bucket centres), so 9 buckets is the constructible choice, at the UNet's time-embedding width.
         Extra keyword inputs for the parts that are out of scope here: ref_image_latents=(1,4,h,w), audio_features=(F,L_a,D),
-        speed_embeddings=(1,4*C0), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
+        speed_embeddings=(1,4*C0) (takes precedence over head_rotation_speeds), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
         optional): use_graphs (default: HIP-graph replay on a HIP device - the path bench.py measures), reference_group
         (ReferenceNet timesteps per batched pass; default 10, the configuration bench.py measures - 25 would make two passes per 50-step clip,
         40.03 vs 40.38 ms per step), reference_lookahead, fusion_blocks, motion_latents, reuse_state
@@ -1125,18 +1136,48 @@ class EMOAnimationPipeline:
             ref_lat = self._source_image_latents(source_image, width, height)   # :686-689 -> images2latents (:402-414)
         if audio is not None and kwargs.get("audio_features") is None:
             # :592-593 `audio_features = feature_extractor.extract_features_from_mp4(audio, m=2, n=2)` (a module-level extractor
-            # there): here `audio` is the mono 16 kHz waveform (the container demux / resampling of Net.py:670-735 stays with the
-            # caller) and feature_extractor= an emote_hack_amd.wav2vec2.Wav2VecFeatureExtractor with caller-loaded weights
+            # there; the file read, resampling and channel mean of Net.py:627-640 behind it): feature_extractor= is an
+            # emote_hack_amd.wav2vec2.Wav2VecFeatureExtractor with caller-loaded weights
             fx = kwargs.get("feature_extractor")
             if fx is None:
                 raise ValueError("audio= needs feature_extractor= (emote_hack_amd.wav2vec2.Wav2VecFeatureExtractor), or pass audio_features=")
-            if isinstance(audio, (str, bytes)):
-                raise ValueError("audio= takes the decoded mono 16 kHz waveform (file reading / demuxing is outside this path)")
             from .conditioning import audio_context_tokens
-            windows = fx.extract_features(audio, m=2, n=2)
-            kwargs["audio_features"] = audio_context_tokens(windows, video_length, fx.model.config.hidden_size)
+            rate = kwargs.get("audio_sample_rate")
+            if isinstance(audio, bytes):
+                raise ValueError("audio= takes a .wav path, a (samples, sample_rate) pair or a waveform, not the file's bytes")
+            if isinstance(audio, (str, os.PathLike)):
+                if rate is not None:
+                    raise ValueError("audio_sample_rate= names the rate of a bare waveform; a file carries its own")
+                path = os.fspath(audio)
+                windows = (fx.extract_features_from_wav if path.lower().endswith(".wav") else fx.extract_features_from_mp4)(path, m=2, n=2)
+            else:
+                if isinstance(audio, tuple) and len(audio) == 2 and isinstance(audio[1], numbers.Integral):
+                    if rate is not None and int(rate) != audio[1]:
+                        raise ValueError(f"audio=(samples, {audio[1]}) and audio_sample_rate={rate} disagree")
+                    audio, rate = audio[0], int(audio[1])
+                # a bare waveform without a rate stays "mono or multi-channel at 16 kHz", on the host path as before
+                windows = fx.extract_features(audio, m=2, n=2) if rate is None else fx.extract_features(audio, m=2, n=2, sample_rate=int(rate))
+            cfg = fx.model.config
+            kwargs["audio_features"] = audio_context_tokens(windows, video_length, cfg.hidden_size, fps=kwargs.get("fps"),
+                                                            audio_start=kwargs.get("audio_start", 0),
+                                                            audio_frame_rate=(fx.sampling_rate, math.prod(cfg.conv_stride)))
         if head_rotation_speeds is not None and kwargs.get("speed_embeddings") is None:
-            raise NotImplementedError("pass speed_embeddings= (see emote_hack_amd.conditioning.SpeedEncoder)")
+            # :783-784 hands `head_rotation_speeds` to a UNet that rejects it; here ONE speed per clip goes through the pipeline's
+            # SpeedEncoder (Net.py:198-258) into the UNet's class-embedding slot, one row shared by the CFG halves
+            enc = getattr(self, "speed_encoder", None)
+            if enc is None:
+                raise ValueError("head_rotation_speeds= needs a speed_encoder on the pipeline (emote_hack_amd.conditioning.SpeedEncoder(9, "
+                                 "4 * block_out_channels[0]) with loaded weights: pass speed_encoder= to the constructor or assign "
+                                 "pipe.speed_encoder), or pass speed_embeddings=(1, 4 * block_out_channels[0])")
+            v = torch.as_tensor(head_rotation_speeds, dtype=torch.float32).reshape(-1)
+            if v.numel() != 1:
+                raise ValueError(f"head_rotation_speeds= takes ONE speed per clip (a float or a one-element tensor), got {v.numel()} values: "
+                                 "per-frame speeds would need a per-frame time embedding - run one clip per speed, or pass speed_embeddings=")
+            width = 4 * self.unet.config.block_out_channels[0]
+            if enc.speed_embedding_dim != width:
+                raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width}: "
+                                 f"build SpeedEncoder(9, {width})")
+            kwargs["speed_embeddings"] = enc(v)
         if init_latents is not None:   # (b f) c h w -> b c f h w  (:657-658)
             bf, c4, hh, ww = init_latents.shape
             lat = init_latents.reshape(bf // video_length, video_length, c4, hh, ww).permute(0, 2, 1, 3, 4)

@@ -19,6 +19,7 @@ Only the wav2vec2-base family is built (feat_extract_norm "group", post-LN encod
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 
 import torch
@@ -247,20 +248,40 @@ def normalize_waveform(x: torch.Tensor) -> torch.Tensor:
 
 
 class Wav2VecFeatureExtractor:
-    """Net.py:607-667 without the file IO: `model` is a Wav2Vec2Model with caller-loaded weights (the reference downloads
-    'facebook/wav2vec2-base-960h'); `extract_features(waveform)` takes the mono 16 kHz samples `sf.read` / `librosa.resample` produce
-    (Net.py:627-636) and returns what extract_features_from_wav returns: (T, (m + n + 1) * hidden) f32."""
+    """Net.py:607-667: `model` is a Wav2Vec2Model with caller-loaded weights (the reference downloads 'facebook/wav2vec2-base-960h').
+    `extract_features(waveform)` takes the mono 16 kHz samples `sf.read` / `librosa.resample` produce (Net.py:627-636) and returns what
+    extract_features_from_wav returns: (T, (m + n + 1) * hidden) f32.  With `sample_rate=` the samples are at that rate and the whole
+    signal path runs on the device (emote_hack_amd.audio_io.prepare_waveform: downmix + resampling + normalisation kernels);
+    `extract_features_from_wav` also takes the file's path, like the reference."""
     sampling_rate = 16000
 
     def __init__(self, model: Wav2Vec2Model, device="cuda"):
         self.model, self.device = model, torch.device(device)
 
-    def extract_features(self, waveform, m: int = 2, n: int = 2) -> torch.Tensor:
+    def extract_features(self, waveform, m: int = 2, n: int = 2, sample_rate=None) -> torch.Tensor:
+        from .conditioning import audio_windows
+        if sample_rate is not None:        # any rate (16000 too): the device front-end
+            from .audio_io import prepare_waveform
+            return audio_windows(self.model(prepare_waveform(waveform, sample_rate, self.device)).last_hidden_state, m, n)
         wf = torch.as_tensor(waveform, dtype=torch.float32)
         if wf.dim() > 1:
             wf = wf.mean(dim=1)                                    # multi-channel audio: mean over channels (Net.py:634-636)
         hs = self.model(normalize_waveform(wf).to(self.device)).last_hidden_state
-        from .conditioning import audio_windows
         return audio_windows(hs, m, n)
 
-    extract_features_from_wav = extract_features
+    def extract_features_from_wav(self, audio, m: int = 2, n: int = 2, sample_rate=None) -> torch.Tensor:
+        """Net.py:614-667: `audio` is the path of a .wav file (read by emote_hack_amd.audio_io.read_wav, at the file's own rate), or
+        the samples themselves as in extract_features."""
+        if isinstance(audio, (str, os.PathLike)):
+            from .audio_io import read_wav
+            audio, sample_rate = read_wav(audio)
+        return self.extract_features(audio, m, n, sample_rate)
+
+    def extract_features_from_mp4(self, video_path, m: int = 2, n: int = 2) -> torch.Tensor:
+        """Net.py:670-735 reads `<video>.wav` beside the video and writes it from the container first when it is missing (:683-692).
+        Demuxing is not built here: without that .wav this is a ValueError."""
+        audio_path = os.path.splitext(os.fspath(video_path))[0] + ".wav"
+        if not os.path.exists(audio_path):
+            raise ValueError(f"extract_features_from_mp4: {audio_path!r} does not exist and demuxing a video container is not built - "
+                             "extract the audio track to that .wav first (e.g. ffmpeg -i video.mp4 video.wav), or pass the samples")
+        return self.extract_features_from_wav(audio_path, m, n)

@@ -369,6 +369,27 @@ int emo_rows_to_video(const void* x, int64_t ld, float* y, int B, int C, int F, 
 size_t emo_channelnorm_workspace_bytes(int64_t S, int C);
 int emo_channelnorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, int64_t S, int C, float eps,
                     int act, void* workspace, int dtype, void* stream);
+/* emo_audio_resample: the sf.read / librosa.resample / mean(axis=1) of Wav2VecFeatureExtractor.extract_features_from_wav (Net.py:627-640)
+ *   as one pass - channel downmix + rational polyphase resampling, f32.  With g = gcd(in_rate, out_rate), up = out_rate / g,
+ *   down = in_rate / g, half = 10 * max(up, down) and f32 taps h[-half .. half] (a Kaiser-windowed sinc designed on the host in f64,
+ *   emote_hack_amd.audio_io.resample_taps), global output sample n is
+ *     y[n] = sum_j h[n * down - j * up] * x[j]   over every j with |n * down - j * up| <= half, accumulated in ASCENDING j by fmaf,
+ *     x[j] = (in[j][0] + ... + in[j][channels - 1]) / channels, summed in channel order; x[j] = 0 outside the slice.
+ *   in: interleaved frames [n_in][channels] holding GLOBAL frames in_start .. in_start + n_in - 1; out[i] = y[out_start + i],
+ *   i < n_out.  A long recording is resampled in pieces: a sample has the same bits whichever piece produced it, given a slice that
+ *   covers its taps.  All sample indices are 64-bit.  taps: the phase table [up][tpp], tpp = emo_audio_resample_taps_per_phase(up, half)
+ *   = ceil(half / up) + floor(half / up) + 1, entry [p][c] = h[p + up * (c - ceil(half / up))] (0 where that lies outside
+ *   +-half); n_taps = up * tpp is checked.  up, down <= 65536, channels <= 64.
+ * emo_waveform_normalize: the utterance normalisation of `self.processor(...)` (Net.py:639; Wav2Vec2FeatureExtractor do_normalize):
+ *   y = (x - mean) / sqrt(var + eps) over n f32 samples, population variance, TWO passes (the mean, then the centred squares - a
+ *   recording with a DC offset does not cancel).  Block partials in the workspace are combined in index order in f64: the result is
+ *   bit-reproducible from run to run.  workspace_bytes must be >= emo_waveform_normalize_workspace_bytes(n), else EMO_ERR_BAD_SHAPE.
+ *   y must not alias x. */
+int emo_audio_resample_taps_per_phase(int up, int half);
+int emo_audio_resample(const float* in, int64_t in_start, int64_t n_in, int channels, const float* taps, int64_t n_taps, int up, int down,
+                       int half, float* out, int64_t out_start, int64_t n_out, void* stream);
+size_t emo_waveform_normalize_workspace_bytes(int64_t n);
+int emo_waveform_normalize(const float* x, float* y, int64_t n, float eps, void* workspace, size_t workspace_bytes, void* stream);
 /* FaceLocator (Net.py:819-855): nn.MaxPool2d(2, 2) over NHWC rows (H, W -> H/2, W/2), and
  * F.interpolate(logits, size=(Ho, Wo), mode='bilinear', align_corners=False) of rows ((n) h w, ld) into (n, C, Ho, Wo) f32. */
 int emo_maxpool2x2(const void* x, int64_t ldx, void* y, int64_t ldy, int n_img, int H, int W, int C, int dtype, void* stream);
