@@ -91,6 +91,7 @@ SIGNATURES = {
     "emo_groupnorm_apply": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
     "emo_groupnorm_coeffs": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _f, _i, _p]),
     "emo_groupnorm_one_launch_ok": (_i, [_i, _i64, _i, _i, _i]),
+    "emo_groupnorm_plan": (_i, [_i, _i64, _i, _i, _i, C.POINTER(C.c_int)]),
     "emo_groupnorm": (_i, [_p, _i, _p, _p, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
     "emo_groupnorm_apply_mod": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
     "emo_groupnorm_mod": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
@@ -98,6 +99,7 @@ SIGNATURES = {
     "emo_groupnorm_fold_linear": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _f, _i, _p]),
     "emo_layernorm": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _f, _p, _i, _i, _i, _p]),
     "emo_layernorm_stats": (_i, [_p, _i, _p, _i64, _i, _f, _i, _p]),
+    "emo_layernorm_plan": (_i, [_i64, _i, _i, C.POINTER(C.c_int)]),
     "emo_gemm": (_i, [C.POINTER(GemmParams), _p]),
     "emo_conv3x3_gn_fusable": (_i, [C.POINTER(GemmParams)]),
     "emo_gemm_vt_ok": (_i, [C.POINTER(GemmParams)]),

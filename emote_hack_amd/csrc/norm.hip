@@ -61,9 +61,15 @@ static inline GnGeom gn_geom(int N, int64_t S, int C, int G, int V) {
   return g;
 }
 extern "C" size_t emo_groupnorm_workspace_bytes(int N, int64_t S, int C, int G) {
-  // the chunk count depends on the element width through RP; size for the larger of the two
-  const GnGeom a = gn_geom(N, S, C, G, 8), b = gn_geom(N, S, C, G, 4);
-  const int ns = a.nsplit_stats > b.nsplit_stats ? a.nsplit_stats : b.nsplit_stats;
+  // the chunk count depends on the element width through RP; size for the larger of the two - of the widths that divide C (a row
+  // narrower than a vector has no geometry: C = 4 is an f32 tensor only); 0 for a shape no entry serves
+  if (N <= 0 || S <= 0 || C <= 0 || G <= 0) return 0;
+  int ns = 0;
+  for (int V = 8; V >= 4; V >>= 1) {
+    if (C % V) continue;
+    const GnGeom g = gn_geom(N, S, C, G, V);
+    if (g.nsplit_stats > ns) ns = g.nsplit_stats;
+  }
   return (size_t)N * ns * G * 2 * sizeof(float);
 }
 
@@ -585,6 +591,24 @@ extern "C" int emo_groupnorm_one_launch_ok(int N, int64_t S, int C, int G, int d
   return gn1_geom(N, S, C, G, V).ok;
 }
 
+// What the GroupNorm entries would launch for (N, S, C, G, dtype), without a launch: the gn_geom / gn1_geom the launches themselves
+// call.  plan[0..5]: NC, channels per column part, row slots RP, nsplit_stats, nsplit_apply, wide (a part wider than one block's
+// 256 column vectors: the GN_MAXJ arm);  plan[6..11] the one-launch kernel: ok, GPB, Wc, NT, R, row slots (zeros where it does
+// not fit).  Returns what gn_check returns for contiguous rows and writes nothing on a refusal.
+extern "C" int emo_groupnorm_plan(int N, int64_t S, int C, int G, int dtype, int plan[12]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_groupnorm_plan: null pointer");
+  int rc = gn_check("emo_groupnorm_plan", N, S, C, G, C, dtype);
+  if (rc) return rc;
+  const int V = emo_dtype_vec(dtype);
+  const GnGeom gg = gn_geom(N, S, C, G, V);
+  const Gn1Geom g1 = gn1_geom(N, S, C, G, V);
+  plan[0] = gg.NC; plan[1] = gg.Cp; plan[2] = gg.RP; plan[3] = gg.nsplit_stats; plan[4] = gg.nsplit_apply;
+  plan[5] = gg.Cp / V > GN_THREADS ? 1 : 0;
+  plan[6] = g1.ok; plan[7] = g1.ok ? g1.GPB : 0; plan[8] = g1.ok ? g1.Wc : 0; plan[9] = g1.NT; plan[10] = g1.R;
+  plan[11] = g1.ok ? g1.NT / (g1.Wc / V) : 0;
+  return EMO_OK;
+}
+
 static int gn_one_launch(const char* who, const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y,
                          int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
   EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "%s: null pointer", who);
@@ -728,6 +752,41 @@ extern "C" int emo_groupnorm_fold_linear(const void* partials, const float* gamm
 // Optional fused temporal positional-encoding add (motion_module.py:246-248 applied after the norm, :282-283).
 static constexpr int LN_MAXV = 5;
 
+// Launch geometry of both LayerNorm kernels: the lanes per row, the rows a wavefront holds, the grid of 4-wave blocks (capped:
+// the kernels stride over the rows by whole grids) and whether that stride runs a second trip.
+struct LnGeom { int lpr, rpw, grid, second_trip; };
+static inline LnGeom ln_geom(int64_t M, int CV) {
+  LnGeom g;
+  g.lpr = 1;
+  while (g.lpr * LN_MAXV < CV) g.lpr *= 2;
+  g.rpw = 64 / g.lpr;
+  int64_t n = (M + 4 * g.rpw - 1) / (4 * g.rpw);
+  g.second_trip = n > 256 * 16;
+  if (n > 256 * 16) n = 256 * 16;
+  g.grid = (int)n;
+  return g;
+}
+
+static int ln_check(const char* who, int64_t M, int C, int ldx, int ldy, int dtype) {
+  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "%s: dtype %d", who, dtype);
+  const int V = emo_dtype_vec(dtype);
+  EMO_CHECK(M > 0 && C > 0 && C % V == 0 && ldx % V == 0 && ldy % V == 0 && ldx >= C && ldy >= C, EMO_ERR_BAD_SHAPE,
+            "%s: M=%lld C=%d ldx=%d ldy=%d", who, (long long)M, C, ldx, ldy);
+  EMO_CHECK(C / V <= 64 * LN_MAXV, EMO_ERR_UNSUPPORTED, "%s: C=%d too wide", who, C);
+  return EMO_OK;
+}
+
+// What emo_layernorm / emo_layernorm_stats would launch for (M, C, dtype), without a launch: plan = LPR, rows per wavefront, grid,
+// second trip of the grid-stride loop (0 / 1).  Returns what their shape checks return and writes nothing on a refusal.
+extern "C" int emo_layernorm_plan(int64_t M, int C, int dtype, int plan[4]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_layernorm_plan: null pointer");
+  int rc = ln_check("emo_layernorm_plan", M, C, C, C, dtype);
+  if (rc) return rc;
+  const LnGeom g = ln_geom(M, C / emo_dtype_vec(dtype));
+  plan[0] = g.lpr; plan[1] = g.rpw; plan[2] = g.grid; plan[3] = g.second_trip;
+  return EMO_OK;
+}
+
 template <typename T, int LPR>
 __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, T* __restrict__ y, int ldy, int64_t M, int C,
@@ -839,19 +898,13 @@ __global__ __launch_bounds__(256) void layernorm_stats_kernel(const T* __restric
 
 extern "C" int emo_layernorm_stats(const void* x, int ldx, float* stats, int64_t M, int C, float eps, int dtype, void* stream) {
   EMO_CHECK(x && stats, EMO_ERR_NULL, "emo_layernorm_stats: null pointer");
-  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_layernorm_stats: dtype %d", dtype);
-  const int V = emo_dtype_vec(dtype);
-  EMO_CHECK(M > 0 && C > 0 && C % V == 0 && ldx % V == 0 && ldx >= C, EMO_ERR_BAD_SHAPE, "emo_layernorm_stats: M=%lld C=%d ldx=%d", (long long)M, C, ldx);
-  EMO_CHECK(C / V <= 64 * LN_MAXV, EMO_ERR_UNSUPPORTED, "emo_layernorm_stats: C=%d too wide", C);
+  int rc = ln_check("emo_layernorm_stats", M, C, ldx, ldx, dtype);
+  if (rc) return rc;
   EMO_CHECK(((uintptr_t)stats % 8) == 0, EMO_ERR_BAD_SHAPE, "emo_layernorm_stats: stats alignment");
   hipStream_t st = as_stream(stream);
-  const int CV = C / V;
-  int lpr = 1;
-  while (lpr * LN_MAXV < CV) lpr *= 2;
-  const int rpw = 64 / lpr;
-  int64_t g = (M + 4 * rpw - 1) / (4 * rpw); if (g > 256 * 16) g = 256 * 16;
-#define EMO_LNS(L) EMO_DISPATCH(dtype, "emo_layernorm_stats", (layernorm_stats_kernel<T, L><<<(int)g, 256, 0, st>>>((const T*)x, ldx, stats, M, C, eps)))
-  switch (lpr) {
+  const LnGeom lg = ln_geom(M, C / emo_dtype_vec(dtype));
+#define EMO_LNS(L) EMO_DISPATCH(dtype, "emo_layernorm_stats", (layernorm_stats_kernel<T, L><<<lg.grid, 256, 0, st>>>((const T*)x, ldx, stats, M, C, eps)))
+  switch (lg.lpr) {
     case 1: EMO_LNS(1); break;
     case 2: EMO_LNS(2); break;
     case 4: EMO_LNS(4); break;
@@ -868,13 +921,9 @@ extern "C" int emo_layernorm_stats(const void* x, int ldx, float* stats, int64_t
 template <typename T>
 static void launch_layernorm(const T* x, int ldx, const float* gamma, const float* beta, T* y, int ldy, int64_t M, int C, float eps,
                              const float* pe, int rpf, int frames, hipStream_t st) {
-  const int CV = C / TT<T>::VEC;
-  int lpr = 1;
-  while (lpr * LN_MAXV < CV) lpr *= 2;
-  const int rpw = 64 / lpr;
-  int64_t g = (M + 4 * rpw - 1) / (4 * rpw); if (g > 256 * 16) g = 256 * 16;
-#define EMO_LN(L) layernorm_kernel<T, L><<<(int)g, 256, 0, st>>>(x, ldx, gamma, beta, y, ldy, M, C, eps, pe, rpf, frames)
-  switch (lpr) {
+  const LnGeom lg = ln_geom(M, C / TT<T>::VEC);
+#define EMO_LN(L) layernorm_kernel<T, L><<<lg.grid, 256, 0, st>>>(x, ldx, gamma, beta, y, ldy, M, C, eps, pe, rpf, frames)
+  switch (lg.lpr) {
     case 1: EMO_LN(1); break;
     case 2: EMO_LN(2); break;
     case 4: EMO_LN(4); break;
@@ -889,11 +938,8 @@ static void launch_layernorm(const T* x, int ldx, const float* gamma, const floa
 extern "C" int emo_layernorm(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int64_t M, int C,
                              float eps, const float* pe, int rows_per_frame, int frames, int dtype, void* stream) {
   EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "emo_layernorm: null pointer");
-  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_layernorm: dtype %d", dtype);
-  const int V = emo_dtype_vec(dtype);
-  EMO_CHECK(M > 0 && C > 0 && C % V == 0 && ldx % V == 0 && ldy % V == 0 && ldx >= C && ldy >= C, EMO_ERR_BAD_SHAPE,
-            "emo_layernorm: M=%lld C=%d ldx=%d ldy=%d", (long long)M, C, ldx, ldy);
-  EMO_CHECK(C / V <= 64 * LN_MAXV, EMO_ERR_UNSUPPORTED, "emo_layernorm: C=%d too wide", C);
+  int rc = ln_check("emo_layernorm", M, C, ldx, ldy, dtype);
+  if (rc) return rc;
   EMO_CHECK(!pe || (rows_per_frame > 0 && frames > 0), EMO_ERR_BAD_SHAPE, "emo_layernorm: pe needs rows_per_frame/frames");
   EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "emo_layernorm: gamma/beta alignment");
   hipStream_t st = as_stream(stream);

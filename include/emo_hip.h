@@ -126,6 +126,16 @@ int emo_groupnorm_one_launch_ok(int N, int64_t S, int C, int G, int dtype);
 int emo_groupnorm(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int N, int64_t S,
                   int C, int G, float eps, int silu, int dtype, void* stream);
 
+/* What the GroupNorm entries would launch for (N, S, C, G, dtype), asked without a launch (host only; the geometry functions the
+ * launches call):
+ *   plan[0..5]   the two launches: NC (column parts of whole groups, blockIdx.y), channels per part, row slots per block,
+ *                nsplit_stats (row chunks = partials per instance, <= 256), nsplit_apply (row chunks of the apply pass),
+ *                wide (1: a part holds more than 256 column vectors, up to 3 per thread)
+ *   plan[6..11]  the one-launch kernel: ok (= emo_groupnorm_one_launch_ok), groups per slab, channels per slab, threads per block,
+ *                rows per thread the kernel is instantiated for (2 / 4 / 8 / 16), row slots per block (zeros where ok is 0)
+ * Returns what the entries' shape checks return for contiguous rows, and writes nothing on a refusal. */
+int emo_groupnorm_plan(int N, int64_t S, int C, int G, int dtype, int plan[12]);
+
 /* GroupNorm folded into the Linear / 1x1 conv that consumes it (attention.py:124,135-146 `norm` -> `proj_in`;
  * motion_module.py:147-151): GN(x) W^T + b over an instance n = x W'_n^T + b'_n with
  *   W'_n[o, c] = W[o, c] * gamma_c * rstd_{n, g(c)}      (rounded to the compute dtype, [N][Cout][C] -> `w_out`)
@@ -145,6 +155,10 @@ int emo_layernorm(const void* x, int ldx, const float* gamma, const float* beta,
 /* the statistics half of it: stats[m] = (mean, 1 / sqrt(var + eps)) of row m (two-pass, f32) for the LayerNorm fold of
  * emo_gemm (emo_gemm_params.ln_stats) - a read-only pass over x. */
 int emo_layernorm_stats(const void* x, int ldx, float* stats, int64_t M, int C, float eps, int dtype, void* stream);
+/* What both would launch for (M, C, dtype), asked without a launch (host only): plan = lanes per row (1 .. 64), rows per
+ * wavefront, grid (blocks of 4 wavefronts, <= 4096), 1 if the rows need a second trip of the grid.  Returns what their shape
+ * checks return for contiguous rows, and writes nothing on a refusal. */
+int emo_layernorm_plan(int64_t M, int C, int dtype, int plan[4]);
 
 /* ---- GEMM / convolution (MFMA) ----------------------------------------------------------------
  * C[M,N] = epilogue( A[M,K] . W[N,K]^T ).  Replaces F.linear / 1x1 conv (orig_attention.py:566-575,

@@ -443,3 +443,111 @@ def test_halo_sweeps_reach_every_instantiation():
     plan = (C.c_int * 8)(*([-7] * 8))
     assert _lib.load().emo_conv3x3_halo_plan(C.byref(_lib.GemmParams()), plan) != 0 and list(plan) == [-7] * 8
     assert _lib.load().emo_conv3x3_halo_plan(None, plan) != 0
+
+
+def _gn_plan(N, S, Cc, G, dt):
+    import ctypes as C
+    plan = (C.c_int * 12)(*([-7] * 12))
+    return _lib.load().emo_groupnorm_plan(N, S, Cc, G, dt, plan), tuple(plan)
+
+
+def _ln_plan(M, Cc, dt):
+    import ctypes as C
+    plan = (C.c_int * 4)(*([-7] * 4))
+    return _lib.load().emo_layernorm_plan(M, Cc, dt, plan), tuple(plan)
+
+
+def test_norm_sweeps_reach_every_arm():
+    """emo_groupnorm_plan / emo_layernorm_plan (csrc/norm.hip: the gn_geom / gn1_geom / ln_geom the launches call, asked without a
+    launch) against the case tables tests/test_gpu_norm_sweeps.py launches: every case plans what it was written for in every dtype of
+    its class, the one-launch query and the workspace size agree with the plan, and between them the tables reach the wide arm, every
+    column split, both chunk-count mismatches, the empty chunks, the group extremes, every (threads, rows per thread, groups per slab)
+    of the one-launch kernel and every lanes-per-row choice of the LayerNorm at a partly filled wavefront and past the grid.  A table
+    that shrinks, or a retuning that moves a case to another arm, fails here."""
+    from tests import norm_sweep_cases as S
+    lib = _lib.load()
+    arms, one_shapes = set(), {"h": set(), "f": set()}
+    for c in S.GN:
+        N, Sr, Cc, G = c["N"], c["S"], c["C"], c["G"]
+        for dtype in S.CLASS_DTYPES[c["cls"]]:
+            rc, plan = _gn_plan(N, Sr, Cc, G, _dt(dtype))
+            assert rc == 0 and plan == c["two"] + c["one"], (S.gn_id(c), dtype, plan)
+            assert lib.emo_groupnorm_one_launch_ok(N, Sr, Cc, G, _dt(dtype)) == plan[6]
+        # sized for the larger chunk count of the two vector widths - of those that divide C (C = 4, an f32-only row, used to divide by zero)
+        ns = max(_gn_plan(N, Sr, Cc, G, _dt(dtype))[1][3] for dtype in (torch.bfloat16, torch.float32) if Cc % S.vec(S.cls_of(dtype)) == 0)
+        assert lib.emo_groupnorm_workspace_bytes(N, Sr, Cc, G) == N * ns * G * 8
+        NC, Cp, RP, n_s, n_a, wide = c["two"]
+        assert NC * Cp == Cc and wide == (Cp // S.vec(c["cls"]) > S.GN_THREADS) and n_s <= 256 and n_s <= n_a
+        assert S.gn_max_chunk_elems(c) * 16 < 2 ** 24       # the grid probe's integer sums (|x| <= 4) stay exact in an f32 partial
+        assert N * Sr * Cc * (2 if c["cls"] == "h" else 4) <= 50e6
+        arms |= S.gn_arms(c)
+        if c["one"][0]:
+            ok, gpb, Wc, NT, R, slots = c["one"]
+            assert Wc == gpb * (Cc // G) and slots == NT // (Wc // S.vec(c["cls"])) and -(-Sr // slots) <= R
+            one_shapes[c["cls"]].add((NT, R, gpb))
+    assert arms == S.GN_TWO_ARMS, (arms ^ S.GN_TWO_ARMS)
+    assert one_shapes == S.GN_ONE_SHAPES, {k: one_shapes[k] ^ S.GN_ONE_SHAPES[k] for k in one_shapes}
+    # the two instantiations the workload never launches: 16 rows per thread (f32) and 8 rows per thread in a 2-byte type
+    assert any(c["cls"] == "f" and c["one"][4] == 16 for c in S.GN) and any(c["cls"] == "h" and c["one"][4] == 8 for c in S.GN)
+    assert S.gn_rerun_as_views(next(c for c in S.GN if c["name"] == "split")) and not S.gn_rerun_as_views(next(c for c in S.GN if c["name"] == "idle"))
+
+    seen = set()
+    for c in S.LN:
+        M, Cc = c["M"], c["C"]
+        for dtype in S.CLASS_DTYPES[c["cls"]]:
+            rc, plan = _ln_plan(M, Cc, _dt(dtype))
+            assert rc == 0 and plan == c["plan"], (S.ln_id(c), dtype, plan)
+        lpr, rpw, grid, second = c["plan"]
+        assert lpr * rpw == 64 and grid == min(-(-M // (4 * rpw)), S.LN_MAXGRID) and second == (M > S.LN_MAXGRID * 4 * rpw)
+        assert M * Cc * (2 if c["cls"] == "h" else 4) <= 51e6
+        kinds = {"one_row"} if M == 1 else set()
+        if M % rpw:
+            kinds.add("ragged_wave")
+        if M % (4 * rpw):
+            kinds.add("ragged_block")
+        if second:
+            kinds.add("second_trip")
+        if Cc // S.vec(c["cls"]) == S.LN_MAXV * lpr:
+            kinds.add("full_lanes")
+        seen |= {(c["cls"], lpr, k) for k in kinds}
+    # (64 lanes per row: a wavefront holds one row and is never partly filled - its last BLOCK is, at M = 2)
+    assert seen == {(cls, lpr, k) for cls in "hf" for lpr in S.LN_LPRS for k in ("one_row", "ragged_wave", "ragged_block", "second_trip", "full_lanes")
+                    if not (lpr == 64 and k == "ragged_wave")}
+
+
+def test_norm_plans_run_the_argument_checks():
+    """emo_groupnorm_plan returns what the GroupNorm entries' shape check returns and emo_layernorm_plan what the LayerNorm's returns,
+    and neither writes anything on a refusal; the fold keeps its own width limit."""
+    import ctypes as C
+    from tests import norm_sweep_cases as S
+    lib = _lib.load()
+    for N, Sr, Cc, G, cls in S.GN_REFUSED:
+        for dtype in S.CLASS_DTYPES[cls]:
+            rc, plan = _gn_plan(N, Sr, Cc, G, _dt(dtype))
+            assert rc != 0 and plan == (-7,) * 12, (N, Sr, Cc, G, dtype)
+            assert lib.emo_groupnorm_one_launch_ok(N, Sr, Cc, G, _dt(dtype)) == 0
+            # the launching entries refuse the same shapes in their checks, before they touch a pointer (these are not dereferenced)
+            buf = (C.c_float * 16)()
+            p = C.addressof(buf)
+            assert lib.emo_groupnorm_stats(p, Cc, p, N, Sr, Cc, G, _dt(dtype), None) == rc
+            assert lib.emo_groupnorm_apply(p, Cc, p, p, p, p, Cc, N, Sr, Cc, G, 1e-5, 0, _dt(dtype), None) == rc
+            assert lib.emo_groupnorm(p, Cc, p, p, p, Cc, N, Sr, Cc, G, 1e-5, 0, _dt(dtype), None) == rc
+            assert lib.emo_groupnorm_coeffs(p, p, p, p, N, Sr, Cc, G, 1e-5, _dt(dtype), None) == rc
+    assert _gn_plan(2, 37, 320, 32, 7)[0] != 0 and _gn_plan(0, 37, 320, 32, BF16)[0] != 0 and _gn_plan(2, 0, 320, 32, BF16)[0] != 0
+    assert lib.emo_groupnorm_plan(2, 37, 320, 32, BF16, None) != 0
+    assert lib.emo_groupnorm_workspace_bytes(32, 1, 4, 4) == 32 * 4 * 8 and lib.emo_groupnorm_workspace_bytes(2, 37, 0, 4) == 0
+    # 768 column vectors, 128 groups: the last shapes served
+    assert _gn_plan(2, 37, 768 * 8, 128, BF16)[0] == 0 and _gn_plan(2, 37, 768 * 4, 128, F32)[0] == 0
+    # the fold: C <= 2560 (its LDS tables), whatever the plan says of the norm itself
+    buf = (C.c_float * 16)()
+    p = C.addressof(buf)
+    for dt, V in ((BF16, 8), (F32, 4)):
+        assert _gn_plan(2, 50, S.GNF_MAXC + 32, 32, dt)[0] == 0
+        assert lib.emo_groupnorm_fold_linear(p, p, p, p, None, p, p, 2, 50, S.GNF_MAXC + 32, 32, 13, 1e-6, dt, None) != 0
+    for dt, V in ((BF16, 8), (_dt(torch.float16), 8), (F32, 4)):
+        assert _ln_plan(0, 64, dt) == (_ln_plan(0, 64, dt)[0], (-7,) * 4) and _ln_plan(0, 64, dt)[0] != 0
+        assert _ln_plan(5, 64 + V // 2, dt)[0] != 0 and _ln_plan(5, (64 * S.LN_MAXV + 1) * V, dt)[0] != 0
+        assert _ln_plan(5, 64 * S.LN_MAXV * V, dt) == (0, (64, 1, 2, 0))
+        assert lib.emo_layernorm(p, 64, p, p, p, 64, 0, 64, 1e-5, None, 0, 0, dt, None) == _ln_plan(0, 64, dt)[0]
+        assert lib.emo_layernorm_stats(p, (64 * S.LN_MAXV + 1) * V, p, 5, (64 * S.LN_MAXV + 1) * V, 1e-5, dt, None) == _ln_plan(5, (64 * S.LN_MAXV + 1) * V, dt)[0]
+    assert _ln_plan(5, 64, 7)[0] != 0 and lib.emo_layernorm_plan(5, 64, BF16, None) != 0
