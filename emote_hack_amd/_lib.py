@@ -82,6 +82,8 @@ SIGNATURES = {
     "emo_rows_to_ncfhw": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "emo_copy_cols": (_i, [_p, _i, _p, _i, _i, _i64, _i, _i, _p]),
     "emo_add": (_i, [_p, _i, _p, _i, _f, _p, _i, _i64, _i, _i, _p]),
+    "emo_add_periodic": (_i, [_p, _i64, _p, _i64, _p, _i64, _i64, _i, _i64, _i, _p]),
+    "emo_mask_pool": (_i, [_p, _p, _i, _i, _i, _f, _i, _p]),
     "emo_convert": (_i, [_p, _i, _p, _i, _i64, _i, _p]),
     "emo_silu": (_i, [_p, _p, _i64, _i, _p]),
     "emo_timestep_embedding": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
@@ -96,6 +98,9 @@ SIGNATURES = {
     "emo_groupnorm_apply_mod": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
     "emo_groupnorm_mod": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
     "emo_groupnorm_coeffs_mod": (_i, [_p, _p, _p, _p, _i, _p, _i, _i64, _i, _i, _f, _i, _p]),
+    "emo_groupnorm_apply_mod_rows": (_i, [_p, _i, _p, _p, _p, _p, _i, _i64, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
+    "emo_groupnorm_mod_rows": (_i, [_p, _i, _p, _p, _p, _i, _i64, _p, _i, _i, _i64, _i, _i, _f, _i, _i, _p]),
+    "emo_groupnorm_coeffs_mod_rows": (_i, [_p, _p, _p, _p, _i, _i64, _p, _i, _i64, _i, _i, _f, _i, _p]),
     "emo_groupnorm_fold_linear": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _f, _i, _p]),
     "emo_layernorm": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _f, _p, _i, _i, _i, _p]),
     "emo_layernorm_stats": (_i, [_p, _i, _p, _i64, _i, _f, _i, _p]),

@@ -29,6 +29,10 @@ class AppearanceEncoderModel(UNet3DConditionModel):
         super().__init__(**kwargs)
 
     def forward(self, sample, timestep, encoder_hidden_states, **kw):
+        se = kw.get("speed_embeddings")
+        if se is not None and se.dim() != 2:
+            raise ValueError("AppearanceEncoderModel takes speed_embeddings (N, 4*C0) only: per-frame speed embeddings (B, F, 4*C0) condition "
+                             "the Backbone")
         if sample.dim() == 4:
             sample = sample.unsqueeze(2)
         return super().forward(sample, timestep, encoder_hidden_states, **kw)

@@ -159,6 +159,29 @@ class FaceRegionController(_HipModule):
                 x = ops.act(x, "relu")
         return ops.rows_to_ncfhw(x, B, self.chans[-1], 1, H, W).squeeze(2)
 
+    @property
+    def in_channels(self):
+        return self.chans[0]
+
+    @property
+    def out_channels(self):
+        return self.chans[-1]
+
+    def forward_rows(self, rows, B, H, W):
+        """The same four convs, rows in and rows out: rows (B * H * W, in_channels rounded up to 8) in the compute dtype with zero pad
+        channels (ops.mask_pool's output for a one-channel mask) -> (B * H * W, out_channels) rows - what the UNet's face_features=
+        takes; no round trip through NCHW."""
+        self._need()
+        cpad = (self.chans[0] + 7) // 8 * 8
+        if rows.dim() != 2 or tuple(rows.shape) != (B * H * W, cpad) or rows.dtype != self.dtype:
+            raise ValueError(f"forward_rows: rows must be ({B * H * W}, {cpad}) {self.dtype}, got {tuple(rows.shape)} {rows.dtype}")
+        x = rows
+        for i, k in enumerate((0, 2, 4, 6)):
+            x, _, _ = ops.conv3x3(x, self._w[f"encoder.{k}.weight"], self._w[f"encoder.{k}.bias"], B, H, W)
+            if k != 6:
+                x = ops.act(x, "relu")
+        return x
+
 
 class CrossAttentionLayer(_HipModule):
     """Net.py:263-303: single head, q/k/v Linear with bias, scores / sqrt(feature_dim)."""

@@ -94,19 +94,23 @@ class ControlNetModel(UNet3DConditionModel):
         return self._cond_embedding(controlnet_cond.to(self.device).float(), controlnet_cond.shape[0], controlnet_cond.shape[2], controlnet_cond.shape[3])
 
     def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale=1.0, class_labels=None,
-                timestep_cond=None, attention_mask=None, cross_attention_kwargs=None, return_dict=True, _cond_rows=None):
+                timestep_cond=None, attention_mask=None, cross_attention_kwargs=None, return_dict=True, _cond_rows=None,
+                speed_embeddings=None):
         """controlnet.py:450-567.  sample (N,4,h,w); controlnet_cond (N,3,8h,8w); returns the 12 down residuals (N,C,h',w')
         and the mid residual, each multiplied by `conditioning_scale`.  `_cond_rows` = a precomputed `cond_embedding()` of
         controlnet_cond (which may then be None)."""
         if attention_mask is not None or class_labels is not None or timestep_cond is not None:
             raise NotImplementedError("attention_mask / class_labels / timestep_cond are outside the hot path (always None in the pipeline)")
+        if speed_embeddings is not None and speed_embeddings.dim() != 2:
+            raise ValueError("ControlNetModel takes speed_embeddings (N, 4*C0) only: per-frame speed embeddings (B, F, 4*C0) condition the Backbone")
         if sample.dim() != 4:
             raise ValueError("ControlNetModel works on 2-D batches: sample (N,C,h,w), controlnet_cond (N,3,H,W)")
         N, _, h, w_ = sample.shape
         cond_rows, ch, cw = _cond_rows if _cond_rows is not None else self.cond_embedding(controlnet_cond)
         if (ch, cw) != (h, w_):
             raise ValueError(f"conditioning image maps to {ch}x{cw} but the latent is {h}x{w_}")
-        s = self._begin(sample.unsqueeze(2), timestep, encoder_hidden_states, add_after_conv_in=cond_rows)
+        s = self._begin(sample.unsqueeze(2), timestep, encoder_hidden_states, add_after_conv_in=cond_rows,
+                        **({} if speed_embeddings is None else dict(speed_embeddings=speed_embeddings)))
         self._run_down(s)
         x_mid = self._run_mid(s, s.x)
         w = self._w

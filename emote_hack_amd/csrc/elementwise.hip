@@ -151,6 +151,77 @@ extern "C" int emo_add(const void* a, int lda, const void* b, int ldb, float alp
   return EMO_OK;
 }
 
+// y[m, :] = x[m, :] + f[m % P, :]: a (P, C) map added to every period of P rows (the face-region features behind conv_in, one period
+// per frame).  y may BE x (no __restrict__ on the two): every element is read, added in f32 and written by the same thread.
+template <typename T>
+__global__ __launch_bounds__(256) void add_periodic_kernel(const T* x, int64_t ldx, const T* __restrict__ f, int64_t ldf, T* y, int64_t ldy,
+                                                           int64_t M, int C, int64_t P) {
+  constexpr int V = TT<T>::VEC;
+  const int cv = C / V;
+  const int64_t total = M * cv;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = i / cv; const int c = (int)(i % cv) * V;
+    float fx[V], ff[V];
+    unpack16<T>(*(const uint4*)(x + m * ldx + c), fx);
+    unpack16<T>(*(const uint4*)(f + (m % P) * ldf + c), ff);
+#pragma unroll
+    for (int j = 0; j < V; j++) fx[j] += ff[j];
+    *(uint4*)(y + m * ldy + c) = pack16<T>(fx);
+  }
+}
+extern "C" int emo_add_periodic(const void* x, int64_t ldx, const void* f, int64_t ldf, void* y, int64_t ldy, int64_t M, int C, int64_t P,
+                                int dtype, void* stream) {
+  EMO_CHECK(x && f && y, EMO_ERR_NULL, "emo_add_periodic: null pointer");
+  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_add_periodic: dtype %d", dtype);
+  const int V = emo_dtype_vec(dtype);
+  EMO_CHECK(M > 0 && C > 0 && P > 0 && C % V == 0 && ldx % V == 0 && ldf % V == 0 && ldy % V == 0 && ldx >= C && ldf >= C && ldy >= C,
+            EMO_ERR_BAD_SHAPE, "emo_add_periodic: M=%lld C=%d P=%lld ldx=%lld ldf=%lld ldy=%lld (widths multiples of %d)", (long long)M, C,
+            (long long)P, (long long)ldx, (long long)ldf, (long long)ldy, V);
+  EMO_CHECK(M % P == 0, EMO_ERR_BAD_SHAPE, "emo_add_periodic: M=%lld is not a whole number of periods of P=%lld rows", (long long)M, (long long)P);
+  EMO_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)f % 16) == 0 && ((uintptr_t)y % 16) == 0, EMO_ERR_BAD_SHAPE,
+            "emo_add_periodic: operands must be 16-byte aligned");
+  const int grid = grid_for(M * (C / V), 256);
+  EMO_DISPATCH(dtype, "emo_add_periodic",
+               (add_periodic_kernel<T><<<grid, 256, 0, as_stream(stream)>>>((const T*)x, ldx, (const T*)f, ldf, (T*)y, ldy, M, C, P)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// (Hp, Wp) f32 map -> (Hp / 8 * Wp / 8, 8) rows: channel 0 = the mean of the cell's 8 x 8 pixels (of x > thr ? 1 : 0 with use_thr),
+// channels 1..7 = 0.  One thread per cell: 64 loads summed in row-major order, one multiply by 1/64 (exact), one 8-channel store.
+template <typename T>
+__global__ __launch_bounds__(256) void mask_pool_kernel(const float* __restrict__ x, T* __restrict__ y, int Hc, int Wc, int Wp, int use_thr,
+                                                        float thr) {
+  const int n = Hc * Wc;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int cy = i / Wc, cx = i % Wc;
+    const float* p = x + (int64_t)cy * 8 * Wp + cx * 8;
+    float s = 0.f;
+    for (int r = 0; r < 8; r++) {
+      const float4 a = *(const float4*)(p + (int64_t)r * Wp), b = *(const float4*)(p + (int64_t)r * Wp + 4);
+      const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 8; j++) s += use_thr ? (v[j] > thr ? 1.0f : 0.0f) : v[j];
+    }
+    T* o = y + (int64_t)i * 8;
+    TT<T>::st(o, s * 0.015625f);
+#pragma unroll
+    for (int j = 1; j < 8; j++) TT<T>::st(o + j, 0.0f);
+  }
+}
+extern "C" int emo_mask_pool(const float* x, void* y, int Hp, int Wp, int use_thr, float thr, int dtype, void* stream) {
+  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_mask_pool: dtype %d", dtype);
+  EMO_CHECK(Hp > 0 && Wp > 0 && Hp % 8 == 0 && Wp % 8 == 0, EMO_ERR_BAD_SHAPE, "emo_mask_pool: Hp=%d Wp=%d must be multiples of 8", Hp, Wp);
+  EMO_CHECK((int64_t)Hp * Wp < ((int64_t)1 << 31), EMO_ERR_BAD_SHAPE, "emo_mask_pool: %d x %d pixels (at most 2^31 - 1)", Hp, Wp);
+  EMO_CHECK(x && y, EMO_ERR_NULL, "emo_mask_pool: null pointer");
+  EMO_CHECK(((uintptr_t)x % 16) == 0, EMO_ERR_BAD_SHAPE, "emo_mask_pool: the map must be 16-byte aligned");
+  const int Hc = Hp / 8, Wc = Wp / 8;
+  const int grid = grid_for((int64_t)Hc * Wc, 256);
+  EMO_DISPATCH(dtype, "emo_mask_pool", (mask_pool_kernel<T><<<grid, 256, 0, as_stream(stream)>>>(x, (T*)y, Hc, Wc, Wp, use_thr, thr)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
 // ---------------------------------------------------------------- convert / silu (scalar tails allowed)
 __device__ __forceinline__ float round_through_half(float f) { return (float)(_Float16)f; }  // IEEE half, RNE
 

@@ -14,6 +14,9 @@
 // (xh gamma + beta)(1 + s) + t = xh gamma' + beta' with gamma' = gamma (1 + s), beta' = beta (1 + s) + t: the modulation is folded into
 // the thread's copy of the affine right where that is loaded - before the statistics, so nothing more is held across them - and
 // the plain arithmetic runs on (gamma', beta'): the same registers, the same streaming loop, the same traffic plus N * 2C floats.
+// MOD == 2 is the PER-FRAME form of the same modulation (a speed embedding per frame in the time embedding: statistics joint over the
+// instance's frames, (s, t) = mod[m / mod_rows] for row m of x): the affine cannot be folded once per thread, so the thread keeps the plain
+// (gamma, beta, mean, rstd) and folds per row - gn_modulate, then the same two factor expressions - with the row's mod vectors (L2 hits).
 #include "common.h"
 
 // The scale-shift modulation of a channel's GroupNorm affine.  ONE statement of its three roundings (1 + s, gamma m, fma(beta, m, t))
@@ -172,18 +175,19 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
 
 static constexpr int GN_MAXG = 128;   // groups held in the apply pass's LDS statistics table
 
-template <typename T, bool MOD>
+template <typename T, int MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ partials,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               T* __restrict__ y, int ldy, int64_t S, int C, int G, int G_all,
                                                               int nsplit_stats, int nsplit, double count, float eps, int silu,
-                                                              const float* __restrict__ mod, int ldmod, int C_all) {
+                                                              const float* __restrict__ mod, int ldmod, int C_all, int64_t mod_rows) {
   constexpr int V = TT<T>::VEC;
   __shared__ float s_stats[GN_MAXG * 2];
   const int n = blockIdx.x / nsplit, sp = blockIdx.x % nsplit;
   x += (int64_t)blockIdx.y * C; y += (int64_t)blockIdx.y * C;
   gamma += (int64_t)blockIdx.y * C; beta += (int64_t)blockIdx.y * C;
-  if constexpr (MOD) mod += (int64_t)(blockIdx.x / nsplit) * ldmod + (int64_t)blockIdx.y * C;   // (scale | shift) row of this instance, this column part
+  if constexpr (MOD == 1) mod += (int64_t)(blockIdx.x / nsplit) * ldmod + (int64_t)blockIdx.y * C;   // (scale | shift) row of this instance, this column part
+  if constexpr (MOD == 2) mod += (int64_t)blockIdx.y * C;                                             // this column part; the row changes with the frame
   const int CV = C / V, cpg = C / G;
   const int64_t rows_per = (S + nsplit - 1) / nsplit;
   const int64_t s0 = sp * rows_per;
@@ -201,13 +205,13 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
   float gm[V], bt[V];
   uint4 v[4];
   int64_t s = s0 + r;
-  bool have = active && s + 3 * RP < s1;
+  bool have = MOD != 2 && active && s + 3 * RP < s1;   // (the per-frame form streams row by row)
   if (active) {
 #pragma unroll
     for (int e = 0; e < V; e += 4) {
       *(float4*)(gm + e) = *(const float4*)(gamma + cv * V + e);
       *(float4*)(bt + e) = *(const float4*)(beta + cv * V + e);
-      if constexpr (MOD) {
+      if constexpr (MOD == 1) {
         const float4 ms = *(const float4*)(mod + cv * V + e), mt = *(const float4*)(mod + C_all + cv * V + e);
         gn_modulate(gm[e], bt[e], ms.x, mt.x); gn_modulate(gm[e + 1], bt[e + 1], ms.y, mt.y);
         gn_modulate(gm[e + 2], bt[e + 2], ms.z, mt.z); gn_modulate(gm[e + 3], bt[e + 3], ms.w, mt.w);
@@ -245,6 +249,34 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
   }
   if (narrow) {
     if (!active) return;
+    if constexpr (MOD == 2) {
+      float mean[V], rstd[V];
+#pragma unroll
+      for (int e = 0; e < V; e++) {
+        const int g = (cv * V + e) / cpg;
+        mean[e] = s_stats[2 * g]; rstd[e] = s_stats[2 * g + 1];
+      }
+      for (; s < s1; s += RP) {
+        const float* mr = mod + (((int64_t)n * S + s) / mod_rows) * ldmod + cv * V;
+        float f[V];
+        unpack16<T>(*(const uint4*)(xc + s * ldx), f);
+#pragma unroll
+        for (int e = 0; e < V; e += 4) {
+          const float4 ms4 = *(const float4*)(mr + e), mt4 = *(const float4*)(mr + C_all + e);
+          const float ms[4] = {ms4.x, ms4.y, ms4.z, ms4.w}, mt[4] = {mt4.x, mt4.y, mt4.z, mt4.w};
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            float gc = gm[e + q], bc = bt[e + q];
+            gn_modulate(gc, bc, ms[q], mt[q]);
+            const float a = rstd[e + q] * gc, b = fmaf(-mean[e + q], a, bc);
+            const float t = f[e + q] * a + b;
+            f[e + q] = silu ? silu_f(t) : t;
+          }
+        }
+        *(uint4*)(yc + s * ldy) = pack16<T>(f);
+      }
+      return;
+    }
     float a[V], b[V];
 #pragma unroll
     for (int e = 0; e < V; e++) {
@@ -284,12 +316,30 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(const T* __restric
       int cv = tid + j * GN_THREADS;
       if (cv >= CV) break;
       float a[V], b[V];
+      if constexpr (MOD == 2) {
+        for (int64_t s = s0; s < s1; s++) {
+          const float* mr = mod + (((int64_t)n * S + s) / mod_rows) * ldmod;
+          float f[V];
+          unpack16<T>(*(const uint4*)(xb + s * ldx + cv * V), f);
+#pragma unroll
+          for (int e = 0; e < V; e++) {
+            const int c = cv * V + e, g = c / cpg;
+            float gc = gamma[c], bc = beta[c];
+            gn_modulate(gc, bc, mr[c], mr[C_all + c]);
+            const float a_ = s_stats[2 * g + 1] * gc, b_ = fmaf(-s_stats[2 * g], a_, bc);
+            const float v = f[e] * a_ + b_;
+            f[e] = silu ? silu_f(v) : v;
+          }
+          *(uint4*)(yb + s * ldy + cv * V) = pack16<T>(f);
+        }
+        continue;
+      }
 #pragma unroll
       for (int e = 0; e < V; e++) {
         int c = cv * V + e, g = c / cpg;
         float mean = s_stats[2 * g], rstd = s_stats[2 * g + 1];
         float gc = gamma[c], bc = beta[c];
-        if constexpr (MOD) gn_modulate(gc, bc, mod[c], mod[C_all + c]);
+        if constexpr (MOD == 1) gn_modulate(gc, bc, mod[c], mod[C_all + c]);
         a[e] = rstd * gc; b[e] = fmaf(-mean, a[e], bc);
       }
       for (int64_t s = s0; s < s1; s++) {
@@ -335,9 +385,19 @@ static int gn_mod_check(const char* who, const float* mod, int ldmod, int C) {
   return EMO_OK;
 }
 
+// ... and of the *_mod_rows entries: rows [N * S / mod_rows][(scale | shift)], one per mod_rows consecutive rows of x; an instance holds
+// whole frames
+static int gn_mod_rows_check(const char* who, const float* mod, int ldmod, int64_t mod_rows, int64_t S, int C) {
+  int rc = gn_mod_check(who, mod, ldmod, C);
+  if (rc) return rc;
+  EMO_CHECK(mod_rows > 0 && S > 0 && S % mod_rows == 0, EMO_ERR_BAD_SHAPE, "%s: mod_rows=%lld must divide the instance's S=%lld rows", who,
+            (long long)mod_rows, (long long)S);
+  return EMO_OK;
+}
+
 static int gn_apply_launch(const char* who, const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
-                           const float* mod, int ldmod, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype,
-                           void* stream) {
+                           const float* mod, int ldmod, int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu,
+                           int dtype, void* stream) {
   EMO_CHECK(x && partials && gamma && beta && y, EMO_ERR_NULL, "%s: null pointer", who);
   int rc = gn_check(who, N, S, C, G, ldx, dtype);
   if (rc) return rc;
@@ -348,21 +408,25 @@ static int gn_apply_launch(const char* who, const void* x, int ldx, const void* 
   const double count = (double)S * (C / G);
   hipStream_t st = as_stream(stream);
   const dim3 grid((unsigned)(N * gg.nsplit_apply), (unsigned)gg.NC);
-  if (mod)
+  if (mod && mod_rows)
     EMO_DISPATCH(dtype, who,
-                 (gn_apply_kernel<T, true><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
-                                                                        G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, mod, ldmod, C)));
+                 (gn_apply_kernel<T, 2><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
+                                                                     G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, mod, ldmod, C, mod_rows)));
+  else if (mod)
+    EMO_DISPATCH(dtype, who,
+                 (gn_apply_kernel<T, 1><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
+                                                                     G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, mod, ldmod, C, 0)));
   else
     EMO_DISPATCH(dtype, who,
-                 (gn_apply_kernel<T, false><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
-                                                                         G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, nullptr, 0, C)));
+                 (gn_apply_kernel<T, 0><<<grid, GN_THREADS, 0, st>>>((const T*)x, ldx, (const float*)partials, gamma, beta, (T*)y, ldy, S, gg.Cp, gg.Gp,
+                                                                     G, gg.nsplit_stats, gg.nsplit_apply, count, eps, silu, nullptr, 0, C, 0)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
 extern "C" int emo_groupnorm_apply(const void* x, int ldx, const void* partials, const float* gamma, const float* beta, void* y,
                                    int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
-  return gn_apply_launch("emo_groupnorm_apply", x, ldx, partials, gamma, beta, nullptr, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+  return gn_apply_launch("emo_groupnorm_apply", x, ldx, partials, gamma, beta, nullptr, 0, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
 }
 
 extern "C" int emo_groupnorm_apply_mod(const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
@@ -370,17 +434,26 @@ extern "C" int emo_groupnorm_apply_mod(const void* x, int ldx, const void* parti
                                        int dtype, void* stream) {
   int rc = gn_mod_check("emo_groupnorm_apply_mod", mod, ldmod, C);
   if (rc) return rc;
-  return gn_apply_launch("emo_groupnorm_apply_mod", x, ldx, partials, gamma, beta, mod, ldmod, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+  return gn_apply_launch("emo_groupnorm_apply_mod", x, ldx, partials, gamma, beta, mod, ldmod, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_apply_mod_rows(const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
+                                            const float* mod, int ldmod, int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G,
+                                            float eps, int silu, int dtype, void* stream) {
+  int rc = gn_mod_rows_check("emo_groupnorm_apply_mod_rows", mod, ldmod, mod_rows, S, C);
+  if (rc) return rc;
+  return gn_apply_launch("emo_groupnorm_apply_mod_rows", x, ldx, partials, gamma, beta, mod, ldmod, mod_rows, y, ldy, N, S, C, G, eps, silu, dtype,
+                         stream);
 }
 
 // The coefficient half of the apply pass for consumers that normalise on the fly (the halo conv, emo_gemm_params.gn_coef): one
 // block per instance runs the SAME statistics prologue as gn_apply_kernel - per column part, TPG lanes per group, strided f64
 // sums + shuffle tree - and writes scale = rstd * gamma, shift = beta - mean * scale, channel pairs interleaved (s, s, b, b).
-template <bool MOD>
+template <int MOD>
 __global__ __launch_bounds__(GN_THREADS) void gn_coeffs_kernel(const float* __restrict__ partials, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ coef,
                                                                int C, int G_all, int NC, int nsplit_stats, double count, float eps,
-                                                               const float* __restrict__ mod, int ldmod) {
+                                                               const float* __restrict__ mod, int ldmod, int64_t fpi) {
   __shared__ float s_stats[GN_MAXG * 2];
   const int n = blockIdx.x, tid = threadIdx.x;
   const int G = G_all / NC;
@@ -408,11 +481,27 @@ __global__ __launch_bounds__(GN_THREADS) void gn_coeffs_kernel(const float* __re
   }
   __syncthreads();
   const int cpg = C / G_all;
+  if constexpr (MOD == 2) {   // one table row per FRAME of the instance (fpi of them): the instance's statistics, the frame's modulation
+    for (int64_t fr = 0; fr < fpi; fr++) {
+      const int64_t row = (int64_t)n * fpi + fr;
+      for (int c = tid; c < C; c += GN_THREADS) {
+        const int g = c / cpg;
+        const float mean = s_stats[2 * g], rstd = s_stats[2 * g + 1];
+        float gc = gamma[c], bc = beta[c];
+        gn_modulate(gc, bc, mod[row * ldmod + c], mod[row * ldmod + C + c]);
+        const float a = rstd * gc;
+        float* dst = coef + row * 2 * C + (c >> 1) * 4 + (c & 1);
+        dst[0] = a;
+        dst[2] = fmaf(-mean, a, bc);
+      }
+    }
+    return;
+  }
   for (int c = tid; c < C; c += GN_THREADS) {
     const int g = c / cpg;
     const float mean = s_stats[2 * g], rstd = s_stats[2 * g + 1];
     float gc = gamma[c], bc = beta[c];
-    if constexpr (MOD) gn_modulate(gc, bc, mod[(int64_t)n * ldmod + c], mod[(int64_t)n * ldmod + C + c]);
+    if constexpr (MOD == 1) gn_modulate(gc, bc, mod[(int64_t)n * ldmod + c], mod[(int64_t)n * ldmod + C + c]);
     const float a = rstd * gc;
     float* dst = coef + (int64_t)n * 2 * C + (c >> 1) * 4 + (c & 1);
     dst[0] = a;
@@ -421,32 +510,42 @@ __global__ __launch_bounds__(GN_THREADS) void gn_coeffs_kernel(const float* __re
 }
 
 static int gn_coeffs_launch(const char* who, const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
-                            float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
+                            int64_t mod_rows, float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
   EMO_CHECK(partials && gamma && beta && coef, EMO_ERR_NULL, "%s: null pointer", who);
   int rc = gn_check(who, N, S, C, G, C, dtype);
   if (rc) return rc;
   const GnGeom gg = gn_geom(N, S, C, G, emo_dtype_vec(dtype));
   const double count = (double)S * (C / G);
-  if (mod)
-    gn_coeffs_kernel<true><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
-                                                                              gg.nsplit_stats, count, eps, mod, ldmod);
+  if (mod && mod_rows)
+    gn_coeffs_kernel<2><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
+                                                                           gg.nsplit_stats, count, eps, mod, ldmod, S / mod_rows);
+  else if (mod)
+    gn_coeffs_kernel<1><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
+                                                                           gg.nsplit_stats, count, eps, mod, ldmod, 0);
   else
-    gn_coeffs_kernel<false><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
-                                                                               gg.nsplit_stats, count, eps, nullptr, 0);
+    gn_coeffs_kernel<0><<<(unsigned)N, GN_THREADS, 0, as_stream(stream)>>>((const float*)partials, gamma, beta, coef, C, G, gg.NC,
+                                                                           gg.nsplit_stats, count, eps, nullptr, 0, 0);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
 extern "C" int emo_groupnorm_coeffs(const void* partials, const float* gamma, const float* beta, float* coef, int N,
                                     int64_t S, int C, int G, float eps, int dtype, void* stream) {
-  return gn_coeffs_launch("emo_groupnorm_coeffs", partials, gamma, beta, nullptr, 0, coef, N, S, C, G, eps, dtype, stream);
+  return gn_coeffs_launch("emo_groupnorm_coeffs", partials, gamma, beta, nullptr, 0, 0, coef, N, S, C, G, eps, dtype, stream);
 }
 
 extern "C" int emo_groupnorm_coeffs_mod(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
                                         float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
   int rc = gn_mod_check("emo_groupnorm_coeffs_mod", mod, ldmod, C);
   if (rc) return rc;
-  return gn_coeffs_launch("emo_groupnorm_coeffs_mod", partials, gamma, beta, mod, ldmod, coef, N, S, C, G, eps, dtype, stream);
+  return gn_coeffs_launch("emo_groupnorm_coeffs_mod", partials, gamma, beta, mod, ldmod, 0, coef, N, S, C, G, eps, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_coeffs_mod_rows(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
+                                             int64_t mod_rows, float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream) {
+  int rc = gn_mod_rows_check("emo_groupnorm_coeffs_mod_rows", mod, ldmod, mod_rows, S, C);
+  if (rc) return rc;
+  return gn_coeffs_launch("emo_groupnorm_coeffs_mod_rows", partials, gamma, beta, mod, ldmod, mod_rows, coef, N, S, C, G, eps, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------ GroupNorm in one launch
@@ -485,11 +584,11 @@ static inline Gn1Geom gn1_geom(int N, int64_t S, int C, int G, int V) {
   return g;
 }
 
-template <typename T, int R, bool MOD>
+template <typename T, int R, int MOD>
 __global__ __launch_bounds__(GN1_MAXT) void gn_one_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, T* __restrict__ y, int ldy, int S, int Wc,
                                                           int GPB, int slabs, double count, float eps, int silu,
-                                                          const float* __restrict__ mod, int ldmod, int C_all) {
+                                                          const float* __restrict__ mod, int ldmod, int C_all, int64_t mod_rows) {
   constexpr int V = TT<T>::VEC;
   extern __shared__ float lds[];   // [RP][Wc][2]
   __shared__ float s_stats[GN1_MAXGPB * 2];
@@ -513,7 +612,7 @@ __global__ __launch_bounds__(GN1_MAXT) void gn_one_kernel(const T* __restrict__ 
     for (int e = 0; e < V; e += 4) {
       *(float4*)(gm + e) = *(const float4*)(gamma + c0 + e);
       *(float4*)(bt + e) = *(const float4*)(beta + c0 + e);
-      if constexpr (MOD) {
+      if constexpr (MOD == 1) {
         const float4 ms = *(const float4*)(mod + (int64_t)n * ldmod + c0 + e), mt = *(const float4*)(mod + (int64_t)n * ldmod + C_all + c0 + e);
         gn_modulate(gm[e], bt[e], ms.x, mt.x); gn_modulate(gm[e + 1], bt[e + 1], ms.y, mt.y);
         gn_modulate(gm[e + 2], bt[e + 2], ms.z, mt.z); gn_modulate(gm[e + 3], bt[e + 3], ms.w, mt.w);
@@ -561,6 +660,39 @@ __global__ __launch_bounds__(GN1_MAXT) void gn_one_kernel(const T* __restrict__ 
   }
   __syncthreads();
   if (!active) return;
+  if constexpr (MOD == 2) {   // per-frame modulation: fold per row, from the registers that hold the rows
+    const int cpg = Wc / GPB;
+    float mean[V], rstd[V];
+#pragma unroll
+    for (int e = 0; e < V; e++) {
+      const int g = (cv * V + e) / cpg;
+      mean[e] = s_stats[2 * g]; rstd[e] = s_stats[2 * g + 1];
+    }
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+      const int s = r + k * RP;
+      if (s < S) {
+        const float* mr = mod + (((int64_t)n * S + s) / mod_rows) * ldmod + c0;
+        float f[V];
+        unpack16<T>(v[k], f);
+#pragma unroll
+        for (int e = 0; e < V; e += 4) {
+          const float4 ms4 = *(const float4*)(mr + e), mt4 = *(const float4*)(mr + C_all + e);
+          const float ms[4] = {ms4.x, ms4.y, ms4.z, ms4.w}, mt[4] = {mt4.x, mt4.y, mt4.z, mt4.w};
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            float gc = gm[e + q], bc = bt[e + q];
+            gn_modulate(gc, bc, ms[q], mt[q]);
+            const float a = rstd[e + q] * gc, b = fmaf(-mean[e + q], a, bc);
+            const float t = f[e + q] * a + b;
+            f[e + q] = silu ? silu_f(t) : t;
+          }
+        }
+        *(uint4*)(yc + (int64_t)s * ldy) = pack16<T>(f);
+      }
+    }
+    return;
+  }
   float a[V], b[V];
   {
     const int cpg = Wc / GPB;
@@ -609,8 +741,8 @@ extern "C" int emo_groupnorm_plan(int N, int64_t S, int C, int G, int dtype, int
   return EMO_OK;
 }
 
-static int gn_one_launch(const char* who, const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y,
-                         int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
+static int gn_one_launch(const char* who, const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod,
+                         int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
   EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "%s: null pointer", who);
   int rc = gn_check(who, N, S, C, G, ldx, dtype);
   if (rc) return rc;
@@ -629,17 +761,22 @@ static int gn_one_launch(const char* who, const void* x, int ldx, const float* g
   const dim3 grid((unsigned)(N * slabs));
 #define GN1_LAUNCH(RR, MM) \
   EMO_DISPATCH(dtype, who, (gn_one_kernel<T, RR, MM><<<grid, gg.NT, lds, st>>>((const T*)x, ldx, gamma, beta, (T*)y, ldy, (int)S, gg.Wc, gg.GPB, \
-                                                                               slabs, count, eps, silu, mod, ldmod, C)))
-  if (mod) {
-    if (gg.R == 2) { GN1_LAUNCH(2, true); }
-    else if (gg.R == 4) { GN1_LAUNCH(4, true); }
-    else if (gg.R == 8) { GN1_LAUNCH(8, true); }
-    else { GN1_LAUNCH(16, true); }
+                                                                               slabs, count, eps, silu, mod, ldmod, C, mod_rows)))
+  if (mod && mod_rows) {
+    if (gg.R == 2) { GN1_LAUNCH(2, 2); }
+    else if (gg.R == 4) { GN1_LAUNCH(4, 2); }
+    else if (gg.R == 8) { GN1_LAUNCH(8, 2); }
+    else { GN1_LAUNCH(16, 2); }
+  } else if (mod) {
+    if (gg.R == 2) { GN1_LAUNCH(2, 1); }
+    else if (gg.R == 4) { GN1_LAUNCH(4, 1); }
+    else if (gg.R == 8) { GN1_LAUNCH(8, 1); }
+    else { GN1_LAUNCH(16, 1); }
   } else {
-    if (gg.R == 2) { GN1_LAUNCH(2, false); }
-    else if (gg.R == 4) { GN1_LAUNCH(4, false); }
-    else if (gg.R == 8) { GN1_LAUNCH(8, false); }
-    else { GN1_LAUNCH(16, false); }
+    if (gg.R == 2) { GN1_LAUNCH(2, 0); }
+    else if (gg.R == 4) { GN1_LAUNCH(4, 0); }
+    else if (gg.R == 8) { GN1_LAUNCH(8, 0); }
+    else { GN1_LAUNCH(16, 0); }
   }
 #undef GN1_LAUNCH
   EMO_LAUNCH_CHECK();
@@ -648,14 +785,22 @@ static int gn_one_launch(const char* who, const void* x, int ldx, const float* g
 
 extern "C" int emo_groupnorm(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int N, int64_t S, int C,
                              int G, float eps, int silu, int dtype, void* stream) {
-  return gn_one_launch("emo_groupnorm", x, ldx, gamma, beta, nullptr, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+  return gn_one_launch("emo_groupnorm", x, ldx, gamma, beta, nullptr, 0, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
 }
 
 extern "C" int emo_groupnorm_mod(const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod, void* y, int ldy,
                                  int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream) {
   int rc = gn_mod_check("emo_groupnorm_mod", mod, ldmod, C);
   if (rc) return rc;
-  return gn_one_launch("emo_groupnorm_mod", x, ldx, gamma, beta, mod, ldmod, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+  return gn_one_launch("emo_groupnorm_mod", x, ldx, gamma, beta, mod, ldmod, 0, y, ldy, N, S, C, G, eps, silu, dtype, stream);
+}
+
+extern "C" int emo_groupnorm_mod_rows(const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod,
+                                      int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype,
+                                      void* stream) {
+  int rc = gn_mod_rows_check("emo_groupnorm_mod_rows", mod, ldmod, mod_rows, S, C);
+  if (rc) return rc;
+  return gn_one_launch("emo_groupnorm_mod_rows", x, ldx, gamma, beta, mod, ldmod, mod_rows, y, ldy, N, S, C, G, eps, silu, dtype, stream);
 }
 
 // ------------------------------------------------------------------------------------------ GroupNorm folded into a Linear

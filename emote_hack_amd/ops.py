@@ -141,6 +141,33 @@ def add(a: torch.Tensor, b: torch.Tensor, alpha=1.0, out=None) -> torch.Tensor:
     return out
 
 
+def add_periodic(x: torch.Tensor, f: torch.Tensor, out=None) -> torch.Tensor:
+    """y[m, :] = x[m, :] + f[m % P, :] over rows views (emo_add_periodic): the face-region map added behind conv_in to every frame of
+    every batch row (Net.py:509-516).  out=None runs IN PLACE on x - the zero-copy skip slot keeps its address."""
+    _need_cuda(x, f, out)
+    out = x if out is None else out
+    assert f.dtype == x.dtype == out.dtype and f.shape[1] == x.shape[1] and tuple(out.shape) == tuple(x.shape), (x.shape, f.shape, out.shape)
+    px, ldx = _rows(x)
+    pf, ldf = _rows(f)
+    po, ldo = _rows(out)
+    _launch("add_periodic", 0.0, x.element_size() * (2.0 * x.shape[0] + f.shape[0]) * x.shape[1],
+            lambda: check(_lib.load().emo_add_periodic(px, ldx, pf, ldf, po, ldo, x.shape[0], x.shape[1], f.shape[0], dt(x), _stream()),
+                          "emo_add_periodic"), tag=f"M={x.shape[0]} C={x.shape[1]} P={f.shape[0]}")
+    return out
+
+
+def mask_pool(mask: torch.Tensor, dtype, threshold=None) -> torch.Tensor:
+    """f32 (Hp, Wp) map -> (Hp/8 * Wp/8, 8) rows in `dtype`: channel 0 the 8x8 area mean, channels 1..7 zero - the cpad=8 rows
+    FaceRegionController consumes (emo_mask_pool).  threshold=t pools (x > t ? 1 : 0) instead: FaceLocator logits take t = 0."""
+    _need_cuda(mask)
+    assert mask.dtype == torch.float32 and mask.dim() == 2 and mask.is_contiguous(), (mask.dtype, mask.shape)
+    Hp, Wp = mask.shape
+    out = torch.empty(max(Hp // 8, 0) * max(Wp // 8, 0), 8, device=mask.device, dtype=dtype)
+    check(_lib.load().emo_mask_pool(_ptr(mask), _ptr(out), Hp, Wp, int(threshold is not None), float(threshold or 0.0), dt(dtype), _stream()),
+          "emo_mask_pool")
+    return out
+
+
 def convert(src: torch.Tensor, dtype, fp16_round=False) -> torch.Tensor:
     _need_cuda(src)
     src = src.contiguous()
@@ -177,11 +204,20 @@ def _mod_rows(mod, n_inst, Cc):
     return _ptr(mod), mod.stride(0)
 
 
-def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, silu_: bool, out=None, mod=None) -> torch.Tensor:
+def _mod_per_rows(mod, M, S, mod_rows, Cc):
+    """(ptr, ld) of a PER-FRAME modulation operand: f32 (M / mod_rows, 2C), one (scale | shift) row per mod_rows consecutive rows of x;
+    an instance of S rows holds whole frames"""
+    assert mod_rows > 0 and S % mod_rows == 0, (S, mod_rows)
+    return _mod_rows(mod, M // mod_rows, Cc)
+
+
+def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, silu_: bool, out=None, mod=None, mod_rows=0) -> torch.Tensor:
     """GroupNorm over NHWC rows; x (n_inst*S, C).  n_inst=B -> joint 5-D statistics (resnet.py:180),
     n_inst=B*F -> per frame (attention.py:124).
     mod = f32 (n_inst, 2C) rows (scale | shift): the scale-shift form y = act(GN(x) * (1 + scale) + shift) (resnet.py:191-197) in the
-    same launches - emo_hip.h emo_groupnorm_apply_mod / emo_groupnorm_mod."""
+    same launches - emo_hip.h emo_groupnorm_apply_mod / emo_groupnorm_mod.
+    mod_rows = r > 0: mod is (M / r, 2C) instead - one row per r consecutive rows of x (per FRAME under joint statistics: the per-frame
+    speed embedding, resnet.py:188-195) - emo_groupnorm_apply_mod_rows / emo_groupnorm_mod_rows."""
     _need_cuda(x, mod)
     lib = _lib.load()
     M, Cc = x.shape
@@ -189,6 +225,22 @@ def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: floa
     px, ldx = _rows(x)
     y = torch.empty(M, Cc, device=x.device, dtype=x.dtype) if out is None else out
     py, ldy = _rows(y)
+    if mod is not None and mod_rows:
+        pm, ldm = _mod_per_rows(mod, M, S, mod_rows, Cc)
+        tag = f"M={M} C={Cc}{' silu' if silu_ else ''} mod/{mod_rows}"
+        if GN_ONE_LAUNCH and lib.emo_groupnorm_one_launch_ok(n_inst, S, Cc, groups, dt(x)):
+            _launch("groupnorm", 0.0, x.element_size() * 2.0 * M * Cc,
+                    lambda: check(lib.emo_groupnorm_mod_rows(px, ldx, _ptr(gamma), _ptr(beta), pm, ldm, int(mod_rows), py, ldy, n_inst, S, Cc, groups,
+                                                             float(eps), int(silu_), dt(x), _stream()), "emo_groupnorm_mod_rows"), tag=tag + " 1L")
+            return y
+        part = torch.empty(max(lib.emo_groupnorm_workspace_bytes(n_inst, S, Cc, groups) // 4, 1), device=x.device, dtype=torch.float32)
+
+        def run_mod_rows():
+            check(lib.emo_groupnorm_stats(px, ldx, _ptr(part), n_inst, S, Cc, groups, dt(x), _stream()), "emo_groupnorm_stats")
+            check(lib.emo_groupnorm_apply_mod_rows(px, ldx, _ptr(part), _ptr(gamma), _ptr(beta), pm, ldm, int(mod_rows), py, ldy, n_inst, S, Cc,
+                                                   groups, float(eps), int(silu_), dt(x), _stream()), "emo_groupnorm_apply_mod_rows")
+        _launch("groupnorm", 0.0, x.element_size() * 2.0 * M * Cc, run_mod_rows, tag=tag)
+        return y
     if mod is not None:
         pm, ldm = _mod_rows(mod, n_inst, Cc)
         tag = f"M={M} C={Cc}{' silu' if silu_ else ''} mod"
@@ -221,21 +273,29 @@ def group_norm(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: floa
     return y
 
 
-def group_norm_coeffs(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, mod=None) -> torch.Tensor:
+def group_norm_coeffs(x: torch.Tensor, gamma, beta, n_inst: int, groups: int, eps: float, mod=None, mod_rows=0) -> torch.Tensor:
     """The statistics half of a GroupNorm whose normalisation runs inside its consumer (conv3x3(gn=...)): one read-only pass over x,
     then the per-(instance, channel) factors (n_inst, 2C) f32, channel pairs interleaved (scale, scale, shift, shift) - emo_hip.h
     emo_groupnorm_coeffs.  The normalised tensor is never materialised.
-    mod = f32 (n_inst, 2C) rows (scale | shift): the factors carry the scale-shift modulation (emo_groupnorm_coeffs_mod)."""
+    mod = f32 (n_inst, 2C) rows (scale | shift): the factors carry the scale-shift modulation (emo_groupnorm_coeffs_mod).
+    mod_rows = r > 0: mod is (M / r, 2C), one row per r consecutive rows of x, and the table has one row per mod row, (M / r, 2C):
+    the consumer reads it with ONE image per table row (emo_groupnorm_coeffs_mod_rows)."""
     _need_cuda(x, mod)
     lib = _lib.load()
     M, Cc = x.shape
     S = M // n_inst
     px, ldx = _rows(x)
     part = torch.empty(max(lib.emo_groupnorm_workspace_bytes(n_inst, S, Cc, groups) // 4, 1), device=x.device, dtype=torch.float32)
-    coef = torch.empty(n_inst, 2 * Cc, device=x.device, dtype=torch.float32)
+    per_rows = mod is not None and mod_rows
+    coef = torch.empty(M // mod_rows if per_rows else n_inst, 2 * Cc, device=x.device, dtype=torch.float32)
 
     def run():
         check(lib.emo_groupnorm_stats(px, ldx, _ptr(part), n_inst, S, Cc, groups, dt(x), _stream()), "emo_groupnorm_stats")
+        if per_rows:
+            pm, ldm = _mod_per_rows(mod, M, S, mod_rows, Cc)
+            check(lib.emo_groupnorm_coeffs_mod_rows(_ptr(part), _ptr(gamma), _ptr(beta), pm, ldm, int(mod_rows), _ptr(coef), n_inst, S, Cc, groups,
+                                                    float(eps), dt(x), _stream()), "emo_groupnorm_coeffs_mod_rows")
+            return
         if mod is not None:
             pm, ldm = _mod_rows(mod, n_inst, Cc)
             check(lib.emo_groupnorm_coeffs_mod(_ptr(part), _ptr(gamma), _ptr(beta), pm, ldm, _ptr(coef), n_inst, S, Cc, groups, float(eps), dt(x),

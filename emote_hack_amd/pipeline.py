@@ -79,12 +79,14 @@ def slerp(v0: torch.Tensor, v1: torch.Tensor, t: float, DOT_THRESHOLD: float = 0
 
 class EMOAnimationPipeline:
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None, image_encoder=None,
-                 image_processor=None, speed_encoder=None):
+                 image_processor=None, speed_encoder=None, face_region_controller=None, face_locator=None):
         """EMOAnimationPipeline.py:87-130.  The ctor forces steps_offset=1 / clip_sample=False on the
         scheduler it is given, like the reference.  image_encoder= (the reference's ctor call, :909-917) is a
         CLIPVisionModelWithProjection - on these kernels emote_hack_amd.clip_vision's; image_processor= defaults to that module's
         CLIPImageProcessor at the encoder's image_size.  speed_encoder= is an emote_hack_amd.conditioning.SpeedEncoder for
-        `__call__(head_rotation_speeds=)`; the attribute may also be assigned afterwards."""
+        `__call__(head_rotation_speeds=)` / `__call__(head_speeds_per_frame=)`; face_region_controller= an
+        emote_hack_amd.conditioning.FaceRegionController(1, block_out_channels[0]) for `face_mask=` and face_locator= an
+        emote_hack_amd.conditioning.FaceLocator for `face_mask="locate"`; the three attributes may also be assigned afterwards."""
         if unet is None or scheduler is None:
             raise ValueError("unet and scheduler are required")
         if not hasattr(scheduler, "step_plan"):
@@ -102,6 +104,7 @@ class EMOAnimationPipeline:
                                                  device=getattr(image_encoder, "device", unet.device))
         self.image_encoder, self.image_processor = image_encoder, image_processor
         self.speed_encoder = speed_encoder
+        self.face_region_controller, self.face_locator = face_region_controller, face_locator
         # EMOAnimationPipeline.py:105-117: ANY scheduler whose config has the key, not DDIM only - a DDPMScheduler handed to the
         # pipeline runs [981, ..., 1] on 50 of 1000 steps, like a diffusers DDPMScheduler would under the reference ctor
         if getattr(scheduler.config, "steps_offset", 1) != 1:
@@ -189,7 +192,8 @@ class EMOAnimationPipeline:
                         context_batch_size=1, context_schedule="uniform", audio_features=None, speed_embeddings=None, seed=0,
                         fusion_blocks="midup", dist=False, rank=0, world_size=1, return_eps=False, use_graphs=None,
                         controlnet=None, controlnet_cond=None, controlnet_conditioning_scale=1.0, reference_group=10,
-                        reference_lookahead=None, motion_latents=None, text_pairing="reference", _emulate_rank=None):
+                        reference_lookahead=None, motion_latents=None, text_pairing="reference", _emulate_rank=None, face_mask=None,
+                        face_mask_threshold=None):
         """Set up the loop state (EMOAnimationPipeline.py:628-696).  latents f32 (1,4,F_tot,h,w);
         ref_image_latents (1,4,h,w); text_embeddings (2,L,D) = [uncond, cond].
         reference_group = T: ReferenceNet timesteps computed per batched pass (1 = the reference's per-step order).
@@ -206,11 +210,19 @@ class EMOAnimationPipeline:
         cond-text bank - the same function as context_batch_size 1, batched.
         _emulate_rank=(r, n): MEASUREMENT aid (bench.py --emulate-rank): the work of rank r of an n-rank job - its units, its share of every
         ReferenceNet group, the projection of the whole group - in ONE process without collectives (the other ranks' eps slices are
-        missing, so the latents are not a sample of anything): a rank's critical path per step on an otherwise idle GPU."""
+        missing, so the latents are not a sample of anything): a rank's critical path per step on an otherwise idle GPU.
+        speed_embeddings (1 | 2, 4*C0) is one embedding per clip, (1 | 2, F_tot, 4*C0) one per frame: every UNet call gathers its
+        windows' rows with the indices the audio context uses.  face_mask: an (H, W) / (1, 1, H, W) map at pixel or latent size (see
+        `__call__`); the pipeline's FaceRegionController turns it into (h*w, C0) rows ONCE per clip and every UNet call adds them behind
+        conv_in.  face_mask_threshold=t pools (mask > t) instead of the mask (FaceLocator logits: t = 0).  Both inputs are replicated
+        on every rank."""
         if text_pairing not in ("reference", "branch"):
             raise ValueError(f"text_pairing must be 'reference' or 'branch', got {text_pairing!r}")
         unet, sch = self.unet, self.scheduler
         dev = unet.device
+        if face_mask is not None:      # (argument errors before anything is allocated or launched)
+            self._check_face_mask(face_mask, latents.shape[3] * self.vae_scale_factor, latents.shape[4] * self.vae_scale_factor)
+        self._check_speed_embeddings(speed_embeddings, latents.shape[2])
         # `do_classifier_free_guidance = guidance_scale > 1.0` (:622).  Without it the UNet batch is the window batch (:759-763
         # `.repeat(1)`), the text is the cond embedding alone, every row reads the bank and eps = noise_pred / counter.  (The
         # reference's own lines do not run in that mode: `pred_uc, pred_c = pred.chunk(2)` (:790) unpacks a one-row batch, and its
@@ -341,9 +353,9 @@ class EMOAnimationPipeline:
             st.writer_pool = torch.cuda.graph_pool_handle()   # own pool: the ReferenceNet pass runs concurrently with the Backbone
         # ---- contexts of the attn2 layers: their K / V^T projections depend on the context only -> once per clip (_bind_inputs)
         st.audio_features = None if audio_features is None else torch.empty(tuple(audio_features.shape), device=dev, dtype=torch.float32)
-        if speed_embeddings is not None and speed_embeddings.shape[0] not in (1, 2):
-            raise ValueError("speed_embeddings must have 1 row (shared) or 2 rows [uncond, cond]")
         st.speed = None if speed_embeddings is None else torch.empty(tuple(speed_embeddings.shape), device=dev, dtype=torch.float32)
+        # the face-region rows every UNet call adds behind conv_in: ONE buffer, rewritten per clip (captured graphs keep its address)
+        st.face_rows = None if face_mask is None else torch.empty(st.HW, unet.config.block_out_channels[0], device=dev, dtype=unet.dtype)
         for call in st.calls:
             call.ctx = call.ctx_kv = call.speed = None
         st.text_c = st.text[1:2]
@@ -391,7 +403,7 @@ class EMOAnimationPipeline:
                 call.cn_sel = torch.tensor([st.cn_pos[k] for w, _ in call.units for k in st.windows[w]], dtype=torch.int64, device=dev)
             st.cn_down, st.cn_mid, st.cn_embed = None, None, None
         self._bind_inputs(st, latents, ref_image_latents, text_embeddings, audio_features=audio_features, speed_embeddings=speed_embeddings,
-                          motion_latents=motion_latents, controlnet_cond=controlnet_cond,
+                          face_mask=face_mask, face_mask_threshold=face_mask_threshold, motion_latents=motion_latents, controlnet_cond=controlnet_cond,
                           controlnet_conditioning_scale=controlnet_conditioning_scale, guidance_scale=guidance_scale, eta=eta, seed=seed)
         return st
 
@@ -429,9 +441,63 @@ class EMOAnimationPipeline:
             ml = ml[0].permute(1, 0, 2, 3)
         return ml
 
+    @staticmethod
+    def _check_speed_embeddings(speed_embeddings, video_length):
+        """(1 | 2, 4*C0): one embedding per clip, shared or [uncond, cond]; (1 | 2, video_length, 4*C0): one per frame"""
+        se = speed_embeddings
+        if se is None:
+            return
+        if se.dim() not in (2, 3) or se.shape[0] not in (1, 2):
+            raise ValueError("speed_embeddings must have 1 row (shared) or 2 rows [uncond, cond]: (1 | 2, 4*C0) per clip or "
+                             f"(1 | 2, video_length, 4*C0) per frame, got {tuple(se.shape)}")
+        if se.dim() == 3 and se.shape[1] != video_length:
+            raise ValueError(f"per-frame speed_embeddings hold {se.shape[1]} frames, the clip has {video_length}")
+
+    def _check_face_mask(self, face_mask, height, width, locate_ok=False):
+        """The argument checks of `face_mask=` (nothing is launched): a FaceRegionController(1, block_out_channels[0]) on the pipeline,
+        and an (H, W) / (1, 1, H, W) map at pixel size (height, width) or at latent size (height / 8, width / 8).
+        Returns "pixel" or "latent" (or "locate" for that string where the caller resolves it)."""
+        ctl = getattr(self, "face_region_controller", None)
+        C0 = self.unet.config.block_out_channels[0]
+        if ctl is None:
+            raise ValueError("face_mask= needs a face_region_controller on the pipeline (emote_hack_amd.conditioning.FaceRegionController(1, "
+                             f"{C0}) with loaded weights: pass face_region_controller= to the constructor or assign pipe.face_region_controller)")
+        if ctl.in_channels != 1 or ctl.out_channels != C0:
+            raise ValueError(f"the face_region_controller maps {ctl.in_channels} -> {ctl.out_channels} channels; the mask has 1 and conv_in's "
+                             f"output {C0}: build FaceRegionController(1, {C0})")
+        if isinstance(face_mask, str):
+            if face_mask == "locate" and locate_ok:
+                return "locate"
+            raise ValueError(f"face_mask={face_mask!r}: a map, or \"locate\" in the pipeline call")
+        m = torch.as_tensor(face_mask)
+        f = self.vae_scale_factor
+        hw = tuple(m.shape) if m.dim() == 2 else tuple(m.shape[2:]) if (m.dim() == 4 and tuple(m.shape[:2]) == (1, 1)) else None
+        if hw == (height, width):
+            return "pixel"
+        if hw == (height // f, width // f):
+            return "latent"
+        raise ValueError(f"face_mask must be an (H, W) or (1, 1, H, W) map at pixel size ({height}, {width}) or at latent size "
+                         f"({height // f}, {width // f}), got {tuple(m.shape)}")
+
+    def _face_feature_rows(self, st, face_mask, threshold=None):
+        """face mask -> FaceRegionController input rows (h*w, 8) -> (h*w, C0) rows (train_stage_3_speedlayers.py:57-76).  A pixel-size
+        map is pooled 8 x 8 (ops.mask_pool, after the optional threshold); a latent-size one goes in as it is."""
+        f = self.vae_scale_factor
+        kind = self._check_face_mask(face_mask, st.h * f, st.w * f)
+        dev, dtp = st.latents.device, self.unet.dtype
+        m = torch.as_tensor(face_mask).to(dev).float()
+        m = m.reshape(m.shape[-2], m.shape[-1]).contiguous()
+        if kind == "pixel":
+            rows = ops.mask_pool(m, dtp, threshold=threshold)
+        else:
+            if threshold is not None:
+                m = (m > threshold).float()
+            rows = ops.ncfhw_to_rows(m.reshape(1, 1, 1, st.h, st.w), dtp, cpad=8)
+        return self.face_region_controller.forward_rows(rows, 1, st.h, st.w)
+
     def _bind_inputs(self, st, latents, ref_image_latents=None, text_embeddings=None, *, audio_features=None, speed_embeddings=None,
                      motion_latents=None, controlnet_cond=None, controlnet_conditioning_scale=None, guidance_scale=None, eta=None,
-                     seed=None):
+                     seed=None, face_mask=None, face_mask_threshold=None):
         """Copy a clip's inputs into the buffers of a prepared state (None = keep what is bound).  Everything derived from them -
         the attn2 K / V^T of the text / audio context per UNet call, the ReferenceNet's text K / V^T - is recomputed INTO the
         tensors the captured graphs already read; the ReferenceNet groups are marked stale (the reference image and the motion
@@ -482,7 +548,14 @@ class EMOAnimationPipeline:
         if speed_embeddings is not None:
             if st.speed is None:
                 raise ValueError("the state was prepared without speed_embeddings")
+            if speed_embeddings.dim() != st.speed.dim():
+                raise ValueError(f"the state was prepared with {'per-frame' if st.speed.dim() == 3 else 'per-clip'} speed_embeddings "
+                                 f"{tuple(st.speed.shape)}, got {tuple(speed_embeddings.shape)}")
             put(st.speed, speed_embeddings, "speed_embeddings")
+        if face_mask is not None:
+            if st.face_rows is None:
+                raise ValueError("the state was prepared without face_mask")
+            st.face_rows.copy_(self._face_feature_rows(st, face_mask, face_mask_threshold))
         for call in st.calls:
             if ctx_stale:
                 if st.audio_features is None:
@@ -503,7 +576,10 @@ class EMOAnimationPipeline:
                     self._put_kv(call.ctx_kv, pr, kv)
             if speed_embeddings is not None:
                 se = st.speed
-                sp = torch.cat([se[(br if se.shape[0] == 2 else 0):(br if se.shape[0] == 2 else 0) + 1] for _, br in call.units])
+                if se.dim() == 3:   # per frame: the rows of each unit's window, gathered like the audio context -> (n, nf, 4*C0)
+                    sp = torch.stack([se[br if se.shape[0] == 2 else 0].index_select(0, ix) for (_, br), ix in zip(call.units, call.idx)])
+                else:
+                    sp = torch.cat([se[(br if se.shape[0] == 2 else 0):(br if se.shape[0] == 2 else 0) + 1] for _, br in call.units])
                 if call.speed is None:
                     call.speed = sp
                 else:
@@ -696,9 +772,10 @@ class EMOAnimationPipeline:
         bank_tv = call.bank_tv if call.bank_tv is not None else st.bank_variants[0]
         self.unet._reference_control = st.reader
         st.reader.set_projected_banks(st.kv_all[bank_tv], st.bank_idx, call.n_uc)               # replaces reader.update (:774)
+        face = {} if st.face_rows is None else dict(face_features=st.face_rows)      # (a call without one launches what it always did)
         rows = self.unet(x, st.t_buf, encoder_hidden_states=call.ctx, speed_embeddings=call.speed, return_dict=False,
                          _return_rows=True, _ctx_kv=call.ctx_kv, _halves_identical=call.halves_identical,
-                         **self._controlnet_residuals(st, call))   # :777-786
+                         **self._controlnet_residuals(st, call), **face)   # :777-786
         n_rows = st.nf * st.HW
         for k, slot in enumerate(call.slots):
             st.send[slot].copy_(rows[k * n_rows:(k + 1) * n_rows])
@@ -805,7 +882,7 @@ class EMOAnimationPipeline:
         if cached is not None and cached[0] == key:
             st = cached[1]
             bind = {k: kw[k] for k in ("audio_features", "speed_embeddings", "motion_latents", "controlnet_cond",
-                                       "controlnet_conditioning_scale") if kw.get(k) is not None}
+                                       "controlnet_conditioning_scale", "face_mask", "face_mask_threshold") if kw.get(k) is not None}
             # an omitted guidance_scale / eta / seed means the documented DEFAULT, not "what the previous clip used" (they are not
             # part of the plan key, so the hit happens either way; "None = keep" is reset_denoise's contract, not this one's)
             bind.update(guidance_scale=_default(kw.get("guidance_scale"), 7.5), eta=_default(kw.get("eta"), 0.0), seed=_default(kw.get("seed"), 0))
@@ -846,8 +923,11 @@ class EMOAnimationPipeline:
             return id(td.group.WORLD) if td.is_initialized() else None     # (the public handle of the default group)
         plan = {k: v for k, v in kw.items() if k not in ("audio_features", "speed_embeddings", "motion_latents", "controlnet_cond",
                                                             "controlnet_conditioning_scale", "guidance_scale", "eta", "seed",
-                                                            "appearance_encoder", "controlnet")}
+                                                            "appearance_encoder", "controlnet", "face_mask", "face_mask_threshold")}
+        # (a face mask enters the plan by presence: either size ends in the same (h*w, C0) buffer; the speed embeddings by shape - per clip or
+        # per frame)
         return (shp(latents), shp(ref_image_latents), shp(text_embeddings), shp(kw.get("audio_features")), shp(kw.get("speed_embeddings")),
+                kw.get("face_mask") is not None,
                 shp(kw.get("motion_latents")), shp(kw.get("controlnet_cond")), kw.get("controlnet_conditioning_scale", 1.0),
                 self._do_cfg(kw.get("guidance_scale", 7.5)), wid(self.unet), wid(kw.get("appearance_encoder")), wid(kw.get("controlnet")),
                 sched_id(self.scheduler), pg_id(), unet_mod.SHARE_CFG_PREFIX, unet_mod.GN_FOLD_MIN_HW, unet_mod.GN_CONV_MIN_HW, unet_mod.MERGE_QKV,
@@ -855,7 +935,8 @@ class EMOAnimationPipeline:
 
     def reset_denoise(self, st, latents, motion_latents=None, **inputs):
         """Re-arm a prepared loop state for another clip of the SAME geometry: new noisy latents (and motion frames; optionally
-        ref_image_latents / text_embeddings / audio_features / speed_embeddings / controlnet_cond / guidance_scale / eta / seed)
+        ref_image_latents / text_embeddings / audio_features / speed_embeddings / face_mask (+ face_mask_threshold) / controlnet_cond /
+        guidance_scale / eta / seed; per-frame speeds and a face mask for a state prepared with them, refused otherwise)
         are copied IN PLACE, so the captured HIP graphs, the resident bank cache and the communicators are reused - only the
         context K / V^T and the ReferenceNet groups are recomputed (the reference image and the motion frames enter them)."""
         if tuple(latents.shape) != tuple(st.latents.shape):
@@ -893,6 +974,7 @@ class EMOAnimationPipeline:
             else:
                 motion = None
             if st is not None and tuple(st.latents.shape) == tuple(lat.shape):
+                # (same conditioning for every clip of the chain: the face mask, per-frame speeds and the rest stay bound)
                 self.reset_denoise(st, lat, motion)
             else:
                 st = self.prepare_denoise(lat, ref_image_latents, text_embeddings, motion_latents=motion, **kw)
@@ -916,6 +998,10 @@ class EMOAnimationPipeline:
 
     def _source_image_latents(self, source_image, width, height):
         """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is."""
+        return self.images2latents(self._source_image_rgb(source_image, width, height)[None], None)
+
+    @staticmethod
+    def _source_image_rgb(source_image, width, height):
         import numpy as np
         if isinstance(source_image, str):
             from PIL import Image
@@ -926,7 +1012,7 @@ class EMOAnimationPipeline:
             raise ValueError("source_image must be a file path or an (H, W, 3) uint8 RGB array (EMOAnimationPipeline.py:686-689)")
         if source_image.shape[0] % 8 or source_image.shape[1] % 8:
             raise ValueError(f"source_image {source_image.shape[:2]} must be a multiple of 8 in both directions")
-        return self.images2latents(source_image[None], None)
+        return source_image
 
     # ------------------------------------------------------------------ the rest of the reference class's surface
     def prepare_latents(self, batch_size, num_channels_latents, video_length, height, width, dtype, device, generator, latents=None, clip_length=16):
@@ -1085,8 +1171,14 @@ class EMOAnimationPipeline:
         the audio is stretched over the clip.  head_rotation_speeds= is ONE speed per clip (a float or a one-element f32 tensor) encoded by
         the pipeline's speed_encoder into `speed_embeddings` (one shared row); the reference's own `SpeedEncoder(10, 64)` asserts at
         Net.py:212 (9 bucket centres), so 9 buckets is the constructible choice, at the UNet's time-embedding width.
+        head_speeds_per_frame= is `video_length` speeds, one per frame, encoded once into a (video_length, 4*C0) table of per-frame speed
+        embeddings (the time embedding then differs per frame; not together with head_rotation_speeds=).  face_mask= is the face region: an
+        (H, W) or (1, 1, H, W) bool / uint8 / float map at (height, width) - pooled 8 x 8 - or at latent size, or "locate" = the pipeline's
+        face_locator run on source_image (logit > 0); the pipeline's face_region_controller turns it into features added behind conv_in for
+        every frame and both guidance branches (face_mask_threshold=t pools mask > t instead of the mask).
         Extra keyword inputs for the parts that are out of scope here: ref_image_latents=(1,4,h,w), audio_features=(F,L_a,D),
-        speed_embeddings=(1,4*C0) (takes precedence over head_rotation_speeds), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
+        speed_embeddings=(1 | 2, 4*C0) per clip or (1 | 2, video_length, 4*C0) per frame, shared or [uncond, cond] (takes precedence over
+        head_rotation_speeds / head_speeds_per_frame), seed=int; dist/rank/world_size as in the reference (:636-638).  Execution knobs (all
         optional): use_graphs (default: HIP-graph replay on a HIP device - the path bench.py measures), reference_group
         (ReferenceNet timesteps per batched pass; default 10, the configuration bench.py measures - 25 would make two passes per 50-step clip,
         40.03 vs 40.38 ms per step), reference_lookahead, fusion_blocks, motion_latents, reuse_state
@@ -1161,6 +1253,25 @@ class EMOAnimationPipeline:
             kwargs["audio_features"] = audio_context_tokens(windows, video_length, cfg.hidden_size, fps=kwargs.get("fps"),
                                                             audio_start=kwargs.get("audio_start", 0),
                                                             audio_frame_rate=(fx.sampling_rate, math.prod(cfg.conv_stride)))
+        if kwargs.get("head_speeds_per_frame") is not None:
+            # one speed per FRAME: the whole clip goes through the SpeedEncoder once, and the UNet takes the (video_length, 4*C0) table as
+            # per-frame speed embeddings (each UNet call gathers its windows' rows)
+            if head_rotation_speeds is not None:
+                raise ValueError("head_rotation_speeds= (ONE speed per clip) and head_speeds_per_frame= both name the head speed: pass one")
+            if kwargs.get("speed_embeddings") is None:
+                enc = getattr(self, "speed_encoder", None)
+                if enc is None:
+                    raise ValueError("head_speeds_per_frame= needs a speed_encoder on the pipeline (emote_hack_amd.conditioning.SpeedEncoder(9, "
+                                     "4 * block_out_channels[0]) with loaded weights: pass speed_encoder= to the constructor or assign "
+                                     "pipe.speed_encoder), or pass speed_embeddings=(1, video_length, 4 * block_out_channels[0])")
+                v = torch.as_tensor(kwargs["head_speeds_per_frame"], dtype=torch.float32).reshape(-1)
+                if v.numel() != video_length:
+                    raise ValueError(f"head_speeds_per_frame= takes one speed per frame: got {v.numel()} values for video_length {video_length}")
+                width_e = 4 * self.unet.config.block_out_channels[0]
+                if enc.speed_embedding_dim != width_e:
+                    raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width_e}: "
+                                     f"build SpeedEncoder(9, {width_e})")
+                kwargs["speed_embeddings"] = enc(v).reshape(1, video_length, width_e)
         if head_rotation_speeds is not None and kwargs.get("speed_embeddings") is None:
             # :783-784 hands `head_rotation_speeds` to a UNet that rejects it; here ONE speed per clip goes through the pipeline's
             # SpeedEncoder (Net.py:198-258) into the UNet's class-embedding slot, one row shared by the CFG halves
@@ -1173,11 +1284,27 @@ class EMOAnimationPipeline:
             if v.numel() != 1:
                 raise ValueError(f"head_rotation_speeds= takes ONE speed per clip (a float or a one-element tensor), got {v.numel()} values: "
                                  "per-frame speeds would need a per-frame time embedding - run one clip per speed, or pass speed_embeddings=")
-            width = 4 * self.unet.config.block_out_channels[0]
-            if enc.speed_embedding_dim != width:
-                raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width}: "
-                                 f"build SpeedEncoder(9, {width})")
+            width_e = 4 * self.unet.config.block_out_channels[0]      # (not `width`: that is the frame's, read again below)
+            if enc.speed_embedding_dim != width_e:
+                raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width_e}: "
+                                 f"build SpeedEncoder(9, {width_e})")
             kwargs["speed_embeddings"] = enc(v)
+        self._check_speed_embeddings(kwargs.get("speed_embeddings"), video_length)
+        face_mask, face_thr = kwargs.get("face_mask"), kwargs.get("face_mask_threshold")
+        if face_mask is not None:
+            # EMO's face region (Net.py:509-516): a mask, or "locate" = where the pipeline's FaceLocator (Net.py:819-855) sees a face in the
+            # source image (logit > 0, i.e. sigmoid > 0.5); the FaceRegionController turns it into features behind conv_in, once per clip
+            if self._check_face_mask(face_mask, height, width, locate_ok=True) == "locate":
+                loc = getattr(self, "face_locator", None)
+                if loc is None:
+                    raise ValueError("face_mask=\"locate\" needs a face_locator on the pipeline (emote_hack_amd.conditioning.FaceLocator with loaded "
+                                     "weights: pass face_locator= to the constructor or assign pipe.face_locator), or pass the mask itself")
+                if source_image is None:
+                    raise ValueError("face_mask=\"locate\" looks for the face in source_image=: pass it (a path or an (H, W, 3) uint8 array), or "
+                                     "pass the mask itself")
+                rgb = torch.as_tensor(self._source_image_rgb(source_image, width, height))
+                face_mask = loc(rgb.permute(2, 0, 1)[None].float() / 255.0)[0, 0]      # logits (H, W); pixels in [0, 1]
+                face_thr = 0.0
         if init_latents is not None:   # (b f) c h w -> b c f h w  (:657-658)
             bf, c4, hh, ww = init_latents.shape
             lat = init_latents.reshape(bf // video_length, video_length, c4, hh, ww).permute(0, 2, 1, 3, 4)
@@ -1195,6 +1322,7 @@ class EMOAnimationPipeline:
                            context_frames=context_frames, context_stride=context_stride, context_overlap=context_overlap,
                            context_batch_size=context_batch_size, context_schedule=context_schedule,
                            audio_features=kwargs.get("audio_features"), speed_embeddings=kwargs.get("speed_embeddings"),
+                           face_mask=face_mask, face_mask_threshold=face_thr,
                            seed=kwargs.get("seed", 0), dist=kwargs.get("dist", False), rank=kwargs.get("rank", 0),
                            world_size=kwargs.get("world_size", 1), num_actual_inference_steps=num_actual_inference_steps,
                            callback=callback, callback_steps=callback_steps, controlnet=self.controlnet, controlnet_cond=cn_cond,

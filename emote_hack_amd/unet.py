@@ -111,6 +111,7 @@ class _Ctx:
         self.bank_kv = {}           # prefix -> (K rows, V^T, L): bank projections precomputed by the sampler
         self.bank_row = None        # device int32 word: the row of bank_kv in use
         self.active = ()
+        self.temb_per_frame = False  # temb_all has one row per (batch row, frame): the per-frame speed embedding
 
 
 class _State:
@@ -431,24 +432,30 @@ class UNet3DConditionModel:
         n_img = c.B * c.F
         off = self._temb_off[p]
         temb = temb_all[:, off:off + r.temb_cols]
+        # a per-frame time embedding (temb_all has B * F rows): the row bias / the modulation changes every H * W rows, not every F * H * W
+        temb_rows = H * W if c.temb_per_frame else c.F * H * W
         if r.scale_shift:  # resnet.py:191-195: nothing is added in front of norm2; (scale | shift) = temb modulates behind it
             h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps)
         else:
-            h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps, rowbias=temb, rows_per_batch=c.F * H * W)
+            h = self._norm_act_conv(x, p + ".norm1", p + ".conv1", c, H, W, G, eps, rowbias=temb, rows_per_batch=temb_rows)
         sc = ops.gemm(x, w[p + ".sc.w"], w[p + ".sc.b"]) if r.has_shortcut else x
         return self._norm_act_conv(h, p + ".norm2", p + ".conv2", c, H, W, G, eps, inplace=True, mod=temb if r.scale_shift else None,
-                                   residual=sc, out_scale=1.0 / scale, out=out)
+                                   mod_rows=temb_rows if (r.scale_shift and c.temb_per_frame) else 0, residual=sc, out_scale=1.0 / scale, out=out)
 
-    def _norm_act_conv(self, x, norm, conv, c: _Ctx, H, W, G, eps, inplace=False, mod=None, **kw):
+    def _norm_act_conv(self, x, norm, conv, c: _Ctx, H, W, G, eps, inplace=False, mod=None, mod_rows=0, **kw):
         """GroupNorm (joint over the F frames of a batch row) -> SiLU -> 3x3 conv (resnet.py:180-183,191-196; unet_controlnet.py:476-477)
         with the normalisation inside the conv where the halo-reuse kernel serves it (GN_CONV_MIN_HW).
-        mod: f32 (B, 2C) (scale | shift) of a scale-shift resnet's norm2 (resnet.py:193-195), applied by the same kernels."""
+        mod: f32 (B, 2C) (scale | shift) of a scale-shift resnet's norm2 (resnet.py:193-195), applied by the same kernels;
+        mod_rows = H * W: mod is (B * F, 2C), one row per frame - the statistics stay joint, the modulation is the frame's."""
         w = self._w
         n_img = c.B * c.F
         mkw = {} if mod is None else dict(mod=mod)      # (the default path calls exactly what it always called)
+        if mod_rows:
+            mkw["mod_rows"] = mod_rows
         if GN_CONV_MIN_HW and H * W >= GN_CONV_MIN_HW and ops.conv_gn_fusable(x, w[conv + ".w"], n_img, H, W, kw.get("rowbias"), kw.get("rows_per_batch", 0)):
             coef = ops.group_norm_coeffs(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps, **mkw)
-            return ops.conv3x3(x, w[conv + ".w"], w[conv + ".b"], n_img, H, W, gn=(coef, c.F, True), **kw)[0]
+            # (a per-frame table has one row per image)
+            return ops.conv3x3(x, w[conv + ".w"], w[conv + ".b"], n_img, H, W, gn=(coef, 1 if mod_rows else c.F, True), **kw)[0]
         h = ops.group_norm(x, w[norm + ".g"], w[norm + ".b"], c.B, G, eps, True, out=x if inplace else None, **mkw)
         return ops.conv3x3(h, w[conv + ".w"], w[conv + ".b"], n_img, H, W, **kw)[0]
 
@@ -652,7 +659,7 @@ class UNet3DConditionModel:
     # overlap the ReferenceNet pass with the bank-independent down path on a second HIP stream)
     def _begin(self, sample, timestep, encoder_hidden_states, audio_features=None, speed_embeddings=None,
                down_block_additional_residuals=None, mid_block_additional_residual=None, add_after_conv_in=None, _ctx_kv=None,
-               halves_identical=False, class_labels=None):
+               halves_identical=False, class_labels=None, face_features=None):
         if self._w is None:
             absent = self._absent_keys()
             raise EmoHipError("UNet3DConditionModel: weights not loaded / model not on a HIP device "
@@ -701,7 +708,19 @@ class UNet3DConditionModel:
             else:
                 ce = ops.gather_rows(w["class_embedding.table"], cl.reshape(-1).to(torch.int32).expand(B).contiguous())
             emb = ops.add(emb, ce)
-        if speed_embeddings is not None:  # EMO extension: class-embedding slot (unet_controlnet.py:400-408)
+        if speed_embeddings is not None and speed_embeddings.dim() == 3:
+            # one speed embedding per FRAME (train_stage_3_speedlayers.py:242-271 adds a per-sample speed embedding; a clip's samples are
+            # its frames): emb[b * F + f] = emb[b] + speed[b, f], and everything behind it - temb_all, the resnets' row bias /
+            # modulation - has B * F rows
+            if self._controlnet is not None or self._gut_last:
+                raise ValueError(f"{type(self).__name__} takes speed_embeddings (B, {emb.shape[1]}) only: per-frame speed embeddings "
+                                 "(B, F, 4*C0) condition the Backbone")
+            if tuple(speed_embeddings.shape) != (B, F, emb.shape[1]):
+                raise ValueError(f"per-frame speed_embeddings must be (B, F, 4*C0) = ({B}, {F}, {emb.shape[1]}), got {tuple(speed_embeddings.shape)}")
+            se = ops.convert(speed_embeddings.to(dev).float().reshape(B * F, -1), dtp)
+            emb = ops.add_rowbias(se, emb, F)
+            s.c.temb_per_frame = True
+        elif speed_embeddings is not None:  # EMO extension: class-embedding slot (unet_controlnet.py:400-408)
             se = ops.convert(speed_embeddings.to(dev).float().reshape(B, -1), dtp)
             emb = ops.add(emb, se)
         s.temb_all = ops.convert(ops.gemm(ops.silu(emb), w["temb_all.w"], w["temb_all.b"]), torch.float32)
@@ -737,9 +756,13 @@ class UNet3DConditionModel:
         # and duplicated.  Same arithmetic, half the rows: ~0.8 ms of the 44 ms step (a 64x64-level self-attention alone is 0.45).
         s.dup = SHARE_CFG_PREFIX and bool(halves_identical) and B % 2 == 0 and add_after_conv_in is None and speed_embeddings is None and not has_class
         s.x_half = None
+        if face_features is not None:
+            face_features = self._face_rows(face_features, H, W)
         if s.dup:
             Mh = (B // 2) * F * H * W
             s.x_half, _, _ = ops.conv3x3(x[:Mh], w["conv_in.w"], w["conv_in.b"], (B // 2) * F, H, W)
+            if face_features is not None:   # both halves see the face region: added once, in front of the duplication
+                ops.add_periodic(s.x_half, face_features)
             s.x = self._skip_slot(s, B * F * H * W, self.spec.down[0].resnets[0].cin)
             if s.x is None:
                 s.x = torch.empty(B * F * H * W, s.x_half.shape[1], device=dev, dtype=dtp)
@@ -747,11 +770,28 @@ class UNet3DConditionModel:
             ops.copy_cols(s.x_half, s.x[Mh:], 0)
         else:
             s.x, _, _ = ops.conv3x3(x, w["conv_in.w"], w["conv_in.b"], B * F, H, W, out=self._skip_slot(s, B * F * H * W, self.spec.down[0].resnets[0].cin))
+            if face_features is not None:
+                # EMO extension (Net.py:509-516; train_stage_3_speedlayers.py:57-76,242-271): the face-region map joins conv_in's
+                # output of every frame of every batch row - IN PLACE, s.x is the skip's slot in its concat buffer
+                ops.add_periodic(s.x, face_features)
         if add_after_conv_in is not None:   # ControlNet: sample += controlnet_cond_embedding(cond) (controlnet.py:523-525)
             s.x = ops.add(s.x, add_after_conv_in)
         self._push_skip(s, s.x, (H, W))
         s.h, s.w = H, W
         return s
+
+    def _face_rows(self, ff, H, W):
+        """face_features as (H * W, C0) rows in the compute dtype: handed over as such, or as a (1, C0, H, W) map"""
+        C0 = self.config["block_out_channels"][0]
+        if ff.dim() == 4:
+            if tuple(ff.shape) != (1, C0, H, W):
+                raise ValueError(f"face_features must be ({H * W}, {C0}) rows or a (1, {C0}, {H}, {W}) map, got {tuple(ff.shape)}")
+            return ops.ncfhw_to_rows(ff.to(self.device).float().unsqueeze(2), self.dtype)
+        if ff.dim() != 2 or tuple(ff.shape) != (H * W, C0):
+            raise ValueError(f"face_features must be ({H * W}, {C0}) rows or a (1, {C0}, {H}, {W}) map, got {tuple(ff.shape)}")
+        if ff.dtype != self.dtype or not ff.is_cuda:
+            raise ValueError(f"face_features rows must be {self.dtype} on the model's device (FaceRegionController.forward_rows), got {ff.dtype} on {ff.device}")
+        return ff
 
     # ---- skip-connection plumbing
     def _up_resnets(self):
@@ -874,10 +914,13 @@ class UNet3DConditionModel:
                 down_block_additional_residuals: Optional[Tuple[torch.Tensor]] = None,
                 mid_block_additional_residual: Optional[torch.Tensor] = None, return_dict: bool = True,
                 audio_features=None, speed_embeddings=None, _return_rows=False, _ctx_kv=None,
-                _halves_identical=False) -> Union[UNet3DConditionOutput, Tuple]:
+                _halves_identical=False, face_features=None) -> Union[UNet3DConditionOutput, Tuple]:
         """unet_controlnet.py:328-483.  sample (B,C,F,h,w); timestep Tensor|int|float;
         encoder_hidden_states (B|B*F, L, D).  EMO extension kwargs (EMOAnimationPipeline.py:783-784):
-        audio_features (B*F, L_a, D) per-frame attn2 context; speed_embeddings (B, 4*C0) added to emb."""
+        audio_features (B*F, L_a, D) per-frame attn2 context; speed_embeddings (B, 4*C0) added to emb, or (B, F, 4*C0): one per frame
+        (emb, the resnets' row bias and their scale-shift modulation then differ per frame; GroupNorm statistics stay joint);
+        face_features (h*w, C0) rows in the compute dtype or a (1, C0, h, w) map, added to conv_in's output of every frame of
+        every batch row (emote_hack_amd.conditioning.FaceRegionController)."""
         # attention_mask: the reference prepares it (unet_controlnet.py:366-369) and hands it to its blocks, whose forwards never pass it
         # on to their transformers (unet_3d_blocks.py:276-283,384-410,618-660; Transformer3DModel.forward has no such parameter): a DEAD
         # input - the reference's output with a mask equals its output without (tests/golden/unet_switches.safetensors attention_mask/out).
@@ -886,7 +929,7 @@ class UNet3DConditionModel:
             raise TypeError("attention_mask must be a tensor or None")
         s = self._begin(sample, timestep, encoder_hidden_states, audio_features, speed_embeddings,
                         down_block_additional_residuals, mid_block_additional_residual, _ctx_kv=_ctx_kv,
-                        halves_identical=_halves_identical, class_labels=class_labels)
+                        halves_identical=_halves_identical, class_labels=class_labels, face_features=face_features)
         if self._reference_control is not None:
             self._reference_control._prepare(s.c, self)
         self._run_down(s)

@@ -59,6 +59,17 @@ int emo_copy_cols(const void* x, int ldx, void* y, int ldy, int coff, int64_t M,
 /* y = a + alpha*b elementwise over M x C (ControlNet residual adds, unet_controlnet.py:430-447). */
 int emo_add(const void* a, int lda, const void* b, int ldb, float alpha, void* y, int ldy, int64_t M, int C,
             int dtype, void* stream);
+/* y[m, :] = x[m, :] + f[m % P, :] over M x C rows, f a (P, C) map: the face-region features added to the output of conv_in for
+ * every frame of every batch row (Net.py:509-516 `face_features = self.face_locator(face_mask)`; train_stage_3_speedlayers.py:242-271
+ * adds them in front of the UNet), P = H * W.  y may be x (in place: the zero-copy skip slot keeps its address).  f32 sum, rounded once.
+ * C, ldx, ldf, ldy multiples of the 16-byte vector, operands 16-byte aligned; M % P != 0 is refused. */
+int emo_add_periodic(const void* x, int64_t ldx, const void* f, int64_t ldf, void* y, int64_t ldy, int64_t M, int C, int64_t P,
+                     int dtype, void* stream);
+/* A face-region mask at pixel size -> the latent-size input rows of FaceRegionController (train_stage_3_speedlayers.py:57-76: the mask
+ * is fed at the latents' size): x f32 (Hp, Wp), y (Hp / 8 * Wp / 8, 8) rows of `dtype`; channel 0 = the mean over the cell's 8 x 8
+ * pixels, channels 1..7 = 0 (the conv loader's channel pad).  use_thr != 0 pools (x > thr ? 1 : 0) instead - FaceLocator logits
+ * (Net.py:819-855) with thr = 0, i.e. sigmoid > 0.5.  Hp, Wp multiples of 8, x 16-byte aligned. */
+int emo_mask_pool(const float* x, void* y, int Hp, int Wp, int use_thr, float thr, int dtype, void* stream);
 /* dtype conversion of a contiguous buffer (src f32 <-> dst dtype); fp16_round!=0 rounds through IEEE
  * half first (bank hand-off, mutual_self_attention.py:588 `.to(float16)`). */
 int emo_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, int fp16_round, void* stream);
@@ -117,6 +128,26 @@ int emo_groupnorm_mod(const void* x, int ldx, const float* gamma, const float* b
                       int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype, void* stream);
 int emo_groupnorm_coeffs_mod(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
                              float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream);
+
+/* The PER-FRAME form of the scale-shift modulation: with one speed embedding per frame in the time embedding (EMO's head-rotation
+ * speed, train_stage_3_speedlayers.py:57-76,242-271, through time_emb_proj, resnet.py:188-195) the statistics of a resnet's GroupNorm
+ * stay joint over the F frames of a batch row, but (scale | shift) differs per frame.  `mod_rows` is the number of consecutive rows of x
+ * that share one mod row: row m of x (m = n * S + s) takes mod[(m / mod_rows) * ldmod + c] and mod[(m / mod_rows) * ldmod + C + c];
+ * mod has N * S / mod_rows rows and mod_rows divides S (an instance holds whole frames; mod_rows = H * W in the UNet).  Same
+ * partials, same combine, same three roundings of the modulation as the instance form: with every frame of an instance sharing one
+ * mod row the output is bit-identical to emo_groupnorm_apply_mod / emo_groupnorm_mod / emo_groupnorm_coeffs_mod.
+ *   emo_groupnorm_apply_mod_rows   after emo_groupnorm_stats
+ *   emo_groupnorm_mod_rows         the one-launch kernel, where emo_groupnorm_one_launch_ok says 1
+ *   emo_groupnorm_coeffs_mod_rows  the (a', b') table with ONE ROW PER FRAME, coef [N * S / mod_rows][2 * C]: the consumer sets
+ *                                  emo_gemm_params.gn_imgs_per_inst = 1 */
+int emo_groupnorm_apply_mod_rows(const void* x, int ldx, const void* partials, const float* gamma, const float* beta,
+                                 const float* mod, int ldmod, int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G,
+                                 float eps, int silu, int dtype, void* stream);
+int emo_groupnorm_mod_rows(const void* x, int ldx, const float* gamma, const float* beta, const float* mod, int ldmod,
+                           int64_t mod_rows, void* y, int ldy, int N, int64_t S, int C, int G, float eps, int silu, int dtype,
+                           void* stream);
+int emo_groupnorm_coeffs_mod_rows(const void* partials, const float* gamma, const float* beta, const float* mod, int ldmod,
+                                  int64_t mod_rows, float* coef, int N, int64_t S, int C, int G, float eps, int dtype, void* stream);
 
 /* The same GroupNorm in ONE launch, for instances small enough that one workgroup holds (instance, slab of whole groups)
  * in registers (<= 32 K elements per workgroup: the 8x8 level and the per-frame 16x16 norms at the bench size): one read of x, statistics in the same fixed
