@@ -203,6 +203,9 @@ extern "C" int emo_bilinear_to_nchw(const void* x, int64_t ld, float* y, int n_i
 // x rows (S, C): y[s, c] = act((x[s, c] - mean_c) * rstd_c * gamma_c + beta_c), statistics over the S rows of each channel
 // (biased variance, like nn.GroupNorm).  Pass 1: block (chunk, column slab of 64 channels) -> partial (sum, sumsq) per channel.
 // Pass 2: every block re-reduces the chunk partials of its slab in f64 in chunk order, then normalises its rows.
+// Both passes work on x - x[0, c] (the channel's first row; every chunk shifts alike, so the partials still add up): sum(x^2) / S - mean^2
+// on the raw values loses the variance of a channel whose spread is small against its level (two rows 0.01 apart at level 3 in f32: off by
+// 16 x the f32 tolerance), the shifted sums do not.
 static constexpr int CN_COLS = 64, CN_ROWS_T = 4;   // 256 threads = 64 channels x 4 row lanes
 
 template <typename T>
@@ -210,11 +213,13 @@ __global__ __launch_bounds__(256) void channelnorm_stats_kernel(const T* __restr
   const int c = blockIdx.y * CN_COLS + (threadIdx.x & 63), rl = threadIdx.x >> 6;
   const int64_t per = (S + nchunk - 1) / nchunk, s0 = blockIdx.x * per, s1 = s0 + per < S ? s0 + per : S;
   float sum = 0.f, sq = 0.f;
-  if (c < C)
+  if (c < C) {
+    const float x0 = TT<T>::ld(x + c);
     for (int64_t s_ = s0 + rl; s_ < s1; s_ += CN_ROWS_T) {
-      const float v = TT<T>::ld(x + s_ * ldx + c);
+      const float v = TT<T>::ld(x + s_ * ldx + c) - x0;
       sum += v; sq = fmaf(v, v, sq);
     }
+  }
   __shared__ float sh[2][CN_ROWS_T][CN_COLS];
   sh[0][rl][threadIdx.x & 63] = sum; sh[1][rl][threadIdx.x & 63] = sq;
   __syncthreads();
@@ -236,18 +241,18 @@ __global__ __launch_bounds__(256) void channelnorm_apply_kernel(const T* __restr
   if (rl == 0 && c < C) {
     double a = 0.0, b = 0.0;
     for (int k = 0; k < nchunk; k++) { a += (double)part[((int64_t)k * C + c) * 2]; b += (double)part[((int64_t)k * C + c) * 2 + 1]; }
-    const double mean = a / (double)S;
+    const double mean = a / (double)S;          // of x - x[0, c]
     double var = b / (double)S - mean * mean;
     if (var < 0.0) var = 0.0;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     sc[cl] = rstd * gamma[c];
-    sf[cl] = beta[c] - (float)mean * rstd * gamma[c];
+    sf[cl] = (float)mean;
   }
   __syncthreads();
   if (c >= C) return;
-  const float k = sc[cl], o = sf[cl];
+  const float k = sc[cl], ms = sf[cl], o = beta[c], x0 = TT<T>::ld(x + c);
   for (int64_t s_ = (int64_t)blockIdx.x * CN_ROWS_T + rl; s_ < S; s_ += (int64_t)gridDim.x * CN_ROWS_T) {
-    float v = fmaf(TT<T>::ld(x + s_ * ldx + c), k, o);
+    float v = fmaf((TT<T>::ld(x + s_ * ldx + c) - x0) - ms, k, o);
     if (act == 1) v = gelu_for<T>(v);
     TT<T>::st(y + s_ * ldy + c, v);
   }

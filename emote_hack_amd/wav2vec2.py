@@ -199,10 +199,15 @@ class Wav2Vec2Model:
             raise ValueError("input_values must be (1, n_samples): one utterance per call (Net.py:639)")
         c, w, dtp, dev = self._cfg, self._w, self.dtype, self.device
         eps = c["layer_norm_eps"]
-        wave = input_values[0].to(dev).float()
         k0, s0 = c["conv_kernel"][0], c["conv_stride"][0]
-        if wave.numel() < k0:
+        if input_values.shape[1] < k0:
             raise ValueError("input_values shorter than the first convolution's kernel")
+        n_t = input_values.shape[1]        # every layer must keep at least one frame: refuse before the first launch, not at the layer that runs dry
+        for k, s in zip(c["conv_kernel"], c["conv_stride"]):
+            if n_t < k:
+                raise ValueError("input_values too short for the feature encoder")
+            n_t = (n_t - k) // s + 1
+        wave = input_values[0].to(dev).float()
         # layer 0 (Cin = 1): the (T0, k0) window matrix, padded to 16-byte rows (index / pad only)
         a0 = torch.nn.functional.pad(wave.unfold(0, k0, s0), (0, _r8(k0) - k0)).contiguous()
         h = ops.gemm(ops.convert(a0, dtp), w["conv0"])

@@ -15,6 +15,7 @@ from emote_hack_amd.clip_vision import (OPENAI_CLIP_MEAN, OPENAI_CLIP_STD, VITL1
                                         CLIPVisionModelWithProjection, center_crop_offsets, clip_vision_param_shapes,
                                         clip_vision_synth_state_dict, resize_crop_taps, resize_output_size)
 from tests import cases
+from tests.frontend_sweep_cases import IP_CASES
 
 GEOMETRIES = [(512, 512), (480, 640), (768, 512), (300, 200), (224, 224), (225, 301)]      # (H, W); the last has an odd crop difference
 
@@ -131,11 +132,17 @@ def test_size_and_crop_rule_equals_transformers(H, W):
         assert g["resized"] == [rh, rw] and g["crop_top_left"] == [top, left]
 
 
-@pytest.mark.parametrize("H,W", GEOMETRIES + [(100, 160), (1080, 1920)])
-def test_tap_tables_reproduce_torch_antialiased_bicubic(H, W):
+# (H, W, S): the geometries above at crop 224, then the table tests/test_gpu_frontend_sweeps.py runs on the device (the first ones keep
+# their two-number ids)
+_TAP_224 = [(H, W, 224) for H, W in GEOMETRIES + [(100, 160), (1080, 1920)]]
+_TAP_CASES = _TAP_224 + [c for c in IP_CASES if c not in _TAP_224]
+
+
+@pytest.mark.parametrize("H,W,S", _TAP_CASES, ids=[f"{H}-{W}" if i < len(_TAP_224) else f"{H}-{W}-{S}" for i, (H, W, S) in enumerate(_TAP_CASES)])
+def test_tap_tables_reproduce_torch_antialiased_bicubic(H, W, S):
     """What emo_image_preprocess computes from the host tables (both passes in f32, numpy here) == the definition: F.interpolate(bicubic,
-    antialias=True) to the shortest-edge size, centre crop, clamp, rescale, normalise - enlarging (100x160) and strong shrinking too."""
-    S = 224
+    antialias=True) to the shortest-edge size, centre crop, clamp, rescale, normalise - enlarging (100x160) and strong shrinking too,
+    frames smaller than the filter support, extreme aspect ratios, crops of 32 .. 336."""
     t = resize_crop_taps(H, W, S, S)
     assert t["ytap"].shape == t["xtap"].shape == (S, 2) and t["ytap"].dtype == np.int32 and t["yw"].dtype == np.float32
     for tap, wt, n in ((t["ytap"], t["yw"], H), (t["xtap"], t["xw"], W)):       # inside the frame, weights sum to one

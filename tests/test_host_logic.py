@@ -382,6 +382,60 @@ def test_planner_can_pick_a_split_with_an_empty_slice():
     print(f"planned splits with an empty slice: {len(hits)} of the searched shapes; nk >= 41: {long_k[:12]}")
 
 
+def test_window_gemm_sweeps_reach_every_tile_with_lda_below_k():
+    """emo_gemm_plan over the window-GEMM tables of tests/frontend_sweep_cases.py (tests/test_gpu_frontend_gemm_sweeps.py launches
+    them): with lda < K they must reach every tile instantiation 1 .. 7, both main loops and the split-K workspace store; and the
+    GEMMs wav2vec2-base runs at 1 s and 10 s of audio - feature-encoder layers of M = 3199 / 31999 rows and below, N = 512,
+    K = 16 / 1536 / 1024, the positional conv at T = 49 / 499 - must each map to a (tile, main loop, split or not) of their dtype
+    that the tables contain."""
+    from emote_hack_amd import ops
+    from tests import frontend_sweep_cases as S
+    ws = ops.GEMM_STORE_PATHS.index("splitk_ws")
+    below, combos, n_cases = set(), set(), 0
+    for _name, cases, plan in S.win_tables():
+        assert cases
+        for c in cases:
+            fam, tile, phase, flags, split, store, _b_acc, _rb_acc = plan(c)
+            n_cases += 1
+            assert fam == 0 and flags == 0, c                                    # dense, the row-major tile kernel
+            assert phase == int(tile == 7) and (split > 1) == (store == ws), (c, tile, phase, split, store)
+            if c["split_k"] is not None:
+                assert split == c["split_k"], c
+            combos.add((c["dtype"], tile, phase, split > 1))
+            if c["lda"] < c["K"]:
+                below.add((tile, phase, split > 1))
+    assert n_cases == 3 * (4 * 3 * 2 * 8 * 3 * 2 + 3 * 2 * 3 * 2)
+    assert {t for t, _, _ in below} == set(range(1, 8)) and {p for _, p, _ in below} == {0, 1}
+    assert any(s for _, _, s in below)                                           # plan[4] > 1 on store path 5
+    assert any(c["split_k"] is None and plan(c)[4] > 1 for _n, cases, plan in S.win_tables() for c in cases if c["lda"] < c["K"])
+    for n_samples, rows, frames in ((16000, 3199, 49), (160000, 31999, 499)):
+        gemms = S.base_model_gemms(n_samples)
+        assert gemms[0] == (rows, 512, 16, 16) and gemms[1][1:] == (512, 1536, 1024) and gemms[6] == (frames, 512, 1024, 1024)
+        assert gemms[7] == (frames, 48, 6144, 48) and {g[2] for g in gemms[:7]} == {16, 1536, 1024}
+        for dtype in S.DTYPES:
+            for i, (M, N, K, lda) in enumerate(gemms):
+                p = ops.gemm_plan(dtype=dtype, M=M, N=N, K=K, lda=lda, bias=i == 7, split_k=None)      # what Wav2Vec2Model.forward asks
+                assert (dtype, p[1], p[2], p[4] > 1) in combos, (n_samples, dtype, (M, N, K, lda), p)
+
+
+def test_window_gemm_probes_are_exact():
+    """The exact probes of the window GEMMs (tests/frontend_sweep_cases.py win_operands / pos_operands assert it while they build):
+    every expected sum is a multiple of 1/16 below 16, representable in f32, f16 and bf16 - so is every partial sum, in any order."""
+    from tests import frontend_sweep_cases as S
+    for dtype in S.DTYPES:
+        for key in S.win_keys(dtype):
+            op = S.win_operands(dtype, *key, "probe")
+            k, s, C, M = key
+            # the closed form against the convolution it restates
+            ref = torch.nn.functional.conv1d(op["x"].double().t()[None], op["w"].double().view(-1, k, C).permute(0, 2, 1), stride=s)[0].t()
+            assert torch.equal(ref, op["y0"]), key
+            assert op["x"].shape == ((M - 1) * s + k, C) and bool((op["x"].sum(1) == 1).all())
+        for key in S.pos_keys(dtype):
+            S.pos_operands(dtype, *key, "probe")
+    assert [S.cn_chunks(x) for x in (1, 256, 257, 514, 16384, 16385, 33000)] == [(1, 1, 1), (1, 256, 16), (2, 129, 17), (3, 172, 33),
+                                                                                 (64, 256, 512), (64, 257, 512), (64, 516, 512)]
+
+
 def test_halo_sweeps_reach_every_instantiation():
     """emo_conv3x3_halo_plan (csrc/gemm.hip plan_halo: the function the launch path decides by, asked without a launch) against the
     case tables that tests/test_gpu_conv_halo_sweeps.py launches.  Every case must be served by the halo-reuse kernel with the patch
