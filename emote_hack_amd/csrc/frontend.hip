@@ -14,6 +14,11 @@
 //                        librosa.resample / mean(axis=1) of Net.py:627-640), f32, one output sample per lane, 64-bit sample indices
 //   emo_waveform_normalize : the processor's utterance normalisation (Net.py:639), two passes (mean, then centred squares), block
 //                        partials combined in f64 in index order by every block (deterministic)
+//   emo_interp_frames  : interpolate_latents (EMOAnimationPipeline.py:479-512) with util.py:125-138's slerp / linear for a whole clip:
+//                        per-pair dot / norm partials, then every writing block re-reduces them in f64 and takes the threshold branch
+//                        on the device (two launches, no host read, deterministic)
+//   emo_rows_to_frames_u8 : decoded NHWC rows -> packed uint8 (B, F, H, W, C) frames, (x / 2 + 0.5).clamp(0, 1) * 255 truncated
+//                        (decode_latents' tail + save_videos_grid, util.py:21-33)
 // All HBM-bound and tiny; 16-byte accesses where the geometry allows.
 #include "common.h"
 
@@ -413,6 +418,208 @@ extern "C" int emo_waveform_normalize(const float* x, float* y, int64_t n, float
   wavenorm_dev_kernel<<<nb, WN_T, 0, st>>>(x, (float*)workspace, n, per, nb);
   EMO_LAUNCH_CHECK();
   wavenorm_apply_kernel<<<nb, WN_T, 0, st>>>(x, (const float*)workspace, y, n, nb, eps);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ frame interpolation
+// interpolate_latents (EMOAnimationPipeline.py:479-512) over x (B, C, F, HW) f32: output frame j = p * k + r is frame p (r == 0, a copy)
+// or w0 * frame p + w1 * frame p+1 with the weights of util.py:125-138 at t = r / k.  A frame is ONE vector of N = B*C*HW values: plane
+// pl = (b, c) contributes HW contiguous floats at (pl * F + f) * HW, so logical element n lives at plane n / HW, offset n % HW (64-bit).
+// Pass 1: block (pair, slice [s*per, (s+1)*per) of the N elements) -> f32 partials (<v0, v1>, |v0|^2, |v1|^2) at part[(pair * ns + s) * 3].
+// Pass 2: block (output frame, slice); for r != 0 thread 0 re-reduces the pair's ns partials in index order in f64, takes the threshold
+// branch and derives the two weights.  No atomics, no counters: the same bits every run, nothing read back by the host.
+static constexpr int IF_T = 256, IF_SLICE = 2048, IF_MAXS = 256;
+
+static inline int if_slices(int64_t N) {
+  int64_t s = (N + IF_SLICE - 1) / IF_SLICE;
+  return (int)(s > IF_MAXS ? IF_MAXS : (s < 1 ? 1 : s));
+}
+static inline int64_t if_per(int64_t N, int ns) {    // a multiple of 4: a 16-byte chunk never straddles two slices
+  const int64_t per = (N + ns - 1) / ns;
+  return (per + 3) / 4 * 4;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(IF_T) void interp_reduce_kernel(const float* __restrict__ x, float* __restrict__ part, int F, int64_t HW, int64_t N,
+                                                             int64_t per) {
+  const int pair = blockIdx.x, s = blockIdx.y, ns = gridDim.y;
+  const int64_t n0 = s * per, n1 = n0 + per < N ? n0 + per : N;
+  float d = 0.f, a = 0.f, b = 0.f;
+  if constexpr (VEC) {      // HW % 4 == 0 (so N % 4 == 0) and x 16-byte aligned: every chunk lies inside one plane
+    for (int64_t n = n0 + 4 * (int64_t)threadIdx.x; n < n1; n += 4 * IF_T) {
+      const int64_t pl = n / HW, i = n - pl * HW;
+      const float* q = x + (pl * F + pair) * HW + i;
+      const float4 u = *(const float4*)q, v = *(const float4*)(q + HW);
+      d = fmaf(u.x, v.x, d); d = fmaf(u.y, v.y, d); d = fmaf(u.z, v.z, d); d = fmaf(u.w, v.w, d);
+      a = fmaf(u.x, u.x, a); a = fmaf(u.y, u.y, a); a = fmaf(u.z, u.z, a); a = fmaf(u.w, u.w, a);
+      b = fmaf(v.x, v.x, b); b = fmaf(v.y, v.y, b); b = fmaf(v.z, v.z, b); b = fmaf(v.w, v.w, b);
+    }
+  } else {
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += IF_T) {
+      const int64_t pl = n / HW, i = n - pl * HW;
+      const float* q = x + (pl * F + pair) * HW + i;
+      const float u = q[0], v = q[HW];
+      d = fmaf(u, v, d); a = fmaf(u, u, a); b = fmaf(v, v, b);
+    }
+  }
+  d = wave_sum(d); a = wave_sum(a); b = wave_sum(b);
+  __shared__ float sh[3][IF_T / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { sh[0][wave] = d; sh[1][wave] = a; sh[2][wave] = b; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    float t = sh[threadIdx.x][0];
+#pragma unroll
+    for (int w = 1; w < IF_T / 64; w++) t += sh[threadIdx.x][w];
+    part[((int64_t)pair * ns + s) * 3 + threadIdx.x] = t;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(IF_T) void interp_write_kernel(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ y, int F,
+                                                            int Fo, int64_t HW, int64_t N, int64_t per, int ns, int k, int method, float thr) {
+  const int j = blockIdx.x, s = blockIdx.y;
+  const int pr = j / k, r = j - pr * k;
+  __shared__ float wsh[2];
+  if (r != 0) {             // block-uniform
+    if (threadIdx.x == 0) {
+      const double t = (double)r / (double)k;
+      double w0 = 1.0 - t, w1 = t;
+      if (method == 1) {
+        const float* pp = part + (int64_t)pr * ns * 3;
+        double dd = 0.0, aa = 0.0, bb = 0.0;
+        for (int i = 0; i < ns; i++) { dd += (double)pp[3 * i]; aa += (double)pp[3 * i + 1]; bb += (double)pp[3 * i + 2]; }
+        const double c = dd / (sqrt(aa) * sqrt(bb));     // 0 / 0 = NaN for a zero frame: compares false, acos(NaN) = NaN, as upstream
+        if (!(fabs(c) > (double)thr)) {
+          const double om = acos(c), so = sin(om);
+          w0 = sin((1.0 - t) * om) / so;
+          w1 = sin(t * om) / so;
+        }
+      }
+      wsh[0] = (float)w0; wsh[1] = (float)w1;
+    }
+    __syncthreads();
+  }
+  const int64_t n0 = s * per, n1 = n0 + per < N ? n0 + per : N;
+  if (r == 0) {             // bit-for-bit copy of input frame pr (the last output frame is the last input frame: pr + 1 is never read)
+    if constexpr (VEC) {
+      for (int64_t n = n0 + 4 * (int64_t)threadIdx.x; n < n1; n += 4 * IF_T) {
+        const int64_t pl = n / HW, i = n - pl * HW;
+        *(uint4*)(y + (pl * Fo + j) * HW + i) = *(const uint4*)(x + (pl * F + pr) * HW + i);
+      }
+    } else {
+      const uint32_t* xs = (const uint32_t*)x;
+      uint32_t* yd = (uint32_t*)y;
+      for (int64_t n = n0 + threadIdx.x; n < n1; n += IF_T) {
+        const int64_t pl = n / HW, i = n - pl * HW;
+        yd[(pl * Fo + j) * HW + i] = xs[(pl * F + pr) * HW + i];
+      }
+    }
+    return;
+  }
+  const float w0 = wsh[0], w1 = wsh[1];
+  if constexpr (VEC) {
+    for (int64_t n = n0 + 4 * (int64_t)threadIdx.x; n < n1; n += 4 * IF_T) {
+      const int64_t pl = n / HW, i = n - pl * HW;
+      const float* q = x + (pl * F + pr) * HW + i;
+      const float4 u = *(const float4*)q, v = *(const float4*)(q + HW);
+      float4 o;
+      o.x = fmaf(w0, u.x, w1 * v.x); o.y = fmaf(w0, u.y, w1 * v.y); o.z = fmaf(w0, u.z, w1 * v.z); o.w = fmaf(w0, u.w, w1 * v.w);
+      *(float4*)(y + (pl * Fo + j) * HW + i) = o;
+    }
+  } else {
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += IF_T) {
+      const int64_t pl = n / HW, i = n - pl * HW;
+      const float* q = x + (pl * F + pr) * HW + i;
+      y[(pl * Fo + j) * HW + i] = fmaf(w0, q[0], w1 * q[HW]);
+    }
+  }
+}
+
+extern "C" size_t emo_interp_frames_workspace_bytes(int B, int C, int F, int64_t HW) {
+  if (B < 1 || C < 1 || F < 2 || HW < 1) return 0;
+  return (size_t)(F - 1) * if_slices((int64_t)B * C * HW) * 3 * sizeof(float);
+}
+extern "C" int emo_interp_frames(const float* x, float* y, int B, int C, int F, int64_t HW, int k, int method, float dot_threshold, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  EMO_CHECK(x && y && workspace, EMO_ERR_NULL, "emo_interp_frames: null pointer");
+  EMO_CHECK(B > 0 && C > 0 && F >= 2 && HW > 0 && k >= 2, EMO_ERR_BAD_SHAPE, "emo_interp_frames: B=%d C=%d F=%d HW=%lld k=%d (F >= 2, k >= 2)", B, C, F,
+            (long long)HW, k);
+  EMO_CHECK(method == 0 || method == 1, EMO_ERR_BAD_SHAPE, "emo_interp_frames: method %d (0 linear | 1 slerp)", method);
+  const int64_t Fo64 = (int64_t)(F - 1) * k + 1;
+  EMO_CHECK(HW < ((int64_t)1 << 40) && (int64_t)B * C < ((int64_t)1 << 20) && Fo64 <= 0x7fffffff &&
+            (double)B * C * (double)HW * (double)Fo64 < 1.0e18, EMO_ERR_BAD_SHAPE, "emo_interp_frames: index range");
+  const int Fo = (int)Fo64;
+  const int64_t N = (int64_t)B * C * HW;
+  const uintptr_t xa = (uintptr_t)x, xe = xa + (uintptr_t)N * F * sizeof(float), ya = (uintptr_t)y, ye = ya + (uintptr_t)N * Fo * sizeof(float);
+  EMO_CHECK(ya >= xe || xa >= ye, EMO_ERR_BAD_SHAPE, "emo_interp_frames: the output overlaps the input");
+  EMO_CHECK(workspace_bytes >= emo_interp_frames_workspace_bytes(B, C, F, HW), EMO_ERR_BAD_SHAPE,
+            "emo_interp_frames: workspace of %llu bytes, emo_interp_frames_workspace_bytes(%d, %d, %d, %lld) = %llu",
+            (unsigned long long)workspace_bytes, B, C, F, (long long)HW, (unsigned long long)emo_interp_frames_workspace_bytes(B, C, F, HW));
+  const int ns = if_slices(N);
+  const int64_t per = if_per(N, ns);
+  const bool vec = HW % 4 == 0 && xa % 16 == 0 && ya % 16 == 0;
+  hipStream_t st = as_stream(stream);
+  const dim3 g1((unsigned)(F - 1), (unsigned)ns), g2((unsigned)Fo, (unsigned)ns);
+  if (method == 1) {      // the linear weights need no scalars
+    if (vec) interp_reduce_kernel<true><<<g1, IF_T, 0, st>>>(x, (float*)workspace, F, HW, N, per);
+    else interp_reduce_kernel<false><<<g1, IF_T, 0, st>>>(x, (float*)workspace, F, HW, N, per);
+    EMO_LAUNCH_CHECK();
+  }
+  if (vec) interp_write_kernel<true><<<g2, IF_T, 0, st>>>(x, (const float*)workspace, y, F, Fo, HW, N, per, ns, k, method, dot_threshold);
+  else interp_write_kernel<false><<<g2, IF_T, 0, st>>>(x, (const float*)workspace, y, F, Fo, HW, N, per, ns, k, method, dot_threshold);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ 8-bit output frames
+// rows ((b f) h w, ld >= C) -> dense uint8 (B, F, HW, C): t = clamp(fma(x, mul, add), lo, hi), byte = trunc(t * 255).  One lane packs 16
+// consecutive output bytes (they span 16 / C rows) in registers and stores them as one 16-byte vector, as dwords when y is only 4-byte
+// aligned, and bytewise in the ragged tail (total need not be a multiple of 16).  Columns >= C of the rows are never addressed.
+template <typename T>
+__global__ __launch_bounds__(256) void rows_to_frames_u8_kernel(const T* __restrict__ x, int64_t ld, uint8_t* __restrict__ y, int64_t total, int C,
+                                                                float mul, float add, float lo, float hi, int align) {
+  const int64_t nvec = (total + 15) / 16;
+  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t o0 = v * 16, left = total - o0;
+    int64_t row = o0 / C;
+    int col = (int)(o0 - row * C);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      if (e < left) {
+        const float t = fminf(fmaxf(fmaf(TT<T>::ld(x + row * ld + col), mul, add), lo), hi);
+        w[e >> 2] |= (uint32_t)(uint8_t)(t * 255.0f) << (8 * (e & 3));
+      }
+      if (++col == C) { col = 0; row++; }
+    }
+    if (align == 16 && left >= 16) {
+      *(uint4*)(y + o0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (align >= 4 && left >= 4 * q + 4) {
+          *(uint32_t*)(y + o0 + 4 * q) = w[q];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+            if (4 * q + e < left) y[o0 + 4 * q + e] = (uint8_t)(w[q] >> (8 * e));
+        }
+      }
+    }
+  }
+}
+
+extern "C" int emo_rows_to_frames_u8(const void* x, int64_t ld, uint8_t* y, int B, int C, int F, int HW, float mul, float add, float lo, float hi,
+                                     int dtype, void* stream) {
+  EMO_CHECK(x && y, EMO_ERR_NULL, "emo_rows_to_frames_u8: null pointer");
+  EMO_CHECK(B > 0 && C > 0 && F > 0 && HW > 0 && ld >= C, EMO_ERR_BAD_SHAPE, "emo_rows_to_frames_u8: bad shape");
+  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_rows_to_frames_u8: dtype %d", dtype);
+  const int64_t total = (int64_t)B * F * HW * C;
+  const int align = ((uintptr_t)y % 16 == 0) ? 16 : (((uintptr_t)y % 4 == 0) ? 4 : 1);
+  EMO_DISPATCH(dtype, "emo_rows_to_frames_u8", (rows_to_frames_u8_kernel<T><<<fgrid((total + 15) / 16, 256), 256, 0, as_stream(stream)>>>(
+                                                   (const T*)x, ld, y, total, C, mul, add, lo, hi, align)));
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }

@@ -766,6 +766,49 @@ def rows_to_video(x: torch.Tensor, B, Cc, F, H, W, mul=0.5, add=0.5, lo=0.0, hi=
     return y
 
 
+def rows_to_frames_u8(x: torch.Tensor, B, Cc, F, H, W, mul=0.5, add=0.5, lo=0.0, hi=1.0, out=None) -> torch.Tensor:
+    """rows ((b f) h w, >= C) -> (B, F, H, W, C) uint8 = trunc(clamp(x*mul + add, lo, hi) * 255): decode_latents' tail and the
+    `(x * 255).astype(uint8)` of save_videos_grid in one launch (emo_rows_to_frames_u8).  out: a contiguous uint8 tensor of B*F*H*W*C
+    elements to write into (e.g. a slice of a longer clip)."""
+    _need_cuda(x, out)
+    px, ld = _rows(x)
+    assert x.shape[0] == B * F * H * W and x.shape[1] >= Cc, (x.shape, B, Cc, F, H, W)
+    if out is None:
+        out = torch.empty(B, F, H, W, Cc, device=x.device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == B * F * H * W * Cc, (out.dtype, out.shape)
+    _launch("rows_to_frames_u8", 0.0, (x.element_size() + 1.0) * out.numel(),
+            lambda: check(_lib.load().emo_rows_to_frames_u8(px, ld, _ptr(out), B, Cc, F, H * W, float(mul), float(add), float(lo), float(hi), dt(x),
+                                                            _stream()), "emo_rows_to_frames_u8"))
+    return out
+
+
+INTERP_METHODS = {"linear": 0, "slerp": 1}
+
+
+def interpolate_frames(latents: torch.Tensor, factor: int, method="slerp", dot_threshold: float = 0.9995, out=None, workspace=None) -> torch.Tensor:
+    """f32 latents (B, C, F, H, W) -> (B, C, (F - 1) * factor + 1, H, W): `factor - 1` frames between every two consecutive frames, each
+    frame taken as one vector over (B, C, H, W), by slerp (linear when |cos| > dot_threshold) or linear (emo_interp_frames;
+    EMOAnimationPipeline.py:479-512, magicanimate/utils/util.py:125-138).  Two launches on the current stream, no host read: capturable.
+    out / workspace: optional device buffers (workspace of >= emo_interp_frames_workspace_bytes bytes)."""
+    _need_cuda(latents, out, workspace)
+    assert latents.dtype == torch.float32 and latents.dim() == 5, (latents.dtype, latents.shape)
+    latents = latents.contiguous()
+    lib = _lib.load()
+    B, Cc, F, H, W = latents.shape
+    factor = int(factor)
+    m = INTERP_METHODS[method] if isinstance(method, str) else int(method)
+    if workspace is None:
+        workspace = torch.empty(max(lib.emo_interp_frames_workspace_bytes(B, Cc, F, H * W) // 4, 1), device=latents.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, Cc, max((F - 1) * factor + 1, 1), H, W, device=latents.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Cc * max((F - 1) * factor + 1, 1) * H * W, (out.dtype, out.shape)
+    _launch("interp_frames", 0.0, 4.0 * (3.0 * latents.numel() + out.numel()),
+            lambda: check(lib.emo_interp_frames(_ptr(latents), _ptr(out), B, Cc, F, H * W, factor, m, float(dot_threshold), _ptr(workspace),
+                                                workspace.numel() * workspace.element_size(), _stream()), "emo_interp_frames"),
+            tag=f"F={F} k={factor}")
+    return out
+
+
 def channel_norm(x: torch.Tensor, gamma, beta, eps=1e-5, gelu=False) -> torch.Tensor:
     """nn.GroupNorm(C, C) over a sequence: x rows (S, C) normalised per channel over the S rows, affine, optional erf-GELU (emo_channelnorm)."""
     _need_cuda(x)

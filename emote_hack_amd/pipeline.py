@@ -1128,12 +1128,22 @@ class EMOAnimationPipeline:
     def interpolate_latents(self, latents: torch.Tensor, interpolation_factor: int, device):
         """:479-512: `interpolation_factor - 1` frames interpolated between every two consecutive frames with the method set by
         `set_tensor_interpolation_method` (magicanimate/utils/util.py:116-140: slerp over the whole frame tensor, linear when the two are
-        nearly parallel).  `__call__` hard-codes the factor 1 (:824), for which this is the identity - outside the loop, host-level torch math."""
+        nearly parallel).  The reference's `__call__` hard-codes the factor 1 (:824), for which this is the identity; ours takes
+        `interpolation_factor=`.  Latents on a HIP device with this module's own `slerp` / `linear` set go through emo_interp_frames (two
+        launches for the clip, the threshold branch on the device); CPU tensors and a user-installed callable take the host-level torch
+        path below."""
         if interpolation_factor < 2:
             return latents
         method = get_tensor_interpolation_method()
         if method is None:
             raise TypeError("'NoneType' object is not callable: call set_tensor_interpolation_method(is_slerp) first (magicanimate/utils/util.py:116-123)")
+        return self._interpolate_latents(latents, interpolation_factor, device, method)
+
+    def _interpolate_latents(self, latents, interpolation_factor, device, method):
+        if latents.is_cuda and (method is slerp or method is linear):
+            x = latents if latents.dtype == torch.float32 else ops.convert(latents, torch.float32)
+            y = ops.interpolate_frames(x, interpolation_factor, "slerp" if method is slerp else "linear")
+            return y if latents.dtype == torch.float32 else ops.convert(y, latents.dtype)
         n = latents.shape[2]
         out = torch.zeros((latents.shape[0], latents.shape[1], (n - 1) * interpolation_factor + 1, latents.shape[3], latents.shape[4]),
                           device=latents.device, dtype=latents.dtype)
@@ -1182,7 +1192,23 @@ class EMOAnimationPipeline:
         optional): use_graphs (default: HIP-graph replay on a HIP device - the path bench.py measures), reference_group
         (ReferenceNet timesteps per batched pass; default 10, the configuration bench.py measures - 25 would make two passes per 50-step clip,
         40.03 vs 40.38 ms per step), reference_lookahead, fusion_blocks, motion_latents, reuse_state
-        (default True: a second call with the same geometry reuses the prepared plan and its captured graphs)."""
+        (default True: a second call with the same geometry reuses the prepared plan and its captured graphs).
+        interpolation_factor=k (an int >= 1, default 1 as :824 hard-codes) puts k - 1 interpolated frames between every two denoised
+        frames, where upstream has the stage: after the loop, before the decode (`interpolate_latents`, one emo_interp_frames call on the
+        finished latents; every rank of a dist=True run interpolates its identical copy).  interpolation="slerp" | "linear" picks the
+        method for this call only; None takes the one set by `set_tensor_interpolation_method`, slerp when none was set.
+        output_type="uint8" returns `videos` as (1, frames, H, W, 3) uint8 on the device (AutoencoderKL.decode_video(output="uint8"));
+        "latent" returns the (interpolated) latents."""
+        interp_k, interp = kwargs.get("interpolation_factor", 1), kwargs.get("interpolation")
+        if isinstance(interp_k, bool) or not isinstance(interp_k, numbers.Integral) or interp_k < 1:
+            raise ValueError(f"interpolation_factor= takes an int >= 1 (1: no interpolated frames), got {interp_k!r}")
+        if interp is not None and interp not in ("slerp", "linear"):
+            raise ValueError(f"interpolation= takes None (the method set by set_tensor_interpolation_method), \"slerp\" or \"linear\", got {interp!r}")
+        if interp_k >= 2 and (video_length is None or video_length < 2):
+            raise ValueError(f"interpolation_factor={interp_k} interpolates between consecutive frames: video_length must be >= 2, got {video_length!r}")
+        if output_type == "uint8" and self.vae is None:
+            raise ValueError("output_type=\"uint8\" decodes the latents into 8-bit frames: it needs a VAE on the pipeline "
+                             "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor); output_type=\"latent\" returns the latents")
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -1333,7 +1359,12 @@ class EMOAnimationPipeline:
                            reference_lookahead=kwargs.get("reference_lookahead"), fusion_blocks=kwargs.get("fusion_blocks", "midup"),
                            motion_latents=kwargs.get("motion_latents"), reuse_state=kwargs.get("reuse_state", True),
                            text_pairing=kwargs.get("text_pairing", "reference"))
-        if self.vae is not None and output_type != "latent":
+        if interp_k >= 2:      # :824, between the loop and the decode
+            method = {"slerp": slerp, "linear": linear}.get(interp) or get_tensor_interpolation_method() or slerp
+            lat = self._interpolate_latents(lat, int(interp_k), lat.device, method)
+        if output_type == "uint8":
+            video = self.vae.decode_video(lat, output="uint8")
+        elif self.vae is not None and output_type != "latent":
             video = self.vae.decode_video(lat)   # caller-supplied (:291-307)
         else:
             video = lat

@@ -295,11 +295,26 @@ class AutoencoderKL:
         return DecoderOutput(sample=y) if return_dict else (y,)
 
     @torch.no_grad()
-    def decode_video(self, latents, frames_per_call=4):
+    def decode_video(self, latents, frames_per_call=4, output="float"):
         """decode_latents (EMOAnimationPipeline.py:291-307): latents (b, 4, f, h, w) -> video (b, 3, f, 8h, 8w) f32 in [0, 1].
-        The reference decodes one frame per call; frames are batched here (`frames_per_call`) - the network is per-image."""
+        The reference decodes one frame per call; frames are batched here (`frames_per_call`) - the network is per-image.
+        output="uint8" returns (b, f, 8h, 8w, 3) uint8 on the device instead - the frames a video writer takes, what save_videos_grid
+        (magicanimate/utils/util.py:21-33) makes of the float video with `(x * 255).astype(uint8)` - each call's rows converted and
+        written straight into their place (emo_rows_to_frames_u8)."""
+        if output not in ("float", "uint8"):
+            raise ValueError(f"decode_video: output={output!r} (\"float\" | \"uint8\")")
         b, c4, f, h, w = latents.shape
         lat = (latents.to(self.device).float() * (1.0 / self._cfg["scaling_factor"])).permute(0, 2, 1, 3, 4).reshape(b * f, c4, h, w)
+        if output == "uint8":
+            co = self._cfg["out_channels"]
+            frames = None
+            for i0 in range(0, b * f, frames_per_call):
+                i1 = min(i0 + frames_per_call, b * f)
+                rows, H, W = self._decode_rows(lat[i0:i1])
+                if frames is None:
+                    frames = torch.empty(b * f, H, W, co, device=self.device, dtype=torch.uint8)
+                ops.rows_to_frames_u8(rows, 1, co, i1 - i0, H, W, out=frames[i0:i1])       # (b f) is the row order of both
+            return frames.reshape(b, f, H, W, co)
         out = torch.empty(b, self._cfg["out_channels"], f, 8 * h, 8 * w, device=self.device, dtype=torch.float32)
         for i0 in range(0, b * f, frames_per_call):
             i1 = min(i0 + frames_per_call, b * f)

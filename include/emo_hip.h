@@ -439,6 +439,28 @@ int emo_waveform_normalize(const float* x, float* y, int64_t n, float eps, void*
  * F.interpolate(logits, size=(Ho, Wo), mode='bilinear', align_corners=False) of rows ((n) h w, ld) into (n, C, Ho, Wo) f32. */
 int emo_maxpool2x2(const void* x, int64_t ldx, void* y, int64_t ldy, int n_img, int H, int W, int C, int dtype, void* stream);
 int emo_bilinear_to_nchw(const void* x, int64_t ld, float* y, int n_img, int C, int h, int w, int Ho, int Wo, int dtype, void* stream);
+/* emo_interp_frames: `interpolate_latents` (EMOAnimationPipeline.py:479-512) with the slerp / linear of magicanimate/utils/util.py:125-138
+ *   for a whole clip in TWO launches and no host read.  x f32 [B][C][F][HW] contiguous, F >= 2; y f32 [B][C][(F-1)*k + 1][HW], k >= 2.
+ *   Output frame j (p = j / k, r = j % k): r == 0 is input frame p copied bit for bit; otherwise w0 * frame p + w1 * frame p+1 at t = r / k.
+ *   A frame is the whole x[:, :, i] slice as ONE vector of B*C*HW values (batch included, as upstream).
+ *     method 0 (linear): w0 = 1 - t, w1 = t.
+ *     method 1 (slerp):  d = <v0, v1> / (|v0| |v1|); |d| > dot_threshold (either sign: upstream takes abs) -> the linear weights; else
+ *                        w = acos(d), w0 = sin((1 - t) w) / sin(w), w1 = sin(t w) / sin(w).  A zero-norm frame makes d NaN, and the frames
+ *                        strictly between that pair NaN (upstream's behaviour, kept); nothing else is touched.
+ *   Pass 1: block (pair, slice of the frame) -> f32 partials of <v0, v1>, |v0|^2, |v1|^2 in the workspace.  Pass 2: every block that
+ *   writes an interpolated frame re-reduces its pair's partials in index order in f64, derives w0 / w1 (f64, rounded once to f32) and
+ *   writes fmaf(w0, v0, w1 * v1).  No atomics, no counters: the same bits every run; the threshold branch is taken on the device.
+ *   16-byte accesses when HW % 4 == 0 and x, y are 16-byte aligned, scalar otherwise.  workspace_bytes must be >=
+ *   emo_interp_frames_workspace_bytes(B, C, F, HW), else EMO_ERR_BAD_SHAPE; so are F < 2, k < 2, an unknown method and y overlapping x.
+ * emo_rows_to_frames_u8: decoded NHWC rows ((b f) h w, ld >= C) in dtype -> packed uint8 [B][F][HW][C]: the `/ 2 + 0.5`, `clamp(0, 1)` of
+ *   decode_latents followed by the `(x * 255).astype(uint8)` of save_videos_grid (magicanimate/utils/util.py:21-33), per element
+ *     t = fminf(fmaxf(fmaf(x, mul, add), lo), hi);  y = (uint8_t)(t * 255.0f)      (x widened exactly to f32; truncation toward zero)
+ *   Columns >= C of a wide row are never read; the output is dense, stored as 16-byte vectors / dwords with a bytewise ragged tail. */
+size_t emo_interp_frames_workspace_bytes(int B, int C, int F, int64_t HW);
+int emo_interp_frames(const float* x, float* y, int B, int C, int F, int64_t HW, int k, int method, float dot_threshold, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int emo_rows_to_frames_u8(const void* x, int64_t ld, uint8_t* y, int B, int C, int F, int HW, float mul, float add, float lo, float hi,
+                          int dtype, void* stream);
 
 /* ---- CLIP vision encoder front (transformers CLIPVisionModelWithProjection: the `image_encoder` EMOAnimationPipeline.py:867 loads and
  * :909-917 hands to the pipeline; its image_embeds are the `clip_condition_embeddings` of models/videonet.py:255) -----------------------
