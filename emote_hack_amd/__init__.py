@@ -30,6 +30,9 @@ def __getattr__(name):  # heavy modules on demand
                 "clip_vision_synth_state_dict"):
         from . import clip_vision
         return getattr(clip_vision, name)
+    if name in ("save_videos_grid", "images2video", "video2images", "encode_mjpeg", "write_avi", "read_avi", "jpeg_tables"):
+        from . import video_io
+        return getattr(video_io, name)
     if name == "AppearanceEncoderModel":
         from .appearance_encoder import AppearanceEncoderModel
         return AppearanceEncoderModel

@@ -782,6 +782,55 @@ def rows_to_frames_u8(x: torch.Tensor, B, Cc, F, H, W, mul=0.5, add=0.5, lo=0.0,
     return out
 
 
+def jpeg_mcus(H: int, W: int) -> int:
+    """16x16 MCUs of an (H, W) frame at 4:2:0"""
+    return ((int(H) + 15) // 16) * ((int(W) + 15) // 16)
+
+
+def jpeg_blocks(frames: torch.Tensor, quant: torch.Tensor) -> torch.Tensor:
+    """packed uint8 RGB frames (n, H, W, 3) -> quantised DCT coefficients int16 (n, MCUs, 6, 64): 4:2:0, blocks Y00 Y01 Y10 Y11 Cb Cr,
+    zig-zag order, DC undifferenced (emo_jpeg_blocks; T.81 A.3.3 / A.3.4).  quant: device uint16 (2, 64), natural order."""
+    _need_cuda(frames, quant)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    assert quant.dtype == torch.uint16 and quant.numel() == 128 and quant.is_contiguous(), (quant.dtype, quant.shape)
+    n, H, W, _ = frames.shape
+    coefs = torch.empty(n, jpeg_mcus(H, W), 6, 64, device=frames.device, dtype=torch.int16)
+    _launch("jpeg_blocks", 0.0, float(frames.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_blocks(_ptr(frames), _ptr(coefs), n, H, W, _ptr(quant), _stream()), "emo_jpeg_blocks"),
+            tag=f"{n}x{H}x{W}")
+    return coefs
+
+
+def _jpeg_entropy_args(coefs, huff):
+    _need_cuda(coefs, huff)
+    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[2:]) == (6, 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
+    assert huff.dtype == torch.int32 and tuple(huff.shape) == (4, 256) and huff.is_contiguous(), (huff.dtype, huff.shape)
+    return coefs.shape[0], coefs.shape[1]
+
+
+def jpeg_count_bits(coefs: torch.Tensor, huff: torch.Tensor) -> torch.Tensor:
+    """coefficients (n, MCUs, 6, 64) -> the Huffman-coded size of every block in bits, int32 (n, MCUs * 6) (emo_jpeg_count_bits; T.81
+    F.1.2).  huff: device int32 (4, 256), length << 16 | code, DC luma / AC luma / DC chroma / AC chroma."""
+    n, n_mcu = _jpeg_entropy_args(coefs, huff)
+    counts = torch.empty(n, n_mcu * 6, device=coefs.device, dtype=torch.int32)
+    _launch("jpeg_count_bits", 0.0, 2.0 * coefs.numel(),
+            lambda: check(_lib.load().emo_jpeg_count_bits(_ptr(coefs), _ptr(counts), n, n_mcu, _ptr(huff), _stream()), "emo_jpeg_count_bits"))
+    return counts
+
+
+def jpeg_emit_bits(coefs: torch.Tensor, huff: torch.Tensor, bit_offsets: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """writes every block's codes MSB-first at its bit offset (int64 (n, MCUs * 6), from out's first bit) into out, a ZEROED uint8 buffer
+    of a multiple of 4 bytes (emo_jpeg_emit_bits): unstuffed, unpadded streams."""
+    n, n_mcu = _jpeg_entropy_args(coefs, huff)
+    _need_cuda(bit_offsets, out)
+    assert bit_offsets.dtype == torch.int64 and bit_offsets.numel() == n * n_mcu * 6 and bit_offsets.is_contiguous(), (bit_offsets.dtype, bit_offsets.shape)
+    assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), (out.dtype, out.shape)
+    _launch("jpeg_emit_bits", 0.0, 2.0 * coefs.numel() + out.numel(),
+            lambda: check(_lib.load().emo_jpeg_emit_bits(_ptr(coefs), _ptr(bit_offsets), _ptr(out), out.numel(), n, n_mcu, _ptr(huff), _stream()),
+                          "emo_jpeg_emit_bits"))
+    return out
+
+
 INTERP_METHODS = {"linear": 0, "slerp": 1}
 
 

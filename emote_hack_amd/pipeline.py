@@ -30,6 +30,7 @@ import math
 import numbers
 import os
 from dataclasses import dataclass
+from fractions import Fraction
 from types import SimpleNamespace
 from typing import Callable, List, Optional, Union
 
@@ -1159,6 +1160,20 @@ class EMOAnimationPipeline:
         out[:, :, k] = latents[:, :, n - 1]
         return out
 
+    @staticmethod
+    def _audio_for_file(audio):
+        """the samples save_path= puts beside the frames: audio= as a `.wav` path or a (samples, rate) pair, at its own rate and with its
+        own channels -> (float samples (n, channels), rate); anything else (a bare waveform, a container this build cannot demux) -> None"""
+        if isinstance(audio, (str, os.PathLike)):
+            if not os.fspath(audio).lower().endswith(".wav"):
+                return None
+            from .audio_io import read_wav
+            return read_wav(audio)
+        if isinstance(audio, tuple) and len(audio) == 2 and isinstance(audio[1], numbers.Integral):
+            x = audio[0].detach().cpu() if torch.is_tensor(audio[0]) else torch.as_tensor(audio[0])
+            return (x.reshape(len(x), -1).float().numpy(), int(audio[1]))
+        return None
+
     # ------------------------------------------------------------------ reference-compatible entry point
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]], video_length: Optional[int], height: Optional[int] = None,
@@ -1198,7 +1213,13 @@ class EMOAnimationPipeline:
         finished latents; every rank of a dist=True run interpolates its identical copy).  interpolation="slerp" | "linear" picks the
         method for this call only; None takes the one set by `set_tensor_interpolation_method`, slerp when none was set.
         output_type="uint8" returns `videos` as (1, frames, H, W, 3) uint8 on the device (AutoencoderKL.decode_video(output="uint8"));
-        "latent" returns the (interpolated) latents."""
+        "latent" returns the (interpolated) latents.
+        save_path="clip.avi" (with save_quality=1 .. 100, default 90) also writes the clip, where every reference run ends in
+        `save_videos_grid` (magicanimate/utils/util.py:21-33): the latents are decoded as for output_type="uint8" (so a VAE is needed),
+        JPEG-encoded on the device and written as Motion-JPEG in an AVI container (emote_hack_amd.video_io) playing at fps *
+        interpolation_factor - fps= is required.  audio= given as a `.wav` path or a (samples, rate) pair goes into the file as 16-bit PCM,
+        with its own channels at its own rate, from audio_start for the clip's duration (less where the audio ends first).  The return
+        value is what it is without save_path."""
         interp_k, interp = kwargs.get("interpolation_factor", 1), kwargs.get("interpolation")
         if isinstance(interp_k, bool) or not isinstance(interp_k, numbers.Integral) or interp_k < 1:
             raise ValueError(f"interpolation_factor= takes an int >= 1 (1: no interpolated frames), got {interp_k!r}")
@@ -1209,6 +1230,20 @@ class EMOAnimationPipeline:
         if output_type == "uint8" and self.vae is None:
             raise ValueError("output_type=\"uint8\" decodes the latents into 8-bit frames: it needs a VAE on the pipeline "
                              "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor); output_type=\"latent\" returns the latents")
+        save_path, save_quality, save_fps, save_audio = kwargs.get("save_path"), kwargs.get("save_quality", 90), None, None
+        if save_path is not None:
+            from . import video_io
+            save_path = video_io._avi_path(save_path, "save_path=")
+            video_io.jpeg_tables(save_quality)      # quality 1 .. 100
+            if kwargs.get("fps") is None:
+                raise ValueError("save_path= writes a video file and a file has a frame rate: pass fps= (an int, a Fraction or a (num, den) "
+                                 "pair; the file plays at fps * interpolation_factor)")
+            if self.vae is None:
+                raise ValueError("save_path= decodes the latents into 8-bit frames, as output_type=\"uint8\" does: it needs a VAE on the pipeline "
+                                 "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor)")
+            from .conditioning import _as_fraction
+            save_fps = video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k))
+            save_audio = self._audio_for_file(audio)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -1362,8 +1397,18 @@ class EMOAnimationPipeline:
         if interp_k >= 2:      # :824, between the loop and the decode
             method = {"slerp": slerp, "linear": linear}.get(interp) or get_tensor_interpolation_method() or slerp
             lat = self._interpolate_latents(lat, int(interp_k), lat.device, method)
+        frames_u8 = self.vae.decode_video(lat, output="uint8") if output_type == "uint8" or save_path is not None else None
+        if save_path is not None:      # the end of every reference run: save_videos_grid (magicanimate/utils/util.py:21-33)
+            from . import video_io
+            n_frames = frames_u8.shape[0] * frames_u8.shape[1]
+            if save_audio is not None:
+                samples, rate = save_audio
+                first = math.floor(_as_fraction(kwargs.get("audio_start", 0), "audio_start") * rate)
+                count = math.floor(n_frames * rate / save_fps + Fraction(1, 2))
+                save_audio = (samples[first:first + count], rate) if first < len(samples) else None      # cut where the audio ends
+            video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio)
         if output_type == "uint8":
-            video = self.vae.decode_video(lat, output="uint8")
+            video = frames_u8
         elif self.vae is not None and output_type != "latent":
             video = self.vae.decode_video(lat)   # caller-supplied (:291-307)
         else:

@@ -1,0 +1,414 @@
+"""The video writer behind the pipeline: what `save_videos_grid`, `images2video` and `video2images` (magicanimate/utils/util.py:21-33,
+:102-113) do through imageio and ffmpeg, as Motion-JPEG in an AVI container with a 16-bit PCM audio stream - a file every player opens.
+
+  jpeg_tables       the quantisation tables of a quality (T.81 Annex K.1 / K.2 under the IJG scaling rule) and the four Huffman tables of
+                    Annex K.3 - K.6, with the code / length arrays derived from BITS / HUFFVAL as Annex C does
+  encode_mjpeg      packed uint8 frames on the device -> one baseline JPEG file per frame: emo_jpeg_blocks, emo_jpeg_count_bits,
+                    emo_jpeg_emit_bits (csrc/video_out.hip), ONE device-to-host copy of the entropy-coded streams, then per frame on the
+                    host the padding of the last byte, the 0x00 behind every 0xFF and the marker segments (T.81 Annex B)
+  write_avi         a classic RIFF `AVI ` file: hdrl (avih, a vids / MJPG stream, optionally an auds / PCM stream), movi with the 00dc and
+                    01wb chunks interleaved per frame, idx1.  Below 2^31 bytes (OpenDML is not written)
+  read_avi          the reverse, for files write_avi made
+  save_videos_grid, images2video, video2images      the reference surface, `.avi` only (mp4 and gif need encoders that are not here)
+
+File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
+assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line)."""
+from __future__ import annotations
+
+import dataclasses
+import functools
+import os
+import struct
+from fractions import Fraction
+
+import numpy as np
+import torch
+
+from . import ops
+
+# ---------------------------------------------------------------------------------------------------------------------- T.81 tables
+# zig-zag index -> natural (row-major) index, T.81 figure A.6
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63],
+                  dtype=np.int64)
+# Annex K.1 (luminance) and K.2 (chrominance), natural order
+K1_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+           18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+K2_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# Annex K.3 - K.6: (BITS: codes of length 1 .. 16, HUFFVAL), in the order DC luminance, AC luminance, DC chrominance, AC chrominance
+_AC_LUMA_VALS = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f0"
+    "2433627282090a161718191a25262728292a3435363738393a434445464748494a"
+    "535455565758595a636465666768696a737475767778797a838485868788898a"
+    "92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9ca"
+    "d2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+_AC_CHROMA_VALS = bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0"
+    "156272d10a162434e125f11718191a262728292a35363738393a434445464748494a"
+    "535455565758595a636465666768696a737475767778797a82838485868788898a"
+    "92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6c7c8c9ca"
+    "d2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+HUFFMAN_SPECS = (
+    ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), bytes(range(12))),                          # K.3
+    ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D), _AC_LUMA_VALS),                          # K.5
+    ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), bytes(range(12))),                          # K.4
+    ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77), _AC_CHROMA_VALS),                        # K.6
+)
+HUFFMAN_IDS = ((0, 0), (1, 0), (0, 1), (1, 1))       # (table class Tc: 0 DC / 1 AC, destination Th) of the four, as DHT and SOS name them
+
+
+def huffman_codes(bits, huffval):
+    """Annex C (figures C.1 - C.3): BITS / HUFFVAL -> (code, length) arrays indexed by symbol; length 0 where the symbol has no code"""
+    if sum(bits) != len(huffval):
+        raise ValueError(f"BITS counts {sum(bits)} codes, HUFFVAL lists {len(huffval)}")
+    code, length = np.zeros(256, np.uint32), np.zeros(256, np.uint32)
+    c, k = 0, 0
+    for size in range(1, 17):
+        for _ in range(bits[size - 1]):
+            code[huffval[k]], length[huffval[k]] = c, size
+            c, k = c + 1, k + 1
+        c <<= 1
+    return code, length
+
+
+@dataclasses.dataclass(frozen=True)
+class JpegTables:
+    quality: int
+    quant: np.ndarray          # uint16 (2, 64): luminance, chrominance, NATURAL order (DQT stores them in zig-zag order)
+    specs: tuple               # the four (BITS, HUFFVAL) of HUFFMAN_SPECS
+    huff: np.ndarray           # uint32 (4, 256): length << 16 | code per symbol, the layout emo_jpeg_count_bits / emo_jpeg_emit_bits read
+
+
+def _check_quality(quality):
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"JPEG quality runs from 1 to 100, got {quality!r}")
+    return int(quality)
+
+
+@functools.lru_cache(maxsize=None)
+def _jpeg_tables(quality: int) -> JpegTables:
+    s = 5000 // quality if quality < 50 else 200 - 2 * quality          # the IJG rule (jpeg_quality_scaling)
+    quant = np.stack([np.clip((np.array(base, np.int64) * s + 50) // 100, 1, 255) for base in (K1_LUMA, K2_CHROMA)]).astype(np.uint16)
+    huff = np.stack([(ln << 16) | cd for cd, ln in (huffman_codes(*spec) for spec in HUFFMAN_SPECS)]).astype(np.uint32)
+    quant.setflags(write=False)
+    huff.setflags(write=False)
+    return JpegTables(quality, quant, HUFFMAN_SPECS, huff)
+
+
+def jpeg_tables(quality: int = 90) -> JpegTables:
+    """The tables of a baseline file at `quality` (1 .. 100): base * s, s = 5000 / q below 50 and 200 - 2 q from there, each entry
+    clamp((base * s + 50) // 100, 1, 255) - what libjpeg's jpeg_set_quality makes, so a file written here and one Pillow writes at the
+    same quality carry the same DQT and DHT segments."""
+    return _jpeg_tables(_check_quality(quality))
+
+
+# ---------------------------------------------------------------------------------------------------------------------- JPEG framing
+def _segment(marker: int, body: bytes) -> bytes:
+    return struct.pack(">BBH", 0xFF, marker, len(body) + 2) + body
+
+
+@functools.lru_cache(maxsize=64)
+def jpeg_header(height: int, width: int, quality: int) -> bytes:
+    """SOI, JFIF APP0, DQT x 2, SOF0, DHT x 4, SOS (T.81 B.2): everything in front of the entropy-coded segment of a 4:2:0 frame"""
+    t = jpeg_tables(quality)
+    if not (1 <= height <= 65535 and 1 <= width <= 65535):
+        raise ValueError(f"a JPEG frame is 1 .. 65535 pixels each way, got {height} x {width}")
+    out = [b"\xFF\xD8", _segment(0xE0, b"JFIF\x00" + struct.pack(">BBBHHBB", 1, 1, 0, 1, 1, 0, 0))]
+    for i in range(2):
+        out.append(_segment(0xDB, bytes([i]) + t.quant[i][ZIGZAG].astype(np.uint8).tobytes()))
+    out.append(_segment(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])))
+    for (bits, vals), (tc, th) in zip(t.specs, HUFFMAN_IDS):
+        out.append(_segment(0xC4, bytes([tc << 4 | th]) + bytes(bits) + bytes(vals)))
+    out.append(_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
+    return b"".join(out)
+
+
+def finish_scan(stream: np.ndarray, n_bits: int) -> bytes:
+    """An unstuffed entropy-coded stream of n_bits bits (uint8 array, zero beyond the last bit) -> the scan's bytes: the last byte filled
+    with 1-bits (F.1.2.3), a 0x00 behind every 0xFF (B.1.1.5), EOI"""
+    n = (n_bits + 7) // 8
+    a = np.array(stream[:n], dtype=np.uint8)
+    if n_bits & 7:
+        a[-1] |= (1 << (8 - (n_bits & 7))) - 1
+    a = np.insert(a, np.flatnonzero(a == 0xFF) + 1, 0)
+    return a.tobytes() + b"\xFF\xD9"
+
+
+@functools.lru_cache(maxsize=8)
+def _device_tables(quality: int, device: str):
+    t = jpeg_tables(quality)
+    return (torch.from_numpy(t.quant.copy()).to(device), torch.from_numpy(t.huff.astype(np.int64).astype(np.int32)).to(device))
+
+
+def encode_streams(frames_u8: torch.Tensor, quality: int = 90):
+    """The device part of encode_mjpeg: (n, H, W, 3) uint8 device frames -> (streams uint8 device buffer, byte start of every frame, bits
+    of every frame); three launches, one read of the n frame totals."""
+    quality = _check_quality(quality)
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError("encode_mjpeg takes packed uint8 RGB frames, (n, H, W, 3) or (1, n, H, W, 3) as output_type=\"uint8\" returns them, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if frames_u8.dim() == 5:
+        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
+    if frames_u8.shape[0] < 1:
+        raise ValueError("encode_mjpeg: no frames")
+    frames_u8 = frames_u8.contiguous()
+    quant, huff = _device_tables(quality, str(frames_u8.device))
+    coefs = ops.jpeg_blocks(frames_u8, quant)
+    counts = ops.jpeg_count_bits(coefs, huff)
+    ends = torch.cumsum(counts, dim=1, dtype=torch.int64)                       # bits, inside each frame
+    bits = ends[:, -1].cpu().numpy()                                            # the one read before the streams themselves
+    nbytes = (bits + 7) // 8
+    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+    offsets = (ends - counts + torch.from_numpy(starts * 8).to(ends.device)[:, None]).contiguous()
+    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
+    ops.jpeg_emit_bits(coefs, huff, offsets, out)
+    return out, starts, bits
+
+
+def encode_mjpeg(frames_u8: torch.Tensor, quality: int = 90) -> list:
+    """Packed uint8 RGB frames on the device, (n, H, W, 3) (or the (1, n, H, W, 3) of output_type="uint8") -> n baseline JPEG files
+    (bytes; 4:2:0, the standard Huffman tables).  The colour transform, the DCT, the quantisation and the Huffman coding run on the device;
+    the compressed streams come back in one copy, and the host pads, stuffs and wraps each."""
+    out, starts, bits = encode_streams(frames_u8, quality)                      # (checks the arguments)
+    host = out.cpu().numpy()
+    head = jpeg_header(int(frames_u8.shape[-3]), int(frames_u8.shape[-2]), int(quality))
+    return [head + finish_scan(host[s:], int(b)) for s, b in zip(starts, bits)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------- AVI container
+AVI_MAX_BYTES = 2 ** 31 - 1
+AVIF_HASINDEX, AVIF_ISINTERLEAVED, AVIIF_KEYFRAME = 0x10, 0x100, 0x10
+
+
+def fps_fraction(fps) -> Fraction:
+    """an int, a Fraction or a (num, den) pair -> a positive Fraction whose terms fit dwRate / dwScale"""
+    if isinstance(fps, (tuple, list)):
+        if len(fps) != 2:
+            raise ValueError(f"fps: a pair is (numerator, denominator), got {fps!r}")
+        f = Fraction(int(fps[0]), int(fps[1]))
+    elif isinstance(fps, bool) or not isinstance(fps, (int, np.integer, Fraction)):
+        raise ValueError(f"fps is an int, a Fraction or a (numerator, denominator) pair, got {fps!r}")
+    else:
+        f = Fraction(fps)
+    if f <= 0 or f.numerator >= 2 ** 32 or f.denominator >= 2 ** 32:
+        raise ValueError(f"fps must be positive with terms below 2^32, got {fps!r}")
+    return f
+
+
+def pcm16(samples) -> np.ndarray:
+    """float samples (n,) or (n, channels) -> int16 (n, channels): round(clip(x, -1, 1) * 32767)"""
+    x = samples.detach().cpu().numpy() if torch.is_tensor(samples) else np.asarray(samples)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError(f"audio samples are (n,) or (n, channels), got {x.shape}")
+    return np.rint(np.clip(x.astype(np.float64), -1.0, 1.0) * 32767.0).astype("<i2")
+
+
+def _chunk(cid: bytes, body: bytes) -> bytes:
+    return cid + struct.pack("<I", len(body)) + body + (b"\x00" if len(body) & 1 else b"")
+
+
+def write_avi(path, jpegs, width: int, height: int, fps, audio=None) -> None:
+    """JPEG frames (bytes each) -> a RIFF `AVI ` file at `path`: one vids / MJPG stream at fps = dwRate / dwScale and, with
+    audio=(float samples (n,) | (n, channels), rate), one auds stream of 16-bit PCM.  movi holds, per frame, the 00dc chunk followed by
+    the 01wb chunk of that frame's samples: sample boundaries are round(i * rate / fps), so no sample is lost or repeated, and whatever
+    the audio has beyond the last frame goes with the last frame.  ValueError when the file would pass 2^31 - 1 bytes."""
+    jpegs = [bytes(j) for j in jpegs]
+    f = fps_fraction(fps)
+    n = len(jpegs)
+    if n < 1 or not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+        raise ValueError(f"write_avi: {n} frames of {width} x {height}")
+    pcm = rate = None
+    if audio is not None:
+        pcm, rate = pcm16(audio[0]), int(audio[1])
+        if rate < 1:
+            raise ValueError(f"write_avi: audio rate {rate}")
+        channels, align = pcm.shape[1], 2 * pcm.shape[1]
+        cut = [min((2 * i * rate * f.denominator + f.numerator) // (2 * f.numerator), len(pcm)) for i in range(n)] + [len(pcm)]
+    largest = max(len(j) for j in jpegs)
+    movi_size = 4 + sum(8 + len(j) + (len(j) & 1) for j in jpegs)
+    n_wb = 0
+    if pcm is not None:
+        n_wb = sum(1 for i in range(n) if cut[i + 1] > cut[i])
+        movi_size += 8 * n_wb + align * len(pcm)                                 # 2-byte samples: no pad bytes
+    hdrl_size = 4 + (8 + 56) + (12 + (8 + 56) + (8 + 40)) + (0 if pcm is None else 12 + (8 + 56) + (8 + 18))
+    idx_size = 16 * (n + n_wb)
+    total = 12 + (8 + hdrl_size) + (8 + movi_size) + (8 + idx_size)
+    if total > AVI_MAX_BYTES:
+        raise ValueError(f"write_avi: the file would be {total} bytes; a classic AVI file ends at 2^31 - 1 = {AVI_MAX_BYTES} (OpenDML is not written): "
+                         "write shorter clips or lower the quality")
+    usec = (1000000 * f.denominator * 2 + f.numerator) // (2 * f.numerator)
+    per_sec = int(sum(len(j) for j in jpegs) * f / n) + (0 if pcm is None else rate * align)
+    avih = struct.pack("<14I", usec, min(per_sec, 2 ** 32 - 1), 0, AVIF_HASINDEX | AVIF_ISINTERLEAVED, n, 0, 1 if pcm is None else 2, largest,
+                       int(width), int(height), 0, 0, 0, 0)
+    strh_v = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"MJPG", 0, 0, 0, 0, f.denominator, f.numerator, 0, n, largest, 0xFFFFFFFF, 0,
+                         0, 0, int(width), int(height))
+    strf_v = struct.pack("<IiiHH4sIiiII", 40, int(width), int(height), 1, 24, b"MJPG", int(width) * int(height) * 3, 0, 0, 0, 0)
+    hdrl = b"hdrl" + _chunk(b"avih", avih) + b"LIST" + struct.pack("<I", 4 + 8 + 56 + 8 + 40) + b"strl" + _chunk(b"strh", strh_v) + _chunk(b"strf", strf_v)
+    if pcm is not None:
+        strh_a = struct.pack("<4s4sIHHIIIIIIII4H", b"auds", b"\x00\x00\x00\x00", 0, 0, 0, 0, 1, rate, 0, len(pcm),
+                             max(cut[i + 1] - cut[i] for i in range(n)) * align, 0xFFFFFFFF, align, 0, 0, 0, 0)
+        strf_a = struct.pack("<HHIIHHH", 1, channels, rate, rate * align, align, 16, 0)
+        hdrl += b"LIST" + struct.pack("<I", 4 + 8 + 56 + 8 + 18) + b"strl" + _chunk(b"strh", strh_a) + _chunk(b"strf", strf_a)
+    assert len(hdrl) == hdrl_size, (len(hdrl), hdrl_size)
+    movi, index, pos = [b"movi"], [], 4                                          # idx1 offsets count from the `movi` fourcc
+    for i, j in enumerate(jpegs):
+        c = _chunk(b"00dc", j)
+        index.append(struct.pack("<4sIII", b"00dc", AVIIF_KEYFRAME, pos, len(j)))
+        movi.append(c)
+        pos += len(c)
+        if pcm is not None and cut[i + 1] > cut[i]:
+            body = pcm[cut[i]:cut[i + 1]].tobytes()
+            c = _chunk(b"01wb", body)
+            index.append(struct.pack("<4sIII", b"01wb", AVIIF_KEYFRAME, pos, len(body)))
+            movi.append(c)
+            pos += len(c)
+    assert pos == movi_size, (pos, movi_size)
+    body = b"AVI " + b"LIST" + struct.pack("<I", hdrl_size) + hdrl + b"LIST" + struct.pack("<I", movi_size) + b"".join(movi) + _chunk(b"idx1", b"".join(index))
+    assert len(body) + 8 == total, (len(body) + 8, total)
+    with open(os.fspath(path), "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
+def _chunks(raw: bytes, pos: int, end: int):
+    """(id, body start, size) of the chunks in raw[pos:end]"""
+    while pos + 8 <= end:
+        cid, size = raw[pos:pos + 4], struct.unpack_from("<I", raw, pos + 4)[0]
+        if pos + 8 + size > end:
+            raise ValueError(f"read_avi: chunk {cid!r} at {pos} runs past its parent")
+        yield cid, pos + 8, size
+        pos += 8 + size + (size & 1)
+
+
+def read_avi(path):
+    """A file write_avi made -> (jpegs list[bytes], fps Fraction, audio): audio is None or (int16 samples (n, channels), rate) - the
+    stored PCM, undivided.  Anything else (another codec, OpenDML, more streams) is a ValueError."""
+    with open(os.fspath(path), "rb") as fh:
+        raw = fh.read()
+    if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"AVI " or struct.unpack_from("<I", raw, 4)[0] + 8 != len(raw):
+        raise ValueError(f"read_avi: {path!r} is not a RIFF AVI file of the size its header states")
+    top = {}
+    for cid, body, size in _chunks(raw, 12, len(raw)):
+        key = raw[body:body + 4] if cid == b"LIST" else cid
+        if cid == b"LIST" and size < 4 or key in top:
+            raise ValueError(f"read_avi: unexpected chunk {key!r}")
+        top[key] = (body, size)
+    if set(top) != {b"hdrl", b"movi", b"idx1"}:
+        raise ValueError(f"read_avi: expected hdrl, movi and idx1, found {sorted(top)}")
+    streams = []
+    for cid, body, size in _chunks(raw, top[b"hdrl"][0] + 4, sum(top[b"hdrl"])):
+        if cid == b"LIST" and raw[body:body + 4] == b"strl":
+            parts = {c: raw[b:b + s] for c, b, s in _chunks(raw, body + 4, body + size)}
+            if set(parts) != {b"strh", b"strf"} or len(parts[b"strh"]) != 56:
+                raise ValueError("read_avi: a stream list without strh + strf")
+            streams.append(parts)
+        elif cid != b"avih":
+            raise ValueError(f"read_avi: unexpected chunk {cid!r} in hdrl")
+    if not 1 <= len(streams) <= 2 or streams[0][b"strh"][:8] != b"vidsMJPG" or streams[0][b"strf"][16:20] != b"MJPG":
+        raise ValueError("read_avi: the first stream is not Motion-JPEG video")
+    scale, rate_v, _, n_frames = struct.unpack_from("<4I", streams[0][b"strh"], 20)
+    if scale < 1 or rate_v < 1:
+        raise ValueError(f"read_avi: dwRate / dwScale = {rate_v} / {scale}")
+    audio_fmt = None
+    if len(streams) == 2:
+        if streams[1][b"strh"][:4] != b"auds" or len(streams[1][b"strf"]) < 16:
+            raise ValueError("read_avi: the second stream is not audio")
+        tag, channels, rate_a, _, align, bits = struct.unpack_from("<HHIIHH", streams[1][b"strf"], 0)
+        if tag != 1 or bits != 16 or channels < 1 or align != 2 * channels:
+            raise ValueError(f"read_avi: audio format tag {tag} with {bits} bits is not 16-bit PCM")
+        audio_fmt = (channels, rate_a)
+    jpegs, pcm = [], []
+    for cid, body, size in _chunks(raw, top[b"movi"][0] + 4, sum(top[b"movi"])):
+        if cid == b"00dc":
+            jpegs.append(raw[body:body + size])
+        elif cid == b"01wb" and audio_fmt is not None:
+            pcm.append(raw[body:body + size])
+        else:
+            raise ValueError(f"read_avi: unexpected chunk {cid!r} in movi")
+    if len(jpegs) != n_frames:
+        raise ValueError(f"read_avi: the header counts {n_frames} frames, movi holds {len(jpegs)}")
+    audio = None
+    if audio_fmt is not None:
+        audio = (np.frombuffer(b"".join(pcm), dtype="<i2").reshape(-1, audio_fmt[0]).copy(), audio_fmt[1])
+    return jpegs, Fraction(rate_v, scale), audio
+
+
+# ---------------------------------------------------------------------------------------------------------------------- reference surface
+def _avi_path(path, who):
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() != ".avi":
+        raise ValueError(f"{who} writes Motion-JPEG `.avi` files, got {path!r}: name the file `.avi` (mp4 and gif need encoders that are not "
+                         "part of this build)")
+    return path
+
+
+def _makedirs_for(path):
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)            # util.py:32
+
+
+def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None) -> None:
+    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg + write_avi"""
+    path = _avi_path(path, "write_video")
+    if frames_u8.dim() == 5:
+        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
+    jpegs = encode_mjpeg(frames_u8, quality)
+    _makedirs_for(path)
+    write_avi(path, jpegs, int(frames_u8.shape[2]), int(frames_u8.shape[1]), fps, audio=audio)
+
+
+def make_grid_u8(videos: torch.Tensor, rescale=False, n_rows=6) -> torch.Tensor:
+    """(b, c, t, h, w) float in [0, 1] ([-1, 1] with rescale) -> (t, Hg, Wg, 3) uint8, the frames save_videos_grid hands to its writer:
+    torchvision.utils.make_grid(x, nrow=n_rows) with its defaults per time step (b == 1: the frame itself; otherwise xmaps = min(n_rows, b)
+    cells of (h + 2, w + 2) across a zero canvas of (h + 2) * ymaps + 2 by (w + 2) * xmaps + 2, image k at (y * (h + 2) + 2,
+    x * (w + 2) + 2)), then (x * 255) truncated to uint8 (values outside [0, 1] are clamped rather than wrapped).  Torch copies on the
+    videos' device."""
+    if not torch.is_tensor(videos) or videos.dim() != 5 or videos.shape[1] not in (1, 3) or not videos.is_floating_point():
+        raise ValueError(f"save_videos_grid takes a float (b, c, t, h, w) tensor with c = 1 or 3, got {tuple(getattr(videos, 'shape', ()))}")
+    b, c, t, h, w = videos.shape
+    x = videos.permute(2, 0, 3, 4, 1)                                            # t b h w c
+    if c == 1:
+        x = x.expand(t, b, h, w, 3)                                              # make_grid repeats a single channel
+    if b == 1:
+        grid = x[:, 0]
+    else:
+        xmaps = min(int(n_rows), b)
+        ymaps = -(-b // xmaps)
+        grid = torch.zeros(t, (h + 2) * ymaps + 2, (w + 2) * xmaps + 2, 3, device=videos.device, dtype=videos.dtype)
+        for k in range(b):
+            y0, x0 = (k // xmaps) * (h + 2) + 2, (k % xmaps) * (w + 2) + 2
+            grid[:, y0:y0 + h, x0:x0 + w] = x[:, k]
+    if rescale:
+        grid = (grid + 1.0) / 2.0                                                # util.py:28
+    return (grid * 255).clamp(0, 255).to(torch.uint8).contiguous()               # util.py:29
+
+
+def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90):
+    """magicanimate/utils/util.py:21-33 with a Motion-JPEG `.avi` in place of imageio.mimsave.  The frames are encoded on the HIP device:
+    videos held on the host are uploaded."""
+    path = _avi_path(path, "save_videos_grid")
+    if torch.is_tensor(videos) and not videos.is_cuda:
+        videos = videos.to("cuda")
+    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality)
+
+
+def images2video(video, path, fps=8, quality: int = 90):
+    """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file"""
+    path = _avi_path(path, "images2video")
+    frames = video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))
+    write_video(frames.to("cuda"), path, fps, quality)
+
+
+def decode_jpeg(data: bytes) -> np.ndarray:
+    """one JPEG file -> (H, W, 3) uint8 RGB (Pillow's decoder)"""
+    import io
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+
+def video2images(path, step=4, length=16, start=0):
+    """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays"""
+    jpegs, _, _ = read_avi(path)
+    return [decode_jpeg(j) for j in jpegs[start::step][:length]]

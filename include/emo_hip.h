@@ -462,6 +462,38 @@ int emo_interp_frames(const float* x, float* y, int B, int C, int F, int64_t HW,
 int emo_rows_to_frames_u8(const void* x, int64_t ld, uint8_t* y, int B, int C, int F, int HW, float mul, float add, float lo, float hi,
                           int dtype, void* stream);
 
+/* ---- Motion-JPEG output: the device half of the writer that stands in for `imageio.mimsave` at the end of `save_videos_grid`
+ * (magicanimate/utils/util.py:21-33).  Baseline sequential JPEG, ITU-T T.81; the host half (tables, markers, byte stuffing, the AVI
+ * container) is emote_hack_amd/video_io.py.
+ * emo_jpeg_blocks (util.py:21-33; T.81 A.3.3 FDCT, A.3.4 quantisation, A.3.6 zig-zag, A.2.3 / A.2.4 interleaved MCUs): packed uint8 RGB
+ *   frames [n][H][W][3], any H, W in 1 .. 65535 -> quantised coefficients int16 [n][mcu_rows * mcu_cols][6][64], mcu_rows = ceil(H / 16),
+ *   mcu_cols = ceil(W / 16); MCUs in raster order.  4:2:0: the six blocks of a 16x16 MCU in scan order Y00 Y01 Y10 Y11 Cb Cr (Yrc = the
+ *   8x8 luma block at row r, column c of the MCU); 64 coefficients per block in ZIG-ZAG order, the DC term UNDIFFERENCED.  Pixels beyond
+ *   the right and the bottom edge repeat the edge pixel.  All arithmetic in f32 (sums may be fused multiply-adds):
+ *     Y  =  0.299 R + 0.587 G + 0.114 B - 128        Cb = -0.168736 R - 0.331264 G + 0.5 B        Cr = 0.5 R - 0.418688 G - 0.081312 B
+ *     chroma sample = 0.25 * ((a + b) + (c + d)) over each 2x2 of the (edge-replicated) full-resolution Cb / Cr
+ *     S[v][u] = sum_y sum_x C[v][y] C[u][x] s[y][x],  C[u][x] = 0.5 c(u) cos((2x + 1) u pi / 16), c(0) = 1 / sqrt 2, c(u > 0) = 1
+ *       (rows first, then columns; C rounded once to f32)
+ *     coefficient = (int16) rintf(S[v][u] / q[v * 8 + u])
+ *   quant: device uint16 [2][64], luma then chroma, NATURAL order (a 0 entry is taken as 1).  With 8-bit samples |S| <= 1024, so DC
+ *   differences stay inside size category 11 and AC coefficients inside category 10 for every q >= 1.  coefs 4-byte aligned.
+ * emo_jpeg_count_bits (T.81 F.1.2 Huffman encoding procedures, F.1.2.1 DC, F.1.2.2 AC): the exact coded size in bits of every block,
+ *   counts int32 [n][n_mcu * 6].  DC: the difference from the previous block of the same component in the SAME frame (predictor 0 at every
+ *   frame's start, F.1.1.5.1), coded as its size category followed by that many magnitude bits (a negative value v as v - 1).  AC: one
+ *   run / size symbol per non-zero coefficient, one ZRL (0xF0) per 16 zeros of a longer run, EOB (0x00) when the last coefficient is zero.
+ *   huff: device uint32 [4][256] in the order DC luma, AC luma, DC chroma, AC chroma, entry [symbol] = code length << 16 | code
+ *   (length 0: the symbol has no code and contributes nothing - the tables must cover categories 0 .. 11 and every AC symbol).
+ * emo_jpeg_emit_bits (T.81 F.1.2, bit order of F.1.2.3 / figure F.1.2: most significant bit first): the codes counted above, block b
+ *   starting at bit bit_offsets[b] (int64 [n][n_mcu * 6], counted from the first bit of out) - the caller lays the blocks of a frame end
+ *   to end and starts every frame on a byte.  The stream is UNSTUFFED and unpadded: the host adds the 0x00 after every 0xFF and the
+ *   1-bits that fill the last byte.  out must be zeroed up to the last stream byte, 4-byte aligned, out_bytes a multiple of 4: codes
+ *   are OR-ed in as byte-swapped 32-bit words (atomicOr - blocks share words; OR commutes, so the result is the same every run), a word
+ *   is touched only where a code has a 1-bit in it, and never at or beyond out_bytes. */
+int emo_jpeg_blocks(const uint8_t* frames, int16_t* coefs, int n, int H, int W, const uint16_t* quant, void* stream);
+int emo_jpeg_count_bits(const int16_t* coefs, int32_t* counts, int n, int n_mcu, const uint32_t* huff, void* stream);
+int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
+                       const uint32_t* huff, void* stream);
+
 /* ---- CLIP vision encoder front (transformers CLIPVisionModelWithProjection: the `image_encoder` EMOAnimationPipeline.py:867 loads and
  * :909-917 hands to the pipeline; its image_embeds are the `clip_condition_embeddings` of models/videonet.py:255) -----------------------
  * emo_image_preprocess: transformers CLIPImageProcessor (resize to the shortest edge, centre crop, rescale, normalise) in one launch.
