@@ -36,5 +36,3 @@ class AppearanceEncoderModel(UNet3DConditionModel):
         if sample.dim() == 4:
             sample = sample.unsqueeze(2)
         return super().forward(sample, timestep, encoder_hidden_states, **kw)
-
-    __call__ = forward

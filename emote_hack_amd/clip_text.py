@@ -14,14 +14,13 @@ Not built: key-padding masks, non-default position_ids, clip-skip (output_hidden
 """
 from __future__ import annotations
 
-import json
-import os
 from types import SimpleNamespace
 
 import torch
 
 from . import ops
-from ._lib import EmoHipError
+from .clip_layers import ACTS as _ACTS, clip_layer_shapes, load_local_checkpoint, pack_clip_layers, run_clip_layers
+from .module import HipModule
 from .synth import synth_state_dict
 
 # SD-1.5's text_encoder/config.json (openai/clip-vit-large-patch14's text tower); eos_token_id 2 is what that legacy file says
@@ -29,11 +28,6 @@ from .synth import synth_state_dict
 SD15_CONFIG = dict(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12,
                    max_position_embeddings=77, hidden_act="quick_gelu", layer_norm_eps=1e-5, bos_token_id=0, eos_token_id=2,
                    pad_token_id=1)
-_ACTS = {"quick_gelu": "quick_gelu", "gelu": "gelu"}
-
-
-def _r8(x):
-    return (x + 7) // 8 * 8
 
 
 def clip_text_param_shapes(cfg=None):
@@ -42,19 +36,7 @@ def clip_text_param_shapes(cfg=None):
     H, I, P = c["hidden_size"], c["intermediate_size"], c["max_position_embeddings"]
     d = {"text_model.embeddings.token_embedding.weight": (c["vocab_size"], H),
          "text_model.embeddings.position_embedding.weight": (P, H)}
-    for i in range(c["num_hidden_layers"]):
-        p = f"text_model.encoder.layers.{i}"
-        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            d[f"{p}.self_attn.{n}.weight"] = (H, H)
-            d[f"{p}.self_attn.{n}.bias"] = (H,)
-        d[f"{p}.layer_norm1.weight"] = (H,)
-        d[f"{p}.layer_norm1.bias"] = (H,)
-        d[f"{p}.mlp.fc1.weight"] = (I, H)
-        d[f"{p}.mlp.fc1.bias"] = (I,)
-        d[f"{p}.mlp.fc2.weight"] = (H, I)
-        d[f"{p}.mlp.fc2.bias"] = (H,)
-        d[f"{p}.layer_norm2.weight"] = (H,)
-        d[f"{p}.layer_norm2.bias"] = (H,)
+    d.update(clip_layer_shapes("text_model.encoder.layers", c["num_hidden_layers"], H, I))
     d["text_model.final_layer_norm.weight"] = (H,)
     d["text_model.final_layer_norm.bias"] = (H,)
     return d
@@ -65,9 +47,11 @@ def clip_text_synth_state_dict(cfg=None, prefix="clip_text.", device="cpu"):
     return synth_state_dict(clip_text_param_shapes(cfg), prefix=prefix, device=device)
 
 
-class CLIPTextModel:
+class CLIPTextModel(HipModule):
     """forward(input_ids (B, L) with L <= max_position_embeddings) -> namespace(last_hidden_state (B, L, hidden), pooler_output (B, hidden))
     in the model's dtype; `[0]` is last_hidden_state, like the transformers output `_encode_prompt` indexes (EMOAnimationPipeline.py:226-229)."""
+    # older SD-1.5 checkpoints carry the position_ids buffer; transformers ignores it (non-persistent)
+    _tolerated = frozenset({"text_model.embeddings.position_ids"})
 
     def __init__(self, config=None, **kwargs):
         cfg = dict(SD15_CONFIG)
@@ -82,104 +66,27 @@ class CLIPTextModel:
             raise ValueError("CLIPTextModel: the head dim and the widths must be multiples of 8")
         self.config = SimpleNamespace(**cfg)
         self._cfg = cfg
-        self._shapes = clip_text_param_shapes(cfg)
-        self._sd, self._w = None, None
-        self.dtype, self.device = torch.float32, torch.device("cpu")
+        super().__init__(clip_text_param_shapes(cfg))
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path, subfolder="text_encoder", torch_dtype=None, **_ignored):
         """A LOCAL checkpoint folder (`<path>/<subfolder>/config.json` + `model.safetensors` or `pytorch_model.bin`), as
         animation.py:75-76 names it - nothing is fetched."""
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        config_file = os.path.join(path, "config.json")
-        if not os.path.isfile(config_file):
-            raise RuntimeError(f"{config_file} does not exist")
-        with open(config_file) as f:
-            config = json.load(f)
+        config, sd = load_local_checkpoint(pretrained_model_path, subfolder)
         model = cls({k: config[k] for k in SD15_CONFIG if k in config})
-        st_file, bin_file = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-        if os.path.isfile(st_file):
-            from safetensors.torch import load_file
-            sd = load_file(st_file)
-        elif os.path.isfile(bin_file):
-            sd = torch.load(bin_file, map_location="cpu", weights_only=True)
-        else:
-            raise RuntimeError(f"neither {st_file} nor {bin_file} exists")
         model.load_state_dict(sd)
         if torch_dtype is not None:
             model.to(dtype=torch_dtype)
         return model
 
-    # ---- torch-module-like surface
-    def eval(self):
-        return self
-
-    def requires_grad_(self, _flag=True):
-        return self
-
-    def state_dict(self):
-        if self._sd is None:
-            raise EmoHipError("no weights loaded")
-        return dict(self._sd)
-
-    def load_state_dict(self, sd, strict=True):
-        sd = dict(sd)
-        # older SD-1.5 checkpoints carry the position_ids buffer; transformers ignores it (non-persistent)
-        tolerated = {"text_model.embeddings.position_ids"}
-        missing = [k for k in self._shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self._shapes and k not in tolerated]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: {len(missing)} missing {missing[:4]}, {len(unexpected)} unexpected {unexpected[:4]}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shp)}")
-        self._sd = {k: sd[k].detach().float() for k in self._shapes if k in sd}
-        self._pack()
-        return missing, unexpected
-
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            else:
-                device = torch.device(a)
-        if dtype is not None:
-            ops.dt(dtype)
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        self._pack()
-        return self
-
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda" or any(k not in self._sd for k in self._shapes):
-            return
-        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._sd
+    def _pack_weights(self):
+        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._master
         f32 = lambda k: sd[k].to(dev).float().contiguous()
         lin = lambda k: sd[k].to(dev, dtp).contiguous()
-
-        def ln_fold(wt, b, norm):
-            """(W, b) of a Linear behind LayerNorm `norm` -> (W * gamma in the compute dtype, its row sums, b + W . beta):
-            LN(x) W^T + b = rstd (x W'^T - mean colsum) + b' (the UNet's fold, emo_gemm_params.ln_colsum)."""
-            g_, be = sd[norm + ".weight"].to(dev).float(), sd[norm + ".bias"].to(dev).float()
-            wt = wt.to(dev).float()
-            wp = (wt * g_[None, :]).to(dtp)
-            bp = wt.to(dtp).float() @ be + b.to(dev).float()
-            return wp.contiguous(), wp.float().sum(1).contiguous(), bp.contiguous()
-
         w = {"tok": lin("text_model.embeddings.token_embedding.weight"), "pos": lin("text_model.embeddings.position_embedding.weight"),
              "lnf.g": f32("text_model.final_layer_norm.weight"), "lnf.b": f32("text_model.final_layer_norm.bias")}
-        for i in range(c["num_hidden_layers"]):
-            p = f"text_model.encoder.layers.{i}.self_attn"
-            w[f"{i}.qk"] = ln_fold(torch.cat([sd[f"{p}.q_proj.weight"], sd[f"{p}.k_proj.weight"]]),
-                                   torch.cat([sd[f"{p}.q_proj.bias"], sd[f"{p}.k_proj.bias"]]), f"text_model.encoder.layers.{i}.layer_norm1")
-            w[f"{i}.v"] = ln_fold(sd[f"{p}.v_proj.weight"], sd[f"{p}.v_proj.bias"], f"text_model.encoder.layers.{i}.layer_norm1")
-            w[f"{i}.o.w"], w[f"{i}.o.b"] = lin(f"{p}.out_proj.weight"), f32(f"{p}.out_proj.bias")
-            m = f"text_model.encoder.layers.{i}.mlp"
-            w[f"{i}.f1"] = ln_fold(sd[f"{m}.fc1.weight"], sd[f"{m}.fc1.bias"], f"text_model.encoder.layers.{i}.layer_norm2")
-            w[f"{i}.f2.w"], w[f"{i}.f2.b"] = lin(f"{m}.fc2.weight"), f32(f"{m}.fc2.bias")
-        self._w = w
+        w.update(pack_clip_layers(sd, "text_model.encoder.layers", c["num_hidden_layers"], dev, dtp))
+        return w
 
     # ---- forward
     def _check_inputs(self, input_ids, attention_mask, position_ids, output_hidden_states, output_attentions):
@@ -203,29 +110,16 @@ class CLIPTextModel:
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, output_hidden_states=False, output_attentions=False,
                 return_dict=None, **_ignored):
-        if self._w is None:
-            raise EmoHipError("CLIPTextModel: load_state_dict + .to('cuda') first (weights are caller-loaded; there is no CPU execution path)")
+        self._need()
         self._check_inputs(input_ids, attention_mask, position_ids, output_hidden_states, output_attentions)
         c, w, dev = self._cfg, self._w, self.device
         ids = input_ids.detach().cpu().to(torch.int64)
         B, L = ids.shape
-        H, nh, eps = c["hidden_size"], c["num_attention_heads"], c["layer_norm_eps"]
-        d = H // nh
-        act = _ACTS[c["hidden_act"]]
+        H = c["hidden_size"]
         h = ops.text_embed(ids, w["tok"], w["pos"])                                               # (B*L, H)
-        for i in range(c["num_hidden_layers"]):
-            st = ops.layer_norm_stats(h, eps)
-            wq, cs, bq = w[f"{i}.qk"]
-            qk = ops.gemm(h, wq, bq, ln=(cs, st))                                                 # LN1 -> q | k
-            wv, cs, bv = w[f"{i}.v"]
-            vt = ops.gemm(h, wv, bv, ln=(cs, st), transpose_rows=L, transpose_ld=_r8(L))          # LN1 -> V^T (B, H, ld)
-            att = ops.attention(qk[:, :H], qk[:, H:], vt, L, B=B, Lq=L, heads=nh, d=d, scale=d ** -0.5, causal=True)
-            h = ops.gemm(att, w[f"{i}.o.w"], w[f"{i}.o.b"], residual=h)
-            st = ops.layer_norm_stats(h, eps)
-            w1, cs, b1 = w[f"{i}.f1"]
-            f = ops.act(ops.gemm(h, w1, b1, ln=(cs, st)), act)                                    # LN2 -> fc1 -> activation
-            h = ops.gemm(f, w[f"{i}.f2.w"], w[f"{i}.f2.b"], residual=h)
-        h = ops.layer_norm(h, w["lnf.g"], w["lnf.b"], eps)
+        h = run_clip_layers(h, w, n_layers=c["num_hidden_layers"], B=B, L=L, H=H, heads=c["num_attention_heads"],
+                            eps=c["layer_norm_eps"], act=_ACTS[c["hidden_act"]], causal=True)
+        h = ops.layer_norm(h, w["lnf.g"], w["lnf.b"], c["layer_norm_eps"])
         # pooling (transformers CLIPTextTransformer): the legacy eos_token_id 2 takes the argmax of the ids, otherwise the first EOS
         if c["eos_token_id"] == 2:
             pos = ids.to(torch.int).argmax(dim=-1)
@@ -234,8 +128,6 @@ class CLIPTextModel:
         rows = (torch.arange(B) * L + pos).to(torch.int32).to(dev)
         pooled = ops.gather_rows(h, rows)
         return CLIPTextModelOutput(last_hidden_state=h.view(B, L, H), pooler_output=pooled)
-
-    __call__ = forward
 
 
 class CLIPTextModelOutput(SimpleNamespace):

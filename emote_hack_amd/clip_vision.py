@@ -20,9 +20,7 @@ its logits).
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -30,18 +28,15 @@ import torch
 
 from . import ops
 from ._lib import EmoHipError
+from .clip_layers import ACTS as _ACTS, clip_layer_shapes, load_local_checkpoint, pack_clip_layers, run_clip_layers
+from .module import HipModule, round_up
 from .synth import synth_state_dict
 
 # the vision tower of openai/clip-vit-large-patch14 (= the image_encoder of lambdalabs/sd-image-variations-diffusers)
 VITL14_CONFIG = dict(hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16, num_channels=3, image_size=224,
                      patch_size=14, projection_dim=768, hidden_act="quick_gelu", layer_norm_eps=1e-5)
-_ACTS = {"quick_gelu": "quick_gelu", "gelu": "gelu"}
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
-
-
-def _r8(x):
-    return (x + 7) // 8 * 8
 
 
 def clip_vision_param_shapes(cfg=None, projection=True):
@@ -56,19 +51,7 @@ def clip_vision_param_shapes(cfg=None, projection=True):
          f"{v}.embeddings.position_embedding.weight": (n_pos, H),
          f"{v}.pre_layrnorm.weight": (H,),
          f"{v}.pre_layrnorm.bias": (H,)}
-    for i in range(c["num_hidden_layers"]):
-        p = f"{v}.encoder.layers.{i}"
-        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
-            d[f"{p}.self_attn.{n}.weight"] = (H, H)
-            d[f"{p}.self_attn.{n}.bias"] = (H,)
-        d[f"{p}.layer_norm1.weight"] = (H,)
-        d[f"{p}.layer_norm1.bias"] = (H,)
-        d[f"{p}.mlp.fc1.weight"] = (I, H)
-        d[f"{p}.mlp.fc1.bias"] = (I,)
-        d[f"{p}.mlp.fc2.weight"] = (H, I)
-        d[f"{p}.mlp.fc2.bias"] = (H,)
-        d[f"{p}.layer_norm2.weight"] = (H,)
-        d[f"{p}.layer_norm2.bias"] = (H,)
+    d.update(clip_layer_shapes(f"{v}.encoder.layers", c["num_hidden_layers"], H, I))
     d[f"{v}.post_layernorm.weight"] = (H,)
     d[f"{v}.post_layernorm.bias"] = (H,)
     if projection:
@@ -99,11 +82,14 @@ class CLIPVisionModelWithProjectionOutput(SimpleNamespace):
         return t[i]
 
 
-class CLIPVisionModel:
+class CLIPVisionModel(HipModule):
     """forward(pixel_values (B, 3, S, S), S = image_size) -> namespace(last_hidden_state (B, Np + 1, hidden), pooler_output (B, hidden),
     hidden_states) in the model's dtype."""
     _projection = False
     _name = "CLIPVisionModel"
+    # older checkpoints carry the position_ids buffer; transformers ignores it (non-persistent).  visual_projection: a with-projection
+    # checkpoint read as the bare tower
+    _tolerated = frozenset({"vision_model.embeddings.position_ids", "visual_projection.weight"})
 
     def __init__(self, config=None, **kwargs):
         cfg = dict(VITL14_CONFIG)
@@ -120,115 +106,35 @@ class CLIPVisionModel:
             raise ValueError(f"{self._name}: 3 input channels and an image_size that is a multiple of patch_size")
         self.config = SimpleNamespace(**cfg)
         self._cfg = cfg
-        self._shapes = clip_vision_param_shapes(cfg, self._projection)
-        self._sd, self._w = None, None
-        self.dtype, self.device = torch.float32, torch.device("cpu")
+        super().__init__(clip_vision_param_shapes(cfg, self._projection))
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path, subfolder="image_encoder", torch_dtype=None, **_ignored):
         """A LOCAL checkpoint folder (`<path>/<subfolder>/config.json` + `model.safetensors` or `pytorch_model.bin`), as
         EMOAnimationPipeline.py:867 names it - nothing is fetched."""
-        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
-        config_file = os.path.join(path, "config.json")
-        if not os.path.isfile(config_file):
-            raise RuntimeError(f"{config_file} does not exist")
-        with open(config_file) as f:
-            config = json.load(f)
+        config, sd = load_local_checkpoint(pretrained_model_path, subfolder)
         config = dict(config.get("vision_config") or {}, **config)      # a joint CLIPConfig nests the tower's settings
         model = cls({k: config[k] for k in VITL14_CONFIG if k in config})
-        st_file, bin_file = os.path.join(path, "model.safetensors"), os.path.join(path, "pytorch_model.bin")
-        if os.path.isfile(st_file):
-            from safetensors.torch import load_file
-            sd = load_file(st_file)
-        elif os.path.isfile(bin_file):
-            sd = torch.load(bin_file, map_location="cpu", weights_only=True)
-        else:
-            raise RuntimeError(f"neither {st_file} nor {bin_file} exists")
         model.load_state_dict(sd)
         if torch_dtype is not None:
             model.to(dtype=torch_dtype)
         return model
 
-    # ---- torch-module-like surface
-    def eval(self):
-        return self
-
-    def requires_grad_(self, _flag=True):
-        return self
-
-    def state_dict(self):
-        if self._sd is None:
-            raise EmoHipError("no weights loaded")
-        return dict(self._sd)
-
-    def load_state_dict(self, sd, strict=True):
-        sd = dict(sd)
-        # older checkpoints carry the position_ids buffer; transformers ignores it (non-persistent)
-        tolerated = {"vision_model.embeddings.position_ids"}
-        if not self._projection:
-            tolerated.add("visual_projection.weight")       # a with-projection checkpoint read as the bare tower
-        missing = [k for k in self._shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self._shapes and k not in tolerated]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: {len(missing)} missing {missing[:4]}, {len(unexpected)} unexpected {unexpected[:4]}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shp)}")
-        self._sd = {k: sd[k].detach().float() for k in self._shapes if k in sd}
-        self._pack()
-        return missing, unexpected
-
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            else:
-                device = torch.device(a)
-        if dtype is not None:
-            ops.dt(dtype)
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        self._pack()
-        return self
-
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda" or any(k not in self._sd for k in self._shapes):
-            return
-        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._sd
+    def _pack_weights(self):
+        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._master
         f32 = lambda k: sd[k].to(dev).float().contiguous()
         lin = lambda k: sd[k].to(dev, dtp).contiguous()
-
-        def ln_fold(wt, b, norm):
-            """(W, b) of a Linear behind LayerNorm `norm` -> (W * gamma in the compute dtype, its row sums, b + W . beta):
-            LN(x) W^T + b = rstd (x W'^T - mean colsum) + b' (the UNet's fold, emo_gemm_params.ln_colsum)."""
-            g_, be = sd[norm + ".weight"].to(dev).float(), sd[norm + ".bias"].to(dev).float()
-            wt = wt.to(dev).float()
-            wp = (wt * g_[None, :]).to(dtp)
-            bp = wt.to(dtp).float() @ be + b.to(dev).float()
-            return wp.contiguous(), wp.float().sum(1).contiguous(), bp.contiguous()
-
         v = "vision_model"
         H, K = c["hidden_size"], 3 * c["patch_size"] ** 2
-        wpe = torch.zeros(H, _r8(K), device=dev, dtype=dtp)                 # the conv weight as GEMM rows, K padded like emo_patch_rows' rows
+        wpe = torch.zeros(H, round_up(K, 8), device=dev, dtype=dtp)       # the conv weight as GEMM rows, K padded like emo_patch_rows' rows
         wpe[:, :K] = sd[f"{v}.embeddings.patch_embedding.weight"].reshape(H, K).to(dev, dtp)
         w = {"patch": wpe, "cls": lin(f"{v}.embeddings.class_embedding"), "pos": lin(f"{v}.embeddings.position_embedding.weight"),
              "pre.g": f32(f"{v}.pre_layrnorm.weight"), "pre.b": f32(f"{v}.pre_layrnorm.bias"),
              "post.g": f32(f"{v}.post_layernorm.weight"), "post.b": f32(f"{v}.post_layernorm.bias")}
         if self._projection:
             w["proj"] = lin("visual_projection.weight")
-        for i in range(c["num_hidden_layers"]):
-            ly = f"{v}.encoder.layers.{i}"
-            p = f"{ly}.self_attn"
-            w[f"{i}.qk"] = ln_fold(torch.cat([sd[f"{p}.q_proj.weight"], sd[f"{p}.k_proj.weight"]]),
-                                   torch.cat([sd[f"{p}.q_proj.bias"], sd[f"{p}.k_proj.bias"]]), f"{ly}.layer_norm1")
-            w[f"{i}.v"] = ln_fold(sd[f"{p}.v_proj.weight"], sd[f"{p}.v_proj.bias"], f"{ly}.layer_norm1")
-            w[f"{i}.o.w"], w[f"{i}.o.b"] = lin(f"{p}.out_proj.weight"), f32(f"{p}.out_proj.bias")
-            m = f"{ly}.mlp"
-            w[f"{i}.f1"] = ln_fold(sd[f"{m}.fc1.weight"], sd[f"{m}.fc1.bias"], f"{ly}.layer_norm2")
-            w[f"{i}.f2.w"], w[f"{i}.f2.b"] = lin(f"{m}.fc2.weight"), f32(f"{m}.fc2.bias")
-        self._w = w
+        w.update(pack_clip_layers(sd, f"{v}.encoder.layers", c["num_hidden_layers"], dev, dtp))
+        return w
 
     # ---- forward
     def _check_inputs(self, pixel_values, output_attentions, interpolate_pos_encoding):
@@ -246,35 +152,20 @@ class CLIPVisionModel:
         """-> (last_hidden_state rows (B * L, H), pooler_output (B, H), [hidden states rows] or None, B, L)"""
         c, w, dev = self._cfg, self._w, self.device
         B = pixel_values.shape[0]
-        H, nh, eps, P = c["hidden_size"], c["num_attention_heads"], c["layer_norm_eps"], c["patch_size"]
+        H, eps, P = c["hidden_size"], c["layer_norm_eps"], c["patch_size"]
         L = (c["image_size"] // P) ** 2 + 1
-        d = H // nh
-        act = _ACTS[c["hidden_act"]]
         a = ops.patch_rows(pixel_values.detach().to(dev).float(), P, self.dtype)                  # (B*Np, r8(3 P P))
         h = ops.vision_embed(ops.gemm(a, w["patch"]), w["cls"], w["pos"], w["pre.g"], w["pre.b"], B, eps)     # (B*L, H) = hidden_states[0]
         hs = [h] if output_hidden_states else None
-        for i in range(c["num_hidden_layers"]):
-            st = ops.layer_norm_stats(h, eps)
-            wq, cs, bq = w[f"{i}.qk"]
-            qk = ops.gemm(h, wq, bq, ln=(cs, st))                                                 # LN1 -> q | k
-            wv, cs, bv = w[f"{i}.v"]
-            vt = ops.gemm(h, wv, bv, ln=(cs, st), transpose_rows=L, transpose_ld=_r8(L))          # LN1 -> V^T (B, H, ld)
-            att = ops.attention(qk[:, :H], qk[:, H:], vt, L, B=B, Lq=L, heads=nh, d=d, scale=d ** -0.5)
-            h = ops.gemm(att, w[f"{i}.o.w"], w[f"{i}.o.b"], residual=h)
-            st = ops.layer_norm_stats(h, eps)
-            w1, cs, b1 = w[f"{i}.f1"]
-            f = ops.act(ops.gemm(h, w1, b1, ln=(cs, st)), act)                                    # LN2 -> fc1 -> activation
-            h = ops.gemm(f, w[f"{i}.f2.w"], w[f"{i}.f2.b"], residual=h)
-            if hs is not None:
-                hs.append(h)
+        h = run_clip_layers(h, w, n_layers=c["num_hidden_layers"], B=B, L=L, H=H, heads=c["num_attention_heads"], eps=eps,
+                            act=_ACTS[c["hidden_act"]], causal=False, collect=hs)
         pooled = ops.layer_norm(h.view(B, L * H)[:, :H], w["post.g"], w["post.b"], eps)           # the class token of every image: a strided rows view
         return h, pooled, hs, B, L
 
     @torch.no_grad()
     def forward(self, pixel_values=None, output_attentions=False, output_hidden_states=False, interpolate_pos_encoding=False,
                 return_dict=None, **_ignored):
-        if self._w is None:
-            raise EmoHipError(f"{self._name}: load_state_dict + .to('cuda') first (weights are caller-loaded; there is no CPU execution path)")
+        self._need()
         self._check_inputs(pixel_values, output_attentions, interpolate_pos_encoding)
         h, pooled, hs, B, L = self._encode(pixel_values, output_hidden_states)
         H = self._cfg["hidden_size"]
@@ -284,14 +175,13 @@ class CLIPVisionModel:
         return CLIPVisionModelWithProjectionOutput(image_embeds=ops.gemm(pooled, self._w["proj"]), last_hidden_state=h.view(B, L, H),
                                                    pooler_output=pooled, hidden_states=hidden)
 
-    __call__ = forward
-
 
 class CLIPVisionModelWithProjection(CLIPVisionModel):
     """forward(pixel_values) -> namespace(image_embeds (B, projection_dim), last_hidden_state, pooler_output, hidden_states); `[0]` is
     image_embeds, what the image-conditioned pipelines read."""
     _projection = True
     _name = "CLIPVisionModelWithProjection"
+    _tolerated = frozenset({"vision_model.embeddings.position_ids"})
 
 
 # ---------------------------------------------------------------------------------------------------------------- image processor

@@ -21,56 +21,27 @@ import math
 import torch
 
 from . import ops
-from ._lib import EmoHipError
+from .module import HipModule
 
 
-class _HipModule:
-    """state-dict driven module: shapes declared by subclasses; weights packed on .to(device, dtype)."""
-    _shapes: dict = {}
+class _HipModule(HipModule):
+    """state-dict driven module: shapes declared by subclasses; weights packed on .to(device, dtype).  Lenient like the reference's
+    training scripts: strict raises on missing keys only, unexpected ones are returned."""
+    _strict_unexpected = False
 
     def __init__(self):
-        self._sd = None
-        self.dtype, self.device = torch.float32, torch.device("cpu")
-        self._w = None
+        super().__init__({})
 
     def state_dict_shapes(self):
         return dict(self._shapes)
 
-    def load_state_dict(self, sd, strict=True):
-        missing = [k for k in self._shapes if k not in sd]
-        if strict and missing:
-            raise RuntimeError(f"missing keys {missing}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}")
-        self._sd = {k: sd[k].detach().float() for k in self._shapes if k in sd}
-        self._pack()
-        return missing, [k for k in sd if k not in self._shapes]
-
-    def to(self, device=None, dtype=None):
-        if dtype is not None:
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        self._pack()
-        return self
-
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
-        self._w = {k: (v.to(self.device, self.dtype if (v.dim() >= 2 and not k.endswith("temperature")) else torch.float32)).contiguous()
-                   for k, v in self._sd.items()}
-
-    def _need(self):
-        if self._w is None:
-            raise EmoHipError(f"{type(self).__name__}: load_state_dict + .to('cuda') first (no CPU execution path)")
+    def _pack_weights(self):
+        return {k: (v.to(self.device, self.dtype if (v.dim() >= 2 and not k.endswith("temperature")) else torch.float32)).contiguous()
+                for k, v in self._master.items()}
 
     def _lin(self, x, name, relu=False):
         y = ops.gemm(x, self._w[name + ".weight"], self._w.get(name + ".bias"))
         return ops.act(y, "relu") if relu else y
-
-    def __call__(self, *a, **k):
-        return self.forward(*a, **k)
 
 
 class SpeedEncoder(_HipModule):
@@ -85,15 +56,15 @@ class SpeedEncoder(_HipModule):
         D = speed_embedding_dim
         self._shapes = {"mlp.0.weight": (D, num_speed_buckets), "mlp.0.bias": (D,), "mlp.2.weight": (D, D), "mlp.2.bias": (D,)}
 
-    def _pack(self):
-        super()._pack()
-        if self._w is not None:
-            nb = self.num_speed_buckets
-            w0 = torch.zeros(self.speed_embedding_dim, 16, device=self.device, dtype=self.dtype)   # K padded 9 -> 16
-            w0[:, :nb] = self._w["mlp.0.weight"]
-            self._w["mlp.0.weight"] = w0
-            self._centers = torch.tensor(self.CENTERS + [0.0] * (16 - nb), device=self.device)
-            self._radii = torch.tensor([0.1] * nb + [1e30] * (16 - nb), device=self.device)  # pad: tanh(~0)=0 x zero weight
+    def _pack_weights(self):
+        w = super()._pack_weights()
+        nb = self.num_speed_buckets
+        w0 = torch.zeros(self.speed_embedding_dim, 16, device=self.device, dtype=self.dtype)   # K padded 9 -> 16
+        w0[:, :nb] = w["mlp.0.weight"]
+        w["mlp.0.weight"] = w0
+        self._centers = torch.tensor(self.CENTERS + [0.0] * (16 - nb), device=self.device)
+        self._radii = torch.tensor([0.1] * nb + [1e30] * (16 - nb), device=self.device)  # pad: tanh(~0)=0 x zero weight
+        return w
 
     def encode_speed(self, v):
         assert v.ndim == 1, "head_rotation_speed must be a 1D tensor"
@@ -135,18 +106,17 @@ class FaceRegionController(_HipModule):
             self._shapes[f"encoder.{k}.weight"] = (self.chans[i + 1], self.chans[i], 3, 3)
             self._shapes[f"encoder.{k}.bias"] = (self.chans[i + 1],)
 
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
-        self._w = {}
+    def _pack_weights(self):
+        w = {}
         for i, k in enumerate((0, 2, 4, 6)):
-            t = self._sd[f"encoder.{k}.weight"].to(self.device)
+            t = self._master[f"encoder.{k}.weight"].to(self.device)
             co, ci = t.shape[:2]
             cip = (ci + 7) // 8 * 8
             o = torch.zeros(co, 3, 3, cip, device=self.device)
             o[..., :ci] = t.permute(0, 2, 3, 1)
-            self._w[f"encoder.{k}.weight"] = o.reshape(co, 9 * cip).to(self.dtype).contiguous()
-            self._w[f"encoder.{k}.bias"] = self._sd[f"encoder.{k}.bias"].to(self.device).float().contiguous()
+            w[f"encoder.{k}.weight"] = o.reshape(co, 9 * cip).to(self.dtype).contiguous()
+            w[f"encoder.{k}.bias"] = self._master[f"encoder.{k}.bias"].to(self.device).float().contiguous()
+        return w
 
     def forward(self, mask):
         """mask (B, Cin, H, W) -> (B, D, H, W) f32."""
@@ -281,16 +251,14 @@ class TemporalAttention(_HipModule):
         self.dim, self.num_heads = dim, num_heads
         self._shapes = {"temperature": (num_heads, 1, 1), "qkv.weight": (3 * dim, dim), "proj.weight": (dim, dim), "proj.bias": (dim,)}
 
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
-        C, H = self.dim, self.num_heads
-        wq = self._sd["qkv.weight"].clone()
-        wq[:C] = wq[:C] * self._sd["temperature"].reshape(H, 1, 1).expand(H, C // H, 1).reshape(C, 1)
-        self._w = {"q": wq[:C].to(self.device, self.dtype).contiguous(), "k": wq[C:2 * C].to(self.device, self.dtype).contiguous(),
-                   "v": wq[2 * C:].to(self.device, self.dtype).contiguous(),
-                   "proj.weight": self._sd["proj.weight"].to(self.device, self.dtype).contiguous(),
-                   "proj.bias": self._sd["proj.bias"].to(self.device).float().contiguous()}
+    def _pack_weights(self):
+        C, H, sd = self.dim, self.num_heads, self._master
+        wq = sd["qkv.weight"].clone()
+        wq[:C] = wq[:C] * sd["temperature"].reshape(H, 1, 1).expand(H, C // H, 1).reshape(C, 1)
+        return {"q": wq[:C].to(self.device, self.dtype).contiguous(), "k": wq[C:2 * C].to(self.device, self.dtype).contiguous(),
+                "v": wq[2 * C:].to(self.device, self.dtype).contiguous(),
+                "proj.weight": sd["proj.weight"].to(self.device, self.dtype).contiguous(),
+                "proj.bias": sd["proj.bias"].to(self.device).float().contiguous()}
 
     def forward(self, x):
         self._need()
@@ -336,11 +304,9 @@ class SpatialAttentionModule(_HipModule):
                         "ffn.weight": (E, E), "ffn.bias": (E,), "norm2.weight": (E,), "norm2.bias": (E,),
                         "proj_out.weight": (C, C, 1, 1), "proj_out.bias": (C,)}
 
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
-        self._w = {k: (v.reshape(v.shape[0], -1).to(self.device, self.dtype) if v.dim() >= 2 else v.to(self.device).float()).contiguous()
-                   for k, v in self._sd.items()}
+    def _pack_weights(self):
+        return {k: (v.reshape(v.shape[0], -1).to(self.device, self.dtype) if v.dim() >= 2 else v.to(self.device).float()).contiguous()
+                for k, v in self._master.items()}
 
     def _tail(self, att, xr, n_rows_shape):
         """LN(attn + x) -> Linear -> LN(. + .) -> 1x1 conv -> + x   (videonet.py:66-77)"""
@@ -378,11 +344,11 @@ class TemporalAttentionModule(SpatialAttentionModule):
         super().__init__(num_inp_channels, embed_dim, num_heads)
         self.num_frames = num_frames
 
-    def _pack(self):
-        super()._pack()
-        if self._w is not None:
-            self._w["qkv.weight"] = torch.cat([self._w["to_q.weight"], self._w["to_k.weight"], self._w["to_v.weight"]]).contiguous()
-            self._w["qkv.bias"] = torch.cat([self._w["to_q.bias"], self._w["to_k.bias"], self._w["to_v.bias"]]).contiguous()
+    def _pack_weights(self):
+        w = super()._pack_weights()
+        w["qkv.weight"] = torch.cat([w["to_q.weight"], w["to_k.weight"], w["to_v.weight"]]).contiguous()
+        w["qkv.bias"] = torch.cat([w["to_q.bias"], w["to_k.bias"], w["to_v.bias"]]).contiguous()
+        return w
 
     def forward(self, x):
         self._need()
@@ -406,11 +372,9 @@ class FaceLocator(_HipModule):
         self._shapes = {"conv1.weight": (16, 3, 3, 3), "conv1.bias": (16,), "conv2.weight": (32, 16, 3, 3), "conv2.bias": (32,),
                         "conv3.weight": (64, 32, 3, 3), "conv3.bias": (64,), "final_conv.weight": (1, 64, 1, 1), "final_conv.bias": (1,)}
 
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
+    def _pack_weights(self):
         w = {}
-        for k, t in self._sd.items():
+        for k, t in self._master.items():
             if k.endswith(".bias"):
                 w[k] = t.to(self.device).float().contiguous()
             elif t.shape[-1] == 3:
@@ -421,7 +385,7 @@ class FaceLocator(_HipModule):
                 w[k] = o.reshape(co, 9 * cip).to(self.device, self.dtype).contiguous()
             else:
                 w[k] = t.reshape(t.shape[0], -1).to(self.device, self.dtype).contiguous()
-        self._w = w
+        return w
 
     def forward(self, images):
         self._need()

@@ -20,7 +20,8 @@ from typing import List
 import torch
 
 from . import ops
-from .unet import UNet3DConditionModel, _round_up
+from .module import round_up
+from .unet import UNet3DConditionModel
 
 
 @dataclass
@@ -71,7 +72,7 @@ class ControlNetModel(UNet3DConditionModel):
         w, dtp = self._w, self.dtype
         ce = "controlnet_cond_embedding"
         cin = cond.shape[1]
-        x = ops.ncfhw_to_rows(cond.unsqueeze(2), dtp, cpad=_round_up(cin, 8))
+        x = ops.ncfhw_to_rows(cond.unsqueeze(2), dtp, cpad=round_up(cin, 8))
         x, h, w_ = ops.conv3x3(x, w[ce + ".conv_in.w"], w[ce + ".conv_in.b"], N, Hc, Wc)
         x = ops.silu(x)
         for i in range(2 * (len(self.conditioning_embedding_out_channels) - 1)):
@@ -133,5 +134,3 @@ class ControlNetModel(UNet3DConditionModel):
         if not return_dict:
             return (down, mid)
         return ControlNetOutput(down_block_res_samples=down, mid_block_res_sample=mid)
-
-    __call__ = forward

@@ -21,10 +21,7 @@ import torch
 
 from . import ops
 from .conditioning import AudioAttentionLayers, ReferenceAttentionLayer, _HipModule
-
-
-def _r8(x):
-    return (x + 7) // 8 * 8
+from .module import round_up
 
 
 class ReferenceAttention(_HipModule):
@@ -45,7 +42,7 @@ class ReferenceAttention(_HipModule):
         L = ref.shape[2] * ref.shape[3]
         q = ops.gemm(ops.layer_norm(xr, w["norm.weight"], w["norm.bias"]), w["q_proj.weight"], w["q_proj.bias"])
         k = ops.gemm(ops.layer_norm(rr, w["norm.weight"], w["norm.bias"]), w["k_proj.weight"], w["k_proj.bias"])
-        vt = ops.gemm(rr, w["v_proj.weight"], w["v_proj.bias"], transpose_rows=L, transpose_ld=_r8(L))      # v from the RAW reference tokens (:1506)
+        vt = ops.gemm(rr, w["v_proj.weight"], w["v_proj.bias"], transpose_rows=L, transpose_ld=round_up(L, 8))      # v from the RAW reference tokens (:1506)
         o = ops.attention(q, k, vt, L, B=B, Lq=H * W, heads=1, d=C, scale=C ** -0.5)
         return ops.rows_to_ncfhw(o, B, C, 1, H, W)[:, :, 0]
 
@@ -66,7 +63,7 @@ class TemporalAttention(_HipModule):
         w, C = self._w, self.channels
         n = ops.layer_norm(rows, w["norm.weight"], w["norm.bias"])
         qkv = ops.gemm(n, w["attention.in_proj_weight"], w["attention.in_proj_bias"])
-        vt = ops.gemm(n, w["attention.in_proj_weight"][2 * C:], w["attention.in_proj_bias"][2 * C:].contiguous(), transpose_rows=T, transpose_ld=_r8(T))
+        vt = ops.gemm(n, w["attention.in_proj_weight"][2 * C:], w["attention.in_proj_bias"][2 * C:].contiguous(), transpose_rows=T, transpose_ld=round_up(T, 8))
         d = C // 8
         o = ops.attention(qkv[:, :C], qkv[:, C:2 * C], vt, T, B=B, Lq=T, heads=8, d=d, scale=d ** -0.5)
         return ops.gemm(o, w["attention.out_proj.weight"], w["attention.out_proj.bias"])
@@ -91,15 +88,13 @@ class MotionModule(_HipModule):
         self._shapes = {"temporal_conv.weight": (C, C, k, 1, 1), "temporal_conv.bias": (C,),
                         **{"temporal_attention." + n: s for n, s in self.temporal_attention._shapes.items()}}
 
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda":
-            return
-        C, k = self.in_channels, self.temporal_length
-        self._w = {"conv.w": self._sd["temporal_conv.weight"].reshape(C, C, k).permute(0, 2, 1).reshape(C, k * C).to(self.device, self.dtype).contiguous(),
-                   "conv.b": self._sd["temporal_conv.bias"].to(self.device).float().contiguous()}
-        ta = self.temporal_attention
-        ta._sd = {n[len("temporal_attention."):]: v for n, v in self._sd.items() if n.startswith("temporal_attention.")}
+    def _pack_weights(self):
+        C, k, sd = self.in_channels, self.temporal_length, self._master
+        ta, p = self.temporal_attention, "temporal_attention."
+        ta.load_state_dict({n[len(p):]: v for n, v in sd.items() if n.startswith(p)})
         ta.to(self.device, self.dtype)
+        return {"conv.w": sd["temporal_conv.weight"].reshape(C, C, k).permute(0, 2, 1).reshape(C, k * C).to(self.device, self.dtype).contiguous(),
+                "conv.b": sd["temporal_conv.bias"].to(self.device).float().contiguous()}
 
     def forward(self, x):
         self._need()

@@ -34,6 +34,7 @@ import torch
 from . import ops
 from ._lib import EmoHipError
 from .config import FrozenConfig, normalize_unet_config
+from .module import HipModule, ln_fold_weights, round_up
 from .spec import UNetSpec, build_spec, param_shapes, reference_block_order
 
 
@@ -43,10 +44,6 @@ class UNet3DConditionOutput:  # unet_controlnet.py:49-51
 
     def __getitem__(self, i):
         return (self.sample,)[i]
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 # Every LayerNorm of the transformer / motion blocks feeds a Linear (attention.py:279-316, motion_module.py:216-224,282-303):
@@ -85,18 +82,6 @@ def ff_tail_weights(w_out, b_out, w2, b2):
     return torch.cat([wo @ w2.float(), wo], 1), wo @ b2.float() + b_out.float()
 
 
-def ln_fold_weights(wt, b, gamma, beta, dtp):
-    """(W, bias) of a Linear behind a LayerNorm with affine (gamma, beta) -> (W * gamma rounded to the compute dtype, its row sums,
-    bias + W . beta): LN(x) W^T + b = rstd (x W'^T - mean colsum) + b' (FOLD_LAYERNORM; ops.gemm(ln=...))."""
-    g_, be = gamma.float(), beta.float()
-    wt = wt.reshape(wt.shape[0], -1).float()
-    wp = (wt * g_[None, :]).to(dtp)
-    bp = wt.to(dtp).float() @ be
-    if b is not None:
-        bp = bp + b.float()
-    return wp.contiguous(), wp.float().sum(1).contiguous(), bp.contiguous()
-
-
 class _Ctx:
     """Per-forward geometry + reference-attention state."""
 
@@ -121,7 +106,7 @@ class _State:
 _STOP = object()   # returned by the gutted last transformer of the ReferenceNet: the rest of the pass is dead
 
 
-class UNet3DConditionModel:
+class UNet3DConditionModel(HipModule):
     def __init__(self, **kwargs):
         self._has_out = kwargs.pop("_has_out", True)
         self._controlnet = kwargs.pop("_controlnet", None)   # ControlNetModel: conditioning-embedding channels
@@ -139,72 +124,14 @@ class UNet3DConditionModel:
         self.sample_size = self.config["sample_size"]
         self.in_channels = self.config["in_channels"]
         self.num_upsamplers = len(self.config["block_out_channels"]) - 1
-        self.dtype = torch.float32
-        self.device = torch.device("cpu")
-        self._shapes = param_shapes(self.spec)
-        self._master = None   # reference-layout fp32 tensors (device)
-        self._w = None        # packed tensors
+        super().__init__(param_shapes(self.spec))       # _master: reference-layout fp32 tensors, moved to the device when packed
         self._reference_control = None
 
-    # ------------------------------------------------------------------ torch-module-like surface
-    def eval(self):
-        return self
-
-    def requires_grad_(self, *_):
-        return self
-
+    # ------------------------------------------------------------------ torch-module-like surface (HipModule)
+    # Partial loads accumulate: the reference workflow is from_pretrained_2d(strict=False) followed by a second strict=False load of
+    # the motion-module checkpoint (animation.py:116-135).
     def parameters(self):
         return iter(self._master.values()) if self._master else iter(())
-
-    def state_dict(self):
-        if self._master is None:
-            raise EmoHipError("no weights loaded")
-        return {k: v.detach().cpu() for k, v in self._master.items()}
-
-    def load_state_dict(self, sd, strict=True):
-        """torch semantics: returns (missing, unexpected) relative to the INCOMING dict; strict raises on either.  Partial
-        loads accumulate (the reference workflow is from_pretrained_2d(strict=False) followed by a second strict=False load of
-        the motion-module checkpoint, animation.py:116-135); the model (re-)packs whenever the merged master is complete."""
-        missing = [k for k in self._shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self._shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: {len(missing)} missing key(s) {missing[:5]}, "
-                               f"{len(unexpected)} unexpected key(s) {unexpected[:5]}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shp)}")
-        master = dict(self._master or {})
-        for k in self._shapes:
-            if k in sd:
-                master[k] = sd[k].detach().to(torch.float32)
-        self._master = master
-        self._w = None                      # packed weights are stale from here on
-        if not self._absent_keys():
-            self._pack()
-        return missing, unexpected
-
-    def _absent_keys(self):
-        return [k for k in self._shapes if self._master is None or k not in self._master]
-
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            else:
-                device = torch.device(a)
-        if dtype is not None:
-            if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-                raise EmoHipError(f"compute dtype {dtype} not supported (float32 | bfloat16 | float16)")
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        if self._master is not None and not self._absent_keys():
-            self._pack()
-        return self
-
-    def cuda(self):
-        return self.to("cuda")
 
     @classmethod
     def from_config(cls, config, **extra):
@@ -236,13 +163,7 @@ class UNet3DConditionModel:
         return model
 
     # ------------------------------------------------------------------ weight packing
-    def _pack(self):
-        if self.device.type != "cuda":
-            return  # packed on the first .to('cuda'); the product path has no CPU execution
-        absent = self._absent_keys()
-        if absent:
-            raise EmoHipError(f"UNet3DConditionModel: {len(absent)} parameter(s) were never loaded, e.g. {absent[:5]} "
-                              "(load_state_dict(strict=False) leaves the model unusable until every key has a value)")
+    def _pack_weights(self):
         dev, dtp = self.device, self.dtype
         m = {k: v.to(dev) for k, v in self._master.items()}
         self._master = m
@@ -259,7 +180,7 @@ class UNet3DConditionModel:
         def conv3(key):  # OIHW -> [Cout][ky][kx][Cin_pad]
             t = m[key]
             co, ci = t.shape[0], t.shape[1]
-            cip = _round_up(ci, 8)
+            cip = round_up(ci, 8)
             o = torch.zeros(co, 3, 3, cip, device=dev, dtype=torch.float32)
             o[..., :ci] = t.permute(0, 2, 3, 1)
             return o.reshape(co, 9 * cip).to(dtp).contiguous()
@@ -421,8 +342,8 @@ class UNet3DConditionModel:
             for k in range(len(skip_channels(spec))):
                 w[f"controlnet_down_blocks.{k}.w"], w[f"controlnet_down_blocks.{k}.b"] = lin(f"controlnet_down_blocks.{k}.weight"), f32(f"controlnet_down_blocks.{k}.bias")
             w["controlnet_mid_block.w"], w["controlnet_mid_block.b"] = lin("controlnet_mid_block.weight"), f32("controlnet_mid_block.bias")
-        self._w = w
         self._pe_rows = {}
+        return w
 
     # ------------------------------------------------------------------ blocks (all HIP launches)
     def _resnet(self, r, x, temb_all, c: _Ctx, H, W, scale=1.0, out=None):
@@ -462,7 +383,7 @@ class UNet3DConditionModel:
     def _kv(self, rows, wk, wv, L):
         """K rows and V^T (per batch of L rows) projections of `rows` (nb*L, Cin)."""
         k = ops.gemm(rows, wk)
-        vt = ops.gemm(rows, wv, transpose_rows=L, transpose_ld=_round_up(L, 8))
+        vt = ops.gemm(rows, wv, transpose_rows=L, transpose_ld=round_up(L, 8))
         return k, vt
 
     def transformer_prefixes(self):
@@ -520,14 +441,14 @@ class UNet3DConditionModel:
             both = None
             if MERGE_QKV:   # one launch: h is read once, q | k row-major, V^T by the V waves of the same tiles
                 wq, cs, bq = w[tb + ".attn1.qkv_ln"]
-                both = ops.gemm(h, wq, bq, ln=(cs, st), vt_cols=C_, vt_rows=HW, vt_ld=_round_up(HW, 8))
+                both = ops.gemm(h, wq, bq, ln=(cs, st), vt_cols=C_, vt_rows=HW, vt_ld=round_up(HW, 8))
             if both is not None:
                 qk, vt = both
             else:
                 wq, cs, bq = w[tb + ".attn1.qk_ln"]
                 qk = ops.gemm(h, wq, bq, ln=(cs, st))
                 wv, cs, bv = w[tb + ".attn1.v_ln"]
-                vt = ops.gemm(h, wv, bv, ln=(cs, st), transpose_rows=HW, transpose_ld=_round_up(HW, 8))
+                vt = ops.gemm(h, wv, bv, ln=(cs, st), transpose_rows=HW, transpose_ld=round_up(HW, 8))
         else:
             n1 = ops.layer_norm(h, w[tb + ".norm1.g"], w[tb + ".norm1.b"])
             if c.bank_mode == "write" and p in c.active:
@@ -537,7 +458,7 @@ class UNet3DConditionModel:
                 # model's output is discarded - the pass ends here
                 return _STOP
             qk = ops.gemm(n1, w[tb + ".attn1.qk"])
-            vt = ops.gemm(n1, w[tb + ".attn1.v"], transpose_rows=HW, transpose_ld=_round_up(HW, 8))
+            vt = ops.gemm(n1, w[tb + ".attn1.v"], transpose_rows=HW, transpose_ld=round_up(HW, 8))
         kw = {}
         if c.bank_mode == "read" and p in c.active and (p in c.banks or p in c.bank_kv):
             if p in c.bank_kv:    # projected once per group of timesteps by the sampler (pipeline._reference_group)
@@ -739,7 +660,7 @@ class UNet3DConditionModel:
         s.ctx_kv = _ctx_kv        # {prefix: (K rows, V^T)} from context_kv(): attn2 projections hoisted out of the step
         s.ctx_rows = None if _ctx_kv is not None else ops.convert(ctx.float().reshape(-1, ctx.shape[2]), dtp)
         s.ctrl = (down_block_additional_residuals, mid_block_additional_residual)
-        x = ops.ncfhw_to_rows(sample, dtp, cpad=_round_up(Cin, 8))
+        x = ops.ncfhw_to_rows(sample, dtp, cpad=round_up(Cin, 8))
         if cfg["center_input_sample"]:      # sample = 2 * sample - 1.0 (unet_controlnet.py:371-373); the pad channels stay zero
             m1 = torch.zeros(1, x.shape[1], device=dev, dtype=dtp)
             m1[:, :Cin] = -1.0
@@ -939,8 +860,6 @@ class UNet3DConditionModel:
         if not return_dict:
             return (out,)
         return UNet3DConditionOutput(sample=out)
-
-    __call__ = forward
 
     # bank plumbing used by ReferenceAttentionControl / the pipeline
     def bank_order(self, fusion_blocks="midup"):

@@ -27,7 +27,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from ._lib import EmoHipError
+from .module import HipModule, round_up
 
 VAE_DEFAULTS = dict(in_channels=3, out_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
                     norm_num_groups=32, scaling_factor=0.18215, sample_size=512)
@@ -61,10 +61,6 @@ class AutoencoderKLOutput:
 
     def __getitem__(self, k):   # diffusers BaseOutput: the reference reads `vae.encode(x)['latent_dist']` (EMOAnimationPipeline.py:411)
         return self.latent_dist if k in ("latent_dist", 0) else getattr(self, k)
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 def vae_param_shapes(cfg) -> "OrderedDict[str, tuple]":
@@ -119,7 +115,7 @@ def vae_param_shapes(cfg) -> "OrderedDict[str, tuple]":
     return d
 
 
-class AutoencoderKL:
+class AutoencoderKL(HipModule):
     def __init__(self, **kwargs):
         cfg = dict(VAE_DEFAULTS)
         for k, v in kwargs.items():
@@ -128,24 +124,9 @@ class AutoencoderKL:
         cfg["block_out_channels"] = tuple(cfg["block_out_channels"])
         self.config = SimpleNamespace(**cfg)
         self._cfg = cfg
-        self._shapes = vae_param_shapes(cfg)
-        self.dtype, self.device = torch.float32, torch.device("cpu")
-        self._master, self._w = None, None
+        super().__init__(vae_param_shapes(cfg))
 
-    # ------------------------------------------------------------------ torch-module-like surface
-    def eval(self):
-        return self
-
-    def requires_grad_(self, *_):
-        return self
-
-    def state_dict(self):
-        if self._master is None:
-            raise EmoHipError("no weights loaded")
-        return {k: v.detach().cpu() for k, v in self._master.items()}
-
-    def load_state_dict(self, sd, strict=True):
-        sd = dict(sd)
+    def _remap_keys(self, sd):
         for k in list(sd):   # older diffusers attention key names; Linear weights stored as 1x1 convs in the oldest checkpoints
             for old, new in _OLD_ATTN.items():
                 tag = f".attentions.0.{old}."
@@ -154,43 +135,9 @@ class AutoencoderKL:
         for k, v in list(sd.items()):
             if ".attentions.0." in k and k.endswith(".weight") and v.dim() == 4:
                 sd[k] = v.reshape(v.shape[0], v.shape[1])
-        missing = [k for k in self._shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self._shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: {len(missing)} missing key(s) {missing[:5]}, "
-                               f"{len(unexpected)} unexpected key(s) {unexpected[:5]}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shp)}")
-        master = dict(self._master or {})
-        for k in self._shapes:
-            if k in sd:
-                master[k] = sd[k].detach().to(torch.float32)
-        self._master, self._w = master, None
-        if all(k in master for k in self._shapes):
-            self._pack()
-        return missing, unexpected
+        return sd
 
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            else:
-                device = torch.device(a)
-        if dtype is not None:
-            if dtype not in (torch.float32, torch.bfloat16, torch.float16):
-                raise EmoHipError(f"compute dtype {dtype} not supported (float32 | bfloat16 | float16)")
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        if self._master is not None and all(k in self._master for k in self._shapes):
-            self._pack()
-        return self
-
-    def _pack(self):
-        if self.device.type != "cuda":
-            return
+    def _pack_weights(self):
         dev, dtp = self.device, self.dtype
         m = {k: v.to(dev) for k, v in self._master.items()}
         self._master = m
@@ -200,7 +147,7 @@ class AutoencoderKL:
                 w[k] = t.float().contiguous()
             elif t.dim() == 4 and t.shape[-1] == 3:            # OIHW -> [Cout][ky][kx][Cin_pad]
                 co, ci = t.shape[0], t.shape[1]
-                cip = _round_up(ci, 8)
+                cip = round_up(ci, 8)
                 o = torch.zeros(co, 3, 3, cip, device=dev, dtype=torch.float32)
                 o[..., :ci] = t.permute(0, 2, 3, 1)
                 w[k] = o.reshape(co, 9 * cip).to(dtp).contiguous()
@@ -209,18 +156,14 @@ class AutoencoderKL:
         # 1x1 convs on 4- / 8-channel latents: pad K to the 16-byte vector
         for k in ("quant_conv.weight", "post_quant_conv.weight"):
             t = w[k]
-            kp = _round_up(t.shape[1], ops.vec(dtp))
+            kp = round_up(t.shape[1], ops.vec(dtp))
             if kp != t.shape[1]:
                 o = torch.zeros(t.shape[0], kp, device=dev, dtype=dtp)
                 o[:, :t.shape[1]] = t
                 w[k] = o.contiguous()
-        self._w = w
+        return w
 
     # ------------------------------------------------------------------ blocks
-    def _need(self):
-        if self._w is None:
-            raise EmoHipError("AutoencoderKL: weights not loaded / model not on a HIP device (no CPU execution path)")
-
     def _gn(self, p, x, n_img, silu):
         return ops.group_norm(x, self._w[p + ".weight"], self._w[p + ".bias"], n_img, self._cfg["norm_num_groups"], 1e-6, silu)
 
@@ -247,7 +190,7 @@ class AutoencoderKL:
         scale = float(C_) ** -0.5
         q = ops.gemm(h, w[p + ".to_q.weight"], w[p + ".to_q.bias"], out_scale=scale)
         k = ops.gemm(h, w[p + ".to_k.weight"], w[p + ".to_k.bias"])
-        ld = _round_up(HW, 8)
+        ld = round_up(HW, 8)
         vt = ops.gemm(h, w[p + ".to_v.weight"], w[p + ".to_v.bias"], transpose_rows=HW, transpose_ld=ld)   # (n, C, ld)
         if ld != HW:
             vt[:, :, HW:].zero_()
@@ -271,8 +214,8 @@ class AutoencoderKL:
         w, cfg, dtp = self._w, self._cfg, self.dtype
         n, lat, H, W = z.shape
         # images ride the frame axis of the layout kernel: (1, lat, n, H, W) -> rows ((n) h w, lat padded to the 16-byte vector)
-        x = ops.ncfhw_to_rows(z.to(self.device).float().permute(1, 0, 2, 3).unsqueeze(0), dtp, cpad=_round_up(lat, ops.vec(dtp)))
-        xin = torch.zeros(x.shape[0], _round_up(lat, 8), device=x.device, dtype=dtp)     # conv_in reads 8-channel rows
+        x = ops.ncfhw_to_rows(z.to(self.device).float().permute(1, 0, 2, 3).unsqueeze(0), dtp, cpad=round_up(lat, ops.vec(dtp)))
+        xin = torch.zeros(x.shape[0], round_up(lat, 8), device=x.device, dtype=dtp)     # conv_in reads 8-channel rows
         ops.gemm(x, w["post_quant_conv.weight"], w["post_quant_conv.bias"], out=xin[:, :lat])
         x, _, _ = self._conv("decoder.conv_in", xin, n, H, W)
         x = self._mid("decoder.mid_block", x, n, H, W)
@@ -330,7 +273,7 @@ class AutoencoderKL:
         self._need()
         w, cfg, dtp = self._w, self._cfg, self.dtype
         n, ci, H, W = x.shape
-        rows = ops.ncfhw_to_rows(x.to(self.device).float().unsqueeze(0).permute(0, 2, 1, 3, 4).contiguous(), dtp, cpad=_round_up(ci, 8))
+        rows = ops.ncfhw_to_rows(x.to(self.device).float().unsqueeze(0).permute(0, 2, 1, 3, 4).contiguous(), dtp, cpad=round_up(ci, 8))
         h, _, _ = self._conv("encoder.conv_in", rows, n, H, W)
         nb = len(cfg["block_out_channels"])
         for i in range(nb):

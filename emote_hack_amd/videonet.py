@@ -173,5 +173,3 @@ class VideoNet(UNet3DConditionModel):
         if intial_noise.dim() != 4:
             raise ValueError("VideoNet takes the 2-D UNet's (b*t, c, h, w) input")
         return super().forward(intial_noise.unsqueeze(2), timesteps, clip_condition_embeddings, return_dict=False)[0][:, :, 0]
-
-    __call__ = forward

@@ -25,17 +25,13 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from ._lib import EmoHipError
+from .module import HipModule, round_up
 from .synth import synth_state_dict, synth_tensor
 
 BASE_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072,
                    conv_dim=(512, 512, 512, 512, 512, 512, 512), conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2),
                    conv_bias=False, feat_extract_norm="group", num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16,
                    do_stable_layer_norm=False, layer_norm_eps=1e-5)
-
-
-def _r8(x):
-    return (x + 7) // 8 * 8
 
 
 def wav2vec2_param_shapes(cfg=None):
@@ -84,9 +80,10 @@ def wav2vec2_synth_state_dict(cfg=None, prefix="wav2vec2.", device="cpu"):
     return sd
 
 
-class Wav2Vec2Model:
+class Wav2Vec2Model(HipModule):
     """forward(input_values (1, n_samples) f32) -> namespace(last_hidden_state=(1, T, hidden) f32), like the transformers class the
     reference calls (Net.py:643-644)."""
+    _tolerated = frozenset({"masked_spec_embed"})
 
     def __init__(self, config=None, **kwargs):
         cfg = dict(BASE_CONFIG)
@@ -101,54 +98,17 @@ class Wav2Vec2Model:
             raise ValueError("Wav2Vec2Model: head dim, positional-conv group width and conv channels must be multiples of 8")
         self.config = SimpleNamespace(**cfg)
         self._cfg = cfg
-        self._shapes = wav2vec2_param_shapes(cfg)
-        self._sd, self._w = None, None
-        self.dtype, self.device = torch.float32, torch.device("cpu")
+        super().__init__(wav2vec2_param_shapes(cfg))
 
-    # ---- torch-module-like surface
-    def eval(self):
-        return self
-
-    def state_dict(self):
-        if self._sd is None:
-            raise EmoHipError("no weights loaded")
-        return dict(self._sd)
-
-    def load_state_dict(self, sd, strict=True):
-        sd = dict(sd)
+    def _remap_keys(self, sd):
         pc = "encoder.pos_conv_embed.conv."
         for old, new in ((pc + "weight_g", pc + "parametrizations.weight.original0"), (pc + "weight_v", pc + "parametrizations.weight.original1")):
             if old in sd and new not in sd:       # checkpoints written before torch's parametrised weight_norm
                 sd[new] = sd.pop(old)
-        missing = [k for k in self._shapes if k not in sd]
-        unexpected = [k for k in sd if k not in self._shapes and k != "masked_spec_embed"]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict: {len(missing)} missing {missing[:4]}, {len(unexpected)} unexpected {unexpected[:4]}")
-        for k, shp in self._shapes.items():
-            if k in sd and tuple(sd[k].shape) != tuple(shp):
-                raise RuntimeError(f"size mismatch for {k}: {tuple(sd[k].shape)} vs {tuple(shp)}")
-        self._sd = {k: sd[k].detach().float() for k in self._shapes if k in sd}
-        self._pack()
-        return missing, unexpected
+        return sd
 
-    def to(self, *args, **kwargs):
-        device, dtype = kwargs.get("device"), kwargs.get("dtype")
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-            else:
-                device = torch.device(a)
-        if dtype is not None:
-            self.dtype = dtype
-        if device is not None:
-            self.device = torch.device(device)
-        self._pack()
-        return self
-
-    def _pack(self):
-        if self._sd is None or self.device.type != "cuda" or any(k not in self._sd for k in self._shapes):
-            return
-        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._sd
+    def _pack_weights(self):
+        c, dev, dtp, sd = self._cfg, self.device, self.dtype, self._master
         w = {}
         f32 = lambda k: sd[k].to(dev).float().contiguous()
         lin = lambda k: sd[k].to(dev, dtp).contiguous()
@@ -156,7 +116,7 @@ class Wav2Vec2Model:
             t = sd[f"feature_extractor.conv_layers.{i}.conv.weight"]              # (Cout, Cin, k) -> [Cout][k][Cin]
             t = t.permute(0, 2, 1).reshape(t.shape[0], -1)
             if i == 0:       # Cin = 1: the k taps padded to a 16-byte multiple (the window matrix is padded alike)
-                t = torch.nn.functional.pad(t, (0, _r8(k) - k))
+                t = torch.nn.functional.pad(t, (0, round_up(k, 8) - k))
             w[f"conv{i}"] = t.to(dev, dtp).contiguous()
         w["gn.g"], w["gn.b"] = f32("feature_extractor.conv_layers.0.layer_norm.weight"), f32("feature_extractor.conv_layers.0.layer_norm.bias")
         w["fp.ln.g"], w["fp.ln.b"] = f32("feature_projection.layer_norm.weight"), f32("feature_projection.layer_norm.bias")
@@ -180,7 +140,7 @@ class Wav2Vec2Model:
             w[f"{i}.f1.w"], w[f"{i}.f1.b"] = lin(f"{p}.feed_forward.intermediate_dense.weight"), f32(f"{p}.feed_forward.intermediate_dense.bias")
             w[f"{i}.f2.w"], w[f"{i}.f2.b"] = lin(f"{p}.feed_forward.output_dense.weight"), f32(f"{p}.feed_forward.output_dense.bias")
             w[f"{i}.ln2.g"], w[f"{i}.ln2.b"] = f32(f"{p}.final_layer_norm.weight"), f32(f"{p}.final_layer_norm.bias")
-        self._w = w
+        return w
 
     # ---- forward
     @staticmethod
@@ -191,8 +151,7 @@ class Wav2Vec2Model:
 
     @torch.no_grad()
     def forward(self, input_values, attention_mask=None, **_ignored):
-        if self._w is None:
-            raise EmoHipError("Wav2Vec2Model: load_state_dict + .to('cuda') first (weights are caller-loaded; there is no CPU execution path)")
+        self._need()
         if attention_mask is not None:
             raise NotImplementedError("attention_mask: wav2vec2-base-960h is used unmasked (its processor returns no mask; Net.py:639-644)")
         if input_values.dim() != 2 or input_values.shape[0] != 1:
@@ -209,7 +168,7 @@ class Wav2Vec2Model:
             n_t = (n_t - k) // s + 1
         wave = input_values[0].to(dev).float()
         # layer 0 (Cin = 1): the (T0, k0) window matrix, padded to 16-byte rows (index / pad only)
-        a0 = torch.nn.functional.pad(wave.unfold(0, k0, s0), (0, _r8(k0) - k0)).contiguous()
+        a0 = torch.nn.functional.pad(wave.unfold(0, k0, s0), (0, round_up(k0, 8) - k0)).contiguous()
         h = ops.gemm(ops.convert(a0, dtp), w["conv0"])
         h = ops.channel_norm(h, w["gn.g"], w["gn.b"], 1e-5, gelu=True)            # GroupNorm(C, C) over time, then GELU
         for i in range(1, len(c["conv_kernel"])):
@@ -234,14 +193,12 @@ class Wav2Vec2Model:
         d = H // nh
         for i in range(c["num_hidden_layers"]):
             qk = ops.gemm(h, w[f"{i}.qk.w"], w[f"{i}.qk.b"])
-            vt = ops.gemm(h, w[f"{i}.v.w"], w[f"{i}.v.b"], transpose_rows=T, transpose_ld=_r8(T))
+            vt = ops.gemm(h, w[f"{i}.v.w"], w[f"{i}.v.b"], transpose_rows=T, transpose_ld=round_up(T, 8))
             att = ops.attention(qk[:, :H], qk[:, H:], vt, T, B=1, Lq=T, heads=nh, d=d, scale=d ** -0.5)
             h = ops.layer_norm(ops.gemm(att, w[f"{i}.o.w"], w[f"{i}.o.b"], residual=h), w[f"{i}.ln1.g"], w[f"{i}.ln1.b"], eps)
             f = ops.act(ops.gemm(h, w[f"{i}.f1.w"], w[f"{i}.f1.b"]), "gelu")
             h = ops.layer_norm(ops.gemm(f, w[f"{i}.f2.w"], w[f"{i}.f2.b"], residual=h), w[f"{i}.ln2.g"], w[f"{i}.ln2.b"], eps)
         return SimpleNamespace(last_hidden_state=ops.convert(h, torch.float32).unsqueeze(0))
-
-    __call__ = forward
 
 
 def normalize_waveform(x: torch.Tensor) -> torch.Tensor:
