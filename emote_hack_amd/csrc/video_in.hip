@@ -1,0 +1,415 @@
+// video_in.hip - baseline JPEG (ITU-T T.81) decoding of Motion-JPEG frames, the device half of the reader that stands in for
+// `VideoReader(path).read()` (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-185) and the reverse of
+// video_out.hip (emote_hack_amd/video_io.py is the host half: marker segments, byte unstuffing, the decoding tables):
+//   emo_jpeg_decode_bits  : Huffman decoding (T.81 F.2.2) of one interleaved 4:2:0 scan per frame.  A frame's stream is serial - where a
+//                           code starts depends on every code before it - and frames are independent: ONE workgroup per frame.  Its 256
+//                           lanes stage the stream through LDS a window at a time and flush the decoded coefficients as coalesced 16-byte
+//                           stores; lane 0 walks the codes in between.  Every loop is counted, every read is masked to the frame's bytes,
+//                           an error ends the frame.
+//   emo_jpeg_idct         : dequantisation and libjpeg's "islow" integer IDCT (jidctint.c); a wavefront takes eight whole blocks
+//                           (1024 contiguous bytes), one column and then one row per lane
+//   emo_jpeg_upsample_rgb : libjpeg's h2v2 "fancy" (triangle) chroma up-sampling on the real chroma plane and its 16-bit fixed-point
+//                           YCbCr -> RGB (jdsample.c, jdcolor.c); every lane writes one whole dword of the packed frames
+// Integer arithmetic throughout: the bytes are those libjpeg's default decoder gives.
+#include "common.h"
+
+// natural (row-major) index of zig-zag position k (T.81 figure A.6)
+__device__ const uint8_t JPEG_NATURAL_OF[64] = {
+  0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+  35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63,
+};
+
+// ------------------------------------------------------------------------------------------------------------ entropy decoding
+#define JD_TABLE_INTS EMO_JPEG_DECODE_TABLE_INTS   // per table: MINCODE[16] MAXCODE[16] VALPTR[16] 16 unused HUFFVAL[256]
+#define JD_STAGE_BYTES 4096                        // the window of the stream held in LDS
+#define JD_STAGE_SLACK 16                          // the reader runs at most 8 bytes ahead of the bits it has handed out
+#define JD_BLOCK_BYTES_MAX 216                     // a block is at most 27 + 63 * 26 = 1665 bits
+#define JD_BLOCKS 48                               // blocks decoded between two flushes (6 KiB of coefficients)
+
+// the bit reader of the walking lane: `acc` holds `cnt` unread bits at its top, `rp` is the next dword of the window
+struct jd_reader {
+  const uint32_t* win;
+  uint64_t acc;
+  int cnt, rp;
+  __device__ __forceinline__ void refill() {      // afterwards cnt >= 32
+    if (cnt < 32) {
+      const uint32_t w = win[min(rp, (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4 - 1)];
+      acc |= (uint64_t)__builtin_bswap32(w) << (32 - cnt);
+      cnt += 32;
+      rp++;
+    }
+  }
+  __device__ __forceinline__ uint32_t peek(int k) const { return k ? (uint32_t)(acc >> (64 - k)) : 0u; }   // k <= 32
+  __device__ __forceinline__ void skip(int k) { acc <<= k; cnt -= k; }
+  __device__ __forceinline__ int64_t used() const { return (int64_t)rp * 32 - cnt; }                         // bits since the window's start
+};
+
+// DECODE of T.81 figure F.16 behind an 8-bit look-up: the symbol, or -1 when no code of the table matches the next 16 bits (with fewer
+// than 16 bits left in the frame that is a code cut short, not an undefined one: the caller tells them apart)
+__device__ __forceinline__ int jd_symbol(jd_reader& r, const uint16_t* lut, const int32_t* tab) {
+  r.refill();
+  const uint32_t e = lut[r.peek(8)];
+  if (e) {
+    r.skip((int)(e >> 8));
+    return (int)(e & 255u);
+  }
+  const uint32_t bits16 = r.peek(16);
+  for (int l = 9; l <= 16; l++) {
+    const int code = (int)(bits16 >> (16 - l));
+    const int maxcode = tab[16 + l - 1];
+    if (code <= maxcode) {
+      r.skip(l);
+      return tab[64 + ((tab[32 + l - 1] + code - tab[l - 1]) & 255)];
+    }
+  }
+  return -1;
+}
+
+// RECEIVE + EXTEND (figures F.17, F.12): the s-bit magnitude, s <= 11
+__device__ __forceinline__ int jd_extend(jd_reader& r, int s) {
+  r.refill();
+  const int v = (int)r.peek(s);
+  r.skip(s);
+  return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v;
+}
+
+__global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
+                                                               const int64_t* __restrict__ offsets, const int32_t* __restrict__ tables,
+                                                               int16_t* __restrict__ coefs, int32_t* __restrict__ status, int n_mcu) {
+  __shared__ int32_t tab[4 * JD_TABLE_INTS];
+  __shared__ uint16_t lut[4][256];                           // length << 8 | symbol of the code that starts the 8 bits; 0: longer than 8
+  __shared__ uint32_t win[(JD_STAGE_BYTES + JD_STAGE_SLACK) / 4];
+  __shared__ __attribute__((aligned(16))) int16_t blk[JD_BLOCKS * 64];
+  __shared__ int64_t sh_bitpos;                              // the walker's place in the frame, in bits
+  __shared__ int sh_done, sh_status, sh_pred[3];
+  const int t = threadIdx.x;
+  const int frame = blockIdx.x;
+  const int n_blocks = n_mcu * 6;
+  // the frame's own bytes: [lo, hi) inside the buffer; offsets that leave it or run backwards give an empty frame
+  int64_t lo = offsets[frame], hi = offsets[frame + 1];
+  lo = min(max(lo, (int64_t)0), scan_bytes);
+  hi = min(max(hi, lo), scan_bytes);
+  const int64_t frame_bits = (hi - lo) * 8;
+
+  for (int i = t; i < 4 * JD_TABLE_INTS; i += 256) tab[i] = tables[i];
+  if (t == 0) {
+    sh_bitpos = 0; sh_done = 0; sh_status = EMO_JPEG_OK;
+    sh_pred[0] = sh_pred[1] = sh_pred[2] = 0;
+  }
+  __syncthreads();
+  for (int i = t; i < 1024; i += 256) {                      // figure F.16 on every 8-bit prefix
+    const int32_t* tb = tab + (i >> 8) * JD_TABLE_INTS;
+    const int p = i & 255;
+    uint16_t e = 0;
+    for (int l = 1; l <= 8; l++) {
+      const int code = p >> (8 - l);
+      if (code <= tb[16 + l - 1]) {
+        e = (uint16_t)(l << 8 | (tb[64 + ((tb[32 + l - 1] + code - tb[l - 1]) & 255)] & 255));
+        break;
+      }
+    }
+    lut[i >> 8][p] = e;
+  }
+  uint4* blk4 = (uint4*)blk;
+  for (int i = t; i < JD_BLOCKS * 8; i += 256) blk4[i] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+
+  int done_blocks = 0;                                       // uniform over the workgroup
+  // every round decodes at least one block or ends the frame, so n_blocks rounds are enough
+  for (int round = 0; round < n_blocks && done_blocks < n_blocks; round++) {
+    const int64_t bit0 = sh_bitpos;
+    const int64_t byte0 = bit0 >> 3;                         // the window starts at this byte of the frame
+    // stage: dword i of the window = frame bytes byte0 + 4 i .. + 3, bytes at or behind the frame's end as 0.  Aligned dword loads of
+    // the buffer (scan_bytes is a multiple of 4), shifted into place
+    for (int i = t; i < (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4; i += 256) {
+      const int64_t g = lo + byte0 + 4 * (int64_t)i;         // the first byte wanted
+      uint32_t v = 0;
+      if (g < hi) {
+        const int64_t a = g & ~(int64_t)3;
+        const int sh = (int)(g & 3) * 8;
+        const uint32_t w0 = *(const uint32_t*)(scan + a);    // a < hi <= scan_bytes, a % 4 == 0: inside the buffer
+        const uint32_t w1 = (sh && a + 4 < hi) ? *(const uint32_t*)(scan + a + 4) : 0u;
+        v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
+        const int64_t left = hi - g;                         // >= 1
+        if (left < 4) v &= (1u << (8 * (int)left)) - 1u;
+      }
+      win[i] = v;
+    }
+    __syncthreads();
+    if (t == 0) {
+      jd_reader r;
+      r.win = win; r.acc = 0; r.cnt = 0; r.rp = 0;
+      r.refill();
+      r.skip((int)(bit0 & 7));
+      const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
+      int pred0 = sh_pred[0], pred1 = sh_pred[1], pred2 = sh_pred[2];
+      int st = EMO_JPEG_OK, nb = 0;
+      for (; nb < JD_BLOCKS && done_blocks + nb < n_blocks; nb++) {
+        if (!holds_end && (r.used() >> 3) + JD_BLOCK_BYTES_MAX > JD_STAGE_BYTES) break;    // the next block may leave the window
+        const int k6 = (done_blocks + nb) % 6;
+        const int comp = k6 < 4 ? 0 : k6 - 3;
+        const int32_t* dc_tab = tab + (comp ? 2 : 0) * JD_TABLE_INTS;
+        const uint16_t* dc_lut = lut[comp ? 2 : 0];
+        int16_t* out = blk + nb * 64;
+        // DC (F.2.2.1)
+        int s = jd_symbol(r, dc_lut, dc_tab);
+        if (s < 0) { st = byte0 * 8 + r.used() + 16 > frame_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE; break; }
+        if (s > 11) { st = EMO_JPEG_BAD_CODE; break; }
+        const int diff = jd_extend(r, s);
+        if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
+        int& pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
+        pred = (int16_t)(pred + diff);
+        out[0] = (int16_t)pred;
+        // AC (F.2.2.2): at most 63 symbols, each moves k on by at least one
+        int k = 1;
+        for (int it = 0; it < 63 && k < 64; it++) {
+          const int rs = jd_symbol(r, dc_lut + 256, dc_tab + JD_TABLE_INTS);
+          if (rs < 0) { st = byte0 * 8 + r.used() + 16 > frame_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE; break; }
+          const int run = rs >> 4;
+          s = rs & 15;
+          if (s == 0) {
+            if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
+            if (rs == 0) break;                              // EOB
+            if (rs != 0xF0) { st = EMO_JPEG_BAD_CODE; break; }   // EOBn belongs to progressive scans
+            k += 16;                                         // ZRL
+            if (k > 64) { st = EMO_JPEG_BAD_RUN; break; }
+            continue;
+          }
+          if (s > 10) { st = EMO_JPEG_BAD_CODE; break; }
+          const int v = jd_extend(r, s);
+          if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
+          k += run;
+          if (k > 63) { st = EMO_JPEG_BAD_RUN; break; }
+          out[k++] = (int16_t)v;
+        }
+        if (st != EMO_JPEG_OK) break;
+      }
+      if (st != EMO_JPEG_OK) {                               // the block the error is in is dropped with the rest of the frame
+        for (int i = 0; i < 64; i++) blk[min(nb, JD_BLOCKS - 1) * 64 + i] = 0;
+        sh_status = st;
+      }
+      sh_pred[0] = pred0; sh_pred[1] = pred1; sh_pred[2] = pred2;
+      sh_bitpos = byte0 * 8 + r.used();
+      sh_done = nb;
+    }
+    __syncthreads();
+    const int nb = sh_done;
+    const int st = sh_status;
+    // flush: nb whole blocks, 128 contiguous bytes each, as 16-byte stores; then clear them for the next round
+    uint4* dst = (uint4*)(coefs + ((int64_t)frame * n_blocks + done_blocks) * 64);
+    for (int i = t; i < nb * 8; i += 256) {
+      dst[i] = blk4[i];
+      blk4[i] = make_uint4(0, 0, 0, 0);
+    }
+    done_blocks += nb;
+    __syncthreads();
+    if (st != EMO_JPEG_OK || nb == 0) break;
+  }
+  // a frame that ended early: its remaining coefficients are zeroed, so the outputs never hold stale memory
+  uint4* rest = (uint4*)(coefs + ((int64_t)frame * n_blocks + done_blocks) * 64);
+  for (int i = t; i < (n_blocks - done_blocks) * 8; i += 256) rest[i] = make_uint4(0, 0, 0, 0);
+  if (t == 0) status[frame] = sh_status != EMO_JPEG_OK ? sh_status : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
+}
+
+extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
+                                    int32_t* status, int n, int n_mcu, void* stream) {
+  EMO_CHECK(scan && offsets && tables && coefs && status, EMO_ERR_NULL, "emo_jpeg_decode_bits: null pointer");
+  EMO_CHECK(n > 0 && n_mcu > 0 && (int64_t)n * n_mcu * 6 < (int64_t)1 << 31 && (int64_t)n_mcu * 6 < (int64_t)1 << 24, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_decode_bits: n=%d n_mcu=%d", n, n_mcu);
+  EMO_CHECK(scan_bytes > 0 && scan_bytes % 4 == 0 && (uintptr_t)scan % 4 == 0, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_decode_bits: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4",
+            (long long)scan_bytes);
+  EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)offsets % 8 == 0, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_decode_bits: coefs must be 16-byte aligned, offsets 8-byte aligned");
+  jpeg_decode_bits_kernel<<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ dequantisation, IDCT
+// jidctint.c (jpeg_idct_islow), CONST_BITS 13, PASS1_BITS 2.  Sums and products wrap in 32 bits (coefficients no encoder of 8-bit
+// samples makes can overflow them: the result is then some value, never undefined behaviour); the shift is arithmetic.
+template <int SHIFT>
+__device__ __forceinline__ void jpeg_idct_1d(const int32_t* in, int32_t* out) {
+  typedef uint32_t u;
+  const u i0 = (u)in[0], i1 = (u)in[1], i2 = (u)in[2], i3 = (u)in[3], i4 = (u)in[4], i5 = (u)in[5], i6 = (u)in[6], i7 = (u)in[7];
+  u z1 = (i2 + i6) * 4433u;
+  const u t2 = z1 - i6 * 15137u, t3 = z1 + i2 * 6270u;
+  const u t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13;
+  const u t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  u a0 = i7, a1 = i5, a2 = i3, a3 = i1;
+  z1 = a0 + a3;
+  u z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+  const u z5 = (z3 + z4) * 9633u;
+  a0 *= 2446u; a1 *= 16819u; a2 *= 25172u; a3 *= 12299u;
+  z1 *= (u)-7373; z2 *= (u)-20995;
+  z3 = z3 * (u)-16069 + z5;
+  z4 = z4 * (u)-3196 + z5;
+  a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+  const u rnd = 1u << (SHIFT - 1);
+  out[0] = (int32_t)(t10 + a3 + rnd) >> SHIFT;
+  out[1] = (int32_t)(t11 + a2 + rnd) >> SHIFT;
+  out[2] = (int32_t)(t12 + a1 + rnd) >> SHIFT;
+  out[3] = (int32_t)(t13 + a0 + rnd) >> SHIFT;
+  out[4] = (int32_t)(t13 - a0 + rnd) >> SHIFT;
+  out[5] = (int32_t)(t12 - a1 + rnd) >> SHIFT;
+  out[6] = (int32_t)(t11 - a2 + rnd) >> SHIFT;
+  out[7] = (int32_t)(t10 - a3 + rnd) >> SHIFT;
+}
+
+#define JI_LD 72       // dwords between two blocks of a wavefront's workspace: 72 % 32 = 8 puts the 64 (block, column) lanes on 64 banks
+
+// A wavefront takes 8 consecutive blocks (1024 contiguous bytes): lane = (block, eighth) loads 8 coefficients as one 16-byte vector,
+// then lane = (block, column) runs pass 1 and lane = (block, row) pass 2, and stores its 8 samples as one 8-byte vector.
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coefs, const uint16_t* __restrict__ quant,
+                                                        uint8_t* __restrict__ yp, uint8_t* __restrict__ cp, int64_t n_blocks, int n_mcu,
+                                                        int mcu_cols, int mcu_rows) {
+  __shared__ __attribute__((aligned(16))) int32_t ws[4][8 * JI_LD];
+  __shared__ uint16_t q[2][64];
+  __shared__ uint8_t nat[64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (t < 128) q[t >> 6][t & 63] = quant[t];
+  if (t < 64) nat[t] = JPEG_NATURAL_OF[t];
+  __syncthreads();
+  int32_t* w = ws[wave] + (lane >> 3) * JI_LD;              // this lane's block
+  const int sub = lane & 7;
+  const int64_t n_groups = (n_blocks + 7) / 8;
+  for (int64_t g0 = (int64_t)blockIdx.x * 4; g0 < n_groups; g0 += (int64_t)gridDim.x * 4) {        // uniform over the workgroup
+    const int64_t b = (g0 + wave) * 8 + (lane >> 3);
+    const bool live = b < n_blocks;
+    const int64_t frame = b / ((int64_t)n_mcu * 6);
+    const int in_frame = (int)(b - frame * n_mcu * 6), m = in_frame / 6, k6 = in_frame - m * 6;
+    if (live) {
+      const uint4 v = *(const uint4*)(coefs + b * 64 + sub * 8);
+      const uint32_t pk[4] = {v.x, v.y, v.z, v.w};
+      const uint16_t* qq = q[k6 >= 4];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int c = (int16_t)(pk[j >> 1] >> ((j & 1) * 16));
+        const int at = nat[sub * 8 + j];
+        w[at] = c * (int)qq[at];
+      }
+    }
+    __syncthreads();
+    int32_t in[8], out[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) in[r] = w[r * 8 + sub];       // pass 1: column `sub`
+    jpeg_idct_1d<11>(in, out);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 8; r++) w[r * 8 + sub] = out[r];
+    __syncthreads();
+#pragma unroll
+    for (int x = 0; x < 8; x++) in[x] = w[sub * 8 + x];       // pass 2: row `sub`
+    jpeg_idct_1d<18>(in, out);
+    __syncthreads();
+    if (live) {
+      uint32_t p0 = 0, p1 = 0;
+#pragma unroll
+      for (int x = 0; x < 4; x++) {
+        p0 |= (uint32_t)min(max(out[x] + 128, 0), 255) << (8 * x);
+        p1 |= (uint32_t)min(max(out[4 + x] + 128, 0), 255) << (8 * x);
+      }
+      const int my = m / mcu_cols, mx = m - my * mcu_cols;
+      uint8_t* dst;
+      if (k6 < 4) {
+        const int64_t row = (frame * mcu_rows + my) * 16 + (k6 >> 1) * 8 + sub;
+        dst = yp + row * ((int64_t)mcu_cols * 16) + mx * 16 + (k6 & 1) * 8;
+      } else {
+        const int64_t row = ((frame * 2 + (k6 - 4)) * mcu_rows + my) * 8 + sub;
+        dst = cp + row * ((int64_t)mcu_cols * 8) + mx * 8;
+      }
+      *(uint2*)dst = make_uint2(p0, p1);
+    }
+  }
+}
+
+static int jpeg_geometry(const char* who, int n, int H, int W, int* mcu_rows, int* mcu_cols) {
+  EMO_CHECK(n > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535, EMO_ERR_BAD_SHAPE, "%s: n=%d H=%d W=%d (1 .. 65535: SOF0 holds 16 bits)", who, n, H, W);
+  *mcu_cols = (W + 15) / 16;
+  *mcu_rows = (H + 15) / 16;
+  EMO_CHECK((int64_t)*mcu_cols * *mcu_rows * n * 6 < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE, "%s: %lld blocks", who,
+            (long long)*mcu_cols * *mcu_rows * n * 6);
+  return EMO_OK;
+}
+
+extern "C" int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream) {
+  EMO_CHECK(coefs && quant && y_plane && c_planes, EMO_ERR_NULL, "emo_jpeg_idct: null pointer");
+  int mcu_rows = 0, mcu_cols = 0;
+  const int rc = jpeg_geometry("emo_jpeg_idct", n, H, W, &mcu_rows, &mcu_cols);
+  if (rc != EMO_OK) return rc;
+  EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)y_plane % 8 == 0 && (uintptr_t)c_planes % 8 == 0, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_idct: coefs must be 16-byte aligned, the planes 8-byte aligned");
+  const int n_mcu = mcu_rows * mcu_cols;
+  const int64_t n_blocks = (int64_t)n * n_mcu * 6, g = (n_blocks + 31) / 32;
+  jpeg_idct_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, quant, y_plane, c_planes, n_blocks, n_mcu, mcu_cols, mcu_rows);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ chroma up-sampling, colour
+// One pixel: h2v2_fancy_upsample (jdsample.c) on the chroma plane of ch x cw real samples, then jdcolor.c's fixed-point transform.
+__device__ __forceinline__ uint32_t jpeg_pixel_rgb(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp, int64_t frame, int y, int x,
+                                                   int ch, int cw, int64_t y_ld, int64_t y_rows, int64_t c_ld, int64_t c_rows) {
+  const int r = y >> 1, c = x >> 1;
+  const int rn = min(max((y & 1) ? r + 1 : r - 1, 0), ch - 1);      // the nearer of the two neighbouring rows, inside the plane
+  const int cn = min(max((x & 1) ? c + 1 : c - 1, 0), cw - 1);
+  const int bias = (x & 1) ? 7 : 8;
+  int cc[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const uint8_t* p = cp + (frame * 2 + k) * c_rows * c_ld;
+    const int s_here = 3 * (int)p[r * c_ld + c] + (int)p[rn * c_ld + c];
+    const int s_side = 3 * (int)p[r * c_ld + cn] + (int)p[rn * c_ld + cn];
+    cc[k] = ((3 * s_here + s_side + bias) >> 4) - 128;
+  }
+  const int lum = yp[(frame * y_rows + y) * y_ld + x];
+  const int cb = cc[0], cr = cc[1];
+  const int R = lum + ((91881 * cr + 32768) >> 16);
+  const int G = lum + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+  const int B = lum + ((116130 * cb + 32768) >> 16);
+  return (uint32_t)min(max(R, 0), 255) | (uint32_t)min(max(G, 0), 255) << 8 | (uint32_t)min(max(B, 0), 255) << 16;
+}
+
+// lane = one dword of the packed output: bytes 4 d .. 4 d + 3 belong to pixels (4 d) / 3 and the one behind it
+__global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp,
+                                                                uint8_t* __restrict__ rgb, int64_t total_bytes, int H, int W, int mcu_rows,
+                                                                int mcu_cols) {
+  const int ch = (H + 1) / 2, cw = (W + 1) / 2;
+  const int64_t y_ld = (int64_t)mcu_cols * 16, y_rows = (int64_t)mcu_rows * 16, c_ld = (int64_t)mcu_cols * 8, c_rows = (int64_t)mcu_rows * 8;
+  const int64_t n_pix = total_bytes / 3, n_dwords = (total_bytes + 3) / 4;
+  for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < n_dwords; d += (int64_t)gridDim.x * 256) {
+    const int64_t byte0 = d * 4, p0 = byte0 / 3;
+    const int phase = (int)(byte0 - p0 * 3);                 // the channel of the dword's first byte
+    uint64_t two = 0;                                        // the 6 bytes of pixels p0, p0 + 1
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const int64_t p = p0 + k;
+      if (p < n_pix) {
+        const int64_t row = p / W;
+        const int x = (int)(p - row * W);
+        const int64_t frame = row / H;
+        const int y = (int)(row - frame * H);
+        two |= (uint64_t)jpeg_pixel_rgb(yp, cp, frame, y, x, ch, cw, y_ld, y_rows, c_ld, c_rows) << (24 * k);
+      }
+    }
+    const uint32_t v = (uint32_t)(two >> (8 * phase));
+    if (byte0 + 4 <= total_bytes) {
+      *(uint32_t*)(rgb + byte0) = v;
+    } else {
+      for (int k = 0; byte0 + k < total_bytes; k++) rgb[byte0 + k] = (uint8_t)(v >> (8 * k));
+    }
+  }
+}
+
+extern "C" int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
+  EMO_CHECK(y_plane && c_planes && rgb, EMO_ERR_NULL, "emo_jpeg_upsample_rgb: null pointer");
+  int mcu_rows = 0, mcu_cols = 0;
+  const int rc = jpeg_geometry("emo_jpeg_upsample_rgb", n, H, W, &mcu_rows, &mcu_cols);
+  if (rc != EMO_OK) return rc;
+  EMO_CHECK((uintptr_t)rgb % 4 == 0, EMO_ERR_BAD_SHAPE, "emo_jpeg_upsample_rgb: rgb must be 4-byte aligned");
+  const int64_t total = (int64_t)n * H * W * 3, g = ((total + 3) / 4 + 255) / 256;
+  jpeg_upsample_rgb_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(y_plane, c_planes, rgb, total, H, W, mcu_rows, mcu_cols);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}

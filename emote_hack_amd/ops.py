@@ -831,6 +831,70 @@ def jpeg_emit_bits(coefs: torch.Tensor, huff: torch.Tensor, bit_offsets: torch.T
     return out
 
 
+JPEG_DECODE_TABLE_INTS = 320                     # EMO_JPEG_DECODE_TABLE_INTS
+JPEG_STATUS = {0: "ok", 1: "a code the Huffman table does not define", 2: "the scan ends before the frame's last block",
+               3: "a zero run leaves its block"}   # EMO_JPEG_OK / _BAD_CODE / _PAST_END / _BAD_RUN
+
+
+def _jpeg_out(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    _need_cuda(out)
+    assert out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous(), (what, out.dtype, out.shape, shape)
+    return out
+
+
+def jpeg_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Tensor, n_mcu: int, out=None, status=None):
+    """the unstuffed scans of n frames (uint8, a multiple of 4 bytes; frame i in bytes offsets[i] .. offsets[i + 1], int64 (n + 1)) ->
+    (coefficients int16 (n, n_mcu, 6, 64) in jpeg_blocks' layout, status int32 (n): a key of JPEG_STATUS) (emo_jpeg_decode_bits; T.81
+    F.2.2).  tables: device int32 (4, JPEG_DECODE_TABLE_INTS), video_io.huffman_decode_table of DC luma / AC luma / DC chroma / AC chroma."""
+    _need_cuda(scan, offsets, tables)
+    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
+    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
+    n, n_mcu = offsets.numel() - 1, int(n_mcu)
+    coefs = _jpeg_out(out, (n, n_mcu, 6, 64), torch.int16, scan.device, "coefs")
+    status = _jpeg_out(status, (n,), torch.int32, scan.device, "status")
+    _launch("jpeg_decode_bits", 0.0, float(scan.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_decode_bits(_ptr(scan), scan.numel(), _ptr(offsets), _ptr(tables), _ptr(coefs), _ptr(status), n, n_mcu,
+                                                           _stream()), "emo_jpeg_decode_bits"), tag=f"{n}x{n_mcu}")
+    return coefs, status
+
+
+def jpeg_idct(coefs: torch.Tensor, quant: torch.Tensor, H: int, W: int, out_y=None, out_c=None):
+    """coefficients int16 (n, MCUs, 6, 64) of (H, W) frames -> (Y plane uint8 (n, mr * 16, mc * 16), Cb / Cr planes uint8 (n, 2, mr * 8,
+    mc * 8)), mr, mc = ceil(H / 16), ceil(W / 16): dequantisation and libjpeg's integer IDCT (emo_jpeg_idct).  quant: device uint16
+    (2, 64), natural order."""
+    _need_cuda(coefs, quant)
+    H, W = int(H), int(W)
+    mr, mc = (H + 15) // 16, (W + 15) // 16
+    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[1:]) == (mr * mc, 6, 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
+    assert quant.dtype == torch.uint16 and quant.numel() == 128 and quant.is_contiguous(), (quant.dtype, quant.shape)
+    n = coefs.shape[0]
+    y = _jpeg_out(out_y, (n, mr * 16, mc * 16), torch.uint8, coefs.device, "y plane")
+    c = _jpeg_out(out_c, (n, 2, mr * 8, mc * 8), torch.uint8, coefs.device, "chroma planes")
+    _launch("jpeg_idct", 0.0, float(2 * coefs.numel() + y.numel() + c.numel()),
+            lambda: check(_lib.load().emo_jpeg_idct(_ptr(coefs), _ptr(quant), _ptr(y), _ptr(c), n, H, W, _stream()), "emo_jpeg_idct"),
+            tag=f"{n}x{H}x{W}")
+    return y, c
+
+
+def jpeg_upsample_rgb(y: torch.Tensor, c: torch.Tensor, H: int, W: int, out=None) -> torch.Tensor:
+    """jpeg_idct's planes -> packed uint8 RGB frames (n, H, W, 3): libjpeg's triangle chroma up-sampling and fixed-point colour
+    transform (emo_jpeg_upsample_rgb)."""
+    _need_cuda(y, c)
+    H, W = int(H), int(W)
+    mr, mc = (H + 15) // 16, (W + 15) // 16
+    n = y.shape[0]
+    assert y.dtype == torch.uint8 and tuple(y.shape) == (n, mr * 16, mc * 16) and y.is_contiguous(), (y.dtype, y.shape)
+    assert c.dtype == torch.uint8 and tuple(c.shape) == (n, 2, mr * 8, mc * 8) and c.is_contiguous(), (c.dtype, c.shape)
+    rgb = _jpeg_out(out, (n, H, W, 3), torch.uint8, y.device, "frames")
+    _launch("jpeg_upsample_rgb", 0.0, float(y.numel() + c.numel() + rgb.numel()),
+            lambda: check(_lib.load().emo_jpeg_upsample_rgb(_ptr(y), _ptr(c), _ptr(rgb), n, H, W, _stream()), "emo_jpeg_upsample_rgb"),
+            tag=f"{n}x{H}x{W}")
+    return rgb
+
+
 INTERP_METHODS = {"linear": 0, "slerp": 1}
 
 

@@ -994,16 +994,54 @@ class EMOAnimationPipeline:
         x = torch.from_numpy(np.ascontiguousarray(images)) if isinstance(images, np.ndarray) else torch.as_tensor(images)
         if x.dim() != 4 or x.shape[-1] != 3:
             raise ValueError(f"images2latents: expected (f, h, w, 3) RGB frames, got {tuple(x.shape)}")
-        x = (x.float() / 127.5 - 1.0).permute(0, 3, 1, 2).contiguous()
+        return self._normalised2latents((x.float() / 127.5 - 1.0).permute(0, 3, 1, 2).contiguous())
+
+    def _normalised2latents(self, x):
         return torch.cat([self.vae.encode(x[i:i + 1])["latent_dist"].mean * 0.18215 for i in range(x.shape[0])])
 
+    @staticmethod
+    def _device_u8_scaled(frames_u8, divisor, shift=0.0):
+        """`x.float() / divisor - shift` of uint8 frames that live on the device, with the HOST's rounding: the 256 possible results are
+        computed on the host and gathered (a division by a scalar is a multiplication by its reciprocal on the device, which differs
+        in the last bit for some x) - frames decoded on the device give the values the same frames give when passed as a host array"""
+        table = torch.arange(256, dtype=torch.float32) / divisor
+        if shift:
+            table = table - shift
+        return table.to(frames_u8.device)[frames_u8.long()]
+
+    @staticmethod
+    def _clip_frames(path, n_frames, width, height, who):
+        """the first n_frames frames of a Motion-JPEG `.avi` file as uint8 (n_frames, height, width, 3) on the device (video_io.read_video).
+        The reference resizes what it reads through PIL (animation.py:174-185); no resize is built here, so another size is refused."""
+        from . import video_io
+        frames, _, _ = video_io.read_video(path, length=n_frames)
+        if frames.shape[0] < n_frames:
+            raise ValueError(f"{who}={os.fspath(path)!r} holds {frames.shape[0]} frames, {n_frames} are needed: pass a clip at least as long as "
+                             "video_length")
+        if tuple(frames.shape[1:3]) != (height, width):
+            raise ValueError(f"{who}={os.fspath(path)!r} holds frames of {frames.shape[1]} x {frames.shape[2]} (height x width), the call runs at "
+                             f"{height} x {width}: frames are not resized here, pass frames at size")
+        return frames
+
     def _source_image_latents(self, source_image, width, height):
-        """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is."""
-        return self.images2latents(self._source_image_rgb(source_image, width, height)[None], None)
+        """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is.  A Motion-JPEG `.avi`
+        path gives its first frame (animation.py:182-185), decoded on the device at (height, width) and encoded from there."""
+        rgb = self._source_image_rgb(source_image, width, height)
+        if torch.is_tensor(rgb):          # the first frame of a clip, on the device
+            if self.vae is None:
+                raise ValueError("images2latents needs a VAE (emote_hack_amd.vae.AutoencoderKL)")
+            return self._normalised2latents(self._device_u8_scaled(rgb[None], 127.5, 1.0).permute(0, 3, 1, 2).contiguous())
+        return self.images2latents(rgb[None], None)
 
     @staticmethod
     def _source_image_rgb(source_image, width, height):
         import numpy as np
+        if isinstance(source_image, (str, os.PathLike)) and os.fspath(source_image).lower().endswith(".avi"):
+            # animation.py:182-185 takes the source image from a video's first frame: decoded on the device, and it stays there
+            frame = EMOAnimationPipeline._clip_frames(source_image, 1, width, height, "source_image")[0]
+            if frame.shape[0] % 8 or frame.shape[1] % 8:
+                raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
+            return frame
         if isinstance(source_image, str):
             from PIL import Image
             source_image = np.array(Image.open(source_image).convert("RGB").resize((width, height)))
@@ -1255,7 +1293,13 @@ class EMOAnimationPipeline:
             if controlnet_condition is None:
                 raise ValueError("controlnet_condition (F,H,W,3 uint8 frames or a (F,3,H,W) float tensor) is required with a ControlNet")
             # prepare_condition (:369-376): uint8 HWC frames / 255 -> (f, c, h, w)
+            from_clip = isinstance(controlnet_condition, (str, os.PathLike))
+            if from_clip:
+                # animation.py:174-180 reads the control sequence from a video file: the first video_length frames, decoded on the device
+                controlnet_condition = self._clip_frames(controlnet_condition, video_length, width, height, "controlnet_condition")
             cn_cond = controlnet_condition if torch.is_tensor(controlnet_condition) else torch.as_tensor(controlnet_condition)
+            if from_clip:
+                cn_cond = self._device_u8_scaled(cn_cond, 255.0).permute(0, 3, 1, 2)
             if cn_cond.dim() == 4 and cn_cond.shape[-1] == 3 and cn_cond.shape[1] != 3:
                 cn_cond = cn_cond.permute(0, 3, 1, 2).float() / 255.0
             cn_cond = cn_cond.float()
@@ -1363,8 +1407,11 @@ class EMOAnimationPipeline:
                 if source_image is None:
                     raise ValueError("face_mask=\"locate\" looks for the face in source_image=: pass it (a path or an (H, W, 3) uint8 array), or "
                                      "pass the mask itself")
-                rgb = torch.as_tensor(self._source_image_rgb(source_image, width, height))
-                face_mask = loc(rgb.permute(2, 0, 1)[None].float() / 255.0)[0, 0]      # logits (H, W); pixels in [0, 1]
+                rgb = self._source_image_rgb(source_image, width, height)
+                if torch.is_tensor(rgb):      # the first frame of a clip, on the device
+                    face_mask = loc(self._device_u8_scaled(rgb, 255.0).permute(2, 0, 1)[None])[0, 0]
+                else:
+                    face_mask = loc(torch.as_tensor(rgb).permute(2, 0, 1)[None].float() / 255.0)[0, 0]      # logits (H, W); pixels in [0, 1]
                 face_thr = 0.0
         if init_latents is not None:   # (b f) c h w -> b c f h w  (:657-658)
             bf, c4, hh, ww = init_latents.shape

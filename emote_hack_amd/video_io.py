@@ -9,6 +9,12 @@
   write_avi         a classic RIFF `AVI ` file: hdrl (avih, a vids / MJPG stream, optionally an auds / PCM stream), movi with the 00dc and
                     01wb chunks interleaved per frame, idx1.  Below 2^31 bytes (OpenDML is not written)
   read_avi          the reverse, for files write_avi made
+  parse_jpeg        one baseline 4:2:0 file -> its size, tables and scan with the stuffed 0x00 bytes taken out (the reverse of jpeg_header
+                    and finish_scan); anything else a JPEG file may be is refused by name
+  decode_mjpeg      JPEG files -> packed uint8 frames on the device: per set of tables ONE host-to-device copy of the scans, then
+                    emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb (csrc/video_in.hip) and one read of the frames' status -
+                    the bytes libjpeg's default decoder gives
+  read_video        read_avi + decode_mjpeg: what `VideoReader(path).read()` is to magicanimate/pipelines/animation.py:174-185
   save_videos_grid, images2video, video2images      the reference surface, `.avi` only (mp4 and gif need encoders that are not here)
 
 File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
@@ -173,6 +179,217 @@ def encode_mjpeg(frames_u8: torch.Tensor, quality: int = 90) -> list:
     host = out.cpu().numpy()
     head = jpeg_header(int(frames_u8.shape[-3]), int(frames_u8.shape[-2]), int(quality))
     return [head + finish_scan(host[s:], int(b)) for s, b in zip(starts, bits)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------- JPEG parsing
+JPEG_MIN_WIDTH = 5      # libjpeg replicates chroma samples instead of filtering when the chroma plane is at most 2 wide; that is not built
+
+
+def huffman_decode_table(bits, huffval) -> np.ndarray:
+    """Annex C and F.2.2.3 (figure F.15): BITS / HUFFVAL -> int32 (ops.JPEG_DECODE_TABLE_INTS), the layout emo_jpeg_decode_bits reads:
+    MINCODE[16] | MAXCODE[16] | VALPTR[16] | 16 unused | HUFFVAL[256]; entry l - 1 belongs to code length l, MAXCODE is -1 where no
+    code has that length"""
+    bits, huffval = tuple(int(b) for b in bits), bytes(huffval)
+    if len(bits) != 16 or sum(bits) != len(huffval) or len(huffval) > 256:
+        raise ValueError(f"a Huffman table has 16 BITS entries that count its at most 256 HUFFVAL entries, got {len(bits)} counting {sum(bits)} "
+                         f"for {len(huffval)}")
+    t = np.zeros(ops.JPEG_DECODE_TABLE_INTS, np.int32)
+    t[16:32] = -1
+    code, k = 0, 0
+    for l in range(16):
+        if bits[l]:
+            if code + bits[l] > 1 << (l + 1):
+                raise ValueError(f"a Huffman table with {bits[l]} codes of length {l + 1} behind {code} taken is over-subscribed")
+            t[l], t[16 + l], t[32 + l] = code, code + bits[l] - 1, k
+            code, k = code + bits[l], k + bits[l]
+        code <<= 1
+    t[64:64 + len(huffval)] = np.frombuffer(huffval, np.uint8)
+    return t
+
+
+@dataclasses.dataclass(frozen=True)
+class ParsedJpeg:
+    height: int
+    width: int
+    quant: np.ndarray          # uint16 (2, 64): luminance, chrominance, NATURAL order
+    specs: tuple               # four (BITS tuple, HUFFVAL bytes): DC luminance, AC luminance, DC chrominance, AC chrominance
+    scan: np.ndarray           # uint8: the entropy-coded segment without the 0x00 behind every 0xFF, up to the marker that ends it
+
+    def table_key(self):
+        return self.quant.tobytes(), self.specs
+
+
+_SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
+              0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic-coded sequential (SOF9)",
+              0xCA: "arithmetic-coded progressive (SOF10)", 0xCB: "arithmetic-coded lossless (SOF11)", 0xCD: "arithmetic-coded differential (SOF13)",
+              0xCE: "arithmetic-coded differential progressive (SOF14)", 0xCF: "arithmetic-coded differential lossless (SOF15)"}
+_ONLY = "decode_mjpeg reads 8-bit baseline (SOF0) files with three components at 2x2 / 1x1 / 1x1 in one interleaved scan"
+
+
+def parse_jpeg(data) -> ParsedJpeg:
+    """One JPEG file -> ParsedJpeg, walking its marker segments (T.81 Annex B).  A file without DHT segments gets the tables of Annex
+    K.3 - K.6 (the Motion-JPEG convention in AVI files).  ValueError, saying what was found, for everything but 8-bit baseline 4:2:0 in
+    one interleaved scan without restart intervals: progressive, extended or arithmetic-coded files, other sampling factors, grey
+    images, a restart interval, 16-bit quantisers, Cb and Cr on different tables, frames narrower than JPEG_MIN_WIDTH."""
+    data = bytes(data)
+    if len(data) < 4 or data[:2] != b"\xFF\xD8":
+        raise ValueError("parse_jpeg: no SOI marker at the start: not a JPEG file")
+    pos, quant, huff, frame = 2, {}, {}, None
+    while True:
+        while pos < len(data) and data[pos] == 0xFF and pos + 1 < len(data) and data[pos + 1] == 0xFF:
+            pos += 1                                                             # fill bytes (B.1.1.2)
+        if pos + 4 > len(data) or data[pos] != 0xFF:
+            raise ValueError(f"parse_jpeg: no marker at byte {pos}: the file ends or is damaged before its scan")
+        marker, size = data[pos + 1], struct.unpack_from(">H", data, pos + 2)[0]
+        body = data[pos + 4:pos + 2 + size]
+        if size < 2 or pos + 2 + size > len(data):
+            raise ValueError(f"parse_jpeg: segment FF{marker:02X} at byte {pos} runs past the end of the file")
+        pos += 2 + size
+        if marker == 0xDB:                                                       # DQT (B.2.4.1)
+            while body:
+                pq, tq = body[0] >> 4, body[0] & 15
+                if pq != 0:
+                    raise ValueError(f"parse_jpeg: quantisation table {tq} has 16-bit entries; {_ONLY}")
+                if len(body) < 65:
+                    raise ValueError("parse_jpeg: a DQT segment ends inside a table")
+                nat = np.zeros(64, np.uint16)
+                nat[ZIGZAG] = np.frombuffer(body[1:65], np.uint8)
+                quant[tq], body = nat, body[65:]
+        elif marker == 0xC4:                                                     # DHT (B.2.4.2)
+            while body:
+                if len(body) < 17 or len(body) < 17 + sum(body[1:17]):
+                    raise ValueError("parse_jpeg: a DHT segment ends inside a table")
+                bits = tuple(body[1:17])
+                huff[(body[0] >> 4, body[0] & 15)], body = (bits, bytes(body[17:17 + sum(bits)])), body[17 + sum(bits):]
+        elif marker == 0xC0:                                                     # SOF0 (B.2.2)
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError("parse_jpeg: a malformed SOF0 segment")
+            precision, height, width, nf = struct.unpack_from(">BHHB", body, 0)
+            comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nf)]
+            if precision != 8:
+                raise ValueError(f"parse_jpeg: {precision}-bit samples; {_ONLY}")
+            if nf != 3:
+                raise ValueError(f"parse_jpeg: {nf} component{'s' if nf != 1 else ' (a grey image)'}; {_ONLY}")
+            factors = [(h, v) for _, h, v, _ in comps]
+            if factors != [(2, 2), (1, 1), (1, 1)]:
+                raise ValueError("parse_jpeg: sampling factors " + " / ".join(f"{h}x{v}" for h, v in factors) + f"; {_ONLY}")
+            if height == 0:
+                raise ValueError(f"parse_jpeg: the frame header leaves the height to a DNL segment; {_ONLY}")
+            if width < JPEG_MIN_WIDTH:
+                raise ValueError(f"parse_jpeg: a frame {width} pixels wide: below {JPEG_MIN_WIDTH} libjpeg replicates chroma samples instead of "
+                                 "filtering them, which is not built")
+            frame = (height, width, comps)
+        elif marker in _SOF_NAMES:
+            raise ValueError(f"parse_jpeg: a {_SOF_NAMES[marker]} file; {_ONLY}")
+        elif marker == 0xDD:                                                     # DRI (B.2.4.4)
+            if len(body) != 2:
+                raise ValueError("parse_jpeg: a malformed DRI segment")
+            if struct.unpack(">H", body)[0]:
+                raise ValueError(f"parse_jpeg: a restart interval of {struct.unpack('>H', body)[0]} MCUs; restart markers are not built; {_ONLY}")
+        elif marker == 0xDA:                                                     # SOS (B.2.3): the scan follows
+            break
+        elif marker in (0xD8, 0xD9) or 0xD0 <= marker <= 0xD7 or marker == 0x01:
+            raise ValueError(f"parse_jpeg: marker FF{marker:02X} at byte {pos - 2 - size} before any scan")
+        # APPn, COM and the rest: skipped
+    if frame is None:
+        raise ValueError("parse_jpeg: a scan without a frame header in front of it")
+    height, width, comps = frame
+    if len(body) != 10 or body[0] != 3:
+        raise ValueError(f"parse_jpeg: a scan of {body[0] if body else 0} of the frame's 3 components (not interleaved); {_ONLY}")
+    sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(3)]
+    if [c for c, _, _ in sel] != [c[0] for c in comps]:
+        raise ValueError(f"parse_jpeg: the scan lists components {[c for c, _, _ in sel]}, the frame {[c[0] for c in comps]}")
+    if tuple(body[7:10]) != (0, 63, 0):
+        raise ValueError(f"parse_jpeg: a scan of coefficients {body[7]} .. {body[8]} with approximation {body[9]:#04x} (progressive); {_ONLY}")
+    if sel[1][1:] != sel[2][1:]:
+        raise ValueError(f"parse_jpeg: Cb decodes with Huffman tables {sel[1][1:]} and Cr with {sel[2][1:]}; one chrominance pair is built")
+    for tq in (comps[0][3], comps[1][3], comps[2][3]):
+        if tq not in quant:
+            raise ValueError(f"parse_jpeg: quantisation table {tq} is used and never defined")
+    if not np.array_equal(quant[comps[1][3]], quant[comps[2][3]]):
+        raise ValueError("parse_jpeg: Cb and Cr use different quantisation tables; one chrominance table is built")
+    if not huff:
+        huff = dict(zip(HUFFMAN_IDS, HUFFMAN_SPECS))                             # no DHT at all: the Motion-JPEG convention
+    specs = []
+    for key in ((0, sel[0][1]), (1, sel[0][2]), (0, sel[1][1]), (1, sel[1][2])):
+        if key not in huff:
+            raise ValueError(f"parse_jpeg: Huffman table (class {key[0]}, destination {key[1]}) is used and never defined")
+        specs.append(huff[key])
+    a = np.frombuffer(data, np.uint8, offset=pos)
+    ends = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0x00)) if len(a) > 1 else np.zeros(0, np.int64)
+    if len(ends):                                                                # the first marker behind the scan: EOI in a whole file
+        if 0xD0 <= a[ends[0] + 1] <= 0xD7:
+            raise ValueError(f"parse_jpeg: a restart marker inside the scan; restart markers are not built; {_ONLY}")
+        a = a[:ends[0]]
+    scan = np.delete(a, np.flatnonzero((a[:-1] == 0xFF) & (a[1:] == 0x00)) + 1) if len(a) > 1 else a.copy()
+    q = np.stack([quant[comps[0][3]], quant[comps[1][3]]])
+    q.setflags(write=False)
+    scan.setflags(write=False)
+    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan)
+
+
+@functools.lru_cache(maxsize=16)
+def _decode_header(quant_bytes: bytes, specs: tuple) -> np.ndarray:
+    """what a group of frames shares, as bytes: the four decoding tables (int32 (4, 320)) and the quantisers (uint16 (2, 64))"""
+    tables = np.stack([huffman_decode_table(*spec) for spec in specs])
+    return np.concatenate([tables.view(np.uint8).reshape(-1), np.frombuffer(quant_bytes, np.uint8)])
+
+
+def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
+    """Baseline 4:2:0 JPEG files of one size (bytes each; what encode_mjpeg, Pillow at subsampling=2 or a Motion-JPEG AVI hold) -> packed
+    uint8 RGB frames (n, H, W, 3) on the device, byte for byte what libjpeg's default decoder (Pillow's) gives.  The host only parses
+    markers and takes the stuffed bytes out; frames that share their tables go up in ONE copy (tables, quantisers, offsets, scans) and
+    through one set of three launches (emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb), followed by one read of their status.
+    ValueError naming the frame for a file parse_jpeg refuses, a frame of another size, or a scan that does not decode.  There is no
+    host decoder behind this."""
+    jpegs = list(jpegs)
+    if not jpegs:
+        raise ValueError("decode_mjpeg: no frames")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ops._lib.EmoHipError(f"decode_mjpeg decodes on the HIP device, got device {device} (there is no host decoder here; "
+                                   "video2images keeps Pillow's)")
+    parsed = []
+    for i, j in enumerate(jpegs):
+        try:
+            parsed.append(parse_jpeg(j))
+        except ValueError as e:
+            raise ValueError(f"decode_mjpeg: frame {i}: {e}") from None
+    H, W = parsed[0].height, parsed[0].width
+    for i, p in enumerate(parsed):
+        if (p.height, p.width) != (H, W):
+            raise ValueError(f"decode_mjpeg: frame {i} is {p.height} x {p.width}, frame 0 is {H} x {W}: the frames of a clip share one size")
+    groups = {}
+    for i, p in enumerate(parsed):
+        groups.setdefault(p.table_key(), []).append(i)
+    n_mcu = ops.jpeg_mcus(H, W)
+    out = torch.empty(len(parsed), H, W, 3, device=device, dtype=torch.uint8)
+    for key, members in groups.items():
+        head = _decode_header(*key)
+        n = len(members)
+        sizes = np.array([len(parsed[i].scan) for i in members], np.int64)
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        pad = -int(offsets[-1]) % 4 or (4 if offsets[-1] == 0 else 0)
+        host = np.concatenate([head, offsets.view(np.uint8)] + [parsed[i].scan for i in members] + [np.zeros(pad, np.uint8)])
+        dev = torch.from_numpy(host).to(device)                                  # the one copy
+        t_end, q_end, o_end = 16 * ops.JPEG_DECODE_TABLE_INTS, 16 * ops.JPEG_DECODE_TABLE_INTS + 256, len(head) + 8 * (n + 1)
+        tables = dev[:t_end].view(torch.int32).view(4, ops.JPEG_DECODE_TABLE_INTS)
+        quant = dev[t_end:q_end].view(torch.uint16).view(2, 64)
+        coefs, status = ops.jpeg_decode_bits(dev[o_end:], dev[q_end:o_end].view(torch.int64), tables, n_mcu)
+        y, c = ops.jpeg_idct(coefs, quant, H, W)
+        whole = n == len(parsed)
+        rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
+        st = status.cpu().numpy()                                                # the one read
+        if st.any():
+            bad = int(np.flatnonzero(st)[0])
+            raise ValueError(f"decode_mjpeg: frame {members[bad]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')} "
+                             f"(emo_jpeg_decode_bits status {int(st[bad])})")
+        if not whole:
+            if members == list(range(members[0], members[0] + n)):
+                out[members[0]:members[0] + n] = rgb
+            else:
+                out[torch.tensor(members, device=device)] = rgb
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------- AVI container
@@ -412,3 +629,14 @@ def video2images(path, step=4, length=16, start=0):
     """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays"""
     jpegs, _, _ = read_avi(path)
     return [decode_jpeg(j) for j in jpegs[start::step][:length]]
+
+
+def read_video(path, step=1, length=None, start=0):
+    """An `.avi` file this module wrote -> (uint8 frames (n, H, W, 3) ON THE DEVICE, fps Fraction, audio as read_avi returns it): the
+    frames [start::step][:length], decoded by decode_mjpeg.  What `VideoReader(path).read()` gives magicanimate/pipelines/animation.py:174-185,
+    without the frames passing through a host decoder."""
+    jpegs, fps, audio = read_avi(path)
+    picked = jpegs[start::step][:length]
+    if not picked:
+        raise ValueError(f"read_video: {os.fspath(path)!r} holds {len(jpegs)} frames; [{start}::{step}][:{length}] selects none")
+    return decode_mjpeg(picked), fps, audio

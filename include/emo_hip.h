@@ -494,6 +494,49 @@ int emo_jpeg_count_bits(const int16_t* coefs, int32_t* counts, int n, int n_mcu,
 int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
                        const uint32_t* huff, void* stream);
 
+/* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
+ * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
+ * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, three components at 2x2 / 1x1 / 1x1 in one interleaved
+ * scan; the host half (marker segments of Annex B, the removal of the stuffed 0x00 bytes, the decoding tables of Annex C / F.2.2.3,
+ * the AVI container) is emote_hack_amd/video_io.py.  The three kernels give the bytes libjpeg's default decoder gives (jidctint.c
+ * islow, jdsample.c h2v2 fancy up-sampling, jdcolor.c); they live in csrc/video_in.hip.
+ * emo_jpeg_decode_bits (T.81 F.2.2 Huffman decoding procedures: F.2.2.1 DC, F.2.2.2 AC, F.2.2.3 DECODE, F.2.2.4 RECEIVE, figure F.12
+ *   EXTEND): the UNSTUFFED scans of n frames lie in `scan` (scan_bytes bytes, a multiple of 4, 4-byte aligned; bytes behind the last
+ *   frame are never used), frame i in bytes offsets[i] .. offsets[i + 1] (int64 [n + 1]).  Output: coefs int16 [n][n_mcu][6][64] in the
+ *   layout emo_jpeg_blocks writes (16x16 MCUs in raster order, blocks Y00 Y01 Y10 Y11 Cb Cr, zig-zag order, the DC term UNDIFFERENCED:
+ *   the differences are summed per component from 0 at every frame's first MCU), 16-byte aligned, and status int32 [n]:
+ *     EMO_JPEG_OK        the frame decoded: n_mcu * 6 blocks inside its bytes (what is left of them - the 1-bits that fill the last
+ *                        byte, anything else - is not looked at)
+ *     EMO_JPEG_BAD_CODE  the next 16 bits start with no code of the table, or with the code of a symbol a baseline scan of 8-bit samples
+ *                        cannot hold: a DC category above 11, an AC category above 10, a run with category 0 other than EOB / ZRL
+ *     EMO_JPEG_PAST_END  a code or its magnitude bits reach past the frame's last byte (a cut file, an empty frame; offsets that run
+ *                        backwards or leave the buffer are taken as an empty frame)
+ *     EMO_JPEG_BAD_RUN   a zero run carries the position past coefficient 63
+ *   A frame with an error stops there: its blocks up to the faulty one are written, the rest of ITS coefficients are zeroed, other
+ *   frames are not touched.  One workgroup per frame; every loop is counted by n_mcu * 6 blocks and 64 coefficients, every read of the
+ *   stream is masked to the frame's own bytes.
+ *   tables: device int32 [4][EMO_JPEG_DECODE_TABLE_INTS] in the order DC luma, AC luma, DC chroma, AC chroma (Cb and Cr share theirs),
+ *   each table = MINCODE[16] | MAXCODE[16] | VALPTR[16] | 16 unused | HUFFVAL[256] of T.81 F.2.2.3 / figure F.15, entry l - 1 for code
+ *   length l, MAXCODE -1 where no code has that length.  (The kernel expands them into an 8-bit look-up in LDS.)
+ * emo_jpeg_idct (T.81 A.3.4 dequantisation, A.3.3 IDCT in libjpeg's integer form jidctint.c jpeg_idct_islow): coefficient * quantiser,
+ *   an 8-point pass over columns descaled by 11 bits, the same pass over rows descaled by 18, sample = clamp(value + 128, 0, 255).
+ *   quant: device uint16 [2][64], luma then chroma, NATURAL order.  Output: y_plane uint8 [n][mcu_rows * 16][mcu_cols * 16] and c_planes
+ *   uint8 [n][2][mcu_rows * 8][mcu_cols * 8] (Cb, Cr), mcu_rows = ceil(H / 16), mcu_cols = ceil(W / 16), both 8-byte aligned.  32-bit
+ *   sums that coefficients of no 8-bit image reach wrap.
+ * emo_jpeg_upsample_rgb (jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert): the planes above -> packed uint8 RGB
+ *   [n][H][W][3], 4-byte aligned.  Chroma: the plane of ceil(H / 2) x ceil(W / 2) real samples (the padded samples behind it are not
+ *   read), s = 3 * c(r) + c(r -+ 1) down the rows for output rows 2 r / 2 r + 1, o(2 x) = (3 s(x) + s(x - 1) + 8) >> 4 and o(2 x + 1) =
+ *   (3 s(x) + s(x + 1) + 7) >> 4 along them, neighbours clamped to the plane.  Colour, cb and cr less 128: R = y + ((91881 cr + 32768)
+ *   >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  (libjpeg
+ *   replicates samples instead when the chroma plane is at most 2 wide, W <= 4: the host refuses such frames.)
+ * H, W in 1 .. 65535 as in emo_jpeg_blocks. */
+#define EMO_JPEG_DECODE_TABLE_INTS 320
+enum { EMO_JPEG_OK = 0, EMO_JPEG_BAD_CODE = 1, EMO_JPEG_PAST_END = 2, EMO_JPEG_BAD_RUN = 3 };
+int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
+                         int32_t* status, int n, int n_mcu, void* stream);
+int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream);
+int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream);
+
 /* ---- CLIP vision encoder front (transformers CLIPVisionModelWithProjection: the `image_encoder` EMOAnimationPipeline.py:867 loads and
  * :909-917 hands to the pipeline; its image_embeds are the `clip_condition_embeddings` of models/videonet.py:255) -----------------------
  * emo_image_preprocess: transformers CLIPImageProcessor (resize to the shortest edge, centre crop, rescale, normalise) in one launch.
