@@ -895,6 +895,38 @@ def jpeg_upsample_rgb(y: torch.Tensor, c: torch.Tensor, H: int, W: int, out=None
     return rgb
 
 
+def image_resize(frames: torch.Tensor, h: int, w: int, xtaps=None, ytaps=None, out=None) -> torch.Tensor:
+    """packed uint8 RGB frames (n, H, W, 3) -> (n, h, w, 3): Pillow's resize of 8-bit pixels, a horizontal integer pass to 8-bit pixels and
+    a vertical one over those (emo_image_resize; animation.py:174-185).  xtaps / ytaps: (bounds int32 (w | h, 2), coef int32 (w | h, k))
+    on the device, video_io.resize_taps of the axis; the pair of an axis that keeps its size is not read and may be None.  The
+    intermediate image is allocated here."""
+    _need_cuda(frames, out)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    n, H, W, _ = frames.shape
+    h, w = int(h), int(w)
+    tabs = []
+    for taps, size_in, size_out, axis in ((xtaps, W, w, "x"), (ytaps, H, h, "y")):
+        if size_in == size_out:
+            tabs += [None, None, 0]
+            continue
+        if taps is None:
+            raise ValueError(f"image_resize: the {axis} axis goes from {size_in} to {size_out} and has no tap tables")
+        bounds, coef = taps
+        _need_cuda(bounds, coef)
+        assert bounds.dtype == torch.int32 and tuple(bounds.shape) == (size_out, 2) and bounds.is_contiguous(), (axis, bounds.dtype, bounds.shape)
+        assert coef.dtype == torch.int32 and coef.dim() == 2 and coef.shape[0] == size_out and coef.is_contiguous(), (axis, coef.dtype, coef.shape)
+        tabs += [bounds, coef, coef.shape[1]]
+    lib = _lib.load()
+    out = _jpeg_out(out, (n, h, w, 3), torch.uint8, frames.device, "frames")
+    ws_bytes = lib.emo_image_resize_workspace_bytes(n, H, W, h, w)
+    ws = torch.empty(ws_bytes, device=frames.device, dtype=torch.uint8) if ws_bytes else None
+    _launch("image_resize", 0.0, float(frames.numel() + 2 * ws_bytes + out.numel()),
+            lambda: check(lib.emo_image_resize(_ptr(frames), _ptr(out), n, H, W, h, w, _ptr(tabs[0]), _ptr(tabs[1]), tabs[2], _ptr(tabs[3]),
+                                               _ptr(tabs[4]), tabs[5], _ptr(ws), ws_bytes, _stream()), "emo_image_resize"),
+            tag=f"{n}x{H}x{W}->{h}x{w}")
+    return out
+
+
 INTERP_METHODS = {"linear": 0, "slerp": 1}
 
 

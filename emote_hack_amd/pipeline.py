@@ -1010,23 +1010,29 @@ class EMOAnimationPipeline:
         return table.to(frames_u8.device)[frames_u8.long()]
 
     @staticmethod
-    def _clip_frames(path, n_frames, width, height, who):
+    def _clip_frames(path, n_frames, width, height, who, resample=None):
         """the first n_frames frames of a Motion-JPEG `.avi` file as uint8 (n_frames, height, width, 3) on the device (video_io.read_video).
-        The reference resizes what it reads through PIL (animation.py:174-185); no resize is built here, so another size is refused."""
+        The reference resizes what it reads through PIL (animation.py:174-185): with resample= (a filter of video_io.RESIZE_FILTERS; PIL's
+        own default is "bicubic") frames of another size are resized on the device as PIL would (video_io.resize_frames); with None
+        another size is refused."""
         from . import video_io
         frames, _, _ = video_io.read_video(path, length=n_frames)
         if frames.shape[0] < n_frames:
             raise ValueError(f"{who}={os.fspath(path)!r} holds {frames.shape[0]} frames, {n_frames} are needed: pass a clip at least as long as "
                              "video_length")
         if tuple(frames.shape[1:3]) != (height, width):
-            raise ValueError(f"{who}={os.fspath(path)!r} holds frames of {frames.shape[1]} x {frames.shape[2]} (height x width), the call runs at "
-                             f"{height} x {width}: frames are not resized here, pass frames at size")
+            if resample is None:
+                raise ValueError(f"{who}={os.fspath(path)!r} holds frames of {frames.shape[1]} x {frames.shape[2]} (height x width), the call runs at "
+                                 f"{height} x {width}: frames are not resized here, pass frames at size (or input_resample=\"bicubic\" to have "
+                                 "them resized on the device as PIL does)")
+            frames = video_io.resize_frames(frames, (width, height), resample)
         return frames
 
-    def _source_image_latents(self, source_image, width, height):
+    def _source_image_latents(self, source_image, width, height, resample=None):
         """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is.  A Motion-JPEG `.avi`
-        path gives its first frame (animation.py:182-185), decoded on the device at (height, width) and encoded from there."""
-        rgb = self._source_image_rgb(source_image, width, height)
+        path gives its first frame (animation.py:182-185), decoded on the device at (height, width) - resized there under resample=, as
+        _clip_frames does - and encoded from there."""
+        rgb = self._source_image_rgb(source_image, width, height, resample)
         if torch.is_tensor(rgb):          # the first frame of a clip, on the device
             if self.vae is None:
                 raise ValueError("images2latents needs a VAE (emote_hack_amd.vae.AutoencoderKL)")
@@ -1034,11 +1040,11 @@ class EMOAnimationPipeline:
         return self.images2latents(rgb[None], None)
 
     @staticmethod
-    def _source_image_rgb(source_image, width, height):
+    def _source_image_rgb(source_image, width, height, resample=None):
         import numpy as np
         if isinstance(source_image, (str, os.PathLike)) and os.fspath(source_image).lower().endswith(".avi"):
             # animation.py:182-185 takes the source image from a video's first frame: decoded on the device, and it stays there
-            frame = EMOAnimationPipeline._clip_frames(source_image, 1, width, height, "source_image")[0]
+            frame = EMOAnimationPipeline._clip_frames(source_image, 1, width, height, "source_image", resample)[0]
             if frame.shape[0] % 8 or frame.shape[1] % 8:
                 raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
             return frame
@@ -1257,7 +1263,16 @@ class EMOAnimationPipeline:
         JPEG-encoded on the device and written as Motion-JPEG in an AVI container (emote_hack_amd.video_io) playing at fps *
         interpolation_factor - fps= is required.  audio= given as a `.wav` path or a (samples, rate) pair goes into the file as 16-bit PCM,
         with its own channels at its own rate, from audio_start for the clip's duration (less where the audio ends first).  The return
-        value is what it is without save_path."""
+        value is what it is without save_path.
+        input_resample="bicubic" | "box" | "bilinear" | "hamming" | "lanczos" lets clips come at any size: a controlnet_condition= clip
+        path or a source_image= `.avi` path whose frames are not height x width is resized on the device, byte for byte as the
+        `Image.resize` of animation.py:174-185 would ("bicubic" is that call's filter; emote_hack_amd.video_io.resize_frames).  None, the
+        default, refuses such a clip as before.  Host arrays and image files are not touched by it, and a clip shorter than
+        video_length is refused either way."""
+        input_resample = kwargs.get("input_resample")
+        if input_resample is not None:
+            from . import video_io
+            input_resample = video_io._resize_filter(input_resample)
         interp_k, interp = kwargs.get("interpolation_factor", 1), kwargs.get("interpolation")
         if isinstance(interp_k, bool) or not isinstance(interp_k, numbers.Integral) or interp_k < 1:
             raise ValueError(f"interpolation_factor= takes an int >= 1 (1: no interpolated frames), got {interp_k!r}")
@@ -1296,7 +1311,7 @@ class EMOAnimationPipeline:
             from_clip = isinstance(controlnet_condition, (str, os.PathLike))
             if from_clip:
                 # animation.py:174-180 reads the control sequence from a video file: the first video_length frames, decoded on the device
-                controlnet_condition = self._clip_frames(controlnet_condition, video_length, width, height, "controlnet_condition")
+                controlnet_condition = self._clip_frames(controlnet_condition, video_length, width, height, "controlnet_condition", input_resample)
             cn_cond = controlnet_condition if torch.is_tensor(controlnet_condition) else torch.as_tensor(controlnet_condition)
             if from_clip:
                 cn_cond = self._device_u8_scaled(cn_cond, 255.0).permute(0, 3, 1, 2)
@@ -1330,7 +1345,7 @@ class EMOAnimationPipeline:
         if ref_lat is None:
             if self.vae is None or source_image is None:
                 raise ValueError("pass ref_image_latents=(1,4,h,w) (no VAE in this build)")
-            ref_lat = self._source_image_latents(source_image, width, height)   # :686-689 -> images2latents (:402-414)
+            ref_lat = self._source_image_latents(source_image, width, height, input_resample)   # :686-689 -> images2latents (:402-414)
         if audio is not None and kwargs.get("audio_features") is None:
             # :592-593 `audio_features = feature_extractor.extract_features_from_mp4(audio, m=2, n=2)` (a module-level extractor
             # there; the file read, resampling and channel mean of Net.py:627-640 behind it): feature_extractor= is an
@@ -1407,7 +1422,7 @@ class EMOAnimationPipeline:
                 if source_image is None:
                     raise ValueError("face_mask=\"locate\" looks for the face in source_image=: pass it (a path or an (H, W, 3) uint8 array), or "
                                      "pass the mask itself")
-                rgb = self._source_image_rgb(source_image, width, height)
+                rgb = self._source_image_rgb(source_image, width, height, input_resample)
                 if torch.is_tensor(rgb):      # the first frame of a clip, on the device
                     face_mask = loc(self._device_u8_scaled(rgb, 255.0).permute(2, 0, 1)[None])[0, 0]
                 else:

@@ -15,10 +15,16 @@
                     emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb (csrc/video_in.hip) and one read of the frames' status -
                     the bytes libjpeg's default decoder gives
   read_video        read_avi + decode_mjpeg: what `VideoReader(path).read()` is to magicanimate/pipelines/animation.py:174-185
+  resize_taps       the per-axis coefficient table of Pillow's `Image.resize` for 8-bit images (Resample.c), in 22-bit fixed point
+  resize_frames     `Image.fromarray(f).resize((width, height), filter)` of device frames, byte for byte: emo_image_resize
+                    (csrc/image_resize.hip) on the tables above; read_video(size=) applies it to what it decodes
+  load_control_clip, comparison_videos      animation.py:174-194 (read, resize, cut, pad to whole context windows) and :217-228 (the
+                    source / control / sample clips cut back to the original length), on the device
   save_videos_grid, images2video, video2images      the reference surface, `.avi` only (mp4 and gif need encoders that are not here)
 
 File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
-assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line)."""
+assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line; the resize tables hold
+coefficients, the pixels meet them in the kernel)."""
 from __future__ import annotations
 
 import dataclasses
@@ -392,6 +398,143 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------------- resizing
+RESIZE_PRECISION_BITS = 22      # Resample.c PRECISION_BITS = 32 - 8 - 2: the fixed point of the coefficients of 8-bit images
+
+
+def _box(x):
+    return 1.0 if -0.5 < x <= 0.5 else 0.0
+
+
+def _bilinear(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+# Resample.c writes the two constants of its Hamming window as single-precision literals (0.54f, 0.46f) inside a double expression: the
+# doubles 0.54 and 0.46 give coefficients one unit off in a few rows (seen at 1080 -> 512)
+_HAMMING_A, _HAMMING_B = float(np.float32(0.54)), float(np.float32(0.46))
+
+
+def _hamming(x):
+    import math
+    x = abs(x)
+    if x == 0.0:
+        return 1.0
+    if x >= 1.0:
+        return 0.0
+    x *= math.pi
+    return math.sin(x) / x * (_HAMMING_A + _HAMMING_B * math.cos(x))
+
+
+def _bicubic(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _sinc(x):
+    import math
+    if x == 0.0:
+        return 1.0
+    x *= math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x):
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+RESIZE_FILTERS = {"box": (_box, 0.5), "bilinear": (_bilinear, 1.0), "hamming": (_hamming, 1.0), "bicubic": (_bicubic, 2.0),
+                  "lanczos": (_lanczos, 3.0)}                      # name -> (filter, support), Resample.c
+
+
+def _resize_filter(resample):
+    if not isinstance(resample, str) or resample.lower() not in RESIZE_FILTERS:
+        what = "nearest-neighbour resizing is not built: " if isinstance(resample, str) and resample.lower() == "nearest" else ""
+        raise ValueError(f"{what}resample= takes one of {', '.join(map(repr, RESIZE_FILTERS))} (\"bicubic\" is what Image.resize does when "
+                         f"it is given no filter), got {resample!r}")
+    return resample.lower()
+
+
+@functools.lru_cache(maxsize=64)
+def _resize_taps(in_size: int, out_size: int, name: str):
+    filt, filter_support = RESIZE_FILTERS[name]
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = filter_support * filterscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    bounds, coef = np.zeros((out_size, 2), np.int32), np.zeros((out_size, ksize), np.int32)
+    one = float(1 << RESIZE_PRECISION_BITS)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [filt((x + xmin - center + 0.5) / filterscale) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        bounds[xx] = xmin, xmax
+        coef[xx, :xmax] = [int(-0.5 + v * one) if v < 0 else int(0.5 + v * one) for v in w]
+    bounds.setflags(write=False)
+    coef.setflags(write=False)
+    return bounds, coef
+
+
+def resize_taps(in_size: int, out_size: int, filter: str = "bicubic"):
+    """The table of one axis of `Image.resize` for 8-bit images, as Pillow's Resample.c builds it (precompute_coeffs,
+    normalize_coeffs_8bpc), in Python doubles: (bounds int32 (out_size, 2) = (first input index, tap count), coef int32 (out_size, ksize),
+    22-bit fixed point, zero behind the taps).  With scale = in / out and filterscale = max(scale, 1): support = the filter's support *
+    filterscale, ksize = ceil(support) * 2 + 1; output xx is centred at (xx + 0.5) * scale, takes the inputs xmin = max(int(center -
+    support + 0.5), 0) up to min(int(center + support + 0.5), in) with weights filter((x + xmin - center + 0.5) / filterscale) divided by
+    their sum, each rounded half away from zero to 1 / 2^22.  Cached per (in_size, out_size, filter); the arrays are read-only.
+    filter: "box", "bilinear", "hamming", "bicubic" (a = -0.5) or "lanczos"; "nearest" is not built."""
+    name = _resize_filter(filter)
+    if any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 1 for s in (in_size, out_size)):
+        raise ValueError(f"resize_taps: sizes are positive ints, got {in_size!r} -> {out_size!r}")
+    return _resize_taps(int(in_size), int(out_size), name)
+
+
+@functools.lru_cache(maxsize=16)
+def _device_resize_taps(in_size: int, out_size: int, name: str, device: str):
+    return tuple(torch.from_numpy(t.copy()).to(device) for t in _resize_taps(in_size, out_size, name))
+
+
+def _resize_size(size, who):
+    if (not isinstance(size, (tuple, list)) or len(size) != 2
+            or any(isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 1 for s in size)):
+        raise ValueError(f"{who}: size=(width, height), two positive ints as Image.resize takes them, got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def resize_frames(frames_u8, size, resample="bicubic", box=None, reducing_gap=None) -> torch.Tensor:
+    """`Image.fromarray(f).resize(size, resample)` of every frame, on the device and byte for byte (ops.image_resize): uint8 RGB frames
+    (n, H, W, 3) or one frame (H, W, 3), a device tensor or a host array (which is uploaded) -> the same rank at size=(width, height),
+    on the device.  resample: a filter of RESIZE_FILTERS; Image.resize without a filter is "bicubic".  Image.resize's box= and
+    reducing_gap= are not built."""
+    if box is not None or reducing_gap is not None:
+        raise ValueError("resize_frames: box= (resizing a region of the frame) and reducing_gap= (a draft reduction in front of the resize) "
+                         "are not built: crop the frames first, and expect the one-step resize")
+    name = _resize_filter(resample)
+    width, height = _resize_size(size, "resize_frames")
+    x = frames_u8 if torch.is_tensor(frames_u8) else torch.from_numpy(np.ascontiguousarray(frames_u8))
+    if x.dtype != torch.uint8 or x.dim() not in (3, 4) or x.shape[-1] != 3 or 0 in x.shape:
+        raise ValueError(f"resize_frames takes packed uint8 RGB frames, (n, H, W, 3) or (H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    if not x.is_cuda:
+        x = x.to("cuda")
+    single = x.dim() == 3
+    x = (x[None] if single else x).contiguous()
+    H, W, dev = int(x.shape[1]), int(x.shape[2]), str(x.device)
+    out = ops.image_resize(x, height, width, None if W == width else _device_resize_taps(W, width, name, dev),
+                           None if H == height else _device_resize_taps(H, height, name, dev))
+    return out[0] if single else out
+
+
 # ---------------------------------------------------------------------------------------------------------------------- AVI container
 AVI_MAX_BYTES = 2 ** 31 - 1
 AVIF_HASINDEX, AVIF_ISINTERLEAVED, AVIIF_KEYFRAME = 0x10, 0x100, 0x10
@@ -631,12 +774,67 @@ def video2images(path, step=4, length=16, start=0):
     return [decode_jpeg(j) for j in jpegs[start::step][:length]]
 
 
-def read_video(path, step=1, length=None, start=0):
+def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"):
     """An `.avi` file this module wrote -> (uint8 frames (n, H, W, 3) ON THE DEVICE, fps Fraction, audio as read_avi returns it): the
     frames [start::step][:length], decoded by decode_mjpeg.  What `VideoReader(path).read()` gives magicanimate/pipelines/animation.py:174-185,
-    without the frames passing through a host decoder."""
+    without the frames passing through a host decoder.  size=(width, height) resizes the decoded frames as animation.py:177 does
+    (resize_frames with `resample`), still on the device; None returns them as stored."""
+    if size is not None:
+        size, resample = _resize_size(size, "read_video"), _resize_filter(resample)
     jpegs, fps, audio = read_avi(path)
     picked = jpegs[start::step][:length]
     if not picked:
         raise ValueError(f"read_video: {os.fspath(path)!r} holds {len(jpegs)} frames; [{start}::{step}][:{length}] selects none")
-    return decode_mjpeg(picked), fps, audio
+    frames = decode_mjpeg(picked)
+    if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
+        frames = resize_frames(frames, size, resample)
+    return frames, fps, audio
+
+
+def load_control_clip(path, size, window, offset=0, max_length=None, resample="bicubic"):
+    """magicanimate/pipelines/animation.py:174-194 for a Motion-JPEG `.avi` file -> (control frames uint8 (t, height, width, 3) on the
+    device, original_length): every frame is read (:175), resized to size=(width, height) when the clip has another size (:176-177; the
+    reference compares the height alone, having square frames on both sides), cut to [offset : offset + max_length] when max_length is
+    given (:178-179) and, when what is left is no multiple of `window` (config.L, the context length), followed by copies of its last
+    frame up to the next multiple (:192-194, np.pad mode="edge").  original_length is the frame count in front of that padding: the
+    length comparison_videos cuts the result back to.  Nothing leaves the device."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f"load_control_clip: window= is the context length, a positive int, got {window!r}")
+    if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+        raise ValueError(f"load_control_clip: offset= is a frame index >= 0, got {offset!r}")
+    if max_length is not None and (isinstance(max_length, bool) or not isinstance(max_length, (int, np.integer)) or max_length < 1):
+        raise ValueError(f"load_control_clip: max_length= is None or a positive int, got {max_length!r}")
+    frames, _, _ = read_video(path, size=_resize_size(size, "load_control_clip"), resample=resample)
+    total = int(frames.shape[0])
+    if max_length is not None:
+        frames = frames[int(offset):int(offset) + int(max_length)]
+    original_length = int(frames.shape[0])
+    if original_length < 1:
+        raise ValueError(f"load_control_clip: {os.fspath(path)!r} holds {total} frames; [{offset}:{offset}+{max_length}] selects none")
+    if original_length % window:
+        frames = torch.cat([frames, frames[-1:].expand(window - original_length % window, *frames.shape[1:])])
+    return frames, original_length
+
+
+def comparison_videos(source_u8, control_u8, sample, original_length) -> torch.Tensor:
+    """magicanimate/pipelines/animation.py:217-228: the three clips every reference run lays side by side - the source image repeated,
+    the control frames / 255 and the sample, each cut to original_length frames - as one float32 (3, c, t, h, w) tensor on the sample's
+    device, ready for save_videos_grid.  source_u8: uint8 (h, w, 3); control_u8: uint8 (>= t, h, w, 3) (load_control_clip's frames);
+    sample: float (1, c, >= t, h, w) in [0, 1] (the pipeline's `.videos`).  The 256 quotients x / 255 are taken on the host in doubles,
+    as the reference takes them, and gathered."""
+    if not torch.is_tensor(sample) or sample.dim() != 5 or sample.shape[0] != 1 or not sample.is_floating_point():
+        raise ValueError(f"comparison_videos: sample is the pipeline's float (1, c, t, h, w) videos, got {tuple(getattr(sample, 'shape', ()))}")
+    t = int(original_length)
+    _, c, f, h, w = sample.shape
+    as_u8 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(sample.device)
+    source_u8, control_u8 = as_u8(source_u8), as_u8(control_u8)
+    if source_u8.dtype != torch.uint8 or tuple(source_u8.shape) != (h, w, c):
+        raise ValueError(f"comparison_videos: source_u8 is one uint8 ({h}, {w}, {c}) frame at the sample's size, got {source_u8.dtype} {tuple(source_u8.shape)}")
+    if control_u8.dtype != torch.uint8 or control_u8.dim() != 4 or tuple(control_u8.shape[1:]) != (h, w, c):
+        raise ValueError(f"comparison_videos: control_u8 is uint8 (t, {h}, {w}, {c}) at the sample's size, got {control_u8.dtype} {tuple(control_u8.shape)}")
+    if not 1 <= t <= min(f, int(control_u8.shape[0])):
+        raise ValueError(f"comparison_videos: original_length {original_length!r} with {control_u8.shape[0]} control frames and a sample of {f}")
+    unit = torch.from_numpy((np.arange(256) / 255.0).astype(np.float32)).to(sample.device)
+    source = unit[source_u8.long()].permute(2, 0, 1)[None, :, None].expand(1, c, t, h, w)             # :217-218
+    control = unit[control_u8[:t].long()].permute(3, 0, 1, 2)[None]                                   # :221-224
+    return torch.cat([source, control, sample[:, :, :t].float()])                                     # :226-228

@@ -537,6 +537,26 @@ int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t*
 int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream);
 int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream);
 
+/* ---- Resizing 8-bit frames: `Image.fromarray(c).resize((size, size))` of every control frame and of the source image
+ * (magicanimate/pipelines/animation.py:174-185) and `Image.open(source_image).resize((width, height))` (EMOAnimationPipeline.py:688),
+ * byte for byte as Pillow's ImagingResample computes it for 8-bit pixels; csrc/image_resize.hip.
+ * emo_image_resize: frames uint8 [n][H][W][3] -> out uint8 [n][h][w][3], 4-byte aligned, not overlapping the frames.  Integer
+ *   arithmetic, two passes: the horizontal one writes 8-bit pixels [n][H][w][3] into the workspace, the vertical one reads those - the
+ *   intermediate image is rounded to 8 bits as Pillow's is.  Per output index o of a pass, with (first, count) = bounds[o]:
+ *     acc = 1 << 21;   acc += pixel[first + t] * coef[o][t]  for t < count;   result = clamp(acc >> 22, 0, 255)      (int32, arithmetic shift)
+ *   xbounds / ybounds: device int32 [w][2] / [h][2] = (first input column / row, tap count); xcoef / ycoef: device int32 [w][kx] /
+ *   [h][ky], 22-bit fixed point, zero behind the taps - the tables emote_hack_amd.video_io.resize_taps builds on the host in doubles, as
+ *   Resample.c's precompute_coeffs and normalize_coeffs_8bpc do.  `first` is clamped to the axis and `count` to kx / ky and to what the
+ *   axis has left behind `first`, so a bad table reads wrong pixels, never out of bounds.
+ *   A pass whose axis keeps its size is skipped and its tables may be NULL; with both skipped the frames are copied.  The workspace is
+ *   used only when both passes run: workspace_bytes must be >= emo_image_resize_workspace_bytes(n, H, W, h, w) (= n * H * w * 3 then, 0
+ *   otherwise), 4-byte aligned and apart from the frames and out, else EMO_ERR_BAD_SHAPE / EMO_ERR_NULL before anything is launched;
+ *   so are sizes below 1 and a frame (in, out or intermediate) of 2^31 bytes or more.  Every launch strides over its work: no size is
+ *   capped by a grid limit. */
+size_t emo_image_resize_workspace_bytes(int n, int H, int W, int h, int w);
+int emo_image_resize(const uint8_t* frames, uint8_t* out, int n, int H, int W, int h, int w, const int32_t* xbounds, const int32_t* xcoef,
+                     int kx, const int32_t* ybounds, const int32_t* ycoef, int ky, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CLIP vision encoder front (transformers CLIPVisionModelWithProjection: the `image_encoder` EMOAnimationPipeline.py:867 loads and
  * :909-917 hands to the pipeline; its image_embeds are the `clip_condition_embeddings` of models/videonet.py:255) -----------------------
  * emo_image_preprocess: transformers CLIPImageProcessor (resize to the shortest edge, centre crop, rescale, normalise) in one launch.
