@@ -140,7 +140,10 @@ SIGNATURES = {
     "emo_jpeg_blocks": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "emo_jpeg_count_bits": (_i, [_p, _p, _i, _i, _p, _p]),
     "emo_jpeg_emit_bits": (_i, [_p, _p, _p, _i64, _i, _i, _p, _p]),
+    "emo_jpeg_count_bits_ri": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "emo_jpeg_emit_bits_ri": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p]),
     "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _p]),
+    "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _p]),
     "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "emo_jpeg_upsample_rgb": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "emo_image_resize_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),

@@ -6,6 +6,11 @@
 //                           lanes stage the stream through LDS a window at a time and flush the decoded coefficients as coalesced 16-byte
 //                           stores; lane 0 walks the codes in between.  Every loop is counted, every read is masked to the frame's bytes,
 //                           an error ends the frame.
+//   emo_jpeg_decode_segments : the same walk, ONE WAVEFRONT per segment - a restart interval (T.81 B.2.4.4, E.1.4: the stream is byte-aligned
+//                           and the DC predictions return to 0 every Ri MCUs, F.1.1.5.1) or a whole frame without restart markers - four
+//                           segments per workgroup.  The tables and look-ups are shared in LDS; every wave has its own window and block
+//                           buffer, its 64 lanes stage and flush, its lane 0 walks.  Segments differ in length: behind the set-up no
+//                           workgroup barrier is met, a wave synchronises with itself only.
 //   emo_jpeg_idct         : dequantisation and libjpeg's "islow" integer IDCT (jidctint.c); a wavefront takes eight whole blocks
 //                           (1024 contiguous bytes), one column and then one row per lane
 //   emo_jpeg_upsample_rgb : libjpeg's h2v2 "fancy" (triangle) chroma up-sampling on the real chroma plane and its 16-bit fixed-point
@@ -73,6 +78,77 @@ __device__ __forceinline__ int jd_extend(jd_reader& r, int s) {
   return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v;
 }
 
+// the four tables into LDS and figure F.16 on every 8-bit prefix of each; all 256 lanes of the workgroup, which meet two barriers here
+__device__ __forceinline__ void jd_tables_to_lds(const int32_t* __restrict__ tables, int32_t* tab, uint16_t (*lut)[256], int t) {
+  for (int i = t; i < 4 * JD_TABLE_INTS; i += 256) tab[i] = tables[i];
+  __syncthreads();
+  for (int i = t; i < 1024; i += 256) {
+    const int32_t* tb = tab + (i >> 8) * JD_TABLE_INTS;
+    const int p = i & 255;
+    uint16_t e = 0;
+    for (int l = 1; l <= 8; l++) {
+      const int code = p >> (8 - l);
+      if (code <= tb[16 + l - 1]) {
+        e = (uint16_t)(l << 8 | (tb[64 + ((tb[32 + l - 1] + code - tb[l - 1]) & 255)] & 255));
+        break;
+      }
+    }
+    lut[i >> 8][p] = e;
+  }
+  __syncthreads();
+}
+
+// One block into out[64] (zeroed): the DC difference (F.2.2.1) added to `pred`, then at most 63 AC symbols, each of which moves k on by
+// at least one (F.2.2.2).  dc_tab / dc_lut: the block's DC table, its AC table right behind.  win_bit0: the window's first bit, counted
+// from the start of the frame or segment, which is total_bits long.  Returns EMO_JPEG_OK or what ended the block.
+__device__ __forceinline__ int jd_block(jd_reader& r, const int32_t* dc_tab, const uint16_t* dc_lut, int& pred, int16_t* out,
+                                        int64_t win_bit0, int64_t total_bits) {
+  int s = jd_symbol(r, dc_lut, dc_tab);
+  if (s < 0) return win_bit0 + r.used() + 16 > total_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE;
+  if (s > 11) return EMO_JPEG_BAD_CODE;
+  const int diff = jd_extend(r, s);
+  if (win_bit0 + r.used() > total_bits) return EMO_JPEG_PAST_END;
+  pred = (int16_t)(pred + diff);
+  out[0] = (int16_t)pred;
+  int k = 1;
+  for (int it = 0; it < 63 && k < 64; it++) {
+    const int rs = jd_symbol(r, dc_lut + 256, dc_tab + JD_TABLE_INTS);
+    if (rs < 0) return win_bit0 + r.used() + 16 > total_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE;
+    const int run = rs >> 4;
+    s = rs & 15;
+    if (s == 0) {
+      if (win_bit0 + r.used() > total_bits) return EMO_JPEG_PAST_END;
+      if (rs == 0) break;                                      // EOB
+      if (rs != 0xF0) return EMO_JPEG_BAD_CODE;                // EOBn belongs to progressive scans
+      k += 16;                                                 // ZRL
+      if (k > 64) return EMO_JPEG_BAD_RUN;
+      continue;
+    }
+    if (s > 10) return EMO_JPEG_BAD_CODE;
+    const int v = jd_extend(r, s);
+    if (win_bit0 + r.used() > total_bits) return EMO_JPEG_PAST_END;
+    k += run;
+    if (k > 63) return EMO_JPEG_BAD_RUN;
+    out[k++] = (int16_t)v;
+  }
+  return EMO_JPEG_OK;
+}
+
+// dword i of a window that starts at byte `first` of the buffer: bytes first + 4 i .. + 3, those at or behind `hi` as 0.  Aligned dword
+// loads of the buffer (scan_bytes is a multiple of 4), shifted into place
+__device__ __forceinline__ uint32_t jd_stage_dword(const uint8_t* __restrict__ scan, int64_t first, int i, int64_t hi) {
+  const int64_t g = first + 4 * (int64_t)i;                    // the first byte wanted
+  if (g >= hi) return 0u;
+  const int64_t a = g & ~(int64_t)3;
+  const int sh = (int)(g & 3) * 8;
+  const uint32_t w0 = *(const uint32_t*)(scan + a);            // a < hi <= scan_bytes, a % 4 == 0: inside the buffer
+  const uint32_t w1 = (sh && a + 4 < hi) ? *(const uint32_t*)(scan + a + 4) : 0u;
+  uint32_t v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
+  const int64_t left = hi - g;                                 // >= 1
+  if (left < 4) v &= (1u << (8 * (int)left)) - 1u;
+  return v;
+}
+
 __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
                                                                const int64_t* __restrict__ offsets, const int32_t* __restrict__ tables,
                                                                int16_t* __restrict__ coefs, int32_t* __restrict__ status, int n_mcu) {
@@ -91,25 +167,11 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
   hi = min(max(hi, lo), scan_bytes);
   const int64_t frame_bits = (hi - lo) * 8;
 
-  for (int i = t; i < 4 * JD_TABLE_INTS; i += 256) tab[i] = tables[i];
   if (t == 0) {
     sh_bitpos = 0; sh_done = 0; sh_status = EMO_JPEG_OK;
     sh_pred[0] = sh_pred[1] = sh_pred[2] = 0;
   }
-  __syncthreads();
-  for (int i = t; i < 1024; i += 256) {                      // figure F.16 on every 8-bit prefix
-    const int32_t* tb = tab + (i >> 8) * JD_TABLE_INTS;
-    const int p = i & 255;
-    uint16_t e = 0;
-    for (int l = 1; l <= 8; l++) {
-      const int code = p >> (8 - l);
-      if (code <= tb[16 + l - 1]) {
-        e = (uint16_t)(l << 8 | (tb[64 + ((tb[32 + l - 1] + code - tb[l - 1]) & 255)] & 255));
-        break;
-      }
-    }
-    lut[i >> 8][p] = e;
-  }
+  jd_tables_to_lds(tables, tab, lut, t);
   uint4* blk4 = (uint4*)blk;
   for (int i = t; i < JD_BLOCKS * 8; i += 256) blk4[i] = make_uint4(0, 0, 0, 0);
   __syncthreads();
@@ -119,22 +181,8 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
   for (int round = 0; round < n_blocks && done_blocks < n_blocks; round++) {
     const int64_t bit0 = sh_bitpos;
     const int64_t byte0 = bit0 >> 3;                         // the window starts at this byte of the frame
-    // stage: dword i of the window = frame bytes byte0 + 4 i .. + 3, bytes at or behind the frame's end as 0.  Aligned dword loads of
-    // the buffer (scan_bytes is a multiple of 4), shifted into place
-    for (int i = t; i < (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4; i += 256) {
-      const int64_t g = lo + byte0 + 4 * (int64_t)i;         // the first byte wanted
-      uint32_t v = 0;
-      if (g < hi) {
-        const int64_t a = g & ~(int64_t)3;
-        const int sh = (int)(g & 3) * 8;
-        const uint32_t w0 = *(const uint32_t*)(scan + a);    // a < hi <= scan_bytes, a % 4 == 0: inside the buffer
-        const uint32_t w1 = (sh && a + 4 < hi) ? *(const uint32_t*)(scan + a + 4) : 0u;
-        v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
-        const int64_t left = hi - g;                         // >= 1
-        if (left < 4) v &= (1u << (8 * (int)left)) - 1u;
-      }
-      win[i] = v;
-    }
+    // stage the window: frame bytes byte0 .., bytes at or behind the frame's end as 0
+    for (int i = t; i < (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4; i += 256) win[i] = jd_stage_dword(scan, lo + byte0, i, hi);
     __syncthreads();
     if (t == 0) {
       jd_reader r;
@@ -150,38 +198,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
         const int comp = k6 < 4 ? 0 : k6 - 3;
         const int32_t* dc_tab = tab + (comp ? 2 : 0) * JD_TABLE_INTS;
         const uint16_t* dc_lut = lut[comp ? 2 : 0];
-        int16_t* out = blk + nb * 64;
-        // DC (F.2.2.1)
-        int s = jd_symbol(r, dc_lut, dc_tab);
-        if (s < 0) { st = byte0 * 8 + r.used() + 16 > frame_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE; break; }
-        if (s > 11) { st = EMO_JPEG_BAD_CODE; break; }
-        const int diff = jd_extend(r, s);
-        if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
-        int& pred = comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2);
-        pred = (int16_t)(pred + diff);
-        out[0] = (int16_t)pred;
-        // AC (F.2.2.2): at most 63 symbols, each moves k on by at least one
-        int k = 1;
-        for (int it = 0; it < 63 && k < 64; it++) {
-          const int rs = jd_symbol(r, dc_lut + 256, dc_tab + JD_TABLE_INTS);
-          if (rs < 0) { st = byte0 * 8 + r.used() + 16 > frame_bits ? EMO_JPEG_PAST_END : EMO_JPEG_BAD_CODE; break; }
-          const int run = rs >> 4;
-          s = rs & 15;
-          if (s == 0) {
-            if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
-            if (rs == 0) break;                              // EOB
-            if (rs != 0xF0) { st = EMO_JPEG_BAD_CODE; break; }   // EOBn belongs to progressive scans
-            k += 16;                                         // ZRL
-            if (k > 64) { st = EMO_JPEG_BAD_RUN; break; }
-            continue;
-          }
-          if (s > 10) { st = EMO_JPEG_BAD_CODE; break; }
-          const int v = jd_extend(r, s);
-          if (byte0 * 8 + r.used() > frame_bits) { st = EMO_JPEG_PAST_END; break; }
-          k += run;
-          if (k > 63) { st = EMO_JPEG_BAD_RUN; break; }
-          out[k++] = (int16_t)v;
-        }
+        st = jd_block(r, dc_tab, dc_lut, comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2), blk + nb * 64, byte0 * 8, frame_bits);
         if (st != EMO_JPEG_OK) break;
       }
       if (st != EMO_JPEG_OK) {                               // the block the error is in is dropped with the rest of the frame
@@ -222,6 +239,112 @@ extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, con
   EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)offsets % 8 == 0, EMO_ERR_BAD_SHAPE,
             "emo_jpeg_decode_bits: coefs must be 16-byte aligned, offsets 8-byte aligned");
   jpeg_decode_bits_kernel<<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu);
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------ segments in parallel
+#define JS_WAVES 4                                 // segments (wavefronts) per workgroup
+static_assert(64 * JS_WAVES == 256, "jd_tables_to_lds strides by 256 lanes");
+
+// What a wave wrote to its part of LDS is read by other lanes of the SAME wave only: a wave's LDS accesses complete in order, so the
+// fences stop the compiler from moving them and the barrier is the wave's own.  No workgroup barrier: the waves of a workgroup walk
+// segments of different lengths.
+__device__ __forceinline__ void jd_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
+                                                                              const int64_t* __restrict__ seg_offsets,
+                                                                              const int32_t* __restrict__ seg_first_block,
+                                                                              const int32_t* __restrict__ seg_blocks,
+                                                                              const int32_t* __restrict__ tables, int16_t* __restrict__ coefs,
+                                                                              int64_t coef_blocks, int32_t* __restrict__ status, int n_seg) {
+  __shared__ int32_t tab[4 * JD_TABLE_INTS];
+  __shared__ uint16_t lut[4][256];
+  __shared__ uint32_t wins[JS_WAVES][(JD_STAGE_BYTES + JD_STAGE_SLACK) / 4];
+  __shared__ __attribute__((aligned(16))) int16_t blks[JS_WAVES][JD_BLOCKS * 64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  uint32_t* win = wins[wave];
+  int16_t* blk = blks[wave];
+  uint4* blk4 = (uint4*)blk;
+  for (int i = lane; i < JD_BLOCKS * 8; i += 64) blk4[i] = make_uint4(0, 0, 0, 0);
+  jd_tables_to_lds(tables, tab, lut, t);                     // the workgroup's last barrier is in here
+  const int seg = blockIdx.x * JS_WAVES + wave;
+  if (seg >= n_seg) return;
+
+  // the segment's own bytes and blocks, clamped to the buffers: offsets that leave the scan or run backwards give an empty segment,
+  // blocks that leave the coefficients are not decoded
+  int64_t lo = seg_offsets[seg], hi = seg_offsets[seg + 1];
+  lo = min(max(lo, (int64_t)0), scan_bytes);
+  hi = min(max(hi, lo), scan_bytes);
+  const int64_t seg_bits = (hi - lo) * 8;
+  const int64_t first = min(max((int64_t)seg_first_block[seg], (int64_t)0), coef_blocks);
+  const int n_blocks = (int)min(max((int64_t)seg_blocks[seg], (int64_t)0), coef_blocks - first);
+
+  int done_blocks = 0, st = EMO_JPEG_OK;                     // uniform over the wave
+  int64_t bitpos = 0;                                        // the walker's place in the segment, uniform too
+  int pred0 = 0, pred1 = 0, pred2 = 0;                       // lane 0's: the DC predictions start at 0 with the segment
+  // every round decodes at least one block or ends the segment, so n_blocks rounds are enough
+  for (int round = 0; round < n_blocks && done_blocks < n_blocks; round++) {
+    const int64_t byte0 = bitpos >> 3;                       // the window starts at this byte of the segment
+    for (int i = lane; i < (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4; i += 64) win[i] = jd_stage_dword(scan, lo + byte0, i, hi);
+    jd_wave_sync();
+    int nb = 0;
+    if (lane == 0) {
+      jd_reader r;
+      r.win = win; r.acc = 0; r.cnt = 0; r.rp = 0;
+      r.refill();
+      r.skip((int)(bitpos & 7));
+      const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
+      for (; nb < JD_BLOCKS && done_blocks + nb < n_blocks; nb++) {
+        if (!holds_end && (r.used() >> 3) + JD_BLOCK_BYTES_MAX > JD_STAGE_BYTES) break;    // the next block may leave the window
+        const int k6 = (done_blocks + nb) % 6;               // a segment starts with an MCU
+        const int comp = k6 < 4 ? 0 : k6 - 3;
+        st = jd_block(r, tab + (comp ? 2 : 0) * JD_TABLE_INTS, lut[comp ? 2 : 0], comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2),
+                      blk + nb * 64, byte0 * 8, seg_bits);
+        if (st != EMO_JPEG_OK) break;                        // the block the error is in is dropped with the rest of the segment
+      }
+      bitpos = byte0 * 8 + r.used();
+    }
+    jd_wave_sync();
+    nb = __builtin_amdgcn_readfirstlane(nb);                 // lane 0's, in scalar registers: the loop stays uniform for the compiler too
+    st = __builtin_amdgcn_readfirstlane(st);
+    bitpos = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bitpos >> 32)) << 32 |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)bitpos));
+    // flush: nb whole blocks, 128 contiguous bytes each, as 16-byte stores; then clear them for the next round
+    uint4* dst = (uint4*)(coefs + (first + done_blocks) * 64);
+    for (int i = lane; i < nb * 8; i += 64) {
+      dst[i] = blk4[i];
+      blk4[i] = make_uint4(0, 0, 0, 0);
+    }
+    done_blocks += nb;
+    jd_wave_sync();
+    if (st != EMO_JPEG_OK || nb == 0) break;
+  }
+  // a segment that ended early: its remaining coefficients are zeroed, so the outputs never hold stale memory
+  uint4* rest = (uint4*)(coefs + (first + done_blocks) * 64);
+  for (int i = lane; i < (n_blocks - done_blocks) * 8; i += 64) rest[i] = make_uint4(0, 0, 0, 0);
+  if (lane == 0) status[seg] = st != EMO_JPEG_OK ? st : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
+}
+
+extern "C" int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
+                                        const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks,
+                                        int32_t* status, int n_seg, void* stream) {
+  EMO_CHECK(scan && seg_offsets && seg_first_block && seg_blocks && tables && coefs && status, EMO_ERR_NULL,
+            "emo_jpeg_decode_segments: null pointer");
+  EMO_CHECK(n_seg > 0 && n_seg <= (1 << 30) && coef_blocks > 0 && coef_blocks < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_decode_segments: n_seg=%d coef_blocks=%lld", n_seg, (long long)coef_blocks);
+  EMO_CHECK(scan_bytes > 0 && scan_bytes % 4 == 0 && (uintptr_t)scan % 4 == 0, EMO_ERR_BAD_SHAPE,
+            "emo_jpeg_decode_segments: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4",
+            (long long)scan_bytes);
+  EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)seg_offsets % 8 == 0 && (uintptr_t)seg_first_block % 4 == 0 &&
+                (uintptr_t)seg_blocks % 4 == 0,
+            EMO_ERR_BAD_SHAPE, "emo_jpeg_decode_segments: coefs must be 16-byte aligned, seg_offsets 8-byte, the block tables 4-byte aligned");
+  jpeg_decode_segments_kernel<<<(n_seg + JS_WAVES - 1) / JS_WAVES, 64 * JS_WAVES, 0, as_stream(stream)>>>(
+      scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables, coefs, coef_blocks, status, n_seg);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }

@@ -8,6 +8,9 @@
 //   emo_jpeg_emit_bits  : the same per-lane codes, placed by a wave prefix sum behind the block's bit offset and OR-ed MSB-first into the
 //                         stream (32-bit atomicOr of byte-swapped words: neighbouring blocks share words, OR commutes, so the bytes are
 //                         the same every run)
+//   emo_jpeg_count_bits_ri, emo_jpeg_emit_bits_ri : the same two kernels with a restart interval (T.81 E.1.4): the DC predictor returns
+//                         to 0 every Ri MCUs, which is all the device has to know of it - where an interval's bits start is the caller's
+//                         business, as where a frame's start is (every interval on a byte)
 // Byte gathers and bit packing, no MFMA; a 512x512 frame is 1024 MCUs.
 #include "common.h"
 
@@ -113,16 +116,17 @@ struct jpeg_lane_code {
   __device__ __forceinline__ int total() const { return nbits + n_zrl * (int)(zrl >> 16); }
 };
 
-__device__ __forceinline__ jpeg_lane_code jpeg_code_of_lane(const int16_t* __restrict__ coefs, int64_t block, int b_in_frame, const uint32_t* huff,
-                                                            int lane) {
-  const int k6 = b_in_frame % 6;
+// b_in_interval: the block's index inside its restart interval (a whole number of MCUs), which is its frame when there are no restarts
+__device__ __forceinline__ jpeg_lane_code jpeg_code_of_lane(const int16_t* __restrict__ coefs, int64_t block, int b_in_interval,
+                                                            const uint32_t* huff, int lane) {
+  const int k6 = b_in_interval % 6;
   const uint32_t* dc_tab = huff + (k6 >= 4 ? 512 : 0);
   const uint32_t* ac_tab = dc_tab + 256;
   int v = coefs[block * 64 + lane];
   if (lane == 0) {
-    // the predictor: the previous block of the same component in this frame, 0 at the frame's first MCU (F.1.1.5.1)
+    // the predictor: the previous block of the same component in this interval, 0 at the interval's first MCU (F.1.1.5.1)
     const int back = k6 == 0 ? 3 : (k6 < 4 ? 1 : 6);            // Y00 follows the previous MCU's Y11
-    if (b_in_frame >= back) v -= coefs[(block - back) * 64];
+    if (b_in_interval >= back) v -= coefs[(block - back) * 64];
   }
   const uint64_t nz = __ballot(v != 0) & ~1ull;                  // the non-zero AC lanes
   const int a = v < 0 ? -v : v;
@@ -156,14 +160,15 @@ __device__ __forceinline__ void jpeg_load_tables(uint32_t* sh, const uint32_t* _
   __syncthreads();
 }
 
-// one wavefront per block, four blocks per workgroup
+// one wavefront per block, four blocks per workgroup.  blocks_per_interval: restart interval * 6, blocks_per_frame without one
 __global__ __launch_bounds__(256) void jpeg_count_bits_kernel(const int16_t* __restrict__ coefs, int32_t* __restrict__ counts, int64_t n_blocks,
-                                                              int blocks_per_frame, const uint32_t* __restrict__ huff) {
+                                                              int blocks_per_frame, int blocks_per_interval,
+                                                              const uint32_t* __restrict__ huff) {
   __shared__ uint32_t sh[1024];
   jpeg_load_tables(sh, huff);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t blk = (int64_t)blockIdx.x * 4 + wave; blk < n_blocks; blk += (int64_t)gridDim.x * 4) {   // wave-uniform
-    int bits = jpeg_code_of_lane(coefs, blk, (int)(blk % blocks_per_frame), sh, lane).total();
+    int bits = jpeg_code_of_lane(coefs, blk, (int)(blk % blocks_per_frame) % blocks_per_interval, sh, lane).total();
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) bits += __shfl_xor(bits, o, 64);
     if (lane == 0) counts[blk] = bits;
@@ -182,12 +187,13 @@ __device__ __forceinline__ void jpeg_put_bits(uint32_t* __restrict__ words, int6
 
 __global__ __launch_bounds__(256) void jpeg_emit_bits_kernel(const int16_t* __restrict__ coefs, const int64_t* __restrict__ bit_offsets,
                                                              uint32_t* __restrict__ words, int64_t n_words, int64_t n_blocks,
-                                                             int blocks_per_frame, const uint32_t* __restrict__ huff) {
+                                                             int blocks_per_frame, int blocks_per_interval,
+                                                             const uint32_t* __restrict__ huff) {
   __shared__ uint32_t sh[1024];
   jpeg_load_tables(sh, huff);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int64_t blk = (int64_t)blockIdx.x * 4 + wave; blk < n_blocks; blk += (int64_t)gridDim.x * 4) {   // wave-uniform
-    const jpeg_lane_code c = jpeg_code_of_lane(coefs, blk, (int)(blk % blocks_per_frame), sh, lane);
+    const jpeg_lane_code c = jpeg_code_of_lane(coefs, blk, (int)(blk % blocks_per_frame) % blocks_per_interval, sh, lane);
     const int mine = c.total();
     int incl = mine;                                  // inclusive prefix sum over the lanes
 #pragma unroll
@@ -212,29 +218,53 @@ static int jpeg_entropy_args(const char* who, const void* coefs, const void* huf
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_count_bits(const int16_t* coefs, int32_t* counts, int n, int n_mcu, const uint32_t* huff, void* stream) {
+static int jpeg_count_bits(const char* who, const int16_t* coefs, int32_t* counts, int n, int n_mcu, int restart_mcus, const uint32_t* huff,
+                           void* stream) {
   int64_t n_blocks = 0;
-  const int rc = jpeg_entropy_args("emo_jpeg_count_bits", coefs, huff, n, n_mcu, &n_blocks);
+  const int rc = jpeg_entropy_args(who, coefs, huff, n, n_mcu, &n_blocks);
   if (rc != EMO_OK) return rc;
-  EMO_CHECK(counts, EMO_ERR_NULL, "emo_jpeg_count_bits: null pointer");
+  EMO_CHECK(counts, EMO_ERR_NULL, "%s: null pointer", who);
+  EMO_CHECK(restart_mcus > 0, EMO_ERR_BAD_SHAPE, "%s: restart_mcus=%d", who, restart_mcus);
   const int64_t g = (n_blocks + 3) / 4;
-  jpeg_count_bits_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, counts, n_blocks, n_mcu * 6, huff);
+  jpeg_count_bits_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, counts, n_blocks, n_mcu * 6,
+                                                                                     (restart_mcus < n_mcu ? restart_mcus : n_mcu) * 6, huff);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
-                                  const uint32_t* huff, void* stream) {
+static int jpeg_emit_bits(const char* who, const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
+                          int restart_mcus, const uint32_t* huff, void* stream) {
   int64_t n_blocks = 0;
-  const int rc = jpeg_entropy_args("emo_jpeg_emit_bits", coefs, huff, n, n_mcu, &n_blocks);
+  const int rc = jpeg_entropy_args(who, coefs, huff, n, n_mcu, &n_blocks);
   if (rc != EMO_OK) return rc;
-  EMO_CHECK(bit_offsets && out, EMO_ERR_NULL, "emo_jpeg_emit_bits: null pointer");
+  EMO_CHECK(bit_offsets && out, EMO_ERR_NULL, "%s: null pointer", who);
+  EMO_CHECK(restart_mcus > 0, EMO_ERR_BAD_SHAPE, "%s: restart_mcus=%d", who, restart_mcus);
   EMO_CHECK(out_bytes > 0 && out_bytes % 4 == 0 && (uintptr_t)out % 4 == 0, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_emit_bits: the stream buffer is written as 32-bit words: out 4-byte aligned, out_bytes (%lld) a multiple of 4",
-            (long long)out_bytes);
+            "%s: the stream buffer is written as 32-bit words: out 4-byte aligned, out_bytes (%lld) a multiple of 4", who, (long long)out_bytes);
   const int64_t g = (n_blocks + 3) / 4;
   jpeg_emit_bits_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, bit_offsets, (uint32_t*)out, out_bytes / 4, n_blocks,
-                                                                                    n_mcu * 6, huff);
+                                                                                    n_mcu * 6, (restart_mcus < n_mcu ? restart_mcus : n_mcu) * 6,
+                                                                                    huff);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
+}
+
+// without a restart interval the one interval is the frame
+extern "C" int emo_jpeg_count_bits(const int16_t* coefs, int32_t* counts, int n, int n_mcu, const uint32_t* huff, void* stream) {
+  return jpeg_count_bits("emo_jpeg_count_bits", coefs, counts, n, n_mcu, n_mcu > 0 ? n_mcu : 1, huff, stream);
+}
+
+extern "C" int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
+                                  const uint32_t* huff, void* stream) {
+  return jpeg_emit_bits("emo_jpeg_emit_bits", coefs, bit_offsets, out, out_bytes, n, n_mcu, n_mcu > 0 ? n_mcu : 1, huff, stream);
+}
+
+extern "C" int emo_jpeg_count_bits_ri(const int16_t* coefs, int32_t* counts, int n, int n_mcu, int restart_mcus, const uint32_t* huff,
+                                      void* stream) {
+  return jpeg_count_bits("emo_jpeg_count_bits_ri", coefs, counts, n, n_mcu, restart_mcus, huff, stream);
+}
+
+extern "C" int emo_jpeg_emit_bits_ri(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
+                                     int restart_mcus, const uint32_t* huff, void* stream) {
+  return jpeg_emit_bits("emo_jpeg_emit_bits_ri", coefs, bit_offsets, out, out_bytes, n, n_mcu, restart_mcus, huff, stream);
 }

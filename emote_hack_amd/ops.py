@@ -808,26 +808,41 @@ def _jpeg_entropy_args(coefs, huff):
     return coefs.shape[0], coefs.shape[1]
 
 
-def jpeg_count_bits(coefs: torch.Tensor, huff: torch.Tensor) -> torch.Tensor:
+def _jpeg_restart_mcus(restart_mcus):
+    assert restart_mcus is None or (isinstance(restart_mcus, int) and not isinstance(restart_mcus, bool) and restart_mcus > 0), restart_mcus
+    return restart_mcus
+
+
+def jpeg_count_bits(coefs: torch.Tensor, huff: torch.Tensor, restart_mcus=None) -> torch.Tensor:
     """coefficients (n, MCUs, 6, 64) -> the Huffman-coded size of every block in bits, int32 (n, MCUs * 6) (emo_jpeg_count_bits; T.81
-    F.1.2).  huff: device int32 (4, 256), length << 16 | code, DC luma / AC luma / DC chroma / AC chroma."""
+    F.1.2).  huff: device int32 (4, 256), length << 16 | code, DC luma / AC luma / DC chroma / AC chroma.  restart_mcus: None, or the
+    restart interval in MCUs - the DC predictions return to 0 at every interval's first MCU (emo_jpeg_count_bits_ri; T.81 E.1.4)."""
     n, n_mcu = _jpeg_entropy_args(coefs, huff)
     counts = torch.empty(n, n_mcu * 6, device=coefs.device, dtype=torch.int32)
-    _launch("jpeg_count_bits", 0.0, 2.0 * coefs.numel(),
-            lambda: check(_lib.load().emo_jpeg_count_bits(_ptr(coefs), _ptr(counts), n, n_mcu, _ptr(huff), _stream()), "emo_jpeg_count_bits"))
+    if _jpeg_restart_mcus(restart_mcus) is None:
+        call = lambda: check(_lib.load().emo_jpeg_count_bits(_ptr(coefs), _ptr(counts), n, n_mcu, _ptr(huff), _stream()), "emo_jpeg_count_bits")
+    else:
+        call = lambda: check(_lib.load().emo_jpeg_count_bits_ri(_ptr(coefs), _ptr(counts), n, n_mcu, restart_mcus, _ptr(huff), _stream()),
+                             "emo_jpeg_count_bits_ri")
+    _launch("jpeg_count_bits", 0.0, 2.0 * coefs.numel(), call)
     return counts
 
 
-def jpeg_emit_bits(coefs: torch.Tensor, huff: torch.Tensor, bit_offsets: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+def jpeg_emit_bits(coefs: torch.Tensor, huff: torch.Tensor, bit_offsets: torch.Tensor, out: torch.Tensor, restart_mcus=None) -> torch.Tensor:
     """writes every block's codes MSB-first at its bit offset (int64 (n, MCUs * 6), from out's first bit) into out, a ZEROED uint8 buffer
-    of a multiple of 4 bytes (emo_jpeg_emit_bits): unstuffed, unpadded streams."""
+    of a multiple of 4 bytes (emo_jpeg_emit_bits): unstuffed, unpadded streams.  restart_mcus as in jpeg_count_bits
+    (emo_jpeg_emit_bits_ri)."""
     n, n_mcu = _jpeg_entropy_args(coefs, huff)
     _need_cuda(bit_offsets, out)
     assert bit_offsets.dtype == torch.int64 and bit_offsets.numel() == n * n_mcu * 6 and bit_offsets.is_contiguous(), (bit_offsets.dtype, bit_offsets.shape)
     assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), (out.dtype, out.shape)
-    _launch("jpeg_emit_bits", 0.0, 2.0 * coefs.numel() + out.numel(),
-            lambda: check(_lib.load().emo_jpeg_emit_bits(_ptr(coefs), _ptr(bit_offsets), _ptr(out), out.numel(), n, n_mcu, _ptr(huff), _stream()),
-                          "emo_jpeg_emit_bits"))
+    if _jpeg_restart_mcus(restart_mcus) is None:
+        call = lambda: check(_lib.load().emo_jpeg_emit_bits(_ptr(coefs), _ptr(bit_offsets), _ptr(out), out.numel(), n, n_mcu, _ptr(huff), _stream()),
+                             "emo_jpeg_emit_bits")
+    else:
+        call = lambda: check(_lib.load().emo_jpeg_emit_bits_ri(_ptr(coefs), _ptr(bit_offsets), _ptr(out), out.numel(), n, n_mcu, restart_mcus,
+                                                               _ptr(huff), _stream()), "emo_jpeg_emit_bits_ri")
+    _launch("jpeg_emit_bits", 0.0, 2.0 * coefs.numel() + out.numel(), call)
     return out
 
 
@@ -858,6 +873,29 @@ def jpeg_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Te
     _launch("jpeg_decode_bits", 0.0, float(scan.numel() + 2 * coefs.numel()),
             lambda: check(_lib.load().emo_jpeg_decode_bits(_ptr(scan), scan.numel(), _ptr(offsets), _ptr(tables), _ptr(coefs), _ptr(status), n, n_mcu,
                                                            _stream()), "emo_jpeg_decode_bits"), tag=f"{n}x{n_mcu}")
+    return coefs, status
+
+
+def jpeg_decode_segments(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_first_block: torch.Tensor, seg_blocks: torch.Tensor,
+                         tables: torch.Tensor, n: int, n_mcu: int, out=None, status=None):
+    """unstuffed segments (restart intervals, or whole frames without restart markers; segment s in bytes seg_offsets[s] ..
+    seg_offsets[s + 1] of scan, int64 (n_seg + 1)) -> (coefficients int16 (n, n_mcu, 6, 64), status int32 (n_seg), a key of JPEG_STATUS
+    PER SEGMENT) (emo_jpeg_decode_segments; T.81 E.1.4, F.2.2).  Segment s fills seg_blocks[s] blocks from block seg_first_block[s] on of
+    the whole coefficient buffer (both int32 (n_seg)); blocks no segment names are not written.  scan and tables as in jpeg_decode_bits."""
+    _need_cuda(scan, seg_offsets, seg_first_block, seg_blocks, tables)
+    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
+    assert seg_offsets.dtype == torch.int64 and seg_offsets.dim() == 1 and seg_offsets.numel() >= 2 and seg_offsets.is_contiguous(), (seg_offsets.dtype, seg_offsets.shape)
+    n_seg = seg_offsets.numel() - 1
+    for tab in (seg_first_block, seg_blocks):
+        assert tab.dtype == torch.int32 and tuple(tab.shape) == (n_seg,) and tab.is_contiguous(), (tab.dtype, tab.shape, n_seg)
+    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
+    n, n_mcu = int(n), int(n_mcu)
+    coefs = _jpeg_out(out, (n, n_mcu, 6, 64), torch.int16, scan.device, "coefs")
+    status = _jpeg_out(status, (n_seg,), torch.int32, scan.device, "status")
+    _launch("jpeg_decode_segments", 0.0, float(scan.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_decode_segments(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_first_block), _ptr(seg_blocks),
+                                                               _ptr(tables), _ptr(coefs), n * n_mcu * 6, _ptr(status), n_seg, _stream()),
+                          "emo_jpeg_decode_segments"), tag=f"{n_seg}/{n}x{n_mcu}")
     return coefs, status
 
 

@@ -1263,7 +1263,9 @@ class EMOAnimationPipeline:
         JPEG-encoded on the device and written as Motion-JPEG in an AVI container (emote_hack_amd.video_io) playing at fps *
         interpolation_factor - fps= is required.  audio= given as a `.wav` path or a (samples, rate) pair goes into the file as 16-bit PCM,
         with its own channels at its own rate, from audio_start for the clip's duration (less where the audio ends first).  The return
-        value is what it is without save_path.
+        value is what it is without save_path.  save_restart_interval="row" (one row of MCUs) or a number of MCUs from 1 to 65535 cuts
+        every frame's scan into restart intervals (a DRI segment and RSTm markers, T.81 E.1.4), which video_io.decode_mjpeg decodes in
+        parallel; None, the default, writes the files written without it.
         input_resample="bicubic" | "box" | "bilinear" | "hamming" | "lanczos" lets clips come at any size: a controlnet_condition= clip
         path or a source_image= `.avi` path whose frames are not height x width is resized on the device, byte for byte as the
         `Image.resize` of animation.py:174-185 would ("bicubic" is that call's filter; emote_hack_amd.video_io.resize_frames).  None, the
@@ -1288,6 +1290,7 @@ class EMOAnimationPipeline:
             from . import video_io
             save_path = video_io._avi_path(save_path, "save_path=")
             video_io.jpeg_tables(save_quality)      # quality 1 .. 100
+            video_io.restart_mcus(kwargs.get("save_restart_interval"), 16)      # None, "row" or 1 .. 65535 MCUs
             if kwargs.get("fps") is None:
                 raise ValueError("save_path= writes a video file and a file has a frame rate: pass fps= (an int, a Fraction or a (num, den) "
                                  "pair; the file plays at fps * interpolation_factor)")
@@ -1468,7 +1471,8 @@ class EMOAnimationPipeline:
                 first = math.floor(_as_fraction(kwargs.get("audio_start", 0), "audio_start") * rate)
                 count = math.floor(n_frames * rate / save_fps + Fraction(1, 2))
                 save_audio = (samples[first:first + count], rate) if first < len(samples) else None      # cut where the audio ends
-            video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio)
+            video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio,
+                                 restart_interval=kwargs.get("save_restart_interval"))
         if output_type == "uint8":
             video = frames_u8
         elif self.vae is not None and output_type != "latent":

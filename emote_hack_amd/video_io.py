@@ -5,15 +5,20 @@
                     Annex K.3 - K.6, with the code / length arrays derived from BITS / HUFFVAL as Annex C does
   encode_mjpeg      packed uint8 frames on the device -> one baseline JPEG file per frame: emo_jpeg_blocks, emo_jpeg_count_bits,
                     emo_jpeg_emit_bits (csrc/video_out.hip), ONE device-to-host copy of the entropy-coded streams, then per frame on the
-                    host the padding of the last byte, the 0x00 behind every 0xFF and the marker segments (T.81 Annex B)
+                    host the padding of the last byte, the 0x00 behind every 0xFF and the marker segments (T.81 Annex B).  With
+                    restart_interval= (MCUs, or "row") the scan is cut into restart intervals (T.81 E.1.4): a DRI segment, every interval
+                    coded from DC predictions 0 (emo_jpeg_count_bits_ri, emo_jpeg_emit_bits_ri), padded and stuffed on its own, RSTm
+                    markers between them - a file whose intervals decode_mjpeg decodes in parallel
   write_avi         a classic RIFF `AVI ` file: hdrl (avih, a vids / MJPG stream, optionally an auds / PCM stream), movi with the 00dc and
                     01wb chunks interleaved per frame, idx1.  Below 2^31 bytes (OpenDML is not written)
   read_avi          the reverse, for files write_avi made
   parse_jpeg        one baseline 4:2:0 file -> its size, tables and scan with the stuffed 0x00 bytes taken out (the reverse of jpeg_header
-                    and finish_scan); anything else a JPEG file may be is refused by name
-  decode_mjpeg      JPEG files -> packed uint8 frames on the device: per set of tables ONE host-to-device copy of the scans, then
-                    emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb (csrc/video_in.hip) and one read of the frames' status -
-                    the bytes libjpeg's default decoder gives
+                    and finish_scan); anything else a JPEG file may be is refused by name.  restart=True also takes files with restart
+                    intervals: the RSTm markers are checked and taken out, and the intervals' boundaries kept
+  decode_mjpeg      JPEG files -> packed uint8 frames on the device: per set of tables ONE host-to-device copy of the scans and the
+                    segment table, then emo_jpeg_decode_segments (one wavefront per restart interval; emo_jpeg_decode_bits, one
+                    workgroup per frame, where no frame has restart intervals), emo_jpeg_idct, emo_jpeg_upsample_rgb
+                    (csrc/video_in.hip) and one read of the segments' status - the bytes libjpeg's default decoder gives
   read_video        read_avi + decode_mjpeg: what `VideoReader(path).read()` is to magicanimate/pipelines/animation.py:174-185
   resize_taps       the per-axis coefficient table of Pillow's `Image.resize` for 8-bit images (Resample.c), in 22-bit fixed point
   resize_frames     `Image.fromarray(f).resize((width, height), filter)` of device frames, byte for byte: emo_image_resize
@@ -119,9 +124,27 @@ def _segment(marker: int, body: bytes) -> bytes:
     return struct.pack(">BBH", 0xFF, marker, len(body) + 2) + body
 
 
+JPEG_MAX_RESTART = 65535      # DRI holds 16 bits (B.2.4.4)
+
+
+def restart_mcus(restart_interval, width):
+    """restart_interval= as the writers take it -> None (no restart intervals: the files written without the keyword) or the interval
+    in MCUs: a positive int below 65536, or "row" for one row of 16x16 MCUs, ceil(width / 16)"""
+    if restart_interval is None:
+        return None
+    if isinstance(restart_interval, str) and restart_interval == "row":
+        restart_interval = (int(width) + 15) // 16
+    if (isinstance(restart_interval, bool) or not isinstance(restart_interval, (int, np.integer))
+            or not 1 <= int(restart_interval) <= JPEG_MAX_RESTART):
+        raise ValueError(f"restart_interval= takes None, \"row\" (one row of MCUs) or a number of MCUs from 1 to {JPEG_MAX_RESTART} (DRI holds 16 "
+                         f"bits), got {restart_interval!r}")
+    return int(restart_interval)
+
+
 @functools.lru_cache(maxsize=64)
-def jpeg_header(height: int, width: int, quality: int) -> bytes:
-    """SOI, JFIF APP0, DQT x 2, SOF0, DHT x 4, SOS (T.81 B.2): everything in front of the entropy-coded segment of a 4:2:0 frame"""
+def jpeg_header(height: int, width: int, quality: int, restart: int = 0) -> bytes:
+    """SOI, JFIF APP0, DQT x 2, SOF0, DHT x 4, [DRI,] SOS (T.81 B.2): everything in front of the entropy-coded segment of a 4:2:0 frame.
+    restart: the restart interval in MCUs (B.2.4.4), 0 for a file without one - part of the cache's key"""
     t = jpeg_tables(quality)
     if not (1 <= height <= 65535 and 1 <= width <= 65535):
         raise ValueError(f"a JPEG frame is 1 .. 65535 pixels each way, got {height} x {width}")
@@ -131,6 +154,10 @@ def jpeg_header(height: int, width: int, quality: int) -> bytes:
     out.append(_segment(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])))
     for (bits, vals), (tc, th) in zip(t.specs, HUFFMAN_IDS):
         out.append(_segment(0xC4, bytes([tc << 4 | th]) + bytes(bits) + bytes(vals)))
+    if not 0 <= restart <= JPEG_MAX_RESTART:
+        raise ValueError(f"a restart interval is 0 (none) .. {JPEG_MAX_RESTART} MCUs, got {restart}")
+    if restart:
+        out.append(_segment(0xDD, struct.pack(">H", restart)))
     out.append(_segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0])))
     return b"".join(out)
 
@@ -146,15 +173,36 @@ def finish_scan(stream: np.ndarray, n_bits: int) -> bytes:
     return a.tobytes() + b"\xFF\xD9"
 
 
+def finish_restart_scan(stream: np.ndarray, interval_bits) -> bytes:
+    """The unstuffed streams of a frame's restart intervals, laid end to end with every interval starting on a byte (uint8 array, zero
+    beyond each interval's last bit), and the bits of each -> the scan's bytes (T.81 B.2.1, E.1.4): every interval's last byte filled
+    with 1-bits and a 0x00 behind every 0xFF (also one that ends an interval), RSTm between two intervals with m counting 0 .. 7 and
+    round again, no marker behind the last, EOI"""
+    bits = np.asarray(interval_bits, np.int64).reshape(-1)
+    if bits.size < 1 or (bits < 1).any():
+        raise ValueError(f"finish_restart_scan: every interval holds at least one bit, got {bits.tolist()[:8]}")
+    ends = np.cumsum((bits + 7) // 8)                                            # byte end of every interval
+    a = np.array(stream[:int(ends[-1])], dtype=np.uint8)
+    ragged = np.flatnonzero(bits & 7)
+    a[ends[ragged] - 1] |= ((1 << (8 - (bits[ragged] & 7))) - 1).astype(np.uint8)
+    ff = np.flatnonzero(a == 0xFF) + 1
+    cuts = ends[:-1]
+    markers = np.stack([np.full(len(cuts), 0xFF), 0xD0 + np.arange(len(cuts)) % 8], axis=1).reshape(-1)
+    # np.insert keeps the given order among values that go to one place: the 0x00 of an 0xFF that ends an interval, then the marker
+    a = np.insert(a, np.concatenate([ff, np.repeat(cuts, 2)]), np.concatenate([np.zeros(len(ff)), markers]).astype(np.uint8))
+    return a.tobytes() + b"\xFF\xD9"
+
+
 @functools.lru_cache(maxsize=8)
 def _device_tables(quality: int, device: str):
     t = jpeg_tables(quality)
     return (torch.from_numpy(t.quant.copy()).to(device), torch.from_numpy(t.huff.astype(np.int64).astype(np.int32)).to(device))
 
 
-def encode_streams(frames_u8: torch.Tensor, quality: int = 90):
+def encode_streams(frames_u8: torch.Tensor, quality: int = 90, restart_interval=None):
     """The device part of encode_mjpeg: (n, H, W, 3) uint8 device frames -> (streams uint8 device buffer, byte start of every frame, bits
-    of every frame); three launches, one read of the n frame totals."""
+    of every frame); three launches, one read of the n frame totals.  With restart_interval (restart_mcus) every restart interval starts
+    on a byte: the starts and the bits come per interval, int64 (n, ceil(MCUs / interval)), from one read of as many totals."""
     quality = _check_quality(quality)
     if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
         raise ValueError("encode_mjpeg takes packed uint8 RGB frames, (n, H, W, 3) or (1, n, H, W, 3) as output_type=\"uint8\" returns them, got "
@@ -163,9 +211,24 @@ def encode_streams(frames_u8: torch.Tensor, quality: int = 90):
         frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
     if frames_u8.shape[0] < 1:
         raise ValueError("encode_mjpeg: no frames")
+    ri = restart_mcus(restart_interval, frames_u8.shape[2])
     frames_u8 = frames_u8.contiguous()
     quant, huff = _device_tables(quality, str(frames_u8.device))
     coefs = ops.jpeg_blocks(frames_u8, quant)
+    if ri is not None:
+        n, n_mcu = int(coefs.shape[0]), int(coefs.shape[1])
+        ri = min(ri, n_mcu)
+        k = -(-n_mcu // ri)                                                      # intervals per frame; the last may be short
+        counts = ops.jpeg_count_bits(coefs, huff, restart_mcus=ri)
+        per = torch.nn.functional.pad(counts.to(torch.int64), (0, (k * ri - n_mcu) * 6)).view(n, k, ri * 6)
+        ends = torch.cumsum(per, dim=2)                                          # bits, inside each interval
+        bits = ends[:, :, -1].cpu().numpy()                                      # the one read: n * k totals
+        nbytes = (bits + 7) // 8
+        starts = (np.cumsum(nbytes.reshape(-1)) - nbytes.reshape(-1)).reshape(n, k).astype(np.int64)
+        offsets = (ends - per + torch.from_numpy(starts * 8).to(ends.device)[:, :, None]).view(n, k * ri * 6)[:, :n_mcu * 6].contiguous()
+        out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
+        ops.jpeg_emit_bits(coefs, huff, offsets, out, restart_mcus=ri)
+        return out, starts, bits
     counts = ops.jpeg_count_bits(coefs, huff)
     ends = torch.cumsum(counts, dim=1, dtype=torch.int64)                       # bits, inside each frame
     bits = ends[:, -1].cpu().numpy()                                            # the one read before the streams themselves
@@ -177,14 +240,23 @@ def encode_streams(frames_u8: torch.Tensor, quality: int = 90):
     return out, starts, bits
 
 
-def encode_mjpeg(frames_u8: torch.Tensor, quality: int = 90) -> list:
+def encode_mjpeg(frames_u8: torch.Tensor, quality: int = 90, restart_interval=None) -> list:
     """Packed uint8 RGB frames on the device, (n, H, W, 3) (or the (1, n, H, W, 3) of output_type="uint8") -> n baseline JPEG files
     (bytes; 4:2:0, the standard Huffman tables).  The colour transform, the DCT, the quantisation and the Huffman coding run on the device;
-    the compressed streams come back in one copy, and the host pads, stuffs and wraps each."""
-    out, starts, bits = encode_streams(frames_u8, quality)                      # (checks the arguments)
+    the compressed streams come back in one copy, and the host pads, stuffs and wraps each.
+    restart_interval: None writes one entropy-coded segment per frame.  A positive int of MCUs below 65536, or "row" for one row of
+    MCUs (ceil(W / 16)), writes a DRI segment and restart intervals of that many MCUs with RSTm markers between them (T.81 E.1.4): the
+    same coefficients, a few bytes more per interval, and a file decode_mjpeg decodes one wavefront per interval.  An interval of at
+    least the frame's MCUs writes the DRI segment and no marker."""
+    out, starts, bits = encode_streams(frames_u8, quality, restart_interval)    # (checks the arguments)
     host = out.cpu().numpy()
-    head = jpeg_header(int(frames_u8.shape[-3]), int(frames_u8.shape[-2]), int(quality))
-    return [head + finish_scan(host[s:], int(b)) for s, b in zip(starts, bits)]
+    height, width = int(frames_u8.shape[-3]), int(frames_u8.shape[-2])
+    ri = restart_mcus(restart_interval, width)
+    if ri is None:
+        head = jpeg_header(height, width, int(quality))
+        return [head + finish_scan(host[s:], int(b)) for s, b in zip(starts, bits)]
+    head = jpeg_header(height, width, int(quality), ri)
+    return [head + finish_restart_scan(host[int(s[0]):], b) for s, b in zip(starts, bits)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------- JPEG parsing
@@ -220,6 +292,9 @@ class ParsedJpeg:
     quant: np.ndarray          # uint16 (2, 64): luminance, chrominance, NATURAL order
     specs: tuple               # four (BITS tuple, HUFFVAL bytes): DC luminance, AC luminance, DC chrominance, AC chrominance
     scan: np.ndarray           # uint8: the entropy-coded segment without the 0x00 behind every 0xFF, up to the marker that ends it
+    restart: int = 0           # the restart interval in MCUs (DRI), 0: none
+    intervals: np.ndarray = None      # int64 (intervals + 1): restart interval k lies in scan[intervals[k]:intervals[k + 1]] (the RSTm
+    #                                   markers are taken out); (0, len(scan)) for a file without restart intervals
 
     def table_key(self):
         return self.quant.tobytes(), self.specs
@@ -232,12 +307,17 @@ _SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0x
 _ONLY = "decode_mjpeg reads 8-bit baseline (SOF0) files with three components at 2x2 / 1x1 / 1x1 in one interleaved scan"
 
 
-def parse_jpeg(data) -> ParsedJpeg:
+def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
     """One JPEG file -> ParsedJpeg, walking its marker segments (T.81 Annex B).  A file without DHT segments gets the tables of Annex
     K.3 - K.6 (the Motion-JPEG convention in AVI files).  ValueError, saying what was found, for everything but 8-bit baseline 4:2:0 in
     one interleaved scan without restart intervals: progressive, extended or arithmetic-coded files, other sampling factors, grey
-    images, a restart interval, 16-bit quantisers, Cb and Cr on different tables, frames narrower than JPEG_MIN_WIDTH."""
+    images, a restart interval, 16-bit quantisers, Cb and Cr on different tables, frames narrower than JPEG_MIN_WIDTH.
+    restart=True takes restart intervals too (B.2.4.4, E.1.4): Ri is that of the last DRI segment in front of the scan (0: none), the
+    entropy-coded bytes are split at the RSTm markers and every interval is unstuffed; the markers must count 0, 1, .. 7, 0, .. and cut
+    the scan into exactly ceil(MCUs / Ri) intervals, anything else is a ValueError that says what was found - a decoder's
+    resynchronisation on damaged files is not built, and neither are fill bytes in front of a marker."""
     data = bytes(data)
+    ri = 0
     if len(data) < 4 or data[:2] != b"\xFF\xD8":
         raise ValueError("parse_jpeg: no SOI marker at the start: not a JPEG file")
     pos, quant, huff, frame = 2, {}, {}, None
@@ -290,8 +370,9 @@ def parse_jpeg(data) -> ParsedJpeg:
         elif marker == 0xDD:                                                     # DRI (B.2.4.4)
             if len(body) != 2:
                 raise ValueError("parse_jpeg: a malformed DRI segment")
-            if struct.unpack(">H", body)[0]:
-                raise ValueError(f"parse_jpeg: a restart interval of {struct.unpack('>H', body)[0]} MCUs; restart markers are not built; {_ONLY}")
+            ri = struct.unpack(">H", body)[0]                                    # the last one in front of the scan holds
+            if ri and not restart:
+                raise ValueError(f"parse_jpeg: a restart interval of {ri} MCUs; restart markers are not built; {_ONLY}")
         elif marker == 0xDA:                                                     # SOS (B.2.3): the scan follows
             break
         elif marker in (0xD8, 0xD9) or 0xD0 <= marker <= 0xD7 or marker == 0x01:
@@ -323,15 +404,42 @@ def parse_jpeg(data) -> ParsedJpeg:
         specs.append(huff[key])
     a = np.frombuffer(data, np.uint8, offset=pos)
     ends = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0x00)) if len(a) > 1 else np.zeros(0, np.int64)
-    if len(ends):                                                                # the first marker behind the scan: EOI in a whole file
-        if 0xD0 <= a[ends[0] + 1] <= 0xD7:
+    rst = []                                                                     # where the RSTm markers start
+    for e in ends:                                                               # up to the first other marker: EOI in a whole file
+        if not 0xD0 <= a[e + 1] <= 0xD7:
+            a = a[:e]
+            break
+        if not restart:
             raise ValueError(f"parse_jpeg: a restart marker inside the scan; restart markers are not built; {_ONLY}")
-        a = a[:ends[0]]
-    scan = np.delete(a, np.flatnonzero((a[:-1] == 0xFF) & (a[1:] == 0x00)) + 1) if len(a) > 1 else a.copy()
+        rst.append(int(e))
+    if rst or ri:
+        n_mcu = ops.jpeg_mcus(height, width)
+        if not ri:
+            raise ValueError(f"parse_jpeg: {len(rst)} restart marker{'s' if len(rst) != 1 else ''} in the scan (the first at byte {pos + rst[0]}) "
+                             "and no restart interval defined by a DRI segment")
+        found = [int(a[e + 1]) - 0xD0 for e in rst]
+        wrong = [k for k, m in enumerate(found) if m != k % 8]
+        if wrong:
+            k = wrong[0]
+            raise ValueError(f"parse_jpeg: restart marker {k} of the scan is RST{found[k]} (FF{0xD0 + found[k]:02X} at byte {pos + rst[k]}), RST{k % 8} "
+                             "is expected there: the markers count 0 .. 7 and round again (a damaged file; resynchronisation is not built)")
+        want = -(-n_mcu // ri)
+        if len(rst) + 1 != want:
+            raise ValueError(f"parse_jpeg: {len(rst) + 1} restart interval{'s' if rst else ''} in the scan, {n_mcu} MCUs at a restart interval of "
+                             f"{ri} make {want} (a damaged file; resynchronisation is not built)")
+    keep = np.ones(len(a), bool)
+    if len(a) > 1:
+        keep[np.flatnonzero((a[:-1] == 0xFF) & (a[1:] == 0x00)) + 1] = False       # the stuffed bytes
+    if rst:
+        keep[np.array(rst)] = keep[np.array(rst) + 1] = False                    # the markers
+    before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)            # bytes of the scan in front of byte i of a
+    scan = a[keep]
+    intervals = before[[0] + rst + [len(a)]]
     q = np.stack([quant[comps[0][3]], quant[comps[1][3]]])
     q.setflags(write=False)
     scan.setflags(write=False)
-    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan)
+    intervals.setflags(write=False)
+    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan, int(ri), intervals)
 
 
 @functools.lru_cache(maxsize=16)
@@ -342,12 +450,15 @@ def _decode_header(quant_bytes: bytes, specs: tuple) -> np.ndarray:
 
 
 def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
-    """Baseline 4:2:0 JPEG files of one size (bytes each; what encode_mjpeg, Pillow at subsampling=2 or a Motion-JPEG AVI hold) -> packed
-    uint8 RGB frames (n, H, W, 3) on the device, byte for byte what libjpeg's default decoder (Pillow's) gives.  The host only parses
-    markers and takes the stuffed bytes out; frames that share their tables go up in ONE copy (tables, quantisers, offsets, scans) and
-    through one set of three launches (emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb), followed by one read of their status.
-    ValueError naming the frame for a file parse_jpeg refuses, a frame of another size, or a scan that does not decode.  There is no
-    host decoder behind this."""
+    """Baseline 4:2:0 JPEG files of one size (bytes each; what encode_mjpeg, Pillow at subsampling=2 or a Motion-JPEG AVI hold), with or
+    without restart intervals -> packed uint8 RGB frames (n, H, W, 3) on the device, byte for byte what libjpeg's default decoder
+    (Pillow's) gives.  The host only parses markers and takes the stuffed bytes out; frames that share their tables go up in ONE copy
+    (tables, quantisers, the segment table, scans) and through one set of three launches (emo_jpeg_decode_segments, emo_jpeg_idct,
+    emo_jpeg_upsample_rgb), followed by one read of the segments' status.  A segment is a restart interval, or a whole frame that has
+    none: frames with different restart intervals and frames without share a launch, and a frame decodes as many wavefronts wide as it
+    has intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits, one workgroup per frame, as it
+    always did.)  ValueError naming the frame for a file parse_jpeg refuses, a frame of another size, or a scan that does not decode
+    (naming the restart interval too when the frame has them).  There is no host decoder behind this."""
     jpegs = list(jpegs)
     if not jpegs:
         raise ValueError("decode_mjpeg: no frames")
@@ -358,7 +469,7 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     parsed = []
     for i, j in enumerate(jpegs):
         try:
-            parsed.append(parse_jpeg(j))
+            parsed.append(parse_jpeg(j, restart=True))
         except ValueError as e:
             raise ValueError(f"decode_mjpeg: frame {i}: {e}") from None
     H, W = parsed[0].height, parsed[0].width
@@ -373,23 +484,47 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     for key, members in groups.items():
         head = _decode_header(*key)
         n = len(members)
+        # the segment table: one segment per restart interval, one for a frame without; frame f of the group owns blocks f * n_mcu * 6 ..
         sizes = np.array([len(parsed[i].scan) for i in members], np.int64)
-        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        pad = -int(offsets[-1]) % 4 or (4 if offsets[-1] == 0 else 0)
-        host = np.concatenate([head, offsets.view(np.uint8)] + [parsed[i].scan for i in members] + [np.zeros(pad, np.uint8)])
+        frame_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        seg_offsets, seg_first, seg_blocks, seg_frame = [], [], [], []
+        for f, i in enumerate(members):
+            p = parsed[i]
+            first_mcu = np.arange(len(p.intervals) - 1, dtype=np.int64) * (p.restart or n_mcu)
+            seg_offsets.append(frame_start[f] + p.intervals[:-1])
+            seg_first.append((f * n_mcu + first_mcu) * 6)
+            seg_blocks.append((np.minimum(first_mcu + (p.restart or n_mcu), n_mcu) - first_mcu) * 6)
+            seg_frame.append(np.full(len(first_mcu), f, np.int64))
+        seg_offsets = np.concatenate(seg_offsets + [frame_start[-1:]]).astype(np.int64)
+        seg_first, seg_blocks, seg_frame = (np.concatenate(x) for x in (seg_first, seg_blocks, seg_frame))
+        n_seg = len(seg_first)
+        pad = -int(frame_start[-1]) % 4 or (4 if frame_start[-1] == 0 else 0)
+        host = np.concatenate([head, seg_offsets.view(np.uint8), seg_first.astype(np.int32).view(np.uint8), seg_blocks.astype(np.int32).view(np.uint8)]
+                              + [parsed[i].scan for i in members] + [np.zeros(pad, np.uint8)])
         dev = torch.from_numpy(host).to(device)                                  # the one copy
-        t_end, q_end, o_end = 16 * ops.JPEG_DECODE_TABLE_INTS, 16 * ops.JPEG_DECODE_TABLE_INTS + 256, len(head) + 8 * (n + 1)
+        t_end, q_end = 16 * ops.JPEG_DECODE_TABLE_INTS, 16 * ops.JPEG_DECODE_TABLE_INTS + 256
+        o_end = q_end + 8 * (n_seg + 1)                                          # head is t_end + 256 bytes: every table stays 8-byte aligned
         tables = dev[:t_end].view(torch.int32).view(4, ops.JPEG_DECODE_TABLE_INTS)
         quant = dev[t_end:q_end].view(torch.uint16).view(2, 64)
-        coefs, status = ops.jpeg_decode_bits(dev[o_end:], dev[q_end:o_end].view(torch.int64), tables, n_mcu)
+        if n_seg > n:
+            entry = "emo_jpeg_decode_segments"
+            coefs, status = ops.jpeg_decode_segments(dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64),
+                                                     dev[o_end:o_end + 4 * n_seg].view(torch.int32),
+                                                     dev[o_end + 4 * n_seg:o_end + 8 * n_seg].view(torch.int32), tables, n, n_mcu)
+        else:       # no frame of the group is cut into intervals: a segment is a frame, which a workgroup of its own decodes faster
+            entry = "emo_jpeg_decode_bits"
+            coefs, status = ops.jpeg_decode_bits(dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64), tables, n_mcu)
         y, c = ops.jpeg_idct(coefs, quant, H, W)
         whole = n == len(parsed)
         rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
         st = status.cpu().numpy()                                                # the one read
         if st.any():
-            bad = int(np.flatnonzero(st)[0])
-            raise ValueError(f"decode_mjpeg: frame {members[bad]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')} "
-                             f"(emo_jpeg_decode_bits status {int(st[bad])})")
+            bad = int(np.flatnonzero(st)[0])                                     # the first in frame order, whichever wave ended first
+            f = int(seg_frame[bad])
+            p = parsed[members[f]]
+            where = f" in restart interval {bad - int(np.searchsorted(seg_frame, f))} of {len(p.intervals) - 1}" if p.restart else ""
+            raise ValueError(f"decode_mjpeg: frame {members[f]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')}"
+                             f"{where} ({entry} status {int(st[bad])})")
         if not whole:
             if members == list(range(members[0], members[0] + n)):
                 out[members[0]:members[0] + n] = rgb
@@ -709,12 +844,12 @@ def _makedirs_for(path):
         os.makedirs(d, exist_ok=True)            # util.py:32
 
 
-def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None) -> None:
-    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg + write_avi"""
+def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None) -> None:
+    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + write_avi"""
     path = _avi_path(path, "write_video")
     if frames_u8.dim() == 5:
         frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
-    jpegs = encode_mjpeg(frames_u8, quality)
+    jpegs = encode_mjpeg(frames_u8, quality, restart_interval)
     _makedirs_for(path)
     write_avi(path, jpegs, int(frames_u8.shape[2]), int(frames_u8.shape[1]), fps, audio=audio)
 
@@ -745,20 +880,21 @@ def make_grid_u8(videos: torch.Tensor, rescale=False, n_rows=6) -> torch.Tensor:
     return (grid * 255).clamp(0, 255).to(torch.uint8).contiguous()               # util.py:29
 
 
-def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90):
+def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90, restart_interval=None):
     """magicanimate/utils/util.py:21-33 with a Motion-JPEG `.avi` in place of imageio.mimsave.  The frames are encoded on the HIP device:
-    videos held on the host are uploaded."""
+    videos held on the host are uploaded.  restart_interval as in encode_mjpeg."""
     path = _avi_path(path, "save_videos_grid")
     if torch.is_tensor(videos) and not videos.is_cuda:
         videos = videos.to("cuda")
-    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality)
+    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality, restart_interval=restart_interval)
 
 
-def images2video(video, path, fps=8, quality: int = 90):
-    """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file"""
+def images2video(video, path, fps=8, quality: int = 90, restart_interval=None):
+    """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file.
+    restart_interval as in encode_mjpeg."""
     path = _avi_path(path, "images2video")
     frames = video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))
-    write_video(frames.to("cuda"), path, fps, quality)
+    write_video(frames.to("cuda"), path, fps, quality, restart_interval=restart_interval)
 
 
 def decode_jpeg(data: bytes) -> np.ndarray:

@@ -488,11 +488,19 @@ int emo_rows_to_frames_u8(const void* x, int64_t ld, uint8_t* y, int B, int C, i
  *   to end and starts every frame on a byte.  The stream is UNSTUFFED and unpadded: the host adds the 0x00 after every 0xFF and the
  *   1-bits that fill the last byte.  out must be zeroed up to the last stream byte, 4-byte aligned, out_bytes a multiple of 4: codes
  *   are OR-ed in as byte-swapped 32-bit words (atomicOr - blocks share words; OR commutes, so the result is the same every run), a word
- *   is touched only where a code has a 1-bit in it, and never at or beyond out_bytes. */
+ *   is touched only where a code has a 1-bit in it, and never at or beyond out_bytes.
+ * emo_jpeg_count_bits_ri / emo_jpeg_emit_bits_ri (T.81 B.2.4.4 DRI, E.1.4 restart intervals, F.1.1.5.1: "at the beginning of each
+ *   restart interval, the prediction for the DC coefficient is initialized to 0"): the two entries above for a scan with a restart
+ *   interval of restart_mcus > 0 MCUs.  The one difference: the DC predictor is 0 at the first MCU of every interval (MCUs 0, Ri, 2 Ri, ...
+ *   of each frame), not of every frame alone.  The caller starts every interval on a byte; the host pads each, stuffs it and puts the
+ *   RSTm markers between them.  restart_mcus >= n_mcu gives what the entries above give. */
 int emo_jpeg_blocks(const uint8_t* frames, int16_t* coefs, int n, int H, int W, const uint16_t* quant, void* stream);
 int emo_jpeg_count_bits(const int16_t* coefs, int32_t* counts, int n, int n_mcu, const uint32_t* huff, void* stream);
 int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
                        const uint32_t* huff, void* stream);
+int emo_jpeg_count_bits_ri(const int16_t* coefs, int32_t* counts, int n, int n_mcu, int restart_mcus, const uint32_t* huff, void* stream);
+int emo_jpeg_emit_bits_ri(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
+                          int restart_mcus, const uint32_t* huff, void* stream);
 
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
@@ -518,6 +526,20 @@ int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t
  *   tables: device int32 [4][EMO_JPEG_DECODE_TABLE_INTS] in the order DC luma, AC luma, DC chroma, AC chroma (Cb and Cr share theirs),
  *   each table = MINCODE[16] | MAXCODE[16] | VALPTR[16] | 16 unused | HUFFVAL[256] of T.81 F.2.2.3 / figure F.15, entry l - 1 for code
  *   length l, MAXCODE -1 where no code has that length.  (The kernel expands them into an 8-bit look-up in LDS.)
+ * emo_jpeg_decode_segments (T.81 B.2.4.4 DRI, E.1.4 restart intervals, F.1.1.5.1 / F.2.1.3.1 the DC predictions return to 0 at every
+ *   restart; the decoding procedures of F.2.2 as above): the same decoding, one wavefront per SEGMENT.  A segment is a run of whole MCUs
+ *   that starts on a byte with DC predictions 0: one restart interval (the bytes between two RSTm markers, the markers themselves and
+ *   the stuffed 0x00 bytes taken out by the host), or a whole frame that has no restart markers.  Segment s lies in bytes
+ *   seg_offsets[s] .. seg_offsets[s + 1] of `scan` (int64 [n_seg + 1], 8-byte aligned; scan as above) and fills seg_blocks[s] blocks (a
+ *   multiple of 6: whole MCUs) from block seg_first_block[s] on of coefs, blocks counted over the whole buffer of coef_blocks blocks of
+ *   64 int16 - for interval k of frame f with restart interval Ri: (f * n_mcu + k * Ri) * 6 and (min((k + 1) * Ri, n_mcu) - k * Ri) * 6,
+ *   so the buffer is the [n][n_mcu][6][64] emo_jpeg_decode_bits fills and emo_jpeg_idct reads.  Frames with different Ri, and frames
+ *   without markers, may share a launch.  Blocks no segment names are not written.  status int32 [n_seg], PER SEGMENT, the values
+ *   above with "segment" for "frame"; a segment with an error stops there, its blocks from the faulty one on are zeroed, other segments
+ *   are not touched.  seg_first_block and seg_blocks are clamped to coef_blocks (a segment that reaches past the buffer decodes the
+ *   blocks that fit and reports on those), seg_offsets to 0 .. scan_bytes and to run forwards: a bad table decodes wrong data or reports
+ *   a status, it never reads or writes outside the buffers.  Every loop is counted by the segment's blocks and 64 coefficients; behind
+ *   the set-up of the shared tables the waves of a workgroup meet no common barrier.
  * emo_jpeg_idct (T.81 A.3.4 dequantisation, A.3.3 IDCT in libjpeg's integer form jidctint.c jpeg_idct_islow): coefficient * quantiser,
  *   an 8-point pass over columns descaled by 11 bits, the same pass over rows descaled by 18, sample = clamp(value + 128, 0, 255).
  *   quant: device uint16 [2][64], luma then chroma, NATURAL order.  Output: y_plane uint8 [n][mcu_rows * 16][mcu_cols * 16] and c_planes
@@ -534,6 +556,9 @@ int emo_jpeg_emit_bits(const int16_t* coefs, const int64_t* bit_offsets, uint8_t
 enum { EMO_JPEG_OK = 0, EMO_JPEG_BAD_CODE = 1, EMO_JPEG_PAST_END = 2, EMO_JPEG_BAD_RUN = 3 };
 int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
                          int32_t* status, int n, int n_mcu, void* stream);
+int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
+                             const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks, int32_t* status,
+                             int n_seg, void* stream);
 int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream);
 int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream);
 
