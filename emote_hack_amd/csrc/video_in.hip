@@ -15,8 +15,28 @@
 //                           (1024 contiguous bytes), one column and then one row per lane
 //   emo_jpeg_upsample_rgb : libjpeg's h2v2 "fancy" (triangle) chroma up-sampling on the real chroma plane and its 16-bit fixed-point
 //                           YCbCr -> RGB (jdsample.c, jdcolor.c); every lane writes one whole dword of the packed frames
+// The four kernels are templates over the scan's layout - the number of components NC and the luminance sampling factors HS x VS (T.81
+// A.1.1, A.2.3), chrominance always 1 x 1 - so an MCU holds BPM = HS * VS + 2 blocks, or 1 when NC is 1:
+//   4:2:0  NC 3, 2 x 2, MCU 16 x 16, blocks Y00 Y01 Y10 Y11 Cb Cr   h2v2_fancy_upsample (jdsample.c), ycc_rgb_convert (jdcolor.c)
+//   4:2:2  NC 3, 2 x 1, MCU 16 x 8,  blocks Y0 Y1 Cb Cr             h2v1_fancy_upsample (jdsample.c), ycc_rgb_convert
+//   4:4:4  NC 3, 1 x 1, MCU 8 x 8,   blocks Y Cb Cr                 fullsize_upsample: chroma as it is, ycc_rgb_convert
+//   grey   NC 1,        MCU 8 x 8,   one block (not interleaved, T.81 A.2.2)   gray_rgb_convert (jdcolor.c): the sample three times
+// The four entries above are the 4:2:0 instances; emo_jpeg_layout_decode_bits / _decode_segments / _idct / _rgb take the layout as
+// three small ints and pick the instance.
 // Integer arithmetic throughout: the bytes are those libjpeg's default decoder gives.
 #include "common.h"
+
+// blocks per MCU of a layout; 0 for one that is not built
+static inline int jpeg_layout_bpm(int ncomp, int hs, int vs) {
+  if (ncomp == 1) return (hs == 1 && vs == 1) ? 1 : 0;
+  if (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return hs * vs + 2;
+  return 0;
+}
+// the component of block k of an MCU of BPM blocks: the luminance blocks first, then Cb, then Cr
+template <int BPM>
+__device__ __forceinline__ int jd_component(int k) {
+  return BPM == 1 ? 0 : (k < BPM - 2 ? 0 : k - (BPM - 3));
+}
 
 // natural (row-major) index of zig-zag position k (T.81 figure A.6)
 __device__ const uint8_t JPEG_NATURAL_OF[64] = {
@@ -149,6 +169,7 @@ __device__ __forceinline__ uint32_t jd_stage_dword(const uint8_t* __restrict__ s
   return v;
 }
 
+template <int BPM>
 __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
                                                                const int64_t* __restrict__ offsets, const int32_t* __restrict__ tables,
                                                                int16_t* __restrict__ coefs, int32_t* __restrict__ status, int n_mcu) {
@@ -160,7 +181,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
   __shared__ int sh_done, sh_status, sh_pred[3];
   const int t = threadIdx.x;
   const int frame = blockIdx.x;
-  const int n_blocks = n_mcu * 6;
+  const int n_blocks = n_mcu * BPM;
   // the frame's own bytes: [lo, hi) inside the buffer; offsets that leave it or run backwards give an empty frame
   int64_t lo = offsets[frame], hi = offsets[frame + 1];
   lo = min(max(lo, (int64_t)0), scan_bytes);
@@ -194,8 +215,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
       int st = EMO_JPEG_OK, nb = 0;
       for (; nb < JD_BLOCKS && done_blocks + nb < n_blocks; nb++) {
         if (!holds_end && (r.used() >> 3) + JD_BLOCK_BYTES_MAX > JD_STAGE_BYTES) break;    // the next block may leave the window
-        const int k6 = (done_blocks + nb) % 6;
-        const int comp = k6 < 4 ? 0 : k6 - 3;
+        const int comp = jd_component<BPM>((done_blocks + nb) % BPM);
         const int32_t* dc_tab = tab + (comp ? 2 : 0) * JD_TABLE_INTS;
         const uint16_t* dc_lut = lut[comp ? 2 : 0];
         st = jd_block(r, dc_tab, dc_lut, comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2), blk + nb * 64, byte0 * 8, frame_bits);
@@ -228,19 +248,36 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
   if (t == 0) status[frame] = sh_status != EMO_JPEG_OK ? sh_status : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
 }
 
-extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
-                                    int32_t* status, int n, int n_mcu, void* stream) {
-  EMO_CHECK(scan && offsets && tables && coefs && status, EMO_ERR_NULL, "emo_jpeg_decode_bits: null pointer");
-  EMO_CHECK(n > 0 && n_mcu > 0 && (int64_t)n * n_mcu * 6 < (int64_t)1 << 31 && (int64_t)n_mcu * 6 < (int64_t)1 << 24, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_decode_bits: n=%d n_mcu=%d", n, n_mcu);
+static int jpeg_decode_bits_launch(const char* who, const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables,
+                                   int16_t* coefs, int32_t* status, int n, int n_mcu, int bpm, void* stream) {
+  EMO_CHECK(scan && offsets && tables && coefs && status, EMO_ERR_NULL, "%s: null pointer", who);
+  EMO_CHECK(n > 0 && n_mcu > 0 && (int64_t)n * n_mcu * bpm < (int64_t)1 << 31 && (int64_t)n_mcu * bpm < (int64_t)1 << 24, EMO_ERR_BAD_SHAPE,
+            "%s: n=%d n_mcu=%d", who, n, n_mcu);
   EMO_CHECK(scan_bytes > 0 && scan_bytes % 4 == 0 && (uintptr_t)scan % 4 == 0, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_decode_bits: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4",
-            (long long)scan_bytes);
+            "%s: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4", who, (long long)scan_bytes);
   EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)offsets % 8 == 0, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_decode_bits: coefs must be 16-byte aligned, offsets 8-byte aligned");
-  jpeg_decode_bits_kernel<<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu);
+            "%s: coefs must be 16-byte aligned, offsets 8-byte aligned", who);
+  switch (bpm) {
+    case 1: jpeg_decode_bits_kernel<1><<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu); break;
+    case 3: jpeg_decode_bits_kernel<3><<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu); break;
+    case 4: jpeg_decode_bits_kernel<4><<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu); break;
+    default: jpeg_decode_bits_kernel<6><<<n, 256, 0, as_stream(stream)>>>(scan, scan_bytes, offsets, tables, coefs, status, n_mcu); break;
+  }
   EMO_LAUNCH_CHECK();
   return EMO_OK;
+}
+
+extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
+                                    int32_t* status, int n, int n_mcu, void* stream) {
+  return jpeg_decode_bits_launch("emo_jpeg_decode_bits", scan, scan_bytes, offsets, tables, coefs, status, n, n_mcu, 6, stream);
+}
+
+extern "C" int emo_jpeg_layout_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables,
+                                           int16_t* coefs, int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream) {
+  const int bpm = jpeg_layout_bpm(ncomp, hs, vs);
+  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_decode_bits: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built",
+            ncomp, hs, vs);
+  return jpeg_decode_bits_launch("emo_jpeg_layout_decode_bits", scan, scan_bytes, offsets, tables, coefs, status, n, n_mcu, bpm, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------ segments in parallel
@@ -256,6 +293,7 @@ __device__ __forceinline__ void jd_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+template <int BPM>
 __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
                                                                               const int64_t* __restrict__ seg_offsets,
                                                                               const int32_t* __restrict__ seg_first_block,
@@ -301,8 +339,7 @@ __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(con
       const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
       for (; nb < JD_BLOCKS && done_blocks + nb < n_blocks; nb++) {
         if (!holds_end && (r.used() >> 3) + JD_BLOCK_BYTES_MAX > JD_STAGE_BYTES) break;    // the next block may leave the window
-        const int k6 = (done_blocks + nb) % 6;               // a segment starts with an MCU
-        const int comp = k6 < 4 ? 0 : k6 - 3;
+        const int comp = jd_component<BPM>((done_blocks + nb) % BPM);      // a segment starts with an MCU
         st = jd_block(r, tab + (comp ? 2 : 0) * JD_TABLE_INTS, lut[comp ? 2 : 0], comp == 0 ? pred0 : (comp == 1 ? pred1 : pred2),
                       blk + nb * 64, byte0 * 8, seg_bits);
         if (st != EMO_JPEG_OK) break;                        // the block the error is in is dropped with the rest of the segment
@@ -330,23 +367,48 @@ __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(con
   if (lane == 0) status[seg] = st != EMO_JPEG_OK ? st : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
 }
 
+static int jpeg_decode_segments_launch(const char* who, const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets,
+                                       const int32_t* seg_first_block, const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs,
+                                       int64_t coef_blocks, int32_t* status, int n_seg, int bpm, void* stream) {
+  EMO_CHECK(scan && seg_offsets && seg_first_block && seg_blocks && tables && coefs && status, EMO_ERR_NULL, "%s: null pointer", who);
+  EMO_CHECK(n_seg > 0 && n_seg <= (1 << 30) && coef_blocks > 0 && coef_blocks < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE,
+            "%s: n_seg=%d coef_blocks=%lld", who, n_seg, (long long)coef_blocks);
+  EMO_CHECK(scan_bytes > 0 && scan_bytes % 4 == 0 && (uintptr_t)scan % 4 == 0, EMO_ERR_BAD_SHAPE,
+            "%s: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4", who, (long long)scan_bytes);
+  EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)seg_offsets % 8 == 0 && (uintptr_t)seg_first_block % 4 == 0 &&
+                (uintptr_t)seg_blocks % 4 == 0,
+            EMO_ERR_BAD_SHAPE, "%s: coefs must be 16-byte aligned, seg_offsets 8-byte, the block tables 4-byte aligned", who);
+  const dim3 grid((n_seg + JS_WAVES - 1) / JS_WAVES), block(64 * JS_WAVES);
+#define JS_LAUNCH(BPM)                                                                                                                \
+  jpeg_decode_segments_kernel<BPM><<<grid, block, 0, as_stream(stream)>>>(scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, \
+                                                                          tables, coefs, coef_blocks, status, n_seg)
+  switch (bpm) {
+    case 1: JS_LAUNCH(1); break;
+    case 3: JS_LAUNCH(3); break;
+    case 4: JS_LAUNCH(4); break;
+    default: JS_LAUNCH(6); break;
+  }
+#undef JS_LAUNCH
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
 extern "C" int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
                                         const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks,
                                         int32_t* status, int n_seg, void* stream) {
-  EMO_CHECK(scan && seg_offsets && seg_first_block && seg_blocks && tables && coefs && status, EMO_ERR_NULL,
-            "emo_jpeg_decode_segments: null pointer");
-  EMO_CHECK(n_seg > 0 && n_seg <= (1 << 30) && coef_blocks > 0 && coef_blocks < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_decode_segments: n_seg=%d coef_blocks=%lld", n_seg, (long long)coef_blocks);
-  EMO_CHECK(scan_bytes > 0 && scan_bytes % 4 == 0 && (uintptr_t)scan % 4 == 0, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_decode_segments: the scan buffer is read as 32-bit words: scan 4-byte aligned, scan_bytes (%lld) a multiple of 4",
-            (long long)scan_bytes);
-  EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)seg_offsets % 8 == 0 && (uintptr_t)seg_first_block % 4 == 0 &&
-                (uintptr_t)seg_blocks % 4 == 0,
-            EMO_ERR_BAD_SHAPE, "emo_jpeg_decode_segments: coefs must be 16-byte aligned, seg_offsets 8-byte, the block tables 4-byte aligned");
-  jpeg_decode_segments_kernel<<<(n_seg + JS_WAVES - 1) / JS_WAVES, 64 * JS_WAVES, 0, as_stream(stream)>>>(
-      scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables, coefs, coef_blocks, status, n_seg);
-  EMO_LAUNCH_CHECK();
-  return EMO_OK;
+  return jpeg_decode_segments_launch("emo_jpeg_decode_segments", scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables, coefs,
+                                     coef_blocks, status, n_seg, 6, stream);
+}
+
+extern "C" int emo_jpeg_layout_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets,
+                                               const int32_t* seg_first_block, const int32_t* seg_blocks, const int32_t* tables,
+                                               int16_t* coefs, int64_t coef_blocks, int32_t* status, int n_seg, int ncomp, int hs, int vs,
+                                               void* stream) {
+  const int bpm = jpeg_layout_bpm(ncomp, hs, vs);
+  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_decode_segments: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built",
+            ncomp, hs, vs);
+  return jpeg_decode_segments_launch("emo_jpeg_layout_decode_segments", scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables,
+                                     coefs, coef_blocks, status, n_seg, bpm, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------ dequantisation, IDCT
@@ -384,14 +446,18 @@ __device__ __forceinline__ void jpeg_idct_1d(const int32_t* in, int32_t* out) {
 
 // A wavefront takes 8 consecutive blocks (1024 contiguous bytes): lane = (block, eighth) loads 8 coefficients as one 16-byte vector,
 // then lane = (block, column) runs pass 1 and lane = (block, row) pass 2, and stores its 8 samples as one 8-byte vector.
+// NQ quantisers: 2 - luminance, chrominance - or one per component.  The planes are padded to whole MCUs: luminance rows of
+// mcu_cols * 8 * HS bytes, chrominance rows of mcu_cols * 8, multiples of 8, so the 8-byte store stays aligned.
+template <int NC, int HS, int VS, int NQ>
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coefs, const uint16_t* __restrict__ quant,
                                                         uint8_t* __restrict__ yp, uint8_t* __restrict__ cp, int64_t n_blocks, int n_mcu,
                                                         int mcu_cols, int mcu_rows) {
   __shared__ __attribute__((aligned(16))) int32_t ws[4][8 * JI_LD];
-  __shared__ uint16_t q[2][64];
+  constexpr int NY = NC == 1 ? 1 : HS * VS, BPM = NC == 1 ? 1 : NY + 2;      // luminance blocks, all blocks of an MCU
+  __shared__ uint16_t q[NQ][64];
   __shared__ uint8_t nat[64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t < 128) q[t >> 6][t & 63] = quant[t];
+  if (t < NQ * 64) q[t >> 6][t & 63] = quant[t];
   if (t < 64) nat[t] = JPEG_NATURAL_OF[t];
   __syncthreads();
   int32_t* w = ws[wave] + (lane >> 3) * JI_LD;              // this lane's block
@@ -400,12 +466,12 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   for (int64_t g0 = (int64_t)blockIdx.x * 4; g0 < n_groups; g0 += (int64_t)gridDim.x * 4) {        // uniform over the workgroup
     const int64_t b = (g0 + wave) * 8 + (lane >> 3);
     const bool live = b < n_blocks;
-    const int64_t frame = b / ((int64_t)n_mcu * 6);
-    const int in_frame = (int)(b - frame * n_mcu * 6), m = in_frame / 6, k6 = in_frame - m * 6;
+    const int64_t frame = b / ((int64_t)n_mcu * BPM);
+    const int in_frame = (int)(b - frame * n_mcu * BPM), m = in_frame / BPM, k = in_frame - m * BPM;
     if (live) {
       const uint4 v = *(const uint4*)(coefs + b * 64 + sub * 8);
       const uint32_t pk[4] = {v.x, v.y, v.z, v.w};
-      const uint16_t* qq = q[k6 >= 4];
+      const uint16_t* qq = q[NQ == 2 ? (k >= NY) : (k < NY ? 0 : k - NY + 1)];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const int c = (int16_t)(pk[j >> 1] >> ((j & 1) * 16));
@@ -435,11 +501,11 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
       }
       const int my = m / mcu_cols, mx = m - my * mcu_cols;
       uint8_t* dst;
-      if (k6 < 4) {
-        const int64_t row = (frame * mcu_rows + my) * 16 + (k6 >> 1) * 8 + sub;
-        dst = yp + row * ((int64_t)mcu_cols * 16) + mx * 16 + (k6 & 1) * 8;
+      if (k < NY) {
+        const int64_t row = (frame * mcu_rows + my) * (8 * VS) + (k / HS) * 8 + sub;
+        dst = yp + row * ((int64_t)mcu_cols * (8 * HS)) + mx * (8 * HS) + (k % HS) * 8;
       } else {
-        const int64_t row = ((frame * 2 + (k6 - 4)) * mcu_rows + my) * 8 + sub;
+        const int64_t row = ((frame * 2 + (k - NY)) * mcu_rows + my) * 8 + sub;
         dst = cp + row * ((int64_t)mcu_cols * 8) + mx * 8;
       }
       *(uint2*)dst = make_uint2(p0, p1);
@@ -447,31 +513,60 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
   }
 }
 
-static int jpeg_geometry(const char* who, int n, int H, int W, int* mcu_rows, int* mcu_cols) {
+// the MCU grid of n frames of H x W at luminance factors hs x vs, bpm blocks per MCU
+static int jpeg_geometry(const char* who, int n, int H, int W, int hs, int vs, int bpm, int* mcu_rows, int* mcu_cols) {
   EMO_CHECK(n > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535, EMO_ERR_BAD_SHAPE, "%s: n=%d H=%d W=%d (1 .. 65535: SOF0 holds 16 bits)", who, n, H, W);
-  *mcu_cols = (W + 15) / 16;
-  *mcu_rows = (H + 15) / 16;
-  EMO_CHECK((int64_t)*mcu_cols * *mcu_rows * n * 6 < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE, "%s: %lld blocks", who,
-            (long long)*mcu_cols * *mcu_rows * n * 6);
+  *mcu_cols = (W + 8 * hs - 1) / (8 * hs);
+  *mcu_rows = (H + 8 * vs - 1) / (8 * vs);
+  EMO_CHECK((int64_t)*mcu_cols * *mcu_rows * n * bpm < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE, "%s: %lld blocks", who,
+            (long long)*mcu_cols * *mcu_rows * n * bpm);
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream) {
-  EMO_CHECK(coefs && quant && y_plane && c_planes, EMO_ERR_NULL, "emo_jpeg_idct: null pointer");
+template <int NC, int HS, int VS, int NQ>
+static int jpeg_idct_launch(const char* who, const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H,
+                            int W, void* stream) {
+  constexpr int BPM = NC == 1 ? 1 : HS * VS + 2;
+  EMO_CHECK(coefs && quant && y_plane && (c_planes || NC == 1), EMO_ERR_NULL, "%s: null pointer", who);
   int mcu_rows = 0, mcu_cols = 0;
-  const int rc = jpeg_geometry("emo_jpeg_idct", n, H, W, &mcu_rows, &mcu_cols);
+  const int rc = jpeg_geometry(who, n, H, W, HS, VS, BPM, &mcu_rows, &mcu_cols);
   if (rc != EMO_OK) return rc;
   EMO_CHECK((uintptr_t)coefs % 16 == 0 && (uintptr_t)y_plane % 8 == 0 && (uintptr_t)c_planes % 8 == 0, EMO_ERR_BAD_SHAPE,
-            "emo_jpeg_idct: coefs must be 16-byte aligned, the planes 8-byte aligned");
+            "%s: coefs must be 16-byte aligned, the planes 8-byte aligned", who);
   const int n_mcu = mcu_rows * mcu_cols;
-  const int64_t n_blocks = (int64_t)n * n_mcu * 6, g = (n_blocks + 31) / 32;
-  jpeg_idct_kernel<<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, quant, y_plane, c_planes, n_blocks, n_mcu, mcu_cols, mcu_rows);
+  const int64_t n_blocks = (int64_t)n * n_mcu * BPM, g = (n_blocks + 31) / 32;
+  jpeg_idct_kernel<NC, HS, VS, NQ><<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, quant, y_plane, c_planes, n_blocks, n_mcu,
+                                                                                               mcu_cols, mcu_rows);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
+extern "C" int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream) {
+  return jpeg_idct_launch<3, 2, 2, 2>("emo_jpeg_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+}
+
+extern "C" int emo_jpeg_layout_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W,
+                                    int ncomp, int hs, int vs, void* stream) {
+  switch (jpeg_layout_bpm(ncomp, hs, vs)) {
+    case 1: return jpeg_idct_launch<1, 1, 1, 1>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 3: return jpeg_idct_launch<3, 1, 1, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 4: return jpeg_idct_launch<3, 2, 1, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 6: return jpeg_idct_launch<3, 2, 2, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+  }
+  return emo_fail(EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_idct: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built", ncomp,
+                  hs, vs);
+}
+
 // ------------------------------------------------------------------------------------------------------------ chroma up-sampling, colour
-// One pixel: h2v2_fancy_upsample (jdsample.c) on the chroma plane of ch x cw real samples, then jdcolor.c's fixed-point transform.
+// ycc_rgb_convert (jdcolor.c): the 16-bit fixed-point transform, cb and cr less 128; R | G << 8 | B << 16
+__device__ __forceinline__ uint32_t jpeg_ycc_rgb(int lum, int cb, int cr) {
+  const int R = lum + ((91881 * cr + 32768) >> 16);
+  const int G = lum + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+  const int B = lum + ((116130 * cb + 32768) >> 16);
+  return (uint32_t)min(max(R, 0), 255) | (uint32_t)min(max(G, 0), 255) << 8 | (uint32_t)min(max(B, 0), 255) << 16;
+}
+
+// One pixel of a 4:2:0 frame: h2v2_fancy_upsample (jdsample.c) on the chroma plane of ch x cw real samples, then the transform.
 __device__ __forceinline__ uint32_t jpeg_pixel_rgb(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp, int64_t frame, int y, int x,
                                                    int ch, int cw, int64_t y_ld, int64_t y_rows, int64_t c_ld, int64_t c_rows) {
   const int r = y >> 1, c = x >> 1;
@@ -486,20 +581,45 @@ __device__ __forceinline__ uint32_t jpeg_pixel_rgb(const uint8_t* __restrict__ y
     const int s_side = 3 * (int)p[r * c_ld + cn] + (int)p[rn * c_ld + cn];
     cc[k] = ((3 * s_here + s_side + bias) >> 4) - 128;
   }
-  const int lum = yp[(frame * y_rows + y) * y_ld + x];
-  const int cb = cc[0], cr = cc[1];
-  const int R = lum + ((91881 * cr + 32768) >> 16);
-  const int G = lum + ((-22554 * cb - 46802 * cr + 32768) >> 16);
-  const int B = lum + ((116130 * cb + 32768) >> 16);
-  return (uint32_t)min(max(R, 0), 255) | (uint32_t)min(max(G, 0), 255) << 8 | (uint32_t)min(max(B, 0), 255) << 16;
+  return jpeg_ycc_rgb(yp[(frame * y_rows + y) * y_ld + x], cc[0], cc[1]);
+}
+
+// One pixel of a 4:2:2 frame: h2v1_fancy_upsample (jdsample.c) along the row - p the chroma sample at column x >> 1, even columns
+// (3 p + left + 1) >> 2, odd ones (3 p + right + 2) >> 2, the neighbour clamped to the cw real samples, which gives libjpeg's first and
+// last columns - and no filter down the columns.
+__device__ __forceinline__ uint32_t jpeg_pixel_rgb_h2v1(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp, int64_t frame, int y, int x,
+                                                        int cw, int64_t y_ld, int64_t y_rows, int64_t c_ld, int64_t c_rows) {
+  const int c = x >> 1;
+  const int cn = min(max((x & 1) ? c + 1 : c - 1, 0), cw - 1);
+  const int bias = (x & 1) ? 2 : 1;
+  int cc[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const uint8_t* p = cp + ((frame * 2 + k) * c_rows + y) * c_ld;
+    cc[k] = ((3 * (int)p[c] + (int)p[cn] + bias) >> 2) - 128;
+  }
+  return jpeg_ycc_rgb(yp[(frame * y_rows + y) * y_ld + x], cc[0], cc[1]);
+}
+
+// One pixel of a 4:4:4 frame (fullsize_upsample: the chroma sample of the pixel itself) or of a grey one (gray_rgb_convert: the sample
+// in all three channels, no transform).
+template <int NC>
+__device__ __forceinline__ uint32_t jpeg_pixel_rgb_full(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp, int64_t frame, int y, int x,
+                                                        int64_t y_ld, int64_t y_rows) {
+  const int64_t at = (frame * y_rows + y) * y_ld + x;
+  const uint32_t lum = yp[at];
+  if (NC == 1) return lum * 0x010101u;
+  const int64_t plane = y_rows * y_ld;                       // chroma planes of the luminance plane's size
+  return jpeg_ycc_rgb((int)lum, (int)cp[at + frame * plane] - 128, (int)cp[at + (frame + 1) * plane] - 128);
 }
 
 // lane = one dword of the packed output: bytes 4 d .. 4 d + 3 belong to pixels (4 d) / 3 and the one behind it
+template <int NC, int HS, int VS>
 __global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp,
                                                                 uint8_t* __restrict__ rgb, int64_t total_bytes, int H, int W, int mcu_rows,
                                                                 int mcu_cols) {
   const int ch = (H + 1) / 2, cw = (W + 1) / 2;
-  const int64_t y_ld = (int64_t)mcu_cols * 16, y_rows = (int64_t)mcu_rows * 16, c_ld = (int64_t)mcu_cols * 8, c_rows = (int64_t)mcu_rows * 8;
+  const int64_t y_ld = (int64_t)mcu_cols * (8 * HS), y_rows = (int64_t)mcu_rows * (8 * VS), c_ld = (int64_t)mcu_cols * 8, c_rows = (int64_t)mcu_rows * 8;
   const int64_t n_pix = total_bytes / 3, n_dwords = (total_bytes + 3) / 4;
   for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < n_dwords; d += (int64_t)gridDim.x * 256) {
     const int64_t byte0 = d * 4, p0 = byte0 / 3;
@@ -513,7 +633,11 @@ __global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* _
         const int x = (int)(p - row * W);
         const int64_t frame = row / H;
         const int y = (int)(row - frame * H);
-        two |= (uint64_t)jpeg_pixel_rgb(yp, cp, frame, y, x, ch, cw, y_ld, y_rows, c_ld, c_rows) << (24 * k);
+        uint32_t px;
+        if (NC == 3 && HS == 2 && VS == 2) px = jpeg_pixel_rgb(yp, cp, frame, y, x, ch, cw, y_ld, y_rows, c_ld, c_rows);
+        else if (NC == 3 && HS == 2) px = jpeg_pixel_rgb_h2v1(yp, cp, frame, y, x, cw, y_ld, y_rows, c_ld, c_rows);
+        else px = jpeg_pixel_rgb_full<NC>(yp, cp, frame, y, x, y_ld, y_rows);
+        two |= (uint64_t)px << (24 * k);
       }
     }
     const uint32_t v = (uint32_t)(two >> (8 * phase));
@@ -525,14 +649,32 @@ __global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* _
   }
 }
 
-extern "C" int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
-  EMO_CHECK(y_plane && c_planes && rgb, EMO_ERR_NULL, "emo_jpeg_upsample_rgb: null pointer");
+template <int NC, int HS, int VS>
+static int jpeg_rgb_launch(const char* who, const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
+  EMO_CHECK(y_plane && (c_planes || NC == 1) && rgb, EMO_ERR_NULL, "%s: null pointer", who);
   int mcu_rows = 0, mcu_cols = 0;
-  const int rc = jpeg_geometry("emo_jpeg_upsample_rgb", n, H, W, &mcu_rows, &mcu_cols);
+  const int rc = jpeg_geometry(who, n, H, W, HS, VS, NC == 1 ? 1 : HS * VS + 2, &mcu_rows, &mcu_cols);
   if (rc != EMO_OK) return rc;
-  EMO_CHECK((uintptr_t)rgb % 4 == 0, EMO_ERR_BAD_SHAPE, "emo_jpeg_upsample_rgb: rgb must be 4-byte aligned");
+  EMO_CHECK((uintptr_t)rgb % 4 == 0, EMO_ERR_BAD_SHAPE, "%s: rgb must be 4-byte aligned", who);
   const int64_t total = (int64_t)n * H * W * 3, g = ((total + 3) / 4 + 255) / 256;
-  jpeg_upsample_rgb_kernel<<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(y_plane, c_planes, rgb, total, H, W, mcu_rows, mcu_cols);
+  jpeg_upsample_rgb_kernel<NC, HS, VS><<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(y_plane, c_planes, rgb, total, H, W, mcu_rows,
+                                                                                                     mcu_cols);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
+}
+
+extern "C" int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
+  return jpeg_rgb_launch<3, 2, 2>("emo_jpeg_upsample_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+}
+
+extern "C" int emo_jpeg_layout_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
+                                   void* stream) {
+  switch (jpeg_layout_bpm(ncomp, hs, vs)) {
+    case 1: return jpeg_rgb_launch<1, 1, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+    case 3: return jpeg_rgb_launch<3, 1, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+    case 4: return jpeg_rgb_launch<3, 2, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+    case 6: return jpeg_rgb_launch<3, 2, 2>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+  }
+  return emo_fail(EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_rgb: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built", ncomp, hs,
+                  vs);
 }

@@ -933,6 +933,113 @@ def jpeg_upsample_rgb(y: torch.Tensor, c: torch.Tensor, H: int, W: int, out=None
     return rgb
 
 
+JPEG_LAYOUTS = {(3, 2, 2): "4:2:0", (3, 2, 1): "4:2:2", (3, 1, 1): "4:4:4", (1, 1, 1): "grey"}      # (components, luminance h, v)
+
+
+def _jpeg_layout(layout):
+    layout = tuple(int(v) for v in layout)
+    assert layout in JPEG_LAYOUTS, f"a layout is (components, luminance h, luminance v), one of {sorted(JPEG_LAYOUTS)}; got {layout}"
+    return layout
+
+
+def jpeg_layout_bpm(layout) -> int:
+    """blocks per MCU: the luminance blocks, Cb, Cr; one for a grey scan, which is not interleaved (T.81 A.2.2, A.2.3)"""
+    nc, hs, vs = _jpeg_layout(layout)
+    return 1 if nc == 1 else hs * vs + 2
+
+
+def jpeg_layout_grid(H: int, W: int, layout):
+    """(MCU rows, MCU columns) of an (H, W) frame: MCUs of 8 h x 8 v pixels"""
+    _, hs, vs = _jpeg_layout(layout)
+    return (int(H) + 8 * vs - 1) // (8 * vs), (int(W) + 8 * hs - 1) // (8 * hs)
+
+
+def jpeg_layout_mcus(H: int, W: int, layout) -> int:
+    """MCUs of an (H, W) frame in `layout`: jpeg_mcus for every layout (for grey, the 8x8 blocks of the frame)"""
+    mr, mc = jpeg_layout_grid(H, W, layout)
+    return mr * mc
+
+
+def jpeg_layout_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Tensor, n_mcu: int, layout, out=None, status=None):
+    """jpeg_decode_bits for a scan in `layout`, a key of JPEG_LAYOUTS -> (coefficients int16 (n, n_mcu, bpm, 64), status int32 (n))
+    (emo_jpeg_layout_decode_bits; T.81 A.2.3, F.2.2).  tables as there: the first pair decodes component 0, the second Cb and Cr."""
+    _need_cuda(scan, offsets, tables)
+    nc, hs, vs = _jpeg_layout(layout)
+    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
+    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
+    n, n_mcu = offsets.numel() - 1, int(n_mcu)
+    coefs = _jpeg_out(out, (n, n_mcu, jpeg_layout_bpm(layout), 64), torch.int16, scan.device, "coefs")
+    status = _jpeg_out(status, (n,), torch.int32, scan.device, "status")
+    _launch("jpeg_layout_decode_bits", 0.0, float(scan.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_layout_decode_bits(_ptr(scan), scan.numel(), _ptr(offsets), _ptr(tables), _ptr(coefs), _ptr(status), n,
+                                                                  n_mcu, nc, hs, vs, _stream()), "emo_jpeg_layout_decode_bits"),
+            tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{n_mcu}")
+    return coefs, status
+
+
+def jpeg_layout_decode_segments(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_first_block: torch.Tensor, seg_blocks: torch.Tensor,
+                                tables: torch.Tensor, n: int, n_mcu: int, layout, out=None, status=None):
+    """jpeg_decode_segments for scans in `layout` -> (coefficients int16 (n, n_mcu, bpm, 64), status int32 (n_seg))
+    (emo_jpeg_layout_decode_segments).  The segment table counts blocks, bpm to an MCU."""
+    _need_cuda(scan, seg_offsets, seg_first_block, seg_blocks, tables)
+    nc, hs, vs = _jpeg_layout(layout)
+    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
+    assert seg_offsets.dtype == torch.int64 and seg_offsets.dim() == 1 and seg_offsets.numel() >= 2 and seg_offsets.is_contiguous(), (seg_offsets.dtype, seg_offsets.shape)
+    n_seg = seg_offsets.numel() - 1
+    for tab in (seg_first_block, seg_blocks):
+        assert tab.dtype == torch.int32 and tuple(tab.shape) == (n_seg,) and tab.is_contiguous(), (tab.dtype, tab.shape, n_seg)
+    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
+    n, n_mcu, bpm = int(n), int(n_mcu), jpeg_layout_bpm(layout)
+    coefs = _jpeg_out(out, (n, n_mcu, bpm, 64), torch.int16, scan.device, "coefs")
+    status = _jpeg_out(status, (n_seg,), torch.int32, scan.device, "status")
+    _launch("jpeg_layout_decode_segments", 0.0, float(scan.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_layout_decode_segments(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_first_block),
+                                                                      _ptr(seg_blocks), _ptr(tables), _ptr(coefs), n * n_mcu * bpm, _ptr(status),
+                                                                      n_seg, nc, hs, vs, _stream()), "emo_jpeg_layout_decode_segments"),
+            tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n_seg}/{n}x{n_mcu}")
+    return coefs, status
+
+
+def jpeg_layout_idct(coefs: torch.Tensor, quant: torch.Tensor, H: int, W: int, layout, out_y=None, out_c=None):
+    """coefficients int16 (n, MCUs, bpm, 64) of (H, W) frames in `layout` -> (Y plane uint8 (n, mr * 8 v, mc * 8 h), Cb / Cr planes uint8
+    (n, 2, mr * 8, mc * 8); None for grey), mr, mc = jpeg_layout_grid(H, W, layout) (emo_jpeg_layout_idct).  quant: device uint16
+    (3, 64), one quantiser per component, natural order."""
+    _need_cuda(coefs, quant)
+    nc, hs, vs = _jpeg_layout(layout)
+    H, W = int(H), int(W)
+    mr, mc = jpeg_layout_grid(H, W, layout)
+    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[1:]) == (mr * mc, jpeg_layout_bpm(layout), 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
+    assert quant.dtype == torch.uint16 and quant.numel() == 192 and quant.is_contiguous(), (quant.dtype, quant.shape)
+    n = coefs.shape[0]
+    y = _jpeg_out(out_y, (n, mr * 8 * vs, mc * 8 * hs), torch.uint8, coefs.device, "y plane")
+    c = _jpeg_out(out_c, (n, 2, mr * 8, mc * 8), torch.uint8, coefs.device, "chroma planes") if nc == 3 else None
+    _launch("jpeg_layout_idct", 0.0, float(2 * coefs.numel() + y.numel() + (c.numel() if nc == 3 else 0)),
+            lambda: check(_lib.load().emo_jpeg_layout_idct(_ptr(coefs), _ptr(quant), _ptr(y), _ptr(c) if nc == 3 else None, n, H, W, nc, hs, vs,
+                                                           _stream()), "emo_jpeg_layout_idct"),
+            tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{H}x{W}")
+    return y, c
+
+
+def jpeg_layout_rgb(y: torch.Tensor, c, H: int, W: int, layout, out=None) -> torch.Tensor:
+    """jpeg_layout_idct's planes -> packed uint8 RGB frames (n, H, W, 3): libjpeg's chroma up-sampling of the layout and its fixed-point
+    colour transform; a grey frame's sample in all three channels (emo_jpeg_layout_rgb).  c: None for grey."""
+    nc, hs, vs = _jpeg_layout(layout)
+    _need_cuda(*((y, c) if nc == 3 else (y,)))
+    H, W = int(H), int(W)
+    mr, mc = jpeg_layout_grid(H, W, layout)
+    n = y.shape[0]
+    assert y.dtype == torch.uint8 and tuple(y.shape) == (n, mr * 8 * vs, mc * 8 * hs) and y.is_contiguous(), (y.dtype, y.shape)
+    if nc == 3:
+        assert c.dtype == torch.uint8 and tuple(c.shape) == (n, 2, mr * 8, mc * 8) and c.is_contiguous(), (c.dtype, c.shape)
+    rgb = _jpeg_out(out, (n, H, W, 3), torch.uint8, y.device, "frames")
+    _launch("jpeg_layout_rgb", 0.0, float(y.numel() + (c.numel() if nc == 3 else 0) + rgb.numel()),
+            lambda: check(_lib.load().emo_jpeg_layout_rgb(_ptr(y), _ptr(c) if nc == 3 else None, _ptr(rgb), n, H, W, nc, hs, vs, _stream()),
+                          "emo_jpeg_layout_rgb"),
+            tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{H}x{W}")
+    return rgb
+
+
 def image_resize(frames: torch.Tensor, h: int, w: int, xtaps=None, ytaps=None, out=None) -> torch.Tensor:
     """packed uint8 RGB frames (n, H, W, 3) -> (n, h, w, 3): Pillow's resize of 8-bit pixels, a horizontal integer pass to 8-bit pixels and
     a vertical one over those (emo_image_resize; animation.py:174-185).  xtaps / ytaps: (bounds int32 (w | h, 2), coef int32 (w | h, k))

@@ -1031,9 +1031,10 @@ class EMOAnimationPipeline:
     def _source_image_latents(self, source_image, width, height, resample=None):
         """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is.  A Motion-JPEG `.avi`
         path gives its first frame (animation.py:182-185), decoded on the device at (height, width) - resized there under resample=, as
-        _clip_frames does - and encoded from there."""
+        _clip_frames does - and encoded from there.  A baseline `.jpg` / `.jpeg` path is decoded and resized to (width, height) on the
+        device as well (video_io.read_image, byte for byte the pixels PIL's open + resize give); what parse_jpeg refuses is PIL's."""
         rgb = self._source_image_rgb(source_image, width, height, resample)
-        if torch.is_tensor(rgb):          # the first frame of a clip, on the device
+        if torch.is_tensor(rgb):          # a still JPEG or the first frame of a clip, on the device
             if self.vae is None:
                 raise ValueError("images2latents needs a VAE (emote_hack_amd.vae.AutoencoderKL)")
             return self._normalised2latents(self._device_u8_scaled(rgb[None], 127.5, 1.0).permute(0, 3, 1, 2).contiguous())
@@ -1048,6 +1049,22 @@ class EMOAnimationPipeline:
             if frame.shape[0] % 8 or frame.shape[1] % 8:
                 raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
             return frame
+        if isinstance(source_image, str) and source_image.lower().endswith((".jpg", ".jpeg")):
+            # a baseline JPEG file is decoded and resized on the device (read_image: both byte for byte as Pillow does, "bicubic" being
+            # the filter of the `.resize((width, height))` below) and stays there; what parse_jpeg refuses - a progressive file, say -
+            # is Pillow's, like every other format
+            from . import video_io
+            with open(source_image, "rb") as f:
+                data = f.read()
+            try:
+                video_io.parse_jpeg(data, restart=True, layouts=True)
+            except ValueError:
+                data = None
+            if data is not None:
+                frame = video_io.read_image(data, size=(width, height), resample="bicubic")
+                if frame.shape[0] % 8 or frame.shape[1] % 8:
+                    raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
+                return frame
         if isinstance(source_image, str):
             from PIL import Image
             source_image = np.array(Image.open(source_image).convert("RGB").resize((width, height)))

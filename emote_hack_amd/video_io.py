@@ -14,11 +14,14 @@
   read_avi          the reverse, for files write_avi made
   parse_jpeg        one baseline 4:2:0 file -> its size, tables and scan with the stuffed 0x00 bytes taken out (the reverse of jpeg_header
                     and finish_scan); anything else a JPEG file may be is refused by name.  restart=True also takes files with restart
-                    intervals: the RSTm markers are checked and taken out, and the intervals' boundaries kept
-  decode_mjpeg      JPEG files -> packed uint8 frames on the device: per set of tables ONE host-to-device copy of the scans and the
-                    segment table, then emo_jpeg_decode_segments (one wavefront per restart interval; emo_jpeg_decode_bits, one
-                    workgroup per frame, where no frame has restart intervals), emo_jpeg_idct, emo_jpeg_upsample_rgb
+                    intervals: the RSTm markers are checked and taken out, and the intervals' boundaries kept.  layouts=True also takes
+                    4:2:2, 4:4:4 and grey files and one quantiser per component; ParsedJpeg.layout says what the file is
+  decode_mjpeg      JPEG files (4:2:0, 4:2:2, 4:4:4, grey) -> packed uint8 frames on the device: per set of tables and layout ONE
+                    host-to-device copy of the scans and the segment table, then emo_jpeg_decode_segments (one wavefront per restart
+                    interval; emo_jpeg_decode_bits, one workgroup per frame, where no frame has restart intervals), emo_jpeg_idct,
+                    emo_jpeg_upsample_rgb - or their emo_jpeg_layout_* counterparts for everything but plain 4:2:0 -
                     (csrc/video_in.hip) and one read of the segments' status - the bytes libjpeg's default decoder gives
+  read_image        one JPEG file -> an (H, W, 3) uint8 frame on the device through decode_mjpeg, resized there under size=
   read_video        read_avi + decode_mjpeg: what `VideoReader(path).read()` is to magicanimate/pipelines/animation.py:174-185
   resize_taps       the per-axis coefficient table of Pillow's `Image.resize` for 8-bit images (Resample.c), in 22-bit fixed point
   resize_frames     `Image.fromarray(f).resize((width, height), filter)` of device frames, byte for byte: emo_image_resize
@@ -260,7 +263,8 @@ def encode_mjpeg(frames_u8: torch.Tensor, quality: int = 90, restart_interval=No
 
 
 # ---------------------------------------------------------------------------------------------------------------------- JPEG parsing
-JPEG_MIN_WIDTH = 5      # libjpeg replicates chroma samples instead of filtering when the chroma plane is at most 2 wide; that is not built
+JPEG_MIN_WIDTH = 5      # where chroma is halved along the rows (4:2:0, 4:2:2): libjpeg replicates chroma samples instead of filtering when
+#                         the chroma plane is at most 2 wide; that is not built
 
 
 def huffman_decode_table(bits, huffval) -> np.ndarray:
@@ -286,32 +290,79 @@ def huffman_decode_table(bits, huffval) -> np.ndarray:
 
 
 @dataclasses.dataclass(frozen=True)
+class JpegLayout:
+    """How a baseline scan lays its components out (T.81 A.1.1, A.2): one entry per component in the three tuples."""
+    components: int            # 3 (Y, Cb, Cr) or 1 (grey)
+    factors: tuple             # (h, v) per component; a grey scan is not interleaved, so its factors count as (1, 1) (T.81 A.2.2)
+    quant: tuple               # per component the quantisation table destination Tq the frame header gives it (B.2.2)
+    huffman: tuple             # per component the (DC, AC) Huffman table destinations (Td, Ta) the scan header gives it (B.2.3)
+
+    @property
+    def key(self):
+        """(components, luminance h, luminance v): what ops.JPEG_LAYOUTS names and the emo_jpeg_layout_* entries take"""
+        return (self.components,) + tuple(self.factors[0])
+
+    @property
+    def name(self):
+        return ops.JPEG_LAYOUTS[self.key]
+
+    @property
+    def blocks_per_mcu(self):
+        return ops.jpeg_layout_bpm(self.key)
+
+
+@dataclasses.dataclass(frozen=True)
 class ParsedJpeg:
     height: int
     width: int
-    quant: np.ndarray          # uint16 (2, 64): luminance, chrominance, NATURAL order
-    specs: tuple               # four (BITS tuple, HUFFVAL bytes): DC luminance, AC luminance, DC chrominance, AC chrominance
+    quant: np.ndarray          # uint16 (2, 64): luminance, chrominance (Cb's), NATURAL order
+    specs: tuple               # four (BITS tuple, HUFFVAL bytes): DC luminance, AC luminance, DC chrominance, AC chrominance (a grey
+    #                            file: the luminance pair twice)
     scan: np.ndarray           # uint8: the entropy-coded segment without the 0x00 behind every 0xFF, up to the marker that ends it
     restart: int = 0           # the restart interval in MCUs (DRI), 0: none
     intervals: np.ndarray = None      # int64 (intervals + 1): restart interval k lies in scan[intervals[k]:intervals[k + 1]] (the RSTm
     #                                   markers are taken out); (0, len(scan)) for a file without restart intervals
+    layout: JpegLayout = None
+    quants: np.ndarray = None  # uint16 (3, 64): the quantiser of every component, NATURAL order (a grey file: its one table three times)
+
+    @property
+    def mcus(self):
+        """MCUs of the frame in its own layout (the 8x8 blocks of a grey frame)"""
+        return ops.jpeg_layout_mcus(self.height, self.width, self.layout.key)
+
+    @property
+    def classic(self):
+        """4:2:0 with one chrominance quantiser: what emo_jpeg_decode_bits / _idct / _upsample_rgb take"""
+        return self.layout.key == (3, 2, 2) and np.array_equal(self.quants[1], self.quants[2])
 
     def table_key(self):
-        return self.quant.tobytes(), self.specs
+        if self.classic:
+            return self.quant.tobytes(), self.specs
+        return self.quants.tobytes(), self.specs, self.layout.key
 
 
 _SOF_NAMES = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xC5: "differential sequential (SOF5)",
               0xC6: "differential progressive (SOF6)", 0xC7: "differential lossless (SOF7)", 0xC9: "arithmetic-coded sequential (SOF9)",
               0xCA: "arithmetic-coded progressive (SOF10)", 0xCB: "arithmetic-coded lossless (SOF11)", 0xCD: "arithmetic-coded differential (SOF13)",
               0xCE: "arithmetic-coded differential progressive (SOF14)", 0xCF: "arithmetic-coded differential lossless (SOF15)"}
-_ONLY = "decode_mjpeg reads 8-bit baseline (SOF0) files with three components at 2x2 / 1x1 / 1x1 in one interleaved scan"
+_ONLY = ("decode_mjpeg reads 8-bit baseline (SOF0) files in one scan: three components (YCbCr) at 2x2 / 1x1 / 1x1 (4:2:0), 2x1 / 1x1 / 1x1 "
+         "(4:2:2) or 1x1 / 1x1 / 1x1 (4:4:4), interleaved, or one component (grey)")
+_NO_LAYOUTS = "without layouts=True parse_jpeg takes 4:2:0 with one chrominance quantiser only"
+_FACTOR_NAMES = {((1, 2), (1, 1), (1, 1)): " (4:4:0)", ((4, 1), (1, 1), (1, 1)): " (4:1:1)", ((2, 2), (1, 1), (1, 1)): " (4:2:0)",
+                 ((2, 1), (1, 1), (1, 1)): " (4:2:2)", ((1, 1), (1, 1), (1, 1)): " (4:4:4)"}
 
 
-def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
+def parse_jpeg(data, restart: bool = False, layouts: bool = False) -> ParsedJpeg:
     """One JPEG file -> ParsedJpeg, walking its marker segments (T.81 Annex B).  A file without DHT segments gets the tables of Annex
     K.3 - K.6 (the Motion-JPEG convention in AVI files).  ValueError, saying what was found, for everything but 8-bit baseline 4:2:0 in
     one interleaved scan without restart intervals: progressive, extended or arithmetic-coded files, other sampling factors, grey
     images, a restart interval, 16-bit quantisers, Cb and Cr on different tables, frames narrower than JPEG_MIN_WIDTH.
+    layouts=True (what decode_mjpeg passes) also takes 4:2:2 (2x1 / 1x1 / 1x1), 4:4:4 (1x1 / 1x1 / 1x1) and grey files (one component,
+    whose stated factors count as 1x1: T.81 A.2.2), and Cb and Cr on different quantisation tables; ParsedJpeg.layout says which and
+    which tables each component uses.  Still refused by name: 4:4:0, 4:1:1 and every other set of factors, four components, Cb and Cr
+    on different Huffman tables, and frames narrower than JPEG_MIN_WIDTH where chroma is halved along the rows (4:2:0, 4:2:2 - 4:4:4
+    and grey take any width).  With or without the keyword, a three-component file libjpeg would read as RGB rather than YCbCr is
+    refused: an Adobe APP14 segment with transform 0, or component ids 'R', 'G', 'B' with neither a JFIF nor an Adobe segment.
     restart=True takes restart intervals too (B.2.4.4, E.1.4): Ri is that of the last DRI segment in front of the scan (0: none), the
     entropy-coded bytes are split at the RSTm markers and every interval is unstuffed; the markers must count 0, 1, .. 7, 0, .. and cut
     the scan into exactly ceil(MCUs / Ri) intervals, anything else is a ValueError that says what was found - a decoder's
@@ -320,7 +371,7 @@ def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
     ri = 0
     if len(data) < 4 or data[:2] != b"\xFF\xD8":
         raise ValueError("parse_jpeg: no SOI marker at the start: not a JPEG file")
-    pos, quant, huff, frame = 2, {}, {}, None
+    pos, quant, huff, frame, jfif, adobe = 2, {}, {}, None, False, None
     while True:
         while pos < len(data) and data[pos] == 0xFF and pos + 1 < len(data) and data[pos + 1] == 0xFF:
             pos += 1                                                             # fill bytes (B.1.1.2)
@@ -354,17 +405,20 @@ def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
             comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nf)]
             if precision != 8:
                 raise ValueError(f"parse_jpeg: {precision}-bit samples; {_ONLY}")
-            if nf != 3:
-                raise ValueError(f"parse_jpeg: {nf} component{'s' if nf != 1 else ' (a grey image)'}; {_ONLY}")
-            factors = [(h, v) for _, h, v, _ in comps]
-            if factors != [(2, 2), (1, 1), (1, 1)]:
-                raise ValueError("parse_jpeg: sampling factors " + " / ".join(f"{h}x{v}" for h, v in factors) + f"; {_ONLY}")
+            if nf not in (1, 3) or (nf == 1 and not layouts):
+                raise ValueError(f"parse_jpeg: {nf} component{'s' if nf != 1 else ' (a grey image)'}; {_NO_LAYOUTS if nf == 1 else _ONLY}")
+            factors = ((1, 1),) if nf == 1 else tuple((h, v) for _, h, v, _ in comps)
+            said = "sampling factors " + " / ".join(f"{h}x{v}" for h, v in factors) + _FACTOR_NAMES.get(factors, "")
+            if nf == 3 and ((3,) + factors[0] not in ops.JPEG_LAYOUTS or factors[1:] != ((1, 1), (1, 1))):
+                raise ValueError(f"parse_jpeg: {said}; {_ONLY}")
+            if factors[0] != (2, 2) and not layouts:
+                raise ValueError(f"parse_jpeg: {said}; {_NO_LAYOUTS}")
             if height == 0:
                 raise ValueError(f"parse_jpeg: the frame header leaves the height to a DNL segment; {_ONLY}")
-            if width < JPEG_MIN_WIDTH:
-                raise ValueError(f"parse_jpeg: a frame {width} pixels wide: below {JPEG_MIN_WIDTH} libjpeg replicates chroma samples instead of "
-                                 "filtering them, which is not built")
-            frame = (height, width, comps)
+            if factors[0][0] == 2 and width < JPEG_MIN_WIDTH:
+                raise ValueError(f"parse_jpeg: a frame {width} pixels wide at {said}: below {JPEG_MIN_WIDTH} libjpeg replicates chroma samples "
+                                 "instead of filtering them, which is not built")
+            frame = (height, width, comps, factors)
         elif marker in _SOF_NAMES:
             raise ValueError(f"parse_jpeg: a {_SOF_NAMES[marker]} file; {_ONLY}")
         elif marker == 0xDD:                                                     # DRI (B.2.4.4)
@@ -377,28 +431,40 @@ def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
             break
         elif marker in (0xD8, 0xD9) or 0xD0 <= marker <= 0xD7 or marker == 0x01:
             raise ValueError(f"parse_jpeg: marker FF{marker:02X} at byte {pos - 2 - size} before any scan")
-        # APPn, COM and the rest: skipped
+        elif marker == 0xE0 and body[:5] == b"JFIF\0":                           # APP0: JFIF implies YCbCr
+            jfif = True
+        elif marker == 0xEE and len(body) >= 12 and body[:5] == b"Adobe":        # APP14: the colour transform flag
+            adobe = body[11]
+        # the other APPn, COM and the rest: skipped
     if frame is None:
         raise ValueError("parse_jpeg: a scan without a frame header in front of it")
-    height, width, comps = frame
-    if len(body) != 10 or body[0] != 3:
-        raise ValueError(f"parse_jpeg: a scan of {body[0] if body else 0} of the frame's 3 components (not interleaved); {_ONLY}")
-    sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(3)]
+    height, width, comps, factors = frame
+    nf = len(comps)
+    # jdapimin.c default_decompress_parms: which colour space libjpeg takes three components for
+    if nf == 3 and adobe == 0:
+        raise ValueError("parse_jpeg: an Adobe APP14 segment with transform 0: the three components are RGB, not YCbCr; " + _ONLY)
+    if nf == 3 and not jfif and adobe is None and bytes(c[0] for c in comps) == b"RGB":
+        raise ValueError("parse_jpeg: neither a JFIF nor an Adobe segment and component ids 'R', 'G', 'B': the three components are RGB, not "
+                         "YCbCr; " + _ONLY)
+    if len(body) != 4 + 2 * nf or body[0] != nf:
+        raise ValueError(f"parse_jpeg: a scan of {body[0] if body else 0} of the frame's {nf} components (not interleaved); {_ONLY}")
+    sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(nf)]
     if [c for c, _, _ in sel] != [c[0] for c in comps]:
         raise ValueError(f"parse_jpeg: the scan lists components {[c for c, _, _ in sel]}, the frame {[c[0] for c in comps]}")
-    if tuple(body[7:10]) != (0, 63, 0):
-        raise ValueError(f"parse_jpeg: a scan of coefficients {body[7]} .. {body[8]} with approximation {body[9]:#04x} (progressive); {_ONLY}")
-    if sel[1][1:] != sel[2][1:]:
+    if tuple(body[1 + 2 * nf:]) != (0, 63, 0):
+        raise ValueError(f"parse_jpeg: a scan of coefficients {body[1 + 2 * nf]} .. {body[2 + 2 * nf]} with approximation "
+                         f"{body[3 + 2 * nf]:#04x} (progressive); {_ONLY}")
+    if nf == 3 and sel[1][1:] != sel[2][1:]:
         raise ValueError(f"parse_jpeg: Cb decodes with Huffman tables {sel[1][1:]} and Cr with {sel[2][1:]}; one chrominance pair is built")
-    for tq in (comps[0][3], comps[1][3], comps[2][3]):
-        if tq not in quant:
-            raise ValueError(f"parse_jpeg: quantisation table {tq} is used and never defined")
-    if not np.array_equal(quant[comps[1][3]], quant[comps[2][3]]):
-        raise ValueError("parse_jpeg: Cb and Cr use different quantisation tables; one chrominance table is built")
+    for c in comps:
+        if c[3] not in quant:
+            raise ValueError(f"parse_jpeg: quantisation table {c[3]} is used and never defined")
+    if nf == 3 and not np.array_equal(quant[comps[1][3]], quant[comps[2][3]]) and not layouts:
+        raise ValueError(f"parse_jpeg: Cb and Cr use different quantisation tables; one chrominance table is built; {_NO_LAYOUTS}")
     if not huff:
         huff = dict(zip(HUFFMAN_IDS, HUFFMAN_SPECS))                             # no DHT at all: the Motion-JPEG convention
     specs = []
-    for key in ((0, sel[0][1]), (1, sel[0][2]), (0, sel[1][1]), (1, sel[1][2])):
+    for key in ((0, sel[0][1]), (1, sel[0][2]), (0, sel[-1][1]), (1, sel[-1][2])):
         if key not in huff:
             raise ValueError(f"parse_jpeg: Huffman table (class {key[0]}, destination {key[1]}) is used and never defined")
         specs.append(huff[key])
@@ -413,7 +479,7 @@ def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
             raise ValueError(f"parse_jpeg: a restart marker inside the scan; restart markers are not built; {_ONLY}")
         rst.append(int(e))
     if rst or ri:
-        n_mcu = ops.jpeg_mcus(height, width)
+        n_mcu = ops.jpeg_layout_mcus(height, width, (nf,) + factors[0])
         if not ri:
             raise ValueError(f"parse_jpeg: {len(rst)} restart marker{'s' if len(rst) != 1 else ''} in the scan (the first at byte {pos + rst[0]}) "
                              "and no restart interval defined by a DRI segment")
@@ -435,30 +501,35 @@ def parse_jpeg(data, restart: bool = False) -> ParsedJpeg:
     before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)            # bytes of the scan in front of byte i of a
     scan = a[keep]
     intervals = before[[0] + rst + [len(a)]]
-    q = np.stack([quant[comps[0][3]], quant[comps[1][3]]])
-    q.setflags(write=False)
-    scan.setflags(write=False)
-    intervals.setflags(write=False)
-    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan, int(ri), intervals)
+    q = np.stack([quant[comps[0][3]], quant[comps[min(1, nf - 1)][3]]])
+    quants = np.stack([quant[comps[min(k, nf - 1)][3]] for k in range(3)])
+    for arr in (q, quants, scan, intervals):
+        arr.setflags(write=False)
+    layout = JpegLayout(nf, factors, tuple(c[3] for c in comps), tuple((td, ta) for _, td, ta in sel))
+    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan, int(ri), intervals, layout, quants)
 
 
 @functools.lru_cache(maxsize=16)
 def _decode_header(quant_bytes: bytes, specs: tuple) -> np.ndarray:
-    """what a group of frames shares, as bytes: the four decoding tables (int32 (4, 320)) and the quantisers (uint16 (2, 64))"""
+    """what a group of frames shares, as bytes: the four decoding tables (int32 (4, 320)) and the quantisers (uint16 (2, 64); (3, 64),
+    one per component, for a group that goes through the emo_jpeg_layout_* entries)"""
     tables = np.stack([huffman_decode_table(*spec) for spec in specs])
     return np.concatenate([tables.view(np.uint8).reshape(-1), np.frombuffer(quant_bytes, np.uint8)])
 
 
 def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
-    """Baseline 4:2:0 JPEG files of one size (bytes each; what encode_mjpeg, Pillow at subsampling=2 or a Motion-JPEG AVI hold), with or
-    without restart intervals -> packed uint8 RGB frames (n, H, W, 3) on the device, byte for byte what libjpeg's default decoder
-    (Pillow's) gives.  The host only parses markers and takes the stuffed bytes out; frames that share their tables go up in ONE copy
-    (tables, quantisers, the segment table, scans) and through one set of three launches (emo_jpeg_decode_segments, emo_jpeg_idct,
-    emo_jpeg_upsample_rgb), followed by one read of the segments' status.  A segment is a restart interval, or a whole frame that has
-    none: frames with different restart intervals and frames without share a launch, and a frame decodes as many wavefronts wide as it
-    has intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits, one workgroup per frame, as it
-    always did.)  ValueError naming the frame for a file parse_jpeg refuses, a frame of another size, or a scan that does not decode
-    (naming the restart interval too when the frame has them).  There is no host decoder behind this."""
+    """Baseline JPEG files of one size (bytes each; what encode_mjpeg, Pillow or a Motion-JPEG AVI hold) - 4:2:0, 4:2:2, 4:4:4 or grey,
+    mixed freely, with or without restart intervals -> packed uint8 RGB frames (n, H, W, 3) on the device, byte for byte what
+    libjpeg's default decoder (Pillow's `Image.open(f).convert("RGB")`) gives; a grey frame comes back with R = G = B.  The host only
+    parses markers and takes the stuffed bytes out; frames that share their tables and their layout go up in ONE copy (tables,
+    quantisers, the segment table, scans) and through one set of three launches (emo_jpeg_decode_segments, emo_jpeg_idct,
+    emo_jpeg_upsample_rgb for 4:2:0 frames with one chrominance quantiser; emo_jpeg_layout_decode_segments, emo_jpeg_layout_idct,
+    emo_jpeg_layout_rgb for the rest), followed by one read of the segments' status.  A segment is a restart interval, or a whole
+    frame that has none: frames with different restart intervals and frames without share a launch, and a frame decodes as many
+    wavefronts wide as it has intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits /
+    emo_jpeg_layout_decode_bits, one workgroup per frame.)  ValueError naming the frame for a file parse_jpeg refuses, a frame of
+    another size, or a scan that does not decode (naming the restart interval too when the frame has them).  There is no host decoder
+    behind this."""
     jpegs = list(jpegs)
     if not jpegs:
         raise ValueError("decode_mjpeg: no frames")
@@ -469,7 +540,7 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     parsed = []
     for i, j in enumerate(jpegs):
         try:
-            parsed.append(parse_jpeg(j, restart=True))
+            parsed.append(parse_jpeg(j, restart=True, layouts=True))
         except ValueError as e:
             raise ValueError(f"decode_mjpeg: frame {i}: {e}") from None
     H, W = parsed[0].height, parsed[0].width
@@ -479,12 +550,13 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     groups = {}
     for i, p in enumerate(parsed):
         groups.setdefault(p.table_key(), []).append(i)
-    n_mcu = ops.jpeg_mcus(H, W)
     out = torch.empty(len(parsed), H, W, 3, device=device, dtype=torch.uint8)
     for key, members in groups.items():
-        head = _decode_header(*key)
+        head = _decode_header(*key[:2])
         n = len(members)
-        # the segment table: one segment per restart interval, one for a frame without; frame f of the group owns blocks f * n_mcu * 6 ..
+        classic, layout = parsed[members[0]].classic, parsed[members[0]].layout.key
+        n_mcu, bpm = parsed[members[0]].mcus, ops.jpeg_layout_bpm(layout)
+        # the segment table: one segment per restart interval, one for a frame without; frame f of the group owns blocks f * n_mcu * bpm ..
         sizes = np.array([len(parsed[i].scan) for i in members], np.int64)
         frame_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         seg_offsets, seg_first, seg_blocks, seg_frame = [], [], [], []
@@ -492,8 +564,8 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
             p = parsed[i]
             first_mcu = np.arange(len(p.intervals) - 1, dtype=np.int64) * (p.restart or n_mcu)
             seg_offsets.append(frame_start[f] + p.intervals[:-1])
-            seg_first.append((f * n_mcu + first_mcu) * 6)
-            seg_blocks.append((np.minimum(first_mcu + (p.restart or n_mcu), n_mcu) - first_mcu) * 6)
+            seg_first.append((f * n_mcu + first_mcu) * bpm)
+            seg_blocks.append((np.minimum(first_mcu + (p.restart or n_mcu), n_mcu) - first_mcu) * bpm)
             seg_frame.append(np.full(len(first_mcu), f, np.int64))
         seg_offsets = np.concatenate(seg_offsets + [frame_start[-1:]]).astype(np.int64)
         seg_first, seg_blocks, seg_frame = (np.concatenate(x) for x in (seg_first, seg_blocks, seg_frame))
@@ -502,21 +574,32 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
         host = np.concatenate([head, seg_offsets.view(np.uint8), seg_first.astype(np.int32).view(np.uint8), seg_blocks.astype(np.int32).view(np.uint8)]
                               + [parsed[i].scan for i in members] + [np.zeros(pad, np.uint8)])
         dev = torch.from_numpy(host).to(device)                                  # the one copy
-        t_end, q_end = 16 * ops.JPEG_DECODE_TABLE_INTS, 16 * ops.JPEG_DECODE_TABLE_INTS + 256
-        o_end = q_end + 8 * (n_seg + 1)                                          # head is t_end + 256 bytes: every table stays 8-byte aligned
+        t_end, q_end = 16 * ops.JPEG_DECODE_TABLE_INTS, len(head)
+        o_end = q_end + 8 * (n_seg + 1)                                          # head is t_end + 256 or 384 bytes: every table stays 8-byte aligned
         tables = dev[:t_end].view(torch.int32).view(4, ops.JPEG_DECODE_TABLE_INTS)
-        quant = dev[t_end:q_end].view(torch.uint16).view(2, 64)
-        if n_seg > n:
-            entry = "emo_jpeg_decode_segments"
-            coefs, status = ops.jpeg_decode_segments(dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64),
-                                                     dev[o_end:o_end + 4 * n_seg].view(torch.int32),
-                                                     dev[o_end + 4 * n_seg:o_end + 8 * n_seg].view(torch.int32), tables, n, n_mcu)
-        else:       # no frame of the group is cut into intervals: a segment is a frame, which a workgroup of its own decodes faster
-            entry = "emo_jpeg_decode_bits"
-            coefs, status = ops.jpeg_decode_bits(dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64), tables, n_mcu)
-        y, c = ops.jpeg_idct(coefs, quant, H, W)
+        quant = dev[t_end:q_end].view(torch.uint16).view(-1, 64)
+        scans, seg_off = dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64)
         whole = n == len(parsed)
-        rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
+        if n_seg > n:
+            seg_tabs = dev[o_end:o_end + 4 * n_seg].view(torch.int32), dev[o_end + 4 * n_seg:o_end + 8 * n_seg].view(torch.int32)
+            if classic:
+                entry = "emo_jpeg_decode_segments"
+                coefs, status = ops.jpeg_decode_segments(scans, seg_off, *seg_tabs, tables, n, n_mcu)
+            else:
+                entry = "emo_jpeg_layout_decode_segments"
+                coefs, status = ops.jpeg_layout_decode_segments(scans, seg_off, *seg_tabs, tables, n, n_mcu, layout)
+        elif classic:       # no frame of the group is cut into intervals: a segment is a frame, which a workgroup of its own decodes faster
+            entry = "emo_jpeg_decode_bits"
+            coefs, status = ops.jpeg_decode_bits(scans, seg_off, tables, n_mcu)
+        else:
+            entry = "emo_jpeg_layout_decode_bits"
+            coefs, status = ops.jpeg_layout_decode_bits(scans, seg_off, tables, n_mcu, layout)
+        if classic:
+            y, c = ops.jpeg_idct(coefs, quant, H, W)
+            rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
+        else:
+            y, c = ops.jpeg_layout_idct(coefs, quant, H, W, layout)
+            rgb = ops.jpeg_layout_rgb(y, c, H, W, layout, out=out if whole else None)
         st = status.cpu().numpy()                                                # the one read
         if st.any():
             bad = int(np.flatnonzero(st)[0])                                     # the first in frame order, whichever wave ended first
@@ -908,6 +991,28 @@ def video2images(path, step=4, length=16, start=0):
     """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays"""
     jpegs, _, _ = read_avi(path)
     return [decode_jpeg(j) for j in jpegs[start::step][:length]]
+
+
+def read_image(path_or_bytes, size=None, resample="bicubic") -> torch.Tensor:
+    """One baseline JPEG file (a path, or the file's bytes) -> (H, W, 3) uint8 ON THE DEVICE, decoded by decode_mjpeg: what
+    `np.array(Image.open(path).convert("RGB"))` gives, byte for byte, without the pixels passing through a host decoder.
+    size=(width, height) resizes the frame as `.resize(size)` does (resize_frames with `resample`), still on the device.  ValueError
+    from parse_jpeg for a file it refuses (progressive, arithmetic-coded, 4:1:1, RGB, ...): Pillow reads those."""
+    if size is not None:
+        size, resample = _resize_size(size, "read_image"), _resize_filter(resample)
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    try:
+        parse_jpeg(data, restart=True, layouts=True)
+    except ValueError as e:
+        raise ValueError(f"read_image: {e}") from None
+    frames = decode_mjpeg([data])
+    if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
+        frames = resize_frames(frames, size, resample)
+    return frames[0]
 
 
 def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"):

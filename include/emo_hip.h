@@ -551,7 +551,36 @@ int emo_jpeg_emit_bits_ri(const int16_t* coefs, const int64_t* bit_offsets, uint
  *   (3 s(x) + s(x + 1) + 7) >> 4 along them, neighbours clamped to the plane.  Colour, cb and cr less 128: R = y + ((91881 cr + 32768)
  *   >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  (libjpeg
  *   replicates samples instead when the chroma plane is at most 2 wide, W <= 4: the host refuses such frames.)
- * H, W in 1 .. 65535 as in emo_jpeg_blocks. */
+ * H, W in 1 .. 65535 as in emo_jpeg_blocks.
+ *
+ * The emo_jpeg_layout_* entries do the same for the four common baseline layouts.  A layout is three small ints: ncomp, the number of
+ * components, and hs x vs, the sampling factors of the first (luminance) component; chrominance is always 1 x 1 (T.81 A.1.1).  An MCU of
+ * an interleaved scan holds hs * vs luminance blocks, row by row, then one Cb and one Cr block (T.81 A.2.3); a one-component scan is not
+ * interleaved and its MCU is one block, whatever factors the frame header states (T.81 A.2.2):
+ *     ncomp hs vs   MCU       blocks per MCU (bpm)           chroma step, colour (libjpeg)
+ *     3     2  2    16 x 16   6: Y00 Y01 Y10 Y11 Cb Cr      jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert (as emo_jpeg_upsample_rgb)
+ *     3     2  1    16 x 8    4: Y0 Y1 Cb Cr                jdsample.c h2v1_fancy_upsample, ycc_rgb_convert
+ *     3     1  1    8 x 8     3: Y Cb Cr                    jdsample.c fullsize_upsample (chroma as it is), ycc_rgb_convert
+ *     1     1  1    8 x 8     1                             jdcolor.c gray_rgb_convert: R = G = B = the sample
+ *   Anything else (4:4:0, 4:1:1, four components) is EMO_ERR_BAD_SHAPE.  mcu_cols = ceil(W / (8 hs)), mcu_rows = ceil(H / (8 vs)),
+ *   n_mcu their product.
+ * emo_jpeg_layout_decode_bits / emo_jpeg_layout_decode_segments (T.81 F.2.2, A.2.3 the order of blocks in an MCU, E.1.4): as
+ *   emo_jpeg_decode_bits / emo_jpeg_decode_segments with bpm for 6.  Block k % bpm of an MCU belongs to component 0 for k < bpm - 2 (all
+ *   of them when bpm is 1), then to Cb, then to Cr; the component selects the DC prediction and the table pair - tables [0], [1] for
+ *   component 0, [2], [3] for Cb and Cr (a grey scan never reads those).  coefs int16 [n][n_mcu][bpm][64], zig-zag order, DC
+ *   undifferenced; the segment table stays in blocks (seg_blocks a multiple of bpm).  Status values, clamping and "a frame (segment) that
+ *   ended early has its remaining coefficients zeroed" as above; n * n_mcu * bpm < 2^31.
+ * emo_jpeg_layout_idct (T.81 A.3.4, jidctint.c jpeg_idct_islow): as emo_jpeg_idct, with one quantiser PER COMPONENT, quant uint16
+ *   [3][64] in natural order (a grey frame reads the first only), into planes padded to whole MCUs: y_plane uint8
+ *   [n][mcu_rows * 8 vs][mcu_cols * 8 hs], c_planes uint8 [n][2][mcu_rows * 8][mcu_cols * 8] (Cb, Cr; not touched and may be NULL when
+ *   ncomp is 1), both 8-byte aligned.
+ * emo_jpeg_layout_rgb: those planes -> packed uint8 RGB [n][H][W][3], 4-byte aligned.  4:2:0 as emo_jpeg_upsample_rgb.  4:2:2
+ *   (h2v1_fancy_upsample): no filter down the columns; along a row of cw = ceil(W / 2) real chroma samples, p the sample at column
+ *   x >> 1, o(x) = (3 p + p(left) + 1) >> 2 for even x and (3 p + p(right) + 2) >> 2 for odd x, the neighbour clamped to 0 .. cw - 1 -
+ *   which is libjpeg's special case for the first and the last column; the padded samples behind cw are not read.  (As above, libjpeg
+ *   replicates instead when cw <= 2, W <= 4: the host refuses such frames at 4:2:2 and 4:2:0.)  4:4:4 (fullsize_upsample): the chroma
+ *   sample of the pixel itself.  Then ycc_rgb_convert's fixed-point transform as above.  Grey (gray_rgb_convert): the sample in all
+ *   three channels, no transform; c_planes is not read and may be NULL.  Any W from 1 at 4:4:4 and grey. */
 #define EMO_JPEG_DECODE_TABLE_INTS 320
 enum { EMO_JPEG_OK = 0, EMO_JPEG_BAD_CODE = 1, EMO_JPEG_PAST_END = 2, EMO_JPEG_BAD_RUN = 3 };
 int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
@@ -561,6 +590,15 @@ int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int6
                              int n_seg, void* stream);
 int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream);
 int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream);
+int emo_jpeg_layout_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
+                                int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream);
+int emo_jpeg_layout_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
+                                    const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks, int32_t* status,
+                                    int n_seg, int ncomp, int hs, int vs, void* stream);
+int emo_jpeg_layout_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, int ncomp,
+                         int hs, int vs, void* stream);
+int emo_jpeg_layout_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
+                        void* stream);
 
 /* ---- Resizing 8-bit frames: `Image.fromarray(c).resize((size, size))` of every control frame and of the source image
  * (magicanimate/pipelines/animation.py:174-185) and `Image.open(source_image).resize((width, height))` (EMOAnimationPipeline.py:688),
