@@ -195,10 +195,14 @@ class AutoencoderKL(HipModule):
         if ld != HW:
             vt[:, :, HW:].zero_()
         att = torch.empty(n_img * HW, C_, device=x.device, dtype=x.dtype)
+        # scores and probabilities are (HW, ld) buffers read as [:, :HW]: the rows keep the 16-byte alignment emo_softmax_rows needs when
+        # HW is not a multiple of the vector.  The softmax runs over the HW real columns only; the pad columns of pm stay zero, as those of
+        # V^T do, so the P.V GEMM over K = ld adds nothing for them.  ld == HW: the contiguous (HW, HW) buffers of before.
+        s = torch.empty(HW, ld, device=x.device, dtype=x.dtype)
+        pm = torch.zeros(HW, ld, device=x.device, dtype=x.dtype) if ld != HW else torch.empty(HW, HW, device=x.device, dtype=x.dtype)
         for i in range(n_img):
-            s = ops.gemm(q[i * HW:(i + 1) * HW], k[i * HW:(i + 1) * HW].contiguous())                  # (HW, HW) scaled scores
-            pm = torch.zeros(HW, ld, device=x.device, dtype=x.dtype) if ld != HW else torch.empty(HW, HW, device=x.device, dtype=x.dtype)
-            ops.softmax_rows(s, 1.0, out=pm[:, :HW])
+            ops.gemm(q[i * HW:(i + 1) * HW], k[i * HW:(i + 1) * HW], out=s[:, :HW])                    # (HW, HW) scaled scores
+            ops.softmax_rows(s[:, :HW], 1.0, out=pm[:, :HW])
             ops.gemm(pm, vt[i], out=att[i * HW:(i + 1) * HW])
         return ops.gemm(att, w[p + ".to_out.0.weight"], w[p + ".to_out.0.bias"], residual=x)
 

@@ -49,6 +49,69 @@ def test_vae_encode_vs_oracle(dtype):
         assert s.shape == dist.mean.shape and bool(torch.isfinite(s).all())
 
 
+ODD_LATENTS = [(2, 4, 5, 7), (1, 4, 6, 6)]      # 35 tokens; 36: a multiple of the f32 vector (4), not of the 16-bit one (8)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("shape", ODD_LATENTS)
+def test_vae_decode_token_count_off_the_vector(dtype, shape):
+    """h * w that is no multiple of the 16-byte vector: the mid attention keeps scores and probabilities in (HW, ld) buffers with
+    ld = HW rounded up to 8 and zero pad columns.  Until the scores got that leading dimension too, emo_softmax_rows refused them
+    (ldx = 35), and with them every clip whose latent h * w is not a multiple of 8 - 360 x 360 has 45 x 45."""
+    from oracle import vae_ref as V
+    m, sd = build(SMALL, dtype)
+    z = seeded_randn(shape, 7)
+    ref = V.decode(sd, z, layers_per_block=1, groups=8)
+    got = m.decode(z.to(DEV)).sample
+    assert got.shape == ref.shape == (shape[0], 3, 8 * shape[2], 8 * shape[3])
+    check(got, ref, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_vae_decode_bits_where_the_token_count_is_a_multiple_of_the_vector(dtype):
+    """(2, 4, 8, 8): 64 tokens, no padding - the bits the decode gave on an MI355X at commit 13e289d, before the score matrix of the mid
+    attention could carry a padded leading dimension (tests/golden/vae_decode_small_2x4x8x8.safetensors)."""
+    import os
+    from safetensors import safe_open
+    from tests import cases
+    with safe_open(os.path.join(cases.GOLDEN_DIR, "vae_decode_small_2x4x8x8.safetensors"), "pt") as f:
+        want = f.get_tensor(str(dtype)[6:])
+    m, _ = build(SMALL, dtype)
+    got = m.decode(seeded_randn((2, 4, 8, 8), 7).to(DEV)).sample
+    assert torch.equal(got.cpu(), want)
+
+
+@pytest.mark.parametrize("cfg,hw,dtype", [(SMALL, (40, 56), torch.float32), (SMALL, (40, 56), torch.bfloat16), (SMALL, (40, 56), torch.float16),
+                                          (MID, (64, 96), torch.float16)])
+def test_vae_encode_odd_token_count_and_f16(cfg, hw, dtype):
+    """Encode at 40 x 56 pixels (5 x 7 latents: 35 tokens in the encoder's mid attention) in every dtype, and the (2, 3, 64, 96) of
+    test_vae_encode_vs_oracle in f16, which that test leaves out."""
+    from oracle import vae_ref as V
+    m, sd = build(cfg, dtype)
+    x = seeded_randn((2, 3, *hw), 8).clamp(-1, 1)
+    mom = V.encode(sd, x, layers_per_block=cfg["layers_per_block"], groups=cfg["norm_num_groups"])
+    dist = m.encode(x.to(DEV)).latent_dist
+    assert dist.mean.shape == (2, 4, hw[0] // 8, hw[1] // 8)
+    check(dist.mean, mom[:, :4], dtype)
+    if dtype == torch.float32:
+        torch.testing.assert_close(dist.logvar.cpu(), mom[:, 4:].clamp(-30, 20), rtol=1e-3, atol=1e-4)
+
+
+def test_vae_decode_video_odd_token_count_float_and_uint8():
+    """decode_video at 5 x 7 latents, 3 frames in calls of 2 and 1: the float video against the oracle's decode_latents, and the uint8
+    frames equal to (float * 255) truncated - the same rows went through both tails."""
+    from oracle import vae_ref as V
+    m, sd = build(SMALL, torch.float32)
+    lat = 0.2 * seeded_randn((1, 4, 3, 5, 7), 9)
+    ref = V.decode_latents(sd, lat, layers_per_block=1, groups=8)
+    vid = m.decode_video(lat.to(DEV), frames_per_call=2, output="float")
+    assert vid.shape == (1, 3, 3, 40, 56) and float(vid.min()) >= 0.0 and float(vid.max()) <= 1.0
+    torch.testing.assert_close(vid.cpu(), ref, rtol=1e-3, atol=1e-4)
+    u8 = m.decode_video(lat.to(DEV), frames_per_call=2, output="uint8")
+    assert u8.dtype == torch.uint8 and tuple(u8.shape) == (1, 3, 40, 56, 3)
+    assert torch.equal(u8.cpu(), (vid.cpu() * 255.0).to(torch.uint8).permute(0, 2, 3, 4, 1))
+
+
 def test_vae_decode_video_is_decode_latents():
     """decode_latents (EMOAnimationPipeline.py:291-307): 1 / 0.18215 scaling, per-frame decode, '(b f) c h w -> b c f h w',
     (video / 2 + 0.5).clamp(0, 1) - frames batched 2 per call here, one per call in the reference: the network is per-image."""

@@ -605,3 +605,55 @@ def test_norm_plans_run_the_argument_checks():
         assert lib.emo_layernorm(p, 64, p, p, p, 64, 0, 64, 1e-5, None, 0, 0, dt, None) == _ln_plan(0, 64, dt)[0]
         assert lib.emo_layernorm_stats(p, (64 * S.LN_MAXV + 1) * V, p, 5, (64 * S.LN_MAXV + 1) * V, 1e-5, dt, None) == _ln_plan(5, (64 * S.LN_MAXV + 1) * V, dt)[0]
     assert _ln_plan(5, 64, 7)[0] != 0 and lib.emo_layernorm_plan(5, 64, BF16, None) != 0
+
+
+def test_elementwise_sweep_cases_are_what_they_are_named_for():
+    """tests/elementwise_sweep_cases.py against the launch geometry of csrc/elementwise.hip, redone here: which layout cases have a ragged
+    pixel tile, a channel tile of padding only, and more tiles than the transposes launch blocks; which cases of the grid-stride
+    entries take a second (or third) trip; which sampler-step cases take the float4 path.  And the refusals of the layout pair: they
+    return before anything is launched, so they run here with pointers that are never dereferenced."""
+    import ctypes as C
+    from tests import elementwise_sweep_cases as E
+    by = {E.layout_id(c): c for c in E.LAYOUT}
+    assert len(by) == len(E.LAYOUT) == 7
+    tiles = {k: E.layout_tiles(c) for k, c in by.items()}
+    assert tiles["C5-Cpad8-B2-F3-H6-W10"] == (1, 1, 6)
+    assert tiles["C32-Cpad40-B1-F2-H7-W9"][1] == 2 and E.layout_tiles(by["C32-Cpad40-B1-F2-H7-W9"], to_rows=False)[1] == 1
+    assert tiles["C33-Cpad40-B2-F1-H5-W13"][:2] == (2, 2) and 5 * 13 == E.LAYOUT_TILE_P + 1
+    assert tiles["C31-Cpad32-B1-F2-H9-W7"][:2] == (1, 1) and 9 * 7 == E.LAYOUT_TILE_P - 1
+    assert tiles["C64-Cpad64-B1-F1-H8-W8"] == (1, 2, 2)
+    assert tiles["C4-Cpad8-B1-F1-H1-W1"] == (1, 1, 1)
+    for to_rows in (True, False):
+        pt, ct, n = E.layout_tiles(E.LAYOUT_WALK, to_rows)
+        assert (pt, ct, n) == (2049, 2, 4098) and n > E.LAYOUT_MAX_BLOCKS
+    assert sum(E.layout_tiles(c)[2] > E.LAYOUT_MAX_BLOCKS for c in E.LAYOUT) == 1
+    # grid-stride entries: work items of each named case against one trip of the capped grid
+    assert E.trips(E.ONE_TRIP) == 1 and E.trips(E.ONE_TRIP + 1) == 2
+    assert E.TS_WALK["B"] * E.TS_WALK["dim"] == 526119 and E.trips(526119) == 2
+    assert [E.trips(n) for n in E.SILU_SIZES] == [1, 1, 1, 3] and E.SILU_SIZES[-1] % E.BLOCK != 0
+    w = E.COPY_ADD_WALK
+    assert w["M"] * (w["C"] // E.vec(torch.float32)) == 524672 and E.trips(524672) == 2 and w["ld"] % 4 == 0 and w["ld"] > w["C"]
+    w = E.ADD_PERIODIC_WALK
+    assert w["P"] * w["periods"] == 65541 and E.trips(65541 * (w["C"] // E.vec(torch.bfloat16))) == 2
+    assert E.trips(E.CONVERT_WALK) == 3
+    w = E.ACCUMULATE_WALK
+    assert w["nf"] * w["C"] * w["HW"] == 524400 and E.trips(524400) == 2 and len(w["frames"]) == w["nf"] and max(w["frames"]) < w["F"]
+    for C_, F, HW in E.SCHED_SMALL:
+        assert (C_ * F * HW) % 4 == 0 and (HW < 4 or F == 1)
+    (C_, F, HW), (C2, F2, HW2) = E.SCHED_LARGE
+    assert C_ * F * HW == 2097252 and (C_ * F * HW) % 4 == 0 and E.trips(C_ * F * HW // 4) == 2 and HW % 4 == 3
+    assert C2 * F2 * HW2 == 524289 and (C2 * F2 * HW2) % 4 != 0 and E.trips(524289) == 2
+    # refusals of the layout pair
+    lib = _lib.load()
+    buf = (C.c_float * 16)()
+    p = C.addressof(buf)
+    for c in E.LAYOUT:
+        B, F, H, W = c["shape"]
+        for entry, over in E.layout_refusals(c):
+            a = dict(B=B, C=c["C"], F=F, H=H, W=W, Cpad=c["Cpad"], ldo=c["Cpad"], ldi=c["C"])
+            a.update(over)
+            if entry == "to_rows":
+                rc = lib.emo_ncfhw_to_rows(p, p, a["B"], a["C"], a["F"], a["H"], a["W"], a["Cpad"], a["ldo"], BF16, None)
+            else:
+                rc = lib.emo_rows_to_ncfhw(p, p, a["B"], a["C"], a["F"], a["H"], a["W"], a["ldi"], BF16, None)
+            assert rc != 0, (entry, over)
