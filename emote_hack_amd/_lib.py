@@ -150,6 +150,7 @@ SIGNATURES = {
     "emo_jpeg_layout_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "emo_jpeg_layout_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_layout_rgb": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "emo_jpeg_progressive_scan": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "emo_image_resize_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "emo_image_resize": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, C.c_size_t, _p]),
     "emo_image_preprocess": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float), _p]),

@@ -1040,6 +1040,56 @@ def jpeg_layout_rgb(y: torch.Tensor, c, H: int, W: int, layout, out=None) -> tor
     return rgb
 
 
+def jpeg_scan_units(H: int, W: int, layout, scan_comp: int) -> int:
+    """units of one scan of a progressive frame (T.81 A.2.2, A.2.3): MCUs when the scan is interleaved (scan_comp -1), else the 8x8
+    blocks of component scan_comp's own ceil(W h / hs) x ceil(H v / vs) samples"""
+    nc, hs, vs = _jpeg_layout(layout)
+    scan_comp = int(scan_comp)
+    assert -1 <= scan_comp < nc, (scan_comp, nc)
+    if scan_comp < 0 or nc == 1:
+        return jpeg_layout_mcus(H, W, layout)
+    h, v = (hs, vs) if scan_comp == 0 else (1, 1)
+    return (((int(W) * h + hs - 1) // hs + 7) // 8) * (((int(H) * v + vs - 1) // vs + 7) // 8)
+
+
+def jpeg_progressive_scan(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_frame: torch.Tensor, seg_first_unit: torch.Tensor,
+                          seg_units: torch.Tensor, seg_tables: torch.Tensor, tables: torch.Tensor, coefs: torch.Tensor, H: int, W: int, layout,
+                          Ss: int, Se: int, Ah: int, Al: int, scan_comp: int, status=None) -> torch.Tensor:
+    """ONE scan of a progression, decoded IN PLACE into coefs int16 (n, n_mcu, bpm, 64) - zeroed by the caller before the first scan -
+    for all segments at once -> status int32 (n_seg), a key of JPEG_STATUS per segment (emo_jpeg_progressive_scan; T.81 Annex G).
+    Segment s - a restart interval of this scan in one frame, or the frame's whole scan - lies in bytes seg_offsets[s] ..
+    seg_offsets[s + 1] of scan (int64 (n_seg + 1)), belongs to frame seg_frame[s] and codes seg_units[s] units from seg_first_unit[s]
+    on (int32 (n_seg) each; units as jpeg_scan_units counts them); seg_tables int32 (n_seg, 3) indexes tables, int32 (T,
+    JPEG_DECODE_TABLE_INTS): the DC table of every component of an interleaved scan, or in column 0 the one table of a one-component
+    scan.  scan_comp: -1 interleaved (DC scans only), else the component.  Only positions Ss .. Se of the blocks of the units are
+    written; the launches of a progression follow each other in file order on the stream."""
+    _need_cuda(scan, seg_offsets, seg_frame, seg_first_unit, seg_units, seg_tables, tables, coefs)
+    nc, hs, vs = _jpeg_layout(layout)
+    H, W, Ss, Se, Ah, Al, scan_comp = (int(v) for v in (H, W, Ss, Se, Ah, Al, scan_comp))
+    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
+    assert seg_offsets.dtype == torch.int64 and seg_offsets.dim() == 1 and seg_offsets.numel() >= 2 and seg_offsets.is_contiguous(), (seg_offsets.dtype, seg_offsets.shape)
+    n_seg = seg_offsets.numel() - 1
+    for tab in (seg_frame, seg_first_unit, seg_units):
+        assert tab.dtype == torch.int32 and tuple(tab.shape) == (n_seg,) and tab.is_contiguous(), (tab.dtype, tab.shape, n_seg)
+    assert seg_tables.dtype == torch.int32 and tuple(seg_tables.shape) == (n_seg, 3) and seg_tables.is_contiguous(), (seg_tables.dtype, seg_tables.shape)
+    assert tables.dtype == torch.int32 and tables.dim() == 2 and tables.shape[0] >= 1 and tables.shape[1] == JPEG_DECODE_TABLE_INTS and tables.is_contiguous(), (tables.dtype, tables.shape)
+    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and coefs.shape[0] >= 1 and coefs.is_contiguous() and \
+        tuple(coefs.shape[1:]) == (jpeg_layout_mcus(H, W, layout), jpeg_layout_bpm(layout), 64), (coefs.dtype, coefs.shape)
+    assert -1 <= scan_comp < nc, f"scan_comp {scan_comp}: -1 (interleaved) or a component below {nc}"
+    assert 0 <= Ss <= Se <= 63 and (Se == 0 if Ss == 0 else scan_comp >= 0), \
+        f"a DC scan holds coefficient 0 alone, an AC scan a band inside 1 .. 63 of one component (T.81 G.1.1.1.1); got {Ss} .. {Se}, scan_comp {scan_comp}"
+    assert 0 <= Al <= 13 and 0 <= Ah <= 13 and (Ah == 0 or Al == Ah - 1), f"Ah / Al {Ah} / {Al}: 0 .. 13, a refinement steps down by one bit"
+    n = coefs.shape[0]
+    status = _jpeg_out(status, (n_seg,), torch.int32, scan.device, "status")
+    _launch("jpeg_progressive_scan", 0.0, float(scan.numel() + 2 * coefs.numel() * (Se - Ss + 1) / 64),
+            lambda: check(_lib.load().emo_jpeg_progressive_scan(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_frame), _ptr(seg_first_unit),
+                                                                _ptr(seg_units), _ptr(seg_tables), _ptr(tables), tables.shape[0], _ptr(coefs),
+                                                                _ptr(status), n_seg, n, H, W, nc, hs, vs, Ss, Se, Ah, Al, scan_comp, _stream()),
+                          "emo_jpeg_progressive_scan"),
+            tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n_seg}/{n}x{H}x{W} {Ss}..{Se} {Ah}/{Al} c{scan_comp}")
+    return status
+
+
 def image_resize(frames: torch.Tensor, h: int, w: int, xtaps=None, ytaps=None, out=None) -> torch.Tensor:
     """packed uint8 RGB frames (n, H, W, 3) -> (n, h, w, 3): Pillow's resize of 8-bit pixels, a horizontal integer pass to 8-bit pixels and
     a vertical one over those (emo_image_resize; animation.py:174-185).  xtaps / ytaps: (bounds int32 (w | h, 2), coef int32 (w | h, k))

@@ -1010,13 +1010,14 @@ class EMOAnimationPipeline:
         return table.to(frames_u8.device)[frames_u8.long()]
 
     @staticmethod
-    def _clip_frames(path, n_frames, width, height, who, resample=None):
+    def _clip_frames(path, n_frames, width, height, who, resample=None, progressive=False):
         """the first n_frames frames of a Motion-JPEG `.avi` file as uint8 (n_frames, height, width, 3) on the device (video_io.read_video).
         The reference resizes what it reads through PIL (animation.py:174-185): with resample= (a filter of video_io.RESIZE_FILTERS; PIL's
         own default is "bicubic") frames of another size are resized on the device as PIL would (video_io.resize_frames); with None
-        another size is refused."""
+        another size is refused.  progressive=True takes progressive frames in the clip too (video_io.decode_mjpeg)."""
         from . import video_io
-        frames, _, _ = video_io.read_video(path, length=n_frames)
+        # existing host tests replace video_io.read_video by a stand-in without the keyword: it is handed over only when set
+        frames, _, _ = video_io.read_video(path, length=n_frames, **(dict(progressive=True) if progressive else {}))
         if frames.shape[0] < n_frames:
             raise ValueError(f"{who}={os.fspath(path)!r} holds {frames.shape[0]} frames, {n_frames} are needed: pass a clip at least as long as "
                              "video_length")
@@ -1028,12 +1029,13 @@ class EMOAnimationPipeline:
             frames = video_io.resize_frames(frames, (width, height), resample)
         return frames
 
-    def _source_image_latents(self, source_image, width, height, resample=None):
+    def _source_image_latents(self, source_image, width, height, resample=None, progressive=False):
         """:686-689: a path is opened and resized to (width, height); an (H, W, 3) uint8 array is taken as it is.  A Motion-JPEG `.avi`
         path gives its first frame (animation.py:182-185), decoded on the device at (height, width) - resized there under resample=, as
         _clip_frames does - and encoded from there.  A baseline `.jpg` / `.jpeg` path is decoded and resized to (width, height) on the
-        device as well (video_io.read_image, byte for byte the pixels PIL's open + resize give); what parse_jpeg refuses is PIL's."""
-        rgb = self._source_image_rgb(source_image, width, height, resample)
+        device as well (video_io.read_image, byte for byte the pixels PIL's open + resize give); what parse_jpeg refuses is PIL's - a
+        progressive file too, unless progressive=True sends a complete progression down the same device path."""
+        rgb = self._source_image_rgb(source_image, width, height, resample, progressive)
         if torch.is_tensor(rgb):          # a still JPEG or the first frame of a clip, on the device
             if self.vae is None:
                 raise ValueError("images2latents needs a VAE (emote_hack_amd.vae.AutoencoderKL)")
@@ -1041,27 +1043,27 @@ class EMOAnimationPipeline:
         return self.images2latents(rgb[None], None)
 
     @staticmethod
-    def _source_image_rgb(source_image, width, height, resample=None):
+    def _source_image_rgb(source_image, width, height, resample=None, progressive=False):
         import numpy as np
         if isinstance(source_image, (str, os.PathLike)) and os.fspath(source_image).lower().endswith(".avi"):
             # animation.py:182-185 takes the source image from a video's first frame: decoded on the device, and it stays there
-            frame = EMOAnimationPipeline._clip_frames(source_image, 1, width, height, "source_image", resample)[0]
+            frame = EMOAnimationPipeline._clip_frames(source_image, 1, width, height, "source_image", resample, progressive)[0]
             if frame.shape[0] % 8 or frame.shape[1] % 8:
                 raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
             return frame
         if isinstance(source_image, str) and source_image.lower().endswith((".jpg", ".jpeg")):
             # a baseline JPEG file is decoded and resized on the device (read_image: both byte for byte as Pillow does, "bicubic" being
-            # the filter of the `.resize((width, height))` below) and stays there; what parse_jpeg refuses - a progressive file, say -
-            # is Pillow's, like every other format
+            # the filter of the `.resize((width, height))` below) and stays there; what parse_jpeg refuses - a progressive file without
+            # progressive=True, an incomplete progression with it - is Pillow's, like every other format
             from . import video_io
             with open(source_image, "rb") as f:
                 data = f.read()
             try:
-                video_io.parse_jpeg(data, restart=True, layouts=True)
+                video_io.parse_jpeg(data, restart=True, layouts=True, progressive=progressive)
             except ValueError:
                 data = None
             if data is not None:
-                frame = video_io.read_image(data, size=(width, height), resample="bicubic")
+                frame = video_io.read_image(data, size=(width, height), resample="bicubic", progressive=progressive)
                 if frame.shape[0] % 8 or frame.shape[1] % 8:
                     raise ValueError(f"source_image {tuple(frame.shape[:2])} must be a multiple of 8 in both directions")
                 return frame
@@ -1287,7 +1289,14 @@ class EMOAnimationPipeline:
         path or a source_image= `.avi` path whose frames are not height x width is resized on the device, byte for byte as the
         `Image.resize` of animation.py:174-185 would ("bicubic" is that call's filter; emote_hack_amd.video_io.resize_frames).  None, the
         default, refuses such a clip as before.  Host arrays and image files are not touched by it, and a clip shorter than
-        video_length is refused either way."""
+        video_length is refused either way.
+        input_progressive=True decodes progressive JPEGs (SOF2, a complete progression) on the device too: a source_image= `.jpg` /
+        `.jpeg` path, which otherwise goes through PIL on the host, and progressive frames inside a controlnet_condition= or
+        source_image= clip, which are otherwise refused (emote_hack_amd.video_io.decode_mjpeg(progressive=True); the pixels are
+        PIL's byte for byte).  False, the default, launches what it launched before."""
+        input_progressive = kwargs.get("input_progressive", False)
+        if not isinstance(input_progressive, bool):
+            raise ValueError(f"input_progressive= takes True or False, got {input_progressive!r}")
         input_resample = kwargs.get("input_resample")
         if input_resample is not None:
             from . import video_io
@@ -1331,7 +1340,8 @@ class EMOAnimationPipeline:
             from_clip = isinstance(controlnet_condition, (str, os.PathLike))
             if from_clip:
                 # animation.py:174-180 reads the control sequence from a video file: the first video_length frames, decoded on the device
-                controlnet_condition = self._clip_frames(controlnet_condition, video_length, width, height, "controlnet_condition", input_resample)
+                controlnet_condition = self._clip_frames(controlnet_condition, video_length, width, height, "controlnet_condition", input_resample,
+                                                          input_progressive)
             cn_cond = controlnet_condition if torch.is_tensor(controlnet_condition) else torch.as_tensor(controlnet_condition)
             if from_clip:
                 cn_cond = self._device_u8_scaled(cn_cond, 255.0).permute(0, 3, 1, 2)
@@ -1365,7 +1375,7 @@ class EMOAnimationPipeline:
         if ref_lat is None:
             if self.vae is None or source_image is None:
                 raise ValueError("pass ref_image_latents=(1,4,h,w) (no VAE in this build)")
-            ref_lat = self._source_image_latents(source_image, width, height, input_resample)   # :686-689 -> images2latents (:402-414)
+            ref_lat = self._source_image_latents(source_image, width, height, input_resample, input_progressive)   # :686-689 -> images2latents (:402-414)
         if audio is not None and kwargs.get("audio_features") is None:
             # :592-593 `audio_features = feature_extractor.extract_features_from_mp4(audio, m=2, n=2)` (a module-level extractor
             # there; the file read, resampling and channel mean of Net.py:627-640 behind it): feature_extractor= is an
@@ -1442,7 +1452,7 @@ class EMOAnimationPipeline:
                 if source_image is None:
                     raise ValueError("face_mask=\"locate\" looks for the face in source_image=: pass it (a path or an (H, W, 3) uint8 array), or "
                                      "pass the mask itself")
-                rgb = self._source_image_rgb(source_image, width, height, input_resample)
+                rgb = self._source_image_rgb(source_image, width, height, input_resample, input_progressive)
                 if torch.is_tensor(rgb):      # the first frame of a clip, on the device
                     face_mask = loc(self._device_u8_scaled(rgb, 255.0).permute(2, 0, 1)[None])[0, 0]
                 else:

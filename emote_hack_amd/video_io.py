@@ -312,6 +312,30 @@ class JpegLayout:
 
 
 @dataclasses.dataclass(frozen=True)
+class JpegScan:
+    """One scan of a progressive file (T.81 B.2.3, G.1.1.1.1) with what held when it started."""
+    components: tuple          # indices into the frame's components, in the scan header's order
+    Ss: int                    # the band of the zig-zag sequence, 0 .. 0 for a DC scan
+    Se: int
+    Ah: int                    # 0: the band's first scan, else the Al of the scan this one refines
+    Al: int                    # the bits below this one are left to later scans
+    huffman: tuple             # per component of the scan the (Td, Ta) its header gives it
+    specs: tuple               # per component of the scan the ((BITS, HUFFVAL) of DC destination Td, of AC destination Ta) as the DHT
+    #                            segments in front of THIS scan left them; None for a destination not defined (and not needed) then
+    restart: int               # the restart interval in force at this scan, in its own units (MCUs, or blocks of its one component); 0: none
+    scan: np.ndarray           # uint8: the scan's entropy-coded bytes, unstuffed, RSTm markers taken out
+    intervals: np.ndarray      # int64 (intervals + 1): as ParsedJpeg.intervals
+
+    @property
+    def script(self):
+        """what a progression's scan is, without its tables: frames that share these share launches"""
+        return self.components, self.Ss, self.Se, self.Ah, self.Al
+
+    def __str__(self):
+        return f"{self.Ss}..{self.Se}, Ah/Al {self.Ah}/{self.Al}"
+
+
+@dataclasses.dataclass(frozen=True)
 class ParsedJpeg:
     height: int
     width: int
@@ -324,6 +348,8 @@ class ParsedJpeg:
     #                                   markers are taken out); (0, len(scan)) for a file without restart intervals
     layout: JpegLayout = None
     quants: np.ndarray = None  # uint16 (3, 64): the quantiser of every component, NATURAL order (a grey file: its one table three times)
+    scans: tuple = None        # a progressive file (parse_jpeg(progressive=True)): one JpegScan per scan in file order; specs is then
+    #                            empty, scan and intervals hold no bytes, restart is the interval in force at the first scan.  None: baseline
 
     @property
     def mcus(self):
@@ -336,6 +362,8 @@ class ParsedJpeg:
         return self.layout.key == (3, 2, 2) and np.array_equal(self.quants[1], self.quants[2])
 
     def table_key(self):
+        if self.scans is not None:      # Huffman tables and restart intervals may differ inside a group: libjpeg optimises tables per file
+            return self.quants.tobytes(), self.layout.key, tuple(s.script for s in self.scans)
         if self.classic:
             return self.quant.tobytes(), self.specs
         return self.quants.tobytes(), self.specs, self.layout.key
@@ -352,7 +380,173 @@ _FACTOR_NAMES = {((1, 2), (1, 1), (1, 1)): " (4:4:0)", ((4, 1), (1, 1), (1, 1)):
                  ((2, 1), (1, 1), (1, 1)): " (4:2:2)", ((1, 1), (1, 1), (1, 1)): " (4:4:4)"}
 
 
-def parse_jpeg(data, restart: bool = False, layouts: bool = False) -> ParsedJpeg:
+def _entropy_bytes(data: bytes, pos: int, units: int, ri: int, what: str):
+    """the entropy-coded bytes that start at data[pos] -> (unstuffed bytes without the RSTm markers, intervals as in ParsedJpeg, the
+    position of the marker that ends them); the markers must cut `units` units at a restart interval of `ri` into ceil(units / ri)"""
+    rst, end, at = [], None, pos                                                 # forward from pos to the first marker that is no RSTm:
+    while True:                                                                  # a file of many scans is not searched to its end per scan
+        at = data.find(b"\xFF", at)
+        if at < 0 or at + 1 >= len(data):
+            break
+        if data[at + 1] == 0x00:                                                 # a stuffed byte
+            at += 2
+        elif 0xD0 <= data[at + 1] <= 0xD7:
+            rst.append(at - pos)
+            at += 2
+        else:
+            end = at - pos
+            break
+    if end is None:
+        raise ValueError(f"parse_jpeg: {what} runs to the end of the file: no marker ends it (a cut file)")
+    a = np.frombuffer(data, np.uint8, count=end, offset=pos)
+    if rst or ri:
+        if not ri:
+            raise ValueError(f"parse_jpeg: {len(rst)} restart marker{'s' if len(rst) != 1 else ''} in {what} (the first at byte {pos + rst[0]}) "
+                             "and no restart interval defined by a DRI segment")
+        found = [int(a[e + 1]) - 0xD0 for e in rst]
+        wrong = [k for k, m in enumerate(found) if m != k % 8]
+        if wrong:
+            k = wrong[0]
+            raise ValueError(f"parse_jpeg: restart marker {k} of {what} is RST{found[k]} (FF{0xD0 + found[k]:02X} at byte {pos + rst[k]}), "
+                             f"RST{k % 8} is expected there: the markers count 0 .. 7 and round again (a damaged file; resynchronisation is "
+                             "not built)")
+        want = -(-units // ri)
+        if len(rst) + 1 != want:
+            raise ValueError(f"parse_jpeg: {len(rst) + 1} restart interval{'s' if rst else ''} in {what}, {units} units at a restart interval "
+                             f"of {ri} make {want} (a damaged file; resynchronisation is not built)")
+    keep = np.ones(len(a), bool)
+    if len(a) > 1:
+        keep[np.flatnonzero((a[:-1] == 0xFF) & (a[1:] == 0x00)) + 1] = False       # the stuffed bytes
+    if rst:
+        keep[np.array(rst)] = keep[np.array(rst) + 1] = False                    # the markers
+    before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+    scan, intervals = a[keep], before[[0] + rst + [len(a)]]
+    scan.setflags(write=False)
+    intervals.setflags(write=False)
+    return scan, intervals, pos + end
+
+
+_NO_SMOOTHING = ("libjpeg smooths the blocks of such a file from their neighbours (jdcoefct.c smoothing_ok finds coefficients whose bits "
+                 "are not all known), which is not built")
+
+
+def _progressive_scans(data: bytes, pos: int, body: bytes, frame, quant: dict, huff: dict, ri: int) -> tuple:
+    """the scans of a progressive file (T.81 G.1.1.1.1) from the body of its first SOS segment, whose entropy-coded bytes start at
+    data[pos], to EOI -> a tuple of JpegScan; ValueError for a progression that is not built or not complete"""
+    height, width, comps, factors = frame
+    nf, key = len(comps), (len(comps),) + factors[0]
+    ids = [c[0] for c in comps]
+    huff, quant = dict(huff), dict(quant)
+    known = [[None] * 64 for _ in range(nf)]                                     # per coefficient the Al of its last scan; None: not coded yet
+    scans = []
+    while True:
+        ns = body[0] if body else 0
+        if ns < 1 or len(body) != 4 + 2 * ns:
+            raise ValueError(f"parse_jpeg: scan {len(scans)}: a malformed SOS segment")
+        sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(ns)]
+        Ss, Se, Ah, Al = body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns] >> 4, body[3 + 2 * ns] & 15
+        what = f"scan {len(scans)} (component ids {[c for c, _, _ in sel]}, coefficients {Ss} .. {Se}, Ah / Al {Ah} / {Al})"
+        for c, _, _ in sel:
+            if c not in ids:
+                raise ValueError(f"parse_jpeg: {what} names component {c}, the frame has {ids}")
+        idx = tuple(ids.index(c) for c, _, _ in sel)
+        if list(idx) != sorted(set(idx)):
+            raise ValueError(f"parse_jpeg: {what} lists its components out of the frame's order {ids} (B.2.3)")
+        if Ss == 0:
+            if Se != 0:
+                raise ValueError(f"parse_jpeg: {what}: a scan that starts at the DC coefficient holds it alone (Se = 0; T.81 G.1.1.1.1)")
+            if ns not in (1, nf):
+                raise ValueError(f"parse_jpeg: {what} is interleaved over {ns} of the frame's {nf} components; all of them or one are built")
+        elif ns != 1:
+            raise ValueError(f"parse_jpeg: {what}: an AC scan interleaved over {ns} components; it holds one (T.81 G.1.1.1.1)")
+        elif Se < Ss or Se > 63:
+            raise ValueError(f"parse_jpeg: {what}: an AC band runs from Ss up to Se <= 63 (T.81 G.1.1.1.1)")
+        if Al > 13:
+            raise ValueError(f"parse_jpeg: {what}: Al above 13 (T.81 G.1.1.1.1)")
+        for c in idx:
+            if Ss > 0 and known[c][0] is None:
+                raise ValueError(f"parse_jpeg: {what}: an AC scan of component {ids[c]} in front of that component's first DC scan")
+            for k in range(Ss, Se + 1):
+                if known[c][k] is None:
+                    if Ah != 0:
+                        raise ValueError(f"parse_jpeg: {what}: the first scan of coefficient {k} of component {ids[c]} with Ah = {Ah}, not 0")
+                elif Ah != known[c][k] or Ah == 0:
+                    raise ValueError(f"parse_jpeg: {what}: a refinement of coefficient {k} of component {ids[c]} with Ah = {Ah}, the scan "
+                                     f"before it left Al = {known[c][k]}")
+                elif Al != Ah - 1:
+                    raise ValueError(f"parse_jpeg: {what}: a refinement steps down by one bit, Al = Ah - 1")
+                known[c][k] = Al
+            if comps[c][3] not in quant:
+                raise ValueError(f"parse_jpeg: quantisation table {comps[c][3]} is used and never defined")
+        specs = []
+        for c, td, ta in sel:
+            need = (0, td) if Ss == 0 else (1, ta)
+            if need not in huff and not (Ss == 0 and Ah):                        # a DC refinement reads single bits
+                raise ValueError(f"parse_jpeg: {what}: Huffman table (class {need[0]}, destination {need[1]}) is used and never defined")
+            specs.append((huff.get((0, td)), huff.get((1, ta))))
+        units = ops.jpeg_scan_units(height, width, key, -1 if ns == nf else idx[0])
+        scan, intervals, pos = _entropy_bytes(data, pos, units, ri, what)
+        scans.append(JpegScan(idx, Ss, Se, Ah, Al, tuple((td, ta) for _, td, ta in sel), tuple(specs), int(ri), scan, intervals))
+        while True:                                                              # the marker segments up to the next SOS, or EOI
+            while pos + 1 < len(data) and data[pos] == 0xFF and data[pos + 1] == 0xFF:
+                pos += 1
+            if pos + 2 > len(data) or data[pos] != 0xFF:
+                raise ValueError(f"parse_jpeg: no marker at byte {pos} behind scan {len(scans) - 1}: the file ends or is damaged before its EOI")
+            marker = data[pos + 1]
+            if marker == 0xD9:
+                break
+            if pos + 4 > len(data):
+                raise ValueError(f"parse_jpeg: the file ends inside marker FF{marker:02X} at byte {pos}")
+            size = struct.unpack_from(">H", data, pos + 2)[0]
+            body = data[pos + 4:pos + 2 + size]
+            if size < 2 or pos + 2 + size > len(data):
+                raise ValueError(f"parse_jpeg: segment FF{marker:02X} at byte {pos} runs past the end of the file")
+            pos += 2 + size
+            if marker == 0xDA:
+                break
+            if marker == 0xC4:
+                while body:
+                    if len(body) < 17 or len(body) < 17 + sum(body[1:17]):
+                        raise ValueError("parse_jpeg: a DHT segment ends inside a table")
+                    bits = tuple(body[1:17])
+                    huff[(body[0] >> 4, body[0] & 15)], body = (bits, bytes(body[17:17 + sum(bits)])), body[17 + sum(bits):]
+            elif marker == 0xDD:
+                if len(body) != 2:
+                    raise ValueError("parse_jpeg: a malformed DRI segment")
+                ri = struct.unpack(">H", body)[0]
+            elif marker == 0xDB:
+                while body:
+                    if body[0] >> 4 or len(body) < 65:
+                        raise ValueError(f"parse_jpeg: a DQT segment behind scan {len(scans) - 1} with 16-bit entries or cut short")
+                    nat = np.zeros(64, np.uint16)
+                    nat[ZIGZAG] = np.frombuffer(body[1:65], np.uint8)
+                    tq, body = body[0] & 15, body[65:]
+                    if tq in quant and any(c[3] == tq for c in comps) and not np.array_equal(quant[tq], nat):
+                        raise ValueError(f"parse_jpeg: a DQT segment behind scan {len(scans) - 1} changes quantisation table {tq}, which the "
+                                         "frame uses: libjpeg keeps the table a component had at its first scan; one table per component is built")
+                    quant[tq] = nat
+            elif marker == 0xDC:
+                raise ValueError(f"parse_jpeg: a DNL segment behind scan {len(scans) - 1}: the frame header holds the height here; {_ONLY_PROGRESSIVE}")
+            elif marker in (0xC0, 0xC2, 0xD8) or marker in _SOF_NAMES:
+                raise ValueError(f"parse_jpeg: marker FF{marker:02X} at byte {pos - 2 - size} behind scan {len(scans) - 1}: a second frame")
+        if marker == 0xD9:
+            break
+    for c in range(nf):
+        missing = [k for k in range(64) if known[c][k] is None]
+        coarse = [k for k in range(64) if known[c][k]]
+        if missing or coarse:
+            said = (f"coefficient{'s' if len(missing) != 1 else ''} {missing[0]}{' .. ' + str(missing[-1]) if len(missing) > 1 else ''} of "
+                    f"component {ids[c]} never coded") if missing else \
+                   f"coefficient {coarse[0]} of component {ids[c]} coded down to Al = {known[c][coarse[0]]} only, not to 0"
+            raise ValueError(f"parse_jpeg: the progression is not complete at EOI after {len(scans)} scans: {said}; {_NO_SMOOTHING}")
+    return tuple(scans), quant
+
+
+_ONLY_PROGRESSIVE = ("progressive=True reads 8-bit Huffman-coded progressive (SOF2) files with a complete progression next to baseline ones, "
+                     "in the same layouts")
+
+
+def parse_jpeg(data, restart: bool = False, layouts: bool = False, progressive: bool = False) -> ParsedJpeg:
     """One JPEG file -> ParsedJpeg, walking its marker segments (T.81 Annex B).  A file without DHT segments gets the tables of Annex
     K.3 - K.6 (the Motion-JPEG convention in AVI files).  ValueError, saying what was found, for everything but 8-bit baseline 4:2:0 in
     one interleaved scan without restart intervals: progressive, extended or arithmetic-coded files, other sampling factors, grey
@@ -366,9 +560,23 @@ def parse_jpeg(data, restart: bool = False, layouts: bool = False) -> ParsedJpeg
     restart=True takes restart intervals too (B.2.4.4, E.1.4): Ri is that of the last DRI segment in front of the scan (0: none), the
     entropy-coded bytes are split at the RSTm markers and every interval is unstuffed; the markers must count 0, 1, .. 7, 0, .. and cut
     the scan into exactly ceil(MCUs / Ri) intervals, anything else is a ValueError that says what was found - a decoder's
-    resynchronisation on damaged files is not built, and neither are fill bytes in front of a marker."""
+    resynchronisation on damaged files is not built, and neither are fill bytes in front of a marker.
+    progressive=True (it implies the other two) also takes Huffman-coded progressive files (SOF2, T.81 Annex G) in those layouts and
+    walks them to EOI: ParsedJpeg.scans then holds one JpegScan per scan - components, Ss, Se, Ah, Al, the tables its destinations held
+    and the restart interval in force AT THAT SCAN (DHT and DRI segments between scans change both; in a one-component scan the
+    interval counts that component's blocks), its entropy-coded bytes - and specs / scan / intervals are empty.  Cb and Cr on
+    different Huffman tables are fine there.  Refused, saying what was found: a scan outside T.81 G.1.1.1.1 (a DC scan with Se != 0,
+    an AC scan over several components or with a band outside Ss .. 63, Al > 13), a first scan with Ah != 0, a refinement whose Ah is
+    not the Al before it or whose Al is not Ah - 1, an AC scan in front of its component's DC, a component the frame lacks, a DC scan interleaved over some but not all
+    of the frame's components (T.81 allows it; the kernel's table slots take all components or one), scan components listed out of the
+    frame's order, a DQT
+    behind the first scan that changes a table in use, a DNL segment, and a progression that is NOT COMPLETE at EOI (some coefficient
+    never coded, or not down to Al = 0): libjpeg smooths such files between blocks, which is not built.  A baseline file parses as
+    without the keyword, with scans None."""
     data = bytes(data)
-    ri = 0
+    if progressive:
+        restart = layouts = True
+    ri, sof2 = 0, False
     if len(data) < 4 or data[:2] != b"\xFF\xD8":
         raise ValueError("parse_jpeg: no SOI marker at the start: not a JPEG file")
     pos, quant, huff, frame, jfif, adobe = 2, {}, {}, None, False, None
@@ -398,9 +606,10 @@ def parse_jpeg(data, restart: bool = False, layouts: bool = False) -> ParsedJpeg
                     raise ValueError("parse_jpeg: a DHT segment ends inside a table")
                 bits = tuple(body[1:17])
                 huff[(body[0] >> 4, body[0] & 15)], body = (bits, bytes(body[17:17 + sum(bits)])), body[17 + sum(bits):]
-        elif marker == 0xC0:                                                     # SOF0 (B.2.2)
+        elif marker == 0xC0 or (marker == 0xC2 and progressive):                 # SOF0, SOF2 (B.2.2)
+            sof2 = marker == 0xC2
             if len(body) < 6 or len(body) != 6 + 3 * body[5]:
-                raise ValueError("parse_jpeg: a malformed SOF0 segment")
+                raise ValueError(f"parse_jpeg: a malformed SOF{2 if sof2 else 0} segment")
             precision, height, width, nf = struct.unpack_from(">BHHB", body, 0)
             comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(nf)]
             if precision != 8:
@@ -446,6 +655,17 @@ def parse_jpeg(data, restart: bool = False, layouts: bool = False) -> ParsedJpeg
     if nf == 3 and not jfif and adobe is None and bytes(c[0] for c in comps) == b"RGB":
         raise ValueError("parse_jpeg: neither a JFIF nor an Adobe segment and component ids 'R', 'G', 'B': the three components are RGB, not "
                          "YCbCr; " + _ONLY)
+    if sof2:
+        if not huff:
+            huff = dict(zip(HUFFMAN_IDS, HUFFMAN_SPECS))
+        scans, quant = _progressive_scans(data, pos, body, frame, quant, huff, ri)
+        q = np.stack([quant[comps[0][3]], quant[comps[min(1, nf - 1)][3]]])
+        quants = np.stack([quant[comps[min(k, nf - 1)][3]] for k in range(3)])
+        empty, none = np.zeros(0, np.uint8), np.zeros(2, np.int64)
+        for arr in (q, quants, empty, none):
+            arr.setflags(write=False)
+        return ParsedJpeg(int(height), int(width), q, (), empty, scans[0].restart, none, JpegLayout(nf, factors, tuple(c[3] for c in comps), ()),
+                          quants, scans)
     if len(body) != 4 + 2 * nf or body[0] != nf:
         raise ValueError(f"parse_jpeg: a scan of {body[0] if body else 0} of the frame's {nf} components (not interleaved); {_ONLY}")
     sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(nf)]
@@ -517,7 +737,112 @@ def _decode_header(quant_bytes: bytes, specs: tuple) -> np.ndarray:
     return np.concatenate([tables.view(np.uint8).reshape(-1), np.frombuffer(quant_bytes, np.uint8)])
 
 
-def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
+@functools.lru_cache(maxsize=64)
+def _decode_table_bytes(spec: tuple) -> bytes:
+    return huffman_decode_table(*spec).tobytes()
+
+
+def _progressive_group_plan(parsed, members, device) -> dict:
+    """the progressive frames parsed[i], i in members - one layout, one set of quantisers, one scan script - uploaded in one copy:
+    decoding tables (each once), quantisers, the segment tables of every scan, the scans.  -> what _decode_progressive_group runs:
+    `launches`, one (JpegScan of the first frame, a function that launches emo_jpeg_progressive_scan for that scan of all frames) per
+    scan in file order; `coefs` (not zeroed yet) and `status`, which they fill; `quant`; `seg_frame` / `seg_scan` / `seg_interval`, which
+    frame, scan and restart interval a status belongs to"""
+    first = parsed[members[0]]
+    n, H, W = len(members), first.height, first.width
+    classic, layout = first.classic, first.layout.key
+    n_mcu, bpm, nf = first.mcus, ops.jpeg_layout_bpm(layout), first.layout.components
+    table_of, table_bytes = {}, []                                               # the decoding tables the group uses, each once
+
+    def table(spec):
+        if spec not in table_of:
+            table_of[spec] = len(table_bytes)
+            table_bytes.append(_decode_table_bytes(spec))
+        return table_of[spec]
+
+    seg_offsets, seg_frame, seg_first, seg_units, seg_tables, seg_scan, seg_interval, chunks, launches = [], [], [], [], [], [], [], [], []
+    at = n_seg = 0                                                               # bytes and segments so far; the buffers are scan-major
+    for k, sc in enumerate(first.scans):
+        scan_comp = -1 if len(sc.components) == nf and nf > 1 else sc.components[0]
+        units = ops.jpeg_scan_units(H, W, layout, scan_comp)
+        seg0 = n_seg
+        for f, i in enumerate(members):
+            s = parsed[i].scans[k]
+            tabs = [0, 0, 0]
+            if not (s.Ss == 0 and s.Ah):                                         # a DC refinement reads no table
+                for c, pair in enumerate(s.specs):
+                    tabs[c] = table(pair[0] if s.Ss == 0 else pair[1])
+            n_int = len(s.intervals) - 1
+            first_unit = np.arange(n_int, dtype=np.int64) * (s.restart or units)
+            seg_offsets.append(at + s.intervals[:-1])
+            seg_first.append(first_unit)
+            seg_units.append(np.minimum(first_unit + (s.restart or units), units) - first_unit)
+            seg_frame.append(np.full(n_int, f, np.int64))
+            seg_scan.append(np.full(n_int, k, np.int64))
+            seg_interval.append(np.arange(n_int, dtype=np.int64))
+            seg_tables.append(np.tile(np.array(tabs, np.int64), (n_int, 1)))
+            chunks.append(s.scan)
+            at += len(s.scan)
+            n_seg += n_int
+        launches.append((seg0, n_seg, sc, scan_comp))
+    seg_offsets = np.concatenate(seg_offsets + [np.array([at], np.int64)]).astype(np.int64)
+    seg_frame, seg_first, seg_units, seg_tables, seg_scan, seg_interval = (np.concatenate(x) for x in (seg_frame, seg_first, seg_units, seg_tables,
+                                                                                                       seg_scan, seg_interval))
+    quant_bytes = (first.quant if classic else first.quants).tobytes()
+    pad = -at % 4 or (4 if at == 0 else 0)
+    ints = [x.astype(np.int32).reshape(-1).view(np.uint8) for x in (seg_frame, seg_first, seg_units, seg_tables)]
+    host = np.concatenate([np.frombuffer(b"".join(table_bytes), np.uint8), np.frombuffer(quant_bytes, np.uint8), seg_offsets.view(np.uint8)]
+                          + ints + chunks + [np.zeros(pad, np.uint8)])
+    dev = torch.from_numpy(host).to(device)                                      # the one copy
+    t_end = 4 * ops.JPEG_DECODE_TABLE_INTS * len(table_bytes)
+    q_end = t_end + len(quant_bytes)
+    o_end = q_end + 8 * (n_seg + 1)                                              # every part is a multiple of 8 bytes up to here
+    tables = dev[:t_end].view(torch.int32).view(-1, ops.JPEG_DECODE_TABLE_INTS)
+    quant = dev[t_end:q_end].view(torch.uint16).view(-1, 64)
+    d_off = dev[q_end:o_end].view(torch.int64)
+    d_frame, d_first, d_units = (dev[o_end + 4 * j * n_seg:o_end + 4 * (j + 1) * n_seg].view(torch.int32) for j in range(3))
+    d_tabs = dev[o_end + 12 * n_seg:o_end + 24 * n_seg].view(torch.int32).view(n_seg, 3)
+    scans = dev[o_end + 24 * n_seg:]
+    coefs = torch.empty(n, n_mcu, bpm, 64, device=device, dtype=torch.int16)
+    status = torch.empty(n_seg, device=device, dtype=torch.int32)
+
+    def launch(a, b, sc, scan_comp):
+        return lambda: ops.jpeg_progressive_scan(scans, d_off[a:b + 1], d_frame[a:b], d_first[a:b], d_units[a:b], d_tabs[a:b], tables, coefs, H, W,
+                                                 layout, sc.Ss, sc.Se, sc.Ah, sc.Al, scan_comp, status=status[a:b])
+    return dict(launches=[(sc, launch(a, b, sc, scan_comp)) for a, b, sc, scan_comp in launches], coefs=coefs, status=status, quant=quant,
+                seg_frame=seg_frame, seg_scan=seg_scan, seg_interval=seg_interval)
+
+
+def _decode_progressive_group(parsed, members, out, whole: bool):
+    """_progressive_group_plan's group decoded into out (all of it when `whole`, else a new tensor): the coefficient buffer zeroed once,
+    one emo_jpeg_progressive_scan launch per scan of the script in file order, the baseline IDCT and colour launches, one read of every
+    segment's status"""
+    first = parsed[members[0]]
+    H, W, classic, layout = first.height, first.width, first.classic, first.layout.key
+    plan = _progressive_group_plan(parsed, members, out.device)
+    coefs, status, quant, seg_frame, seg_scan, seg_interval = (plan[k] for k in ("coefs", "status", "quant", "seg_frame", "seg_scan", "seg_interval"))
+    coefs.zero_()                                                                # once: every scan adds to it
+    for _, run in plan["launches"]:                                              # file order on one stream is the only synchronisation
+        run()
+    if classic:
+        y, c = ops.jpeg_idct(coefs, quant, H, W)
+        rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
+    else:
+        y, c = ops.jpeg_layout_idct(coefs, quant, H, W, layout)
+        rgb = ops.jpeg_layout_rgb(y, c, H, W, layout, out=out if whole else None)
+    st = status.cpu().numpy()                                                    # the one read, for all scans
+    if st.any():
+        bad = np.flatnonzero(st)
+        bad = int(bad[np.lexsort((seg_scan[bad], seg_frame[bad]))[0]])        # the first frame, its first scan: later scans build on it
+        f, k = int(seg_frame[bad]), int(seg_scan[bad])
+        s = parsed[members[f]].scans[k]
+        where = f" in restart interval {int(seg_interval[bad])} of {len(s.intervals) - 1}" if s.restart else ""
+        raise ValueError(f"decode_mjpeg: frame {members[f]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')} in scan "
+                         f"{k} of {len(first.scans)} ({s}){where} (emo_jpeg_progressive_scan status {int(st[bad])})")
+    return rgb
+
+
+def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
     """Baseline JPEG files of one size (bytes each; what encode_mjpeg, Pillow or a Motion-JPEG AVI hold) - 4:2:0, 4:2:2, 4:4:4 or grey,
     mixed freely, with or without restart intervals -> packed uint8 RGB frames (n, H, W, 3) on the device, byte for byte what
     libjpeg's default decoder (Pillow's `Image.open(f).convert("RGB")`) gives; a grey frame comes back with R = G = B.  The host only
@@ -529,7 +854,13 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     wavefronts wide as it has intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits /
     emo_jpeg_layout_decode_bits, one workgroup per frame.)  ValueError naming the frame for a file parse_jpeg refuses, a frame of
     another size, or a scan that does not decode (naming the restart interval too when the frame has them).  There is no host decoder
-    behind this."""
+    behind this.
+    progressive=True also takes Huffman-coded progressive files (SOF2) with a complete progression, mixed freely with baseline ones
+    (parse_jpeg(progressive=True) says what is refused).  Progressive frames that share layout, quantisers and scan script - the
+    (components, Ss, Se, Ah, Al) of every scan; Huffman tables and restart intervals may differ from frame to frame - go up in one copy
+    too; their coefficient buffer is zeroed once and filled by ONE emo_jpeg_progressive_scan launch per scan of the script, in file
+    order, before the same IDCT and colour launches, and the status of every segment of every scan is read once.  An error names the
+    frame, the scan (its number, Ss .. Se, Ah / Al) and the restart interval where the scan has them."""
     jpegs = list(jpegs)
     if not jpegs:
         raise ValueError("decode_mjpeg: no frames")
@@ -540,7 +871,7 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
     parsed = []
     for i, j in enumerate(jpegs):
         try:
-            parsed.append(parse_jpeg(j, restart=True, layouts=True))
+            parsed.append(parse_jpeg(j, restart=True, layouts=True, progressive=progressive))
         except ValueError as e:
             raise ValueError(f"decode_mjpeg: frame {i}: {e}") from None
     H, W = parsed[0].height, parsed[0].width
@@ -552,8 +883,13 @@ def decode_mjpeg(jpegs, device=None) -> torch.Tensor:
         groups.setdefault(p.table_key(), []).append(i)
     out = torch.empty(len(parsed), H, W, 3, device=device, dtype=torch.uint8)
     for key, members in groups.items():
-        head = _decode_header(*key[:2])
         n = len(members)
+        if parsed[members[0]].scans is not None:
+            rgb = _decode_progressive_group(parsed, members, out, n == len(parsed))
+            if n != len(parsed):
+                out[torch.tensor(members, device=device)] = rgb
+            continue
+        head = _decode_header(*key[:2])
         classic, layout = parsed[members[0]].classic, parsed[members[0]].layout.key
         n_mcu, bpm = parsed[members[0]].mcus, ops.jpeg_layout_bpm(layout)
         # the segment table: one segment per restart interval, one for a frame without; frame f of the group owns blocks f * n_mcu * bpm ..
@@ -993,11 +1329,14 @@ def video2images(path, step=4, length=16, start=0):
     return [decode_jpeg(j) for j in jpegs[start::step][:length]]
 
 
-def read_image(path_or_bytes, size=None, resample="bicubic") -> torch.Tensor:
+def read_image(path_or_bytes, size=None, resample="bicubic", progressive: bool = False) -> torch.Tensor:
     """One baseline JPEG file (a path, or the file's bytes) -> (H, W, 3) uint8 ON THE DEVICE, decoded by decode_mjpeg: what
     `np.array(Image.open(path).convert("RGB"))` gives, byte for byte, without the pixels passing through a host decoder.
     size=(width, height) resizes the frame as `.resize(size)` does (resize_frames with `resample`), still on the device.  ValueError
-    from parse_jpeg for a file it refuses (progressive, arithmetic-coded, 4:1:1, RGB, ...): Pillow reads those."""
+    from parse_jpeg for a file it refuses (progressive, arithmetic-coded, 4:1:1, RGB, ...): Pillow reads those.
+    progressive=True also decodes a Huffman-coded progressive file (SOF2) with a complete progression on the device, scan by scan
+    (decode_mjpeg(progressive=True)): the same bytes, since libjpeg reads such a file to the coefficients of the baseline one; a
+    progression that stops early, which libjpeg smooths, stays refused."""
     if size is not None:
         size, resample = _resize_size(size, "read_image"), _resize_filter(resample)
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
@@ -1006,46 +1345,48 @@ def read_image(path_or_bytes, size=None, resample="bicubic") -> torch.Tensor:
         with open(path_or_bytes, "rb") as f:
             data = f.read()
     try:
-        parse_jpeg(data, restart=True, layouts=True)
+        parse_jpeg(data, restart=True, layouts=True, progressive=progressive)
     except ValueError as e:
         raise ValueError(f"read_image: {e}") from None
-    frames = decode_mjpeg([data])
+    frames = decode_mjpeg([data], progressive=progressive)
     if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
         frames = resize_frames(frames, size, resample)
     return frames[0]
 
 
-def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"):
+def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic", progressive: bool = False):
     """An `.avi` file this module wrote -> (uint8 frames (n, H, W, 3) ON THE DEVICE, fps Fraction, audio as read_avi returns it): the
     frames [start::step][:length], decoded by decode_mjpeg.  What `VideoReader(path).read()` gives magicanimate/pipelines/animation.py:174-185,
     without the frames passing through a host decoder.  size=(width, height) resizes the decoded frames as animation.py:177 does
-    (resize_frames with `resample`), still on the device; None returns them as stored."""
+    (resize_frames with `resample`), still on the device; None returns them as stored.  progressive=True takes progressive frames
+    too, mixed with baseline ones (decode_mjpeg(progressive=True))."""
     if size is not None:
         size, resample = _resize_size(size, "read_video"), _resize_filter(resample)
     jpegs, fps, audio = read_avi(path)
     picked = jpegs[start::step][:length]
     if not picked:
         raise ValueError(f"read_video: {os.fspath(path)!r} holds {len(jpegs)} frames; [{start}::{step}][:{length}] selects none")
-    frames = decode_mjpeg(picked)
+    frames = decode_mjpeg(picked, progressive=progressive)
     if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
         frames = resize_frames(frames, size, resample)
     return frames, fps, audio
 
 
-def load_control_clip(path, size, window, offset=0, max_length=None, resample="bicubic"):
+def load_control_clip(path, size, window, offset=0, max_length=None, resample="bicubic", progressive: bool = False):
     """magicanimate/pipelines/animation.py:174-194 for a Motion-JPEG `.avi` file -> (control frames uint8 (t, height, width, 3) on the
     device, original_length): every frame is read (:175), resized to size=(width, height) when the clip has another size (:176-177; the
     reference compares the height alone, having square frames on both sides), cut to [offset : offset + max_length] when max_length is
     given (:178-179) and, when what is left is no multiple of `window` (config.L, the context length), followed by copies of its last
     frame up to the next multiple (:192-194, np.pad mode="edge").  original_length is the frame count in front of that padding: the
-    length comparison_videos cuts the result back to.  Nothing leaves the device."""
+    length comparison_videos cuts the result back to.  Nothing leaves the device.  progressive= as in read_video."""
     if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
         raise ValueError(f"load_control_clip: window= is the context length, a positive int, got {window!r}")
     if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
         raise ValueError(f"load_control_clip: offset= is a frame index >= 0, got {offset!r}")
     if max_length is not None and (isinstance(max_length, bool) or not isinstance(max_length, (int, np.integer)) or max_length < 1):
         raise ValueError(f"load_control_clip: max_length= is None or a positive int, got {max_length!r}")
-    frames, _, _ = read_video(path, size=_resize_size(size, "load_control_clip"), resample=resample)
+    # existing host tests replace read_video by a stand-in without the keyword: it is handed over only when set
+    frames, _, _ = read_video(path, size=_resize_size(size, "load_control_clip"), resample=resample, **(dict(progressive=True) if progressive else {}))
     total = int(frames.shape[0])
     if max_length is not None:
         frames = frames[int(offset):int(offset) + int(max_length)]

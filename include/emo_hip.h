@@ -600,6 +600,47 @@ int emo_jpeg_layout_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y
 int emo_jpeg_layout_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
                         void* stream);
 
+/* ---- Progressive JPEG input (T.81 Annex G, SOF2, Huffman coding): the entropy decoder behind decode_mjpeg(progressive=True);
+ * csrc/video_in_progressive.hip.  A progressive file codes its coefficients in several scans - spectral selection (a scan holds the
+ * band Ss .. Se of the zig-zag sequence) and successive approximation (a scan holds the bits down to Al, a later one refines by one
+ * bit) - and the host (emote_hack_amd/video_io.py parse_jpeg(progressive=True)) walks them, keeps the tables and the restart interval
+ * each scan saw, and takes only COMPLETE progressions, which libjpeg decodes without inter-block smoothing (jdcoefct.c smoothing_ok):
+ * the coefficients are then those of the baseline file, and emo_jpeg_layout_idct / emo_jpeg_layout_rgb (emo_jpeg_idct /
+ * emo_jpeg_upsample_rgb) give libjpeg's bytes from them.
+ * emo_jpeg_progressive_scan (T.81 G.1.1.1.1 the scans of a progression, G.1.2 / G.2 the Huffman procedures, A.2.2 / A.2.3 the order of
+ *   the units, E.1.4 restart intervals; jdphuff.c decode_mcu_DC_first, decode_mcu_DC_refine, decode_mcu_AC_first, decode_mcu_AC_refine):
+ *   ONE scan of a progression for many frames at once, into coefs int16 [n][n_mcu][bpm][64] (zig-zag order, the layout of the
+ *   emo_jpeg_layout_* entries), which the caller zeroes before the first scan.  One wavefront per segment, a restart interval of the
+ *   scan in one frame or the frame's whole scan: segment s holds bytes seg_offsets[s] .. seg_offsets[s + 1] of scan (int64 [n_seg + 1];
+ *   unstuffed, markers taken out, scan_bytes a multiple of 4), belongs to frame seg_frame[s] and codes seg_units[s] units from unit
+ *   seg_first_unit[s] on (int32 [n_seg] each).  ncomp, hs, vs: the layout; H, W: the frame.  Ss, Se, Ah, Al: the scan header's; Ss = 0
+ *   needs Se = 0 (a DC scan), Ss > 0 a band inside 1 .. 63 of ONE component; Ah = 0 is a first scan, Ah > 0 a refinement with
+ *   Al = Ah - 1; Al <= 13.  scan_comp: -1 for a scan interleaved over all components (DC scans only), else the one component 0 .. ncomp - 1.
+ *   Units: in an interleaved scan a unit is an MCU, its bpm blocks in the buffer's order.  In a one-component scan a unit is one block
+ *     of the component's OWN grid, bw = ceil(ceil(W h_c / hs) / 8) by bh = ceil(ceil(H v_c / vs) / 8) blocks in raster order - for
+ *     luminance ceil(W / 8) x ceil(H / 8), not the grid padded to whole MCUs: block (by, bx) lives in MCU (by / vs) * mcu_cols + bx / hs
+ *     as block (by % vs) * hs + bx % hs.  Padding blocks no one-component scan visits keep what they hold, as in libjpeg.
+ *   Tables: device int32 [n_tables][EMO_JPEG_DECODE_TABLE_INTS] as above; seg_tables int32 [n_seg][3] names, by index, the DC table of
+ *     each component of an interleaved scan, or in [s][0] the one DC or AC table of a one-component scan (a DC refinement reads none).
+ *     An index is clamped to the array.  A wave loads the tables its segment names into LDS.
+ *   The procedures: DC first - the difference of F.2.2.1 added to the component's prediction, which starts at 0 with every segment;
+ *     the coefficient is the prediction << Al.  DC refine - one bit per block, OR-ed in at 1 << Al.  AC first - RRRRSSSS with SSSS = 0
+ *     and R < 15 is EOBn: EOBRUN = (1 << R) + RECEIVE(R) ends this block's band and those of the next EOBRUN - 1 units; R = 15 is ZRL;
+ *     else R zeros are skipped and the value << Al is stored.  AC refine - the new coefficient (SSSS = 1, one sign bit) of +-(1 << Al)
+ *     goes behind R coefficients with a zero history; every coefficient with a nonzero history that is passed takes one correction bit,
+ *     added towards its sign where bit Al is not yet set; an EOB run corrects the rest of the band's nonzero coefficients.
+ *   Writes: positions Ss .. Se of the blocks of the segment's units, nothing else; a first scan (Ah = 0) stores zeros where it codes
+ *     none, a refinement reads what is there.  The scans of a progression are launched in file order on one stream.
+ *   status int32 [n_seg], the values above: EMO_JPEG_BAD_CODE also for a category above 11 (DC) or 10 (AC first) and SSSS other than 0
+ *     or 1 in an AC refinement; EMO_JPEG_BAD_RUN also for a zero run that leaves the band and an EOBRUN longer than the units the
+ *     segment has left; EMO_JPEG_PAST_END when the bits read reach past the segment's last byte.  A segment with an error stops: the
+ *     block the error is in and those behind it are not written.  Segment offsets, frame, units are clamped to the buffers, every read
+ *     of scan is masked to the segment's bytes, every loop is counted.  n * n_mcu * bpm < 2^31. */
+int emo_jpeg_progressive_scan(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_frame,
+                              const int32_t* seg_first_unit, const int32_t* seg_units, const int32_t* seg_tables, const int32_t* tables,
+                              int n_tables, int16_t* coefs, int32_t* status, int n_seg, int n, int H, int W, int ncomp, int hs, int vs, int Ss,
+                              int Se, int Ah, int Al, int scan_comp, void* stream);
+
 /* ---- Resizing 8-bit frames: `Image.fromarray(c).resize((size, size))` of every control frame and of the source image
  * (magicanimate/pipelines/animation.py:174-185) and `Image.open(source_image).resize((width, height))` (EMOAnimationPipeline.py:688),
  * byte for byte as Pillow's ImagingResample computes it for 8-bit pixels; csrc/image_resize.hip.
