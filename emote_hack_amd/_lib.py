@@ -142,6 +142,11 @@ SIGNATURES = {
     "emo_jpeg_emit_bits": (_i, [_p, _p, _p, _i64, _i, _i, _p, _p]),
     "emo_jpeg_count_bits_ri": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "emo_jpeg_emit_bits_ri": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p, _p]),
+    "emo_gif_histogram": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "emo_gif_map": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "emo_gif_lzw_codes_per_strip": (_i64, [_i, _i, _i]),
+    "emo_gif_lzw_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "emo_gif_lzw_emit": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _p]),
     "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _p]),
     "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

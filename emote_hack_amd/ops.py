@@ -846,6 +846,84 @@ def jpeg_emit_bits(coefs: torch.Tensor, huff: torch.Tensor, bit_offsets: torch.T
     return out
 
 
+GIF_BINS = 32768                                 # (r >> 3, g >> 3, b >> 3)
+
+
+def _gif_frames(frames):
+    _need_cuda(frames)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    return frames.shape[:3]
+
+
+def gif_histogram(frames: torch.Tensor, per_frame: bool = False) -> torch.Tensor:
+    """packed uint8 RGB frames (n, H, W, 3) -> int64 (n if per_frame else 1, 32768, 4): per bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3)
+    the pixel count and the sums of R, G, B (emo_gif_histogram; 64-bit integer atomics, exact and independent of the order)."""
+    n, H, W = _gif_frames(frames)
+    hist = torch.zeros(n if per_frame else 1, GIF_BINS, 4, device=frames.device, dtype=torch.int64)
+    _launch("gif_histogram", 0.0, float(frames.numel()),
+            lambda: check(_lib.load().emo_gif_histogram(_ptr(frames), _ptr(hist), n, H, W, int(bool(per_frame)), _stream()), "emo_gif_histogram"),
+            tag=f"{n}x{H}x{W}")
+    return hist
+
+
+def gif_map(frames: torch.Tensor, palettes: torch.Tensor, n_colors: int, dither_strength: int = 0) -> torch.Tensor:
+    """frames (n, H, W, 3), palettes uint8 (1 | n, 256, 3) -> uint8 (n, H, W): per pixel the nearest of the first n_colors entries of
+    its frame's palette, the lowest index on a tie (emo_gif_map).  dither_strength 1 .. 128 puts the 8x8 Bayer pattern on the pixels
+    before the search; 0 does not."""
+    n, H, W = _gif_frames(frames)
+    _need_cuda(palettes)
+    assert palettes.dtype == torch.uint8 and palettes.dim() == 3 and tuple(palettes.shape[1:]) == (256, 3) and palettes.shape[0] in (1, n) \
+        and palettes.is_contiguous(), (palettes.dtype, palettes.shape)
+    assert isinstance(n_colors, int) and 1 <= n_colors <= 256 and isinstance(dither_strength, int) and 0 <= dither_strength <= 128, \
+        (n_colors, dither_strength)
+    out = torch.empty(n, H, W, device=frames.device, dtype=torch.uint8)
+    per_frame = int(palettes.shape[0] == n and n > 1)
+    _launch("gif_map", 8.0 * n_colors * out.numel(), float(frames.numel() + out.numel()),
+            lambda: check(_lib.load().emo_gif_map(_ptr(frames), _ptr(palettes), _ptr(out), n, H, W, n_colors, per_frame, dither_strength, _stream()),
+                          "emo_gif_map"), tag=f"{n}x{H}x{W}")
+    return out
+
+
+def _gif_strips(indices, strip_rows):
+    _need_cuda(indices)
+    assert indices.dtype == torch.uint8 and indices.dim() == 3 and indices.is_contiguous(), (indices.dtype, indices.shape)
+    n, H, W = indices.shape
+    assert isinstance(strip_rows, int) and not isinstance(strip_rows, bool) and strip_rows >= 1, strip_rows
+    strip_rows = min(strip_rows, H)
+    return n, H, W, strip_rows, -(-H // strip_rows)
+
+
+def gif_lzw_count(indices: torch.Tensor, strip_rows: int):
+    """palette indices uint8 (n, H, W) -> (codes uint16 (n, strips, cap), n_codes int32 (n, strips), bits int32 (n, strips)): every
+    strip of strip_rows rows LZW-coded from an empty dictionary (emo_gif_lzw_count; GIF89a Appendix F at code size 8); bits counts the
+    Clear in front of a frame's first strip and the Clear / End of Information behind every strip."""
+    n, H, W, strip_rows, strips = _gif_strips(indices, strip_rows)
+    cap = int(_lib.load().emo_gif_lzw_codes_per_strip(H, W, strip_rows))
+    codes = torch.empty(n, strips, cap, device=indices.device, dtype=torch.uint16)
+    n_codes = torch.empty(n, strips, device=indices.device, dtype=torch.int32)
+    bits = torch.empty(n, strips, device=indices.device, dtype=torch.int32)
+    _launch("gif_lzw_count", 0.0, float(indices.numel()),
+            lambda: check(_lib.load().emo_gif_lzw_count(_ptr(indices), _ptr(codes), _ptr(n_codes), _ptr(bits), n, H, W, strip_rows, _stream()),
+                          "emo_gif_lzw_count"), tag=f"{n}x{H}x{W}/{strip_rows}")
+    return codes, n_codes, bits
+
+
+def gif_lzw_emit(codes: torch.Tensor, n_codes: torch.Tensor, bit_offsets: torch.Tensor, out: torch.Tensor, H: int, W: int, strip_rows: int):
+    """writes every strip's codes, least significant bit first, at its bit offset (int64 (n, strips), from out's first bit) into out, a
+    ZEROED uint8 buffer of a multiple of 4 bytes (emo_gif_lzw_emit)."""
+    _need_cuda(codes, n_codes, bit_offsets, out)
+    n, strips, cap = codes.shape
+    assert codes.dtype == torch.uint16 and codes.is_contiguous() and strip_rows >= 1 and strips == -(-H // min(strip_rows, H)) \
+        and cap == int(_lib.load().emo_gif_lzw_codes_per_strip(H, W, strip_rows)), (codes.dtype, codes.shape, H, W, strip_rows)
+    assert n_codes.dtype == torch.int32 and tuple(n_codes.shape) == (n, strips) and n_codes.is_contiguous(), (n_codes.dtype, n_codes.shape)
+    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (n, strips) and bit_offsets.is_contiguous(), (bit_offsets.dtype, bit_offsets.shape)
+    assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), (out.dtype, out.shape)
+    _launch("gif_lzw_emit", 0.0, 2.0 * codes.numel() + out.numel(),
+            lambda: check(_lib.load().emo_gif_lzw_emit(_ptr(codes), _ptr(n_codes), _ptr(bit_offsets), _ptr(out), out.numel(), n, H, W, strip_rows,
+                                                       _stream()), "emo_gif_lzw_emit"), tag=f"{n}x{H}x{W}/{strip_rows}")
+    return out
+
+
 JPEG_DECODE_TABLE_INTS = 320                     # EMO_JPEG_DECODE_TABLE_INTS
 JPEG_STATUS = {0: "ok", 1: "a code the Huffman table does not define", 2: "the scan ends before the frame's last block",
                3: "a zero run leaves its block"}   # EMO_JPEG_OK / _BAD_CODE / _PAST_END / _BAD_RUN

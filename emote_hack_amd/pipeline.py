@@ -1285,6 +1285,12 @@ class EMOAnimationPipeline:
         value is what it is without save_path.  save_restart_interval="row" (one row of MCUs) or a number of MCUs from 1 to 65535 cuts
         every frame's scan into restart intervals (a DRI segment and RSTm markers, T.81 E.1.4), which video_io.decode_mjpeg decodes in
         parallel; None, the default, writes the files written without it.
+        save_path="clip.gif" writes an animated GIF instead, the other file `imageio.mimsave` is asked for: the same 8-bit frames are
+        quantised to 256 colours, mapped and LZW-coded on the device (emote_hack_amd.video_io.encode_gif) and play at fps *
+        interpolation_factor, which may not pass 50.  save_palette="global" | "frame" (one colour table for the clip, the default, or one
+        per frame), save_dither=None | "bayer" with save_dither_strength=1 .. 128 (default 32) and save_loop=0 .. 65535 (0, the
+        default: forever) are its options; save_quality= and save_restart_interval= are refused with it.  A GIF has no sound: audio=
+        still drives the model and is not in the file.
         input_resample="bicubic" | "box" | "bilinear" | "hamming" | "lanczos" lets clips come at any size: a controlnet_condition= clip
         path or a source_image= `.avi` path whose frames are not height x width is resized on the device, byte for byte as the
         `Image.resize` of animation.py:174-185 would ("bicubic" is that call's filter; emote_hack_amd.video_io.resize_frames).  None, the
@@ -1314,18 +1320,35 @@ class EMOAnimationPipeline:
         save_path, save_quality, save_fps, save_audio = kwargs.get("save_path"), kwargs.get("save_quality", 90), None, None
         if save_path is not None:
             from . import video_io
-            save_path = video_io._avi_path(save_path, "save_path=")
+            save_gif = os.path.splitext(os.fspath(save_path))[1].lower() == ".gif"
+            if not save_gif:
+                save_path = video_io._avi_path(save_path, "save_path=", "`.gif` for an animated GIF")
+                if any(kwargs.get(k) is not None for k in ("save_palette", "save_dither", "save_dither_strength", "save_loop")):
+                    raise ValueError("save_palette=, save_dither=, save_dither_strength= and save_loop= belong to a `.gif` save_path")
             video_io.jpeg_tables(save_quality)      # quality 1 .. 100
             video_io.restart_mcus(kwargs.get("save_restart_interval"), 16)      # None, "row" or 1 .. 65535 MCUs
+            if save_gif:
+                save_path = os.fspath(save_path)
+                if kwargs.get("save_restart_interval") is not None or save_quality != 90:
+                    raise ValueError("save_restart_interval= and save_quality= belong to the JPEG frames of an `.avi` file, not to a `.gif`")
+                save_gif = dict(palette=kwargs.get("save_palette") or "global", dither=kwargs.get("save_dither"),
+                                dither_strength=32 if kwargs.get("save_dither_strength") is None else kwargs["save_dither_strength"],
+                                loop=0 if kwargs.get("save_loop") is None else kwargs["save_loop"])
+                video_io._gif_quantize_options(256, save_gif["palette"], save_gif["dither"], save_gif["dither_strength"])
+                video_io._int_in(save_gif["loop"], 0, 65535, "save_loop= (0: forever)")
             if kwargs.get("fps") is None:
                 raise ValueError("save_path= writes a video file and a file has a frame rate: pass fps= (an int, a Fraction or a (num, den) "
                                  "pair; the file plays at fps * interpolation_factor)")
+            from .conditioning import _as_fraction
+            if save_gif:      # at most 50 frames a second
+                video_io.gif_delays(video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k)),
+                                    (int(video_length) - 1) * int(interp_k) + 1 if video_length else 1)
             if self.vae is None:
                 raise ValueError("save_path= decodes the latents into 8-bit frames, as output_type=\"uint8\" does: it needs a VAE on the pipeline "
                                  "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor)")
-            from .conditioning import _as_fraction
             save_fps = video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k))
-            save_audio = self._audio_for_file(audio)
+            if not save_gif:
+                save_audio = self._audio_for_file(audio)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
         self.check_inputs(prompt, height, width, callback_steps)
@@ -1498,8 +1521,11 @@ class EMOAnimationPipeline:
                 first = math.floor(_as_fraction(kwargs.get("audio_start", 0), "audio_start") * rate)
                 count = math.floor(n_frames * rate / save_fps + Fraction(1, 2))
                 save_audio = (samples[first:first + count], rate) if first < len(samples) else None      # cut where the audio ends
-            video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio,
-                                 restart_interval=kwargs.get("save_restart_interval"))
+            if save_gif:
+                video_io.write_gif(frames_u8, save_path, save_fps, **save_gif)
+            else:
+                video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio,
+                                     restart_interval=kwargs.get("save_restart_interval"))
         if output_type == "uint8":
             video = frames_u8
         elif self.vae is not None and output_type != "latent":

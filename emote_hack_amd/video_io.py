@@ -28,7 +28,13 @@
                     (csrc/image_resize.hip) on the tables above; read_video(size=) applies it to what it decodes
   load_control_clip, comparison_videos      animation.py:174-194 (read, resize, cut, pad to whole context windows) and :217-228 (the
                     source / control / sample clips cut back to the original length), on the device
-  save_videos_grid, images2video, video2images      the reference surface, `.avi` only (mp4 and gif need encoders that are not here)
+  median_cut, quantize_frames, gif_delays, encode_gif, write_gif      the other file `imageio.mimsave` is asked for, an animated GIF
+                    (GIF89a): emo_gif_histogram -> median cut on the host (table building, like the resize taps) -> emo_gif_map
+                    -> emo_gif_lzw_count / emo_gif_lzw_emit (csrc/gif_out.hip; strips of rows coded independently between Clear codes),
+                    ONE device-to-host copy of the code streams, then the header, the colour tables, the extensions and the sub-blocks
+                    of at most 255 bytes on the host
+  save_videos_grid, images2video, video2images      the reference surface: `.avi`, and with format="gif" a `.gif` (mp4 needs an encoder
+                    that is not here)
 
 File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
 assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line; the resize tables hold
@@ -1248,13 +1254,247 @@ def read_avi(path):
     return jpegs, Fraction(rate_v, scale), audio
 
 
+# ---------------------------------------------------------------------------------------------------------------------- animated GIF
+GIF_STRIP_ROWS = 8      # rows per independently coded strip: the payload stays near the single-stream size (profiles/gif_encode.md)
+GIF_OPTIONS = ("loop", "colors", "palette", "dither", "dither_strength", "strip_rows")
+
+
+def _int_in(value, lo, hi, what):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{what} takes an int from {lo} to {hi}, got {value!r}")
+    return int(value)
+
+
+def gif_delays(fps, n) -> list:
+    """The delay of each of n frames in centiseconds (GIF89a section 23, Delay Time), d_i = r(100 (i + 1) / fps) - r(100 i / fps) with r
+    rounding halves up, in exact fractions: the delays add up to the clip's duration rounded once (30 fps: 3, 4, 3, 3, 4, ... , 100 for
+    30 frames).  fps as fps_fraction takes it.  ValueError when a delay falls below 2: players show such frames at 10, so a rate above
+    50 cannot be kept; and when one passes 65535."""
+    f = fps_fraction(fps)
+    n = _int_in(n, 1, 2 ** 31 - 1, "gif_delays: the number of frames")
+    at = [(200 * i * f.denominator + f.numerator) // (2 * f.numerator) for i in range(n + 1)]
+    delays = [b - a for a, b in zip(at, at[1:])]
+    if min(delays) < 2 or max(delays) > 65535:
+        raise ValueError(f"a GIF frame is shown for 2 .. 65535 hundredths of a second (players show shorter delays as 10): fps = {f} gives "
+                         f"delays of {min(delays)} .. {max(delays)}; at most 50 frames per second can be kept")
+    return delays
+
+
+def median_cut(hist, colors: int = 256):
+    """A histogram as emo_gif_histogram makes it - (32768, 4) integers: per bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) the pixel count
+    and the sums of R, G, B - -> (palette uint8 (k, 3), k), k <= colors.  All pixels start in one box.  While there are fewer than
+    `colors` boxes, the box with the MOST PIXELS among those that hold at least two occupied bins is split (the box made first on a tie)
+    along the axis on which its occupied bins span the most bin steps (R before G before B on a tie), between two bin coordinates: at
+    the first coordinate t at which the bins up to t hold at least half of the box's pixels, one lower where that would leave the upper
+    part empty.  The lower part keeps the box's place, the upper part goes to the end of the list.  It stops early when no box can be
+    split, so k may be below `colors` (one colour bin: k = 1).  Entry i is the mean colour of box i from the sums, each channel rounded
+    half up - not the centre of its bins.  Integer arithmetic throughout: the same histogram gives the same palette everywhere."""
+    colors = _int_in(colors, 2, 256, "colors=")
+    h = np.asarray(hist)
+    if h.shape != (32768, 4) or h.dtype.kind not in "iu":
+        raise ValueError(f"median_cut takes an integer histogram (32768, 4), got {h.dtype} {h.shape}")
+    h = h.astype(np.int64)
+    occ = np.flatnonzero(h[:, 0] > 0)
+    if occ.size == 0:
+        raise ValueError("median_cut: the histogram counts no pixels")
+    coords = np.stack([occ >> 10, (occ >> 5) & 31, occ & 31], axis=1)
+    count, sums = h[occ, 0], h[occ, 1:]
+    boxes = [np.arange(occ.size)]
+    pixels, sizes = np.zeros(colors, np.int64), np.zeros(colors, np.int64)       # per box: its pixels, its occupied bins
+    pixels[0], sizes[0] = count.sum(), occ.size
+    while len(boxes) < colors:
+        pick = int(np.argmax(np.where(sizes >= 2, pixels, -1)))                   # argmax keeps the first of equals
+        if sizes[pick] < 2:
+            break
+        box = boxes[pick]
+        c = coords[box]
+        lo, hi = c.min(axis=0), c.max(axis=0)
+        axis = int(np.argmax(hi - lo))                                           # the first of equal extents
+        v = c[:, axis]
+        if pixels[pick] < 2 ** 53:                                               # bincount sums in float64: whole numbers below 2^53, exact
+            per = np.bincount(v - lo[axis], weights=count[box], minlength=int(hi[axis] - lo[axis]) + 1).astype(np.int64)
+        else:
+            per = np.zeros(int(hi[axis] - lo[axis]) + 1, np.int64)
+            np.add.at(per, v - lo[axis], count[box])
+        t = int(lo[axis]) + int(np.searchsorted(np.cumsum(per) * 2, pixels[pick], side="left"))
+        t = min(t, int(hi[axis]) - 1)
+        low, high = box[v <= t], box[v > t]
+        new = len(boxes)
+        boxes[pick] = low
+        boxes.append(high)
+        pixels[pick], sizes[pick], pixels[new], sizes[new] = count[low].sum(), low.size, count[high].sum(), high.size
+    palette = np.zeros((len(boxes), 3), np.uint8)
+    for i, box in enumerate(boxes):
+        palette[i] = (2 * sums[box].sum(axis=0) + int(pixels[i])) // (2 * int(pixels[i]))
+    return palette, len(boxes)
+
+
+def _gif_frames(frames_u8, who):
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
+        raise ValueError(f"{who} takes packed uint8 RGB frames, (n, H, W, 3) or (1, n, H, W, 3) as output_type=\"uint8\" returns them, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if frames_u8.dim() == 5:
+        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
+    n, height, width = (int(s) for s in frames_u8.shape[:3])
+    if n < 1:
+        raise ValueError(f"{who}: no frames")
+    if not (1 <= height <= 65535 and 1 <= width <= 65535):
+        raise ValueError(f"{who}: a GIF frame is 1 .. 65535 pixels each way, got {height} x {width}")
+    return frames_u8
+
+
+def _gif_quantize_options(colors, palette, dither, dither_strength):
+    colors = _int_in(colors, 2, 256, "colors=")
+    if palette not in ("global", "frame"):
+        raise ValueError(f"palette= takes \"global\" (one colour table for the clip) or \"frame\" (one per frame), got {palette!r}")
+    if dither not in (None, "bayer"):
+        raise ValueError(f"dither= takes None or \"bayer\" (the 8x8 ordered dither), got {dither!r}")
+    strength = _int_in(dither_strength, 1, 128, "dither_strength=")
+    return colors, palette, strength if dither == "bayer" else 0
+
+
+def quantize_frames(frames_u8: torch.Tensor, colors: int = 256, palette: str = "global", dither=None, dither_strength: int = 32):
+    """Packed uint8 RGB device frames (n, H, W, 3) -> (indices uint8 (n, H, W) on the device, palettes uint8 numpy (1, 256, 3) for
+    palette="global" or (n, 256, 3) for "frame", n_colors): emo_gif_histogram, one read of the histogram (512 KiB of counts and sums as
+    64-bit figures: 1 MiB per table), median_cut on the host, emo_gif_map.  n_colors is the number of entries in use - an int for
+    "global", a tuple of n ints for "frame"; the entries behind them are zero and never indexed.  Every pixel gets the nearest entry
+    of its table (squared distance on the 8-bit values, the lowest index on a tie), after the ordered dither when dither="bayer":
+    v + floor((2 B8[y & 7][x & 7] - 63) * dither_strength / 128) clamped to 0 .. 255, dither_strength 1 .. 128."""
+    colors, palette, strength = _gif_quantize_options(colors, palette, dither, dither_strength)
+    frames_u8 = _gif_frames(frames_u8, "quantize_frames").contiguous()
+    n = int(frames_u8.shape[0])
+    hist = ops.gif_histogram(frames_u8, per_frame=palette == "frame").cpu().numpy()
+    palettes = np.zeros((hist.shape[0], 256, 3), np.uint8)
+    used = []
+    for i in range(hist.shape[0]):
+        entries, k = median_cut(hist[i], colors)
+        palettes[i, :k] = entries
+        used.append(k)
+    device_palettes = torch.from_numpy(palettes).to(frames_u8.device)
+    if len(set(used)) == 1:
+        indices = ops.gif_map(frames_u8, device_palettes, used[0], strength)
+    else:                                                                        # tables of different sizes: one launch per frame
+        indices = torch.cat([ops.gif_map(frames_u8[i:i + 1], device_palettes[i:i + 1], used[i], strength) for i in range(n)])
+    return indices, palettes, (used[0] if palette == "global" else tuple(used))
+
+
+def _gif_strip_rows(strip_rows, height):
+    return int(height) if strip_rows is None else _int_in(strip_rows, 1, 65535, "strip_rows= (None: the frame as one stream)")
+
+
+def gif_code_streams(indices: torch.Tensor, strip_rows=GIF_STRIP_ROWS):
+    """The device part of the LZW coding: palette indices uint8 (n, H, W) on the device -> (streams uint8 device buffer, byte start of
+    every frame, bytes of every frame); two launches and one read of the n frame totals between them.  Every frame starts on a byte;
+    inside a frame the strips follow each other bit by bit."""
+    rows = _gif_strip_rows(strip_rows, indices.shape[1])
+    codes, n_codes, bits = ops.gif_lzw_count(indices, rows)
+    ends = torch.cumsum(bits, dim=1, dtype=torch.int64)
+    nbytes = (ends[:, -1].cpu().numpy() + 7) // 8                                # the one read before the streams themselves
+    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+    offsets = (ends - bits + torch.from_numpy(starts * 8).to(ends.device)[:, None]).contiguous()
+    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=indices.device, dtype=torch.uint8)
+    ops.gif_lzw_emit(codes, n_codes, offsets, out, int(indices.shape[1]), int(indices.shape[2]), rows)
+    return out, starts, nbytes
+
+
+def gif_sub_blocks(stream) -> bytes:
+    """image data -> data sub-blocks (GIF89a section 15): a size byte of 1 .. 255 in front of every 255 bytes, a block terminator behind"""
+    a = np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray)) else np.asarray(stream, np.uint8)
+    at = np.arange(0, len(a), 255)
+    sizes = np.minimum(len(a) - at, 255).astype(np.uint8)
+    return np.insert(a, at, sizes).tobytes() + b"\x00"
+
+
+def gif_container(width: int, height: int, palettes: np.ndarray, streams, delays, loop: int = 0) -> bytes:
+    """The file around the frames' LZW streams (bytes or uint8 arrays, code size 8): header `GIF89a`, logical screen descriptor (section
+    18) with a 256-entry global colour table (19) - palettes[0] -, the NETSCAPE2.0 application extension (26) with the loop count
+    (0: forever), and per frame a graphic control extension (23: disposal 1, no transparency, the delay), an image descriptor (20) for
+    the whole frame - with a 256-entry local colour table (21) when palettes holds one table per frame -, the code size and the
+    sub-blocks; the trailer (27)."""
+    palettes = np.asarray(palettes)
+    n = len(streams)
+    if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+        raise ValueError(f"a GIF frame is 1 .. 65535 pixels each way, got {height} x {width}")
+    loop = _int_in(loop, 0, 65535, "loop= (0: forever)")
+    if palettes.dtype != np.uint8 or palettes.ndim != 3 or palettes.shape[1:] != (256, 3) or palettes.shape[0] not in (1, n) or len(delays) != n or n < 1:
+        raise ValueError(f"gif_container: {n} frames, {len(delays)} delays, colour tables {palettes.dtype} {palettes.shape} (uint8 (1 | n, 256, 3))")
+    local = palettes.shape[0] == n and n > 1
+    out = [b"GIF89a", struct.pack("<HHBBB", int(width), int(height), 0xF7, 0, 0), palettes[0].tobytes(),
+           b"\x21\xFF\x0BNETSCAPE2.0\x03\x01" + struct.pack("<H", loop) + b"\x00"]
+    for i in range(n):
+        out.append(b"\x21\xF9\x04\x04" + struct.pack("<H", _int_in(delays[i], 0, 65535, "a frame's delay")) + b"\x00\x00")
+        out.append(b"\x2C" + struct.pack("<HHHHB", 0, 0, int(width), int(height), 0x87 if local else 0x00))
+        if local:
+            out.append(palettes[i].tobytes())
+        out.append(b"\x08" + gif_sub_blocks(streams[i]))
+    out.append(b"\x3B")
+    return b"".join(out)
+
+
+def encode_gif(frames_u8: torch.Tensor, fps, loop: int = 0, colors: int = 256, palette: str = "global", dither=None, dither_strength: int = 32,
+               strip_rows=GIF_STRIP_ROWS) -> bytes:
+    """Packed uint8 RGB frames on the device, (n, H, W, 3) (or the (1, n, H, W, 3) of output_type="uint8") -> an animated GIF89a file
+    as bytes, playing at fps (gif_delays: at most 50) and repeating `loop` times (0: forever).  quantize_frames picks the colours
+    (colors=2 .. 256; palette="global": one table for the clip, "frame": a local table per frame, the global one then holds frame 0's;
+    dither=None | "bayer" at dither_strength=1 .. 128) and maps the pixels on the device; the LZW coding runs there too, every frame
+    cut into strips of strip_rows rows that are coded independently between Clear codes (None: one stream per frame), and the code
+    streams come back in one copy.  Every frame is a whole frame: no differences between frames, no transparency.  All arguments are
+    checked before the first launch."""
+    frames_u8 = _gif_frames(frames_u8, "encode_gif")
+    n, height, width = (int(s) for s in frames_u8.shape[:3])
+    delays = gif_delays(fps, n)
+    loop = _int_in(loop, 0, 65535, "loop= (0: forever)")
+    _gif_quantize_options(colors, palette, dither, dither_strength)
+    _gif_strip_rows(strip_rows, height)
+    indices, palettes, _ = quantize_frames(frames_u8, colors, palette, dither, dither_strength)
+    out, starts, nbytes = gif_code_streams(indices, strip_rows)
+    host = out.cpu().numpy()
+    return gif_container(width, height, palettes, [host[s:s + b] for s, b in zip(starts, nbytes)], delays, loop)
+
+
+def _gif_path(path, who):
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() != ".gif":
+        raise ValueError(f"{who} writes an animated GIF: name the file `.gif`, got {path!r}")
+    return path
+
+
+def write_gif(frames_u8: torch.Tensor, path, fps, **options) -> None:
+    """encode_gif (with its options) into the `.gif` file at path"""
+    path = _gif_path(path, "write_gif")
+    unknown = sorted(set(options) - set(GIF_OPTIONS))
+    if unknown:
+        raise ValueError(f"write_gif: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; a GIF takes {', '.join(GIF_OPTIONS)}")
+    data = encode_gif(frames_u8, fps, **options)
+    _makedirs_for(path)
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
 # ---------------------------------------------------------------------------------------------------------------------- reference surface
-def _avi_path(path, who):
+def _avi_path(path, who, gif_hint="pass format=\"gif\" with a `.gif` path for an animated GIF"):
     path = os.fspath(path)
     if os.path.splitext(path)[1].lower() != ".avi":
-        raise ValueError(f"{who} writes Motion-JPEG `.avi` files, got {path!r}: name the file `.avi` (mp4 and gif need encoders that are not "
-                         "part of this build)")
+        raise ValueError(f"{who} writes Motion-JPEG `.avi` files, got {path!r}: name the file `.avi`, or {gif_hint} (mp4 needs an encoder "
+                         "that is not part of this build)")
     return path
+
+
+def _output_path(path, who, format, quality, restart_interval, gif_options):
+    """what the writers of the reference surface check before anything runs -> (path, is it a GIF)"""
+    if format is None:
+        if gif_options:
+            raise ValueError(f"{who}: {', '.join(sorted(gif_options))} belong{'s' if len(gif_options) == 1 else ''} to format=\"gif\"")
+        return _avi_path(path, who), False
+    if format != "gif":
+        raise ValueError(f"{who}: format= takes None (a Motion-JPEG `.avi` file) or \"gif\", got {format!r}")
+    path = _gif_path(path, f"{who} with format=\"gif\"")
+    unknown = sorted(set(gif_options) - set(GIF_OPTIONS))
+    if unknown:
+        raise ValueError(f"{who}: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; a GIF takes {', '.join(GIF_OPTIONS)}")
+    if quality != 90 or restart_interval is not None:
+        raise ValueError(f"{who}: quality= and restart_interval= belong to the JPEG frames of an `.avi` file; a GIF takes {', '.join(GIF_OPTIONS)}")
+    return path, True
 
 
 def _makedirs_for(path):
@@ -1263,9 +1503,15 @@ def _makedirs_for(path):
         os.makedirs(d, exist_ok=True)            # util.py:32
 
 
-def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None) -> None:
-    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + write_avi"""
-    path = _avi_path(path, "write_video")
+def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None, format=None, **gif_options) -> None:
+    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + write_avi.  With format="gif" and a
+    `.gif` path: an animated GIF instead (write_gif; its options - loop, colors, palette, dither, dither_strength, strip_rows - as
+    keywords; quality=, restart_interval= and audio= have no place in one and are refused)."""
+    path, gif = _output_path(path, "write_video", format, quality, restart_interval, gif_options)
+    if gif:
+        if audio is not None:
+            raise ValueError("write_video: a GIF holds no sound; write an `.avi` file for audio=")
+        return write_gif(frames_u8, path, fps, **gif_options)
     if frames_u8.dim() == 5:
         frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
     jpegs = encode_mjpeg(frames_u8, quality, restart_interval)
@@ -1299,21 +1545,23 @@ def make_grid_u8(videos: torch.Tensor, rescale=False, n_rows=6) -> torch.Tensor:
     return (grid * 255).clamp(0, 255).to(torch.uint8).contiguous()               # util.py:29
 
 
-def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90, restart_interval=None):
+def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90, restart_interval=None, format=None,
+                     **gif_options):
     """magicanimate/utils/util.py:21-33 with a Motion-JPEG `.avi` in place of imageio.mimsave.  The frames are encoded on the HIP device:
-    videos held on the host are uploaded.  restart_interval as in encode_mjpeg."""
-    path = _avi_path(path, "save_videos_grid")
+    videos held on the host are uploaded.  restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes the animated GIF
+    mimsave would (write_video)."""
+    path, _ = _output_path(path, "save_videos_grid", format, quality, restart_interval, gif_options)
     if torch.is_tensor(videos) and not videos.is_cuda:
         videos = videos.to("cuda")
-    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality, restart_interval=restart_interval)
+    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality, restart_interval=restart_interval, format=format, **gif_options)
 
 
-def images2video(video, path, fps=8, quality: int = 90, restart_interval=None):
+def images2video(video, path, fps=8, quality: int = 90, restart_interval=None, format=None, **gif_options):
     """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file.
-    restart_interval as in encode_mjpeg."""
-    path = _avi_path(path, "images2video")
+    restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes an animated GIF (write_video)."""
+    path, _ = _output_path(path, "images2video", format, quality, restart_interval, gif_options)
     frames = video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))
-    write_video(frames.to("cuda"), path, fps, quality, restart_interval=restart_interval)
+    write_video(frames.to("cuda"), path, fps, quality, restart_interval=restart_interval, format=format, **gif_options)
 
 
 def decode_jpeg(data: bytes) -> np.ndarray:

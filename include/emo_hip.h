@@ -502,6 +502,43 @@ int emo_jpeg_count_bits_ri(const int16_t* coefs, int32_t* counts, int n, int n_m
 int emo_jpeg_emit_bits_ri(const int16_t* coefs, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n, int n_mcu,
                           int restart_mcus, const uint32_t* huff, void* stream);
 
+/* ---- Animated GIF output: the device half of the second container `imageio.mimsave(path, frames, fps)` is used for at the end of
+ * `save_videos_grid` (magicanimate/utils/util.py:33).  GIF89a; the host half (median cut over the histogram, the header, the colour
+ * tables, the extensions, the sub-blocks of at most 255 bytes) is emote_hack_amd/video_io.py.  The kernels live in csrc/gif_out.hip.
+ * emo_gif_histogram (util.py:33; the colours a GIF89a colour table, section 19 / 21, is chosen from): packed uint8 RGB frames
+ *   [n][H][W][3] -> hist uint64 [per_frame ? n : 1][32768][4]: per bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) the pixel count and the
+ *   sums of R, G and B.  The figures are ADDED to hist (the caller zeroes it) with 64-bit integer atomics only, so the result does not
+ *   depend on the order of execution.  Exact without wrap-around while n * H * W <= 2^55 (255 * 2^55 < 2^63), which the entry enforces;
+ *   H, W in 1 .. 65535 (the logical screen descriptor, section 18, holds 16 bits).
+ * emo_gif_map (util.py:33; GIF89a section 22, table based image data: one colour table index per pixel): indices uint8 [n][H][W] =
+ *   the k in 0 .. n_colors - 1 that minimises (R - pr[k])^2 + (G - pg[k])^2 + (B - pb[k])^2 on the 8-bit integers, the LOWEST k on a
+ *   tie; an exact search.  palettes uint8 [per_frame ? n : 1][256][3]; entries from n_colors up are never read.  dither_strength 0:
+ *   none; 1 .. 128: before the search every channel v becomes clamp(v + floor((2 * B8[y & 7][x & 7] - 63) * strength / 128), 0, 255), B8
+ *   the 8x8 Bayer matrix of B1 = [[0]], B2k = [[4B, 4B + 2], [4B + 3, 4B + 1]].
+ * emo_gif_lzw_count / emo_gif_lzw_emit (util.py:33; GIF89a Appendix F, variable-length-code LZW compression, with code size 8:
+ *   Clear = 256, End of Information = 257, first free code 258, codes of 9 .. 12 bits packed least significant bit first).  A frame is
+ *   cut into strips of strip_rows rows (the last may be shorter; strip_rows >= H: one strip), at most 2^26 pixels each.  Every strip
+ *   is coded from an empty dictionary at 9 bits and is laid out as
+ *     [Clear, 9 bits: the frame's first strip only]  codes ...  Clear (End of Information behind the frame's last strip)
+ *   so its bits depend on its own pixels only.  The width of a code is the decoder's: it grows when the decoder's next free code
+ *   reaches 1 << width, the closing Clear / End of Information included.  Code 3838 behind a Clear finds the table full (4096): a Clear
+ *   follows it and the dictionary starts again.
+ *   emo_gif_lzw_count walks every strip once: codes uint16 [n * strips][emo_gif_lzw_codes_per_strip(H, W, strip_rows)] takes the
+ *   strip's codes (Clears inside the strip included, the opening and the closing code not), n_codes int32 [n * strips] their number,
+ *   bits int32 [n * strips] the strip's exact size in bits, opening and closing code included.
+ *   emo_gif_lzw_emit ORs them into out at bit_offsets[strip] (int64 [n * strips], from the first bit of out: the caller lays a
+ *   frame's strips end to end and starts every frame on a byte).  out must be zeroed, 4-byte aligned, out_bytes a multiple of 4:
+ *   32-bit atomicOr, since strips and frames share words; a word is touched only where a code has a 1-bit in it and never at or beyond
+ *   out_bytes. */
+int emo_gif_histogram(const uint8_t* frames, uint64_t* hist, int n, int H, int W, int per_frame, void* stream);
+int emo_gif_map(const uint8_t* frames, const uint8_t* palettes, uint8_t* indices, int n, int H, int W, int n_colors, int per_frame,
+                int dither_strength, void* stream);
+int64_t emo_gif_lzw_codes_per_strip(int H, int W, int strip_rows);
+int emo_gif_lzw_count(const uint8_t* indices, uint16_t* codes, int32_t* n_codes, int32_t* bits, int n, int H, int W, int strip_rows,
+                      void* stream);
+int emo_gif_lzw_emit(const uint16_t* codes, const int32_t* n_codes, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n,
+                     int H, int W, int strip_rows, void* stream);
+
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
  * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, three components at 2x2 / 1x1 / 1x1 in one interleaved
