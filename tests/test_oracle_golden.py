@@ -15,6 +15,7 @@ from oracle import scheduler_ref as S
 from oracle import unet_ref as U
 from oracle.pipeline_ref import denoise_loop
 from tests import cases
+from tests.block_cases import motion_shapes, resnet_shapes, tf_shapes  # noqa: F401  (the shape helpers live beside the block tables)
 
 G = cases.GOLDEN_DIR
 RTOL, ATOL = 1e-3, 1e-4
@@ -95,15 +96,6 @@ def test_timestep_embedding(mods):
     close(out, mods["temb/mlp_out"])
 
 
-def resnet_shapes(cin, cout, temb=128):
-    d = {"norm1.weight": (cin,), "norm1.bias": (cin,), "conv1.weight": (cout, cin, 3, 3), "conv1.bias": (cout,),
-         "time_emb_proj.weight": (cout, temb), "time_emb_proj.bias": (cout,), "norm2.weight": (cout,),
-         "norm2.bias": (cout,), "conv2.weight": (cout, cout, 3, 3), "conv2.bias": (cout,)}
-    if cin != cout:
-        d.update({"conv_shortcut.weight": (cout, cin, 1, 1), "conv_shortcut.bias": (cout,)})
-    return d
-
-
 @pytest.mark.parametrize("name,cin,cout", [("resnet_sc", 32, 64), ("resnet_id", 64, 64)])
 def test_resnet(mods, name, cin, cout):
     sd = {"r." + k: v for k, v in sd_for(resnet_shapes(cin, cout), name + ".").items()}
@@ -139,26 +131,12 @@ def test_feed_forward(mods):
     close(U.feed_forward(sd, "f", seeded_randn((2, 16, 64), 30)), mods["ff/out"])
 
 
-def tf_shapes(c, ctx, lin):
-    from emote_hack_amd.spec import TransformerSpec, _transformer_shapes
-    d = {}
-    _transformer_shapes(TransformerSpec("t", c, 4, ctx, lin), d)
-    return {k[2:]: v for k, v in d.items()}
-
-
 @pytest.mark.parametrize("name,lin", [("tf3d", False), ("tf3d_lin", True)])
 def test_transformer3d(mods, name, lin):
     sd = {"t." + k: v for k, v in sd_for(tf_shapes(64, 32, lin), name + ".").items()}
     x = seeded_randn((2, 64, 3, 4, 4), 40)
     close(U.transformer3d(sd, "t", x, seeded_randn((2, 5, 32), 41), 4, 8, lin), mods[f"{name}/out"])
     close(U.transformer3d(sd, "t", x, seeded_randn((6, 5, 32), 42), 4, 8, lin), mods[f"{name}/out_perframe_ctx"])
-
-
-def motion_shapes(c, heads, pe=24):
-    from emote_hack_amd.spec import MotionSpec, _motion_shapes
-    d = {}
-    _motion_shapes(MotionSpec("m", c, heads, 2, pe), d)
-    return {k[2:]: v for k, v in d.items()}
 
 
 def test_motion_module(mods):
