@@ -9,8 +9,10 @@ static inline int cgrid(int64_t n) { int64_t g = (n + 255) / 256; return (int)(g
 template <typename T>
 __global__ void act_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n, int kind) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    float v = TT<T>::ld(x + i);
-    v = kind == 0 ? silu_f(v) : (kind == 1 ? fmaxf(v, 0.f) : (kind == 2 ? tanhf(v) : (kind == 3 ? gelu_for<T>(v) : v / (1.0f + expf(-1.702f * v)))));
+    const float x0 = TT<T>::ld(x + i);
+    // (ReLU keeps a NaN, as torch.relu does: fmaxf returns the other operand)
+    float v = kind == 0 ? silu_f(x0) : (kind == 1 ? (x0 > 0.f ? x0 : (x0 == x0 ? 0.f : x0)) : (kind == 2 ? tanhf(x0) : (kind == 3 ? gelu_for<T>(x0) : x0 / (1.0f + expf(-1.702f * x0)))));
+    if (x0 == -INFINITY && kind != 1 && kind != 2) v = -0.f;   // x * sigmoid(x) and x * Phi(x) at -inf: the limit, not -inf * 0
     TT<T>::st(y + i, v);
   }
 }

@@ -252,8 +252,10 @@ extern "C" int emo_convert(const void* src, int sdt, void* dst, int ddt, int64_t
 
 template <typename T>
 __global__ __launch_bounds__(256) void silu_kernel(const T* __restrict__ x, T* __restrict__ y, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    TT<T>::st(y + i, silu_f(TT<T>::ld(x + i)));
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = TT<T>::ld(x + i);
+    TT<T>::st(y + i, v == -INFINITY ? -0.f : silu_f(v));   // (the limit at -inf, where x * sigmoid(x) is -inf * 0)
+  }
 }
 extern "C" int emo_silu(const void* x, void* y, int64_t n, int dtype, void* stream) {
   EMO_CHECK(x && y, EMO_ERR_NULL, "emo_silu: null pointer");
