@@ -80,9 +80,19 @@ template <int PH_, int BN_ = HaloGeom::BN> struct HaloT {
 // (scale, scale, shift, shift) quads wave 0 brings into LDS on tap 0 (one more direct-to-LDS request).  The arithmetic of a slot is
 // spread over the tap's four k-steps, one packed pair per k-step (its coefficient quad read with the fragments), a quarter of it
 // behind each MFMA: the VALU work fills issue slots the matrix pipe leaves empty (the loop uses 45-55 % of them).
-template <typename T, int PH_, int BN_ = HaloGeom::BN, bool GN = false>
+// UNR: the nine taps of a chunk unrolled (16-row patches, 2-byte types, 128 / 64 channels, no GN fold; emo_gemm_params.tile bit 5
+// keeps the rolled loop: gemm.hip plan_halo).  Same requests, waits, barriers and MFMAs in the same order - the outputs are the same
+// bits; what goes is the per-tap address arithmetic (tap offset, fragment bases, swizzle keys: constants per tap position now), the
+// branch ladder of the halo pieces and the loop control between a stage's barrier and its first fragment reads: +8 to 13 % on
+// the long-K convs, 171 -> 255 VGPRs at 128 channels (114 -> 191 at 64), no scratch (profiles/conv_halo_pipeline.md).  The
+// 192-channel block (96 accumulator registers) spills 252 bytes per lane unrolled and stays rolled, like the GN variant (245 VGPRs
+// rolled).  The rolled instantiations carry an unroll count of 1: hipcc's own choice for them was to leave the loop alone (GN: to
+// peel it, for 0 to 4 % on the fold's convs - tools/bench/gn_conv_bench.py; the fold is off by default, unet.py GN_CONV_MIN_HW).
+template <typename T, int PH_, int BN_ = HaloGeom::BN, bool GN = false, bool UNR = false>
 __global__ __launch_bounds__(32 * PH_, 2) void conv3x3_halo_kernel(const emo_gemm_params p) {
   using Halo = HaloT<PH_, BN_>;
+  constexpr int TAP_UNROLL = UNR ? 9 : 1;
+  static_assert(!UNR || (PH_ == 16 && !GN && sizeof(T) == 2 && BN_ != 192), "halo conv: the unrolled loop's instantiations");
   constexpr int V = TT<T>::VEC, BK = KBYTES / (int)sizeof(T);
   constexpr int WTM = 2, WTN = BN_ / 64, NW = Halo::NW, LH = Halo::LH, LB = Halo::LB, BN = Halo::BN;   // two wave columns of WTN x 32 channels
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -287,8 +297,22 @@ __global__ __launch_bounds__(32 * PH_, 2) void conv3x3_halo_kernel(const emo_gem
         }
     }
 
+    // ---- main loop: the schedule of a stage s (tap t of a chunk), rolled or unrolled
+    //   wait     vmcnt(0): nothing of this wave's stays outstanding - W(s) (requested behind the barrier of stage s - 1), the halo
+    //            piece of tap t - 1 and, at a later tile's head, the epilogue's stores; at t == 0 that completes the chunk's halo
+    //            (pieces requested on taps 0..5 of the previous chunk)
+    //   barrier  publishes W(s) / the halo to every wave; every wave has finished the reads of stage s - 1 (lgkmcnt(0) in front of
+    //            its last MFMAs)
+    //   request  W(s + 1) -> weight slot (s + 1) % 2: last read in stage s - 1, next read behind the barrier of stage s + 1;
+    //            halo piece t (t < 6) of the next chunk -> halo buffer (chunk + 1) % 2: last read in the previous chunk (and by the
+    //            staged epilogue of a tile end, in front of this barrier), next read behind the barrier of the next chunk's tap 0
+    //   reads    weight slot s % 2 and the chunk's halo buffer, k-step kk + 1 behind the MFMAs of kk
+    // A deeper ring (4 slots, counted vmcnt, with and without the next stage's first fragments read a stage ahead) was built and
+    // measured: it gains nothing over this schedule once the taps are unrolled (profiles/conv_halo_pipeline.md,
+    // tools/bench/patches/conv_halo_deep_ring.patch).
     for (int c = 0; c < nchunks; c++, gc++) {
       const unsigned stH = lds_base + (gc & 1) * Halo::HALO_BYTES;
+#pragma unroll TAP_UNROLL
       for (int t = 0; t < 9; t++, gs++) {
         wait_vmcnt<0>();                  // this stage's weights (and, at t == 0, the whole halo) have landed
         __builtin_amdgcn_s_barrier();     // ... for every wave; everyone is done with the previous stage's slot
@@ -440,22 +464,27 @@ __global__ __launch_bounds__(32 * PH_, 2) void conv3x3_halo_kernel(const emo_gem
   }
 }
 
-template <typename T, int PH_, int BN_, bool GN> static int launch_halo(const emo_gemm_params& p, int64_t gx, hipStream_t st) {
+template <typename T, int PH_, int BN_, bool GN, bool UNR = false> static int launch_halo(const emo_gemm_params& p, int64_t gx, hipStream_t st) {
   using Halo = HaloT<PH_, BN_>;
   constexpr int lds_bytes = Halo::LDS_BYTES + (GN ? Halo::GN_BYTES : 0);
   static bool once = false;
   if (!once) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, PH_, BN_, GN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_halo_kernel<T, PH_, BN_, GN, UNR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return emo_fail(EMO_ERR_HIP, "emo_gemm: hipFuncSetAttribute(halo conv): %s", hipGetErrorString(e));
     once = true;
   }
-  conv3x3_halo_kernel<T, PH_, BN_, GN><<<(unsigned)gx, 64 * Halo::NW, lds_bytes, st>>>(p);
+  conv3x3_halo_kernel<T, PH_, BN_, GN, UNR><<<(unsigned)gx, 64 * Halo::NW, lds_bytes, st>>>(p);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
-// bn = output channels per block (128, or 64: the remainder launch of a width that is an odd multiple of 64)
-template <typename T> int gemm_run_halo(const emo_gemm_params& p, int ph, int bn, int64_t gx, hipStream_t st) {
+// bn = output channels per block (128, or 64: the remainder launch of a width that is an odd multiple of 64); unrolled: the main loop
+// with its nine taps unrolled (plan_halo: 16-row patches, 2-byte types, no GN fold; the 192-channel block has no such instantiation)
+template <typename T> int gemm_run_halo(const emo_gemm_params& p, int ph, int bn, int unrolled, int64_t gx, hipStream_t st) {
+  if constexpr (sizeof(T) == 2) {
+    if (unrolled && ph == 16 && !p.gn_coef && bn != 192)
+      return bn == 64 ? launch_halo<T, 16, 64, false, true>(p, gx, st) : launch_halo<T, 16, 128, false, true>(p, gx, st);
+  }
   if (p.gn_coef) {
     if (bn == 64) return ph == 16 ? launch_halo<T, 16, 64, true>(p, gx, st) : launch_halo<T, 8, 64, true>(p, gx, st);
     return ph == 16 ? launch_halo<T, 16, 128, true>(p, gx, st) : launch_halo<T, 8, 128, true>(p, gx, st);

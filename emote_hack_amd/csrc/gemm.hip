@@ -5,9 +5,9 @@
 extern template int gemm_run<float>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
 extern template int gemm_run<bf16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
 extern template int gemm_run<f16_t>(const emo_gemm_params&, const GemmPlan&, int, hipStream_t, GemmLaunchPlan*);
-extern template int gemm_run_halo<float>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
-extern template int gemm_run_halo<bf16_t>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
-extern template int gemm_run_halo<f16_t>(const emo_gemm_params&, int, int, int64_t, hipStream_t);
+extern template int gemm_run_halo<float>(const emo_gemm_params&, int, int, int, int64_t, hipStream_t);
+extern template int gemm_run_halo<bf16_t>(const emo_gemm_params&, int, int, int, int64_t, hipStream_t);
+extern template int gemm_run_halo<f16_t>(const emo_gemm_params&, int, int, int, int64_t, hipStream_t);
 
 extern "C" int emo_gemm_suggest_split_k(int64_t M, int N, int K, int dtype, int geglu, int transpose_out) {
   return plan_gemm(M, N, K, dtype, geglu, transpose_out).split_k;
@@ -76,7 +76,7 @@ extern "C" int emo_gemm_vt_ok(const emo_gemm_params* pp) { return pp && emo_dtyp
 // The launch decisions of the halo family (halo_conv_ok(p) holds): patch height, and per launch the block width, the output columns
 // [n0, n0 + n) it covers, its tiles and its grid.  ONE function for the launch path and emo_conv3x3_halo_plan.
 struct HaloLaunch { int bn, n0, n; int64_t tiles, grid; };   // bn == 0: no such launch
-struct HaloPlan { int served, ph; HaloLaunch main, tail; };
+struct HaloPlan { int served, ph; HaloLaunch main, tail; int unrolled; };   // unrolled: the main loop with its nine taps unrolled (conv_halo_impl.h)
 static HaloPlan plan_halo(const emo_gemm_params& p) {
   const int He = p.upsample2x ? 2 * p.H : p.H, We = p.upsample2x ? 2 * p.W_ : p.W_;
   const int64_t nt = (p.N + HaloGeom::BN - 1) / HaloGeom::BN;
@@ -99,7 +99,12 @@ static HaloPlan plan_halo(const emo_gemm_params& p) {
     const int64_t tiles = n_img * tpx * (ph16 ? He / 16 : (He + 7) / 8) * ntq, slots = ph16 ? 256 : 512;
     return HaloLaunch{bn, n0, n, tiles, tiles > slots ? slots : tiles};
   };
-  HaloPlan h = {1, ph16 ? 16 : 8, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+  // The 16-row patches of the 2-byte types run the main loop with its nine taps unrolled (conv_halo_impl.h UNR) wherever the block
+  // has that instantiation - 128 and 64 channels without the GN fold: 10-13 % faster on every such conv of the cfg2 step, none
+  // slower (profiles/conv_halo_pipeline.md) - so there is no rule on shape.  p.tile bit 5 (32) keeps the rolled loop (tools/bench
+  // A/B, and the bit-identity tests: both loops issue the same MFMAs in the same order).
+  const int unrolled = ph16 && p.dtype != EMO_F32 && !p.gn_coef && !(p.tile & EMO_TILE_HINT_HALO_ROLLED) ? 1 : 0;
+  HaloPlan h = {1, ph16 ? 16 : 8, {0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}, unrolled};
   if (!n_rem) {
     h.main = launch(0, p.N, p.N == 64 ? 64 : ((p.N == 192 && ph16 && !p.gn_coef && !(p.tile & 8)) ? 192 : HaloGeom::BN));
     return h;
@@ -167,13 +172,18 @@ static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* l
     auto launch = [&](const HaloLaunch& l) {
       const emo_gemm_params q = output_columns(p, l.n0, l.n);
       int rc_h = EMO_OK;
-      EMO_DISPATCH(q.dtype, "emo_gemm", rc_h = gemm_run_halo<T>(q, h.ph, l.bn, l.grid, as_stream(stream)));
+      EMO_DISPATCH(q.dtype, "emo_gemm", rc_h = gemm_run_halo<T>(q, h.ph, l.bn, h.unrolled, l.grid, as_stream(stream)));
       return rc_h;
     };
     const int rc_a = h.main.bn ? launch(h.main) : EMO_OK;
     return rc_a || !h.tail.bn ? rc_a : launch(h.tail);
   }
-  GemmPlan pl = plan_gemm(p.M, p.N, p.K, p.dtype, p.geglu, p.transpose_out, p.tile & 15, p.ln_colsum != nullptr);   // (tile >> 4: tile-order override, gemm_impl.h)
+  // A conv that carries hint bits of the halo family (bits 3, 4, 5: plan_halo) but is not served by it falls through to here, where
+  // bit 3 would read as a dense tile id and bits 4, 5 as the tile-order override (tile >> 4, gemm_impl.h): they are dropped, and the
+  // dense path sees the conv's tile pin (bits 0-2) alone
+  emo_gemm_params pd = p;
+  if (conv) pd.tile &= ~EMO_TILE_HINT_HALO_MASK;
+  GemmPlan pl = plan_gemm(p.M, p.N, p.K, p.dtype, p.geglu, p.transpose_out, pd.tile & 15, p.ln_colsum != nullptr);   // (tile >> 4: tile-order override, gemm_impl.h)
   if (S > 1) {
     EMO_CHECK(p.workspace != nullptr && S <= 65535, EMO_ERR_NULL, "emo_gemm: split_k=%d needs a workspace", S);
     EMO_CHECK(p.N % 4 == 0, EMO_ERR_BAD_SHAPE, "emo_gemm: split-K needs N %% 4 == 0");
@@ -181,7 +191,7 @@ static int gemm_entry(const emo_gemm_params* pp, void* stream, GemmLaunchPlan* l
   if (hp) { *hp = HaloPlan{}; return EMO_OK; }   // (not the halo family's: served = 0)
   hipStream_t st = as_stream(stream);
   int rc = EMO_OK;
-  EMO_DISPATCH(p.dtype, "emo_gemm", rc = gemm_run<T>(p, pl, S, st, lp));
+  EMO_DISPATCH(p.dtype, "emo_gemm", rc = gemm_run<T>(pd, pl, S, st, lp));
   return rc;
 }
 

@@ -17,6 +17,11 @@ enum { EMO_TILE_AUTO = 0, EMO_TILE_64x64 = 1, EMO_TILE_128x128 = 2, EMO_TILE_128
        EMO_TILE_256x160 = 5, EMO_TILE_256x320 = 6, EMO_TILE_256x256_PP = 7 };   // 7: the ping-pong main loop on the 256x256 tile (gemm_impl.h)
 // (measured and dropped: 4 waves of 128x128 with 512 registers - 880-900 TFLOP/s at 8192^3 against 1100 and 2-3x slower on short
 // K, hipcc spills ~220 VGPRs around the epilogue; a register-staged loader - tools/bench/patches/gemm_staged_loader.patch)
+// emo_gemm_params.tile of a 3x3 conv carries the halo family's hints (gemm.hip plan_halo): bits 0-1 pin the patch height, bit 2 keeps a
+// single launch at N % 128 == 64, bit 3 the 64-column remainder launch, bit 4 forces 192-column blocks, bit 5 keeps the rolled
+// main loop.  Bits 3-5 mean nothing to the dense path and are dropped before a conv the family does not serve falls through to it.
+enum { EMO_TILE_HINT_HALO_REM64 = 8, EMO_TILE_HINT_HALO_BN192 = 16, EMO_TILE_HINT_HALO_ROLLED = 32,
+       EMO_TILE_HINT_HALO_MASK = EMO_TILE_HINT_HALO_REM64 | EMO_TILE_HINT_HALO_BN192 | EMO_TILE_HINT_HALO_ROLLED };
 struct GemmPlan { int tile, split_k; };
 
 static inline void tile_dims(int tile, int& bm, int& bn) {
@@ -142,4 +147,4 @@ struct GemmLaunchPlan { int family, tile, phase_loop, flags, split_k, store, bia
 
 // per-dtype entry points (defined in gemm_impl.h, explicitly instantiated in gemm_<dtype>.hip); lp != nullptr: decide only
 template <typename T> int gemm_run(const emo_gemm_params& p, const GemmPlan& pl, int S, hipStream_t st, GemmLaunchPlan* lp);        // tiles (+ split-K reduce)
-template <typename T> int gemm_run_halo(const emo_gemm_params& p, int ph, int bn, int64_t gx, hipStream_t st);                   // conv3x3_halo_kernel
+template <typename T> int gemm_run_halo(const emo_gemm_params& p, int ph, int bn, int unrolled, int64_t gx, hipStream_t st);                   // conv3x3_halo_kernel

@@ -229,7 +229,11 @@ typedef struct {
    * folds the LayerNorm affine into the operands once at load: W <- W * gamma[k], bias <- bias + W . beta.  Dense, split_k <= 1. */
   const float* ln_colsum; const float* ln_stats;
   int tile;   /* 0 = planned from the shape; 1..6 pin a tile (64x64, 128x128, 128x160, 256x256, 256x160, 256x320) - tuning hook
-                 in the spirit of a BLAS algorithm id; combinations a tile cannot serve fall back to the nearest one that can */
+                 in the spirit of a BLAS algorithm id; combinations a tile cannot serve fall back to the nearest one that can.
+                 Stride-1 3x3 convs the halo-reuse kernel serves read it as hint bits instead: (tile & 3) 1 / 2 pins 8 / 16-row
+                 patches, 4 keeps one launch at N % 128 == 64, 8 keeps the 64-column remainder launch, 16 forces 192-column blocks,
+                 32 keeps the rolled main loop where the one with its nine taps unrolled is the default (same bits).
+                 A conv the halo kernel does not serve drops bits 8 / 16 / 32 and reads the rest as the tile pin. */
   int conv_asym;   /* conv only: 1 = padding (0, 1, 0, 1) instead of 1 all round - the `F.pad(x, (0,1,0,1))` + stride-2
                       conv of the VAE encoder's Downsample2D (diffusers AutoencoderKL; Ho = (H + 1 - 3) / stride + 1) */
   int up_h; int up_w;  /* conv only: nearest upsampling to an EXPLICIT size folded into the loader (F.interpolate(size=...),

@@ -1,5 +1,5 @@
 import os, sys, torch
-TILE = int(os.environ.get('CONV_TILE', '0')) or None   # emo_gemm_params.tile: 1 / 2 pin the 8 / 16-row patch, +4 keeps one launch at N % 128 == 64
+TILE = int(os.environ.get('CONV_TILE', '0')) or None   # emo_gemm_params.tile: 1 / 2 pin the 8 / 16-row patch, +4 keeps one launch at N % 128 == 64, +32 the rolled main loop
 sys.path.insert(0, '.')
 from emote_hack_amd import ops as o
 dev='cuda'; dt=torch.bfloat16
