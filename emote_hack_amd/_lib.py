@@ -104,6 +104,7 @@ SIGNATURES = {
     "emo_groupnorm_fold_linear": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _f, _i, _p]),
     "emo_layernorm": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _f, _p, _i, _i, _i, _p]),
     "emo_layernorm_stats": (_i, [_p, _i, _p, _i64, _i, _f, _i, _p]),
+    "emo_layernorm_act": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _f, _i, _i, _p]),
     "emo_layernorm_plan": (_i, [_i64, _i, _i, C.POINTER(C.c_int)]),
     "emo_gemm": (_i, [C.POINTER(GemmParams), _p]),
     "emo_conv3x3_gn_fusable": (_i, [C.POINTER(GemmParams)]),
@@ -128,6 +129,8 @@ SIGNATURES = {
     "emo_rows_to_video": (_i, [_p, _i64, _p, _i, _i, _i, _i, _f, _f, _f, _f, _i, _p]),
     "emo_channelnorm_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "emo_channelnorm": (_i, [_p, _i64, _p, _p, _p, _i64, _i64, _i, _f, _i, _p, _i, _p]),
+    "emo_wav_conv0_ln_act_plan": (_i, [_i64, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "emo_wav_conv0_ln_act": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _f, _i, _i, _p]),
     "emo_audio_resample_taps_per_phase": (_i, [_i, _i]),
     "emo_audio_resample": (_i, [_p, _i64, _i64, _i, _p, _i64, _i, _i, _i, _p, _i64, _i64, _p]),
     "emo_waveform_normalize_workspace_bytes": (C.c_size_t, [_i64]),

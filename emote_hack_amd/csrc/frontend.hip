@@ -291,6 +291,188 @@ extern "C" int emo_channelnorm(const void* x, int64_t ldx, const float* gamma, c
 }
 
 
+// ------------------------------------------------------------------------------------------------- wav conv 0 + LayerNorm + act
+// Feature-encoder layer 0 of the layer-norm wav2vec2 family (transformers Wav2Vec2LayerNormConvLayer with Cin = 1) straight from the
+// f32 waveform:  y[t, c] = act(LN_c(bias[c] + sum_{j<k} w[c][j] * wave[t * stride + j])).  Neither the (T0, k) window matrix nor the
+// pre-norm (T0, C) tensor exists in memory: the kernel reads 4 * stride bytes and writes one output row per time step.
+//   lane mapping   a row is held by LPR adjacent lanes, 8 channels (NV = 1) or 2 x 8 channels (NV = 2, C > 512) per lane; a wavefront
+//                  holds 64 / LPR rows at a time and owns `run` consecutive such row groups
+//   weights        NV = 1: the lane's 8 x k taps, its bias and its affine sit in registers for the whole run (C = 512, k = 10: 80 + 24);
+//                  NV = 2 (no checkpoint has it; served for completeness): the taps are re-read per row (L1 / L2 hits)
+//   samples        the k samples of a row are one address per row group (LPR = 64: wave-uniform)
+//   arithmetic     taps in ascending j with fmaf from the bias, f32; two-pass statistics with layernorm_kernel's shuffle pattern
+//                  and output expression; one rounding to T
+// KP is the compile-time tap count the register array is sized and unrolled for (k <= KP; steps j >= k are skipped by a uniform test).
+static constexpr int WC0_MAXC = 1024, WC0_MAXK = 16, WC0_WAVES = 2048;
+
+struct Wc0Geom { int ok, lpr, nv, kp, run, grid; int64_t T0; };
+static inline Wc0Geom wc0_geom(int64_t n, int C, int k, int stride) {
+  Wc0Geom g{0, 0, 0, 0, 0, 0, 0};
+  if (C <= 0 || C % 8 || C > WC0_MAXC || k < 1 || k > WC0_MAXK || stride < 1 || n < k) return g;
+  g.T0 = (n - k) / stride + 1;
+  const int CV = C / 8;
+  g.nv = CV > 64 ? 2 : 1;
+  g.lpr = CV <= 8 ? 8 : 64;
+  g.kp = g.nv == 2 ? 16 : k <= 4 ? 4 : k <= 10 ? 10 : 16;
+  const int rpw = 64 / g.lpr;
+  const int64_t groups = (g.T0 + rpw - 1) / rpw;
+  // a run amortises the lane's weight load (k * C * 4 bytes per wavefront against C * sizeof(T) per row): >= 8 row groups, more once
+  // WC0_WAVES wavefronts (8 per CU) are in flight
+  int64_t run = (groups + WC0_WAVES - 1) / WC0_WAVES;
+  if (run < 8) run = 8;
+  const int64_t waves = (groups + run - 1) / run;
+  g.run = (int)run;
+  g.grid = (int)((waves + 3) / 4);
+  g.ok = 1;
+  return g;
+}
+
+template <typename T> __device__ __forceinline__ void wc0_store8(T* p, const float* f) { *(uint4*)p = pack16<T>(f); }
+template <> __device__ __forceinline__ void wc0_store8<float>(float* p, const float* f) {
+  *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
+  *(float4*)(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
+}
+
+template <typename T, int KP, int LPR, int NV>
+__global__ __launch_bounds__(256) void wav_conv0_ln_act_kernel(const float* __restrict__ wave, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, T* __restrict__ y, int64_t ldy, int64_t T0,
+                                                               int C, int k, int stride, float eps, int act, int run) {
+  constexpr int RPW = 64 / LPR;
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane % LPR, rsel = lane / LPR;
+  const int CV = C / 8;
+  const float invC = 1.0f / (float)C;
+  bool on[NV];
+  int c0[NV];
+  float bs[NV][8], gm[NV][8], bt[NV][8];
+  float wr[NV == 1 ? KP : 1][8];
+#pragma unroll
+  for (int v = 0; v < NV; v++) {
+    const int cv = sub + LPR * v;
+    on[v] = cv < CV;
+    c0[v] = on[v] ? cv * 8 : 0;       // (an idle lane reads channel 0's constants and stores nothing)
+#pragma unroll
+    for (int e = 0; e < 8; e += 4) {
+      *(float4*)&bs[v][e] = *(const float4*)(bias + c0[v] + e);
+      *(float4*)&gm[v][e] = *(const float4*)(gamma + c0[v] + e);
+      *(float4*)&bt[v][e] = *(const float4*)(beta + c0[v] + e);
+    }
+  }
+  if constexpr (NV == 1) {
+#pragma unroll
+    for (int j = 0; j < KP; j++)
+#pragma unroll
+      for (int e = 0; e < 8; e++) wr[j][e] = j < k ? w[(int64_t)(c0[0] + e) * k + j] : 0.f;
+  }
+  const int64_t g0 = ((int64_t)blockIdx.x * 4 + wv) * run;
+  for (int r = 0; r < run; r++) {
+    const int64_t tg = (g0 + r) * RPW;
+    if (tg >= T0) break;              // wave-uniform: the shuffles below stay whole
+    const int64_t t = tg + rsel;
+    const bool ok = t < T0;
+    const float* xs = wave + (ok ? t : T0 - 1) * stride;   // a row past the end re-reads the last one and stores nothing
+    float acc[NV][8];
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+#pragma unroll
+      for (int e = 0; e < 8; e++) acc[v][e] = bs[v][e];
+    if constexpr (NV == 1) {
+#pragma unroll
+      for (int j = 0; j < KP; j++) {
+        if (j < k) {
+          const float xj = xs[j];
+#pragma unroll
+          for (int e = 0; e < 8; e++) acc[0][e] = fmaf(wr[j][e], xj, acc[0][e]);
+        }
+      }
+    } else {
+      for (int j = 0; j < k; j++) {
+        const float xj = xs[j];
+#pragma unroll
+        for (int v = 0; v < NV; v++)
+#pragma unroll
+          for (int e = 0; e < 8; e++) acc[v][e] = fmaf(w[(int64_t)(c0[v] + e) * k + j], xj, acc[v][e]);
+      }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+      if (on[v]) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) s += acc[v][e];
+      }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float mean = s * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+      if (on[v]) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) { const float d = acc[v][e] - mean; q += d * d; }
+      }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    const float rstd = rsqrtf(q * invC + eps);
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      if (ok && on[v]) {
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          const float u = (acc[v][e] - mean) * rstd * gm[v][e] + bt[v][e];
+          o[e] = act == 1 ? gelu_for<T>(u) : u;
+        }
+        wc0_store8<T>(y + t * ldy + c0[v], o);
+      }
+    }
+  }
+}
+
+static int wc0_check(const char* who, int64_t n, int C, int k, int stride) {
+  EMO_CHECK(wc0_geom(n, C, k, stride).ok, EMO_ERR_UNSUPPORTED,
+            "%s: n=%lld C=%d k=%d stride=%d (served: C %% 8 == 0, C <= %d, 1 <= k <= %d, stride >= 1, n >= k)", who, (long long)n, C, k, stride,
+            WC0_MAXC, WC0_MAXK);
+  return EMO_OK;
+}
+
+extern "C" int emo_wav_conv0_ln_act_plan(int64_t n, int C, int k, int stride, int64_t plan[6]) {
+  EMO_CHECK(plan, EMO_ERR_NULL, "emo_wav_conv0_ln_act_plan: null pointer");
+  int rc = wc0_check("emo_wav_conv0_ln_act_plan", n, C, k, stride);
+  if (rc) return rc;
+  const Wc0Geom g = wc0_geom(n, C, k, stride);
+  plan[0] = g.T0; plan[1] = g.lpr; plan[2] = g.nv; plan[3] = g.kp; plan[4] = g.run; plan[5] = g.grid;
+  return EMO_OK;
+}
+
+extern "C" int emo_wav_conv0_ln_act(const float* wave, int64_t n, const float* w, const float* bias, const float* gamma, const float* beta,
+                                    void* y, int64_t ldy, int C, int k, int stride, float eps, int act, int dtype, void* stream) {
+  EMO_CHECK(wave && w && bias && gamma && beta && y, EMO_ERR_NULL, "emo_wav_conv0_ln_act: null pointer");
+  EMO_CHECK(emo_dtype_ok(dtype), EMO_ERR_BAD_DTYPE, "emo_wav_conv0_ln_act: dtype %d", dtype);
+  int rc = wc0_check("emo_wav_conv0_ln_act", n, C, k, stride);
+  if (rc) return rc;
+  EMO_CHECK(ldy >= C && ldy % emo_dtype_vec(dtype) == 0 && (act == 0 || act == 1), EMO_ERR_BAD_SHAPE, "emo_wav_conv0_ln_act: ldy=%lld C=%d act=%d",
+            (long long)ldy, C, act);
+  EMO_CHECK(((uintptr_t)bias % 16) == 0 && ((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0 && ((uintptr_t)y % 16) == 0 &&
+            ((uintptr_t)wave % 4) == 0 && ((uintptr_t)w % 4) == 0, EMO_ERR_BAD_SHAPE, "emo_wav_conv0_ln_act: operand alignment");
+  const Wc0Geom g = wc0_geom(n, C, k, stride);
+  hipStream_t st = as_stream(stream);
+#define EMO_WC0(KP_, LPR_, NV_)                                                                                                          \
+  EMO_DISPATCH(dtype, "emo_wav_conv0_ln_act", (wav_conv0_ln_act_kernel<T, KP_, LPR_, NV_><<<g.grid, 256, 0, st>>>(                        \
+                                                  wave, w, bias, gamma, beta, (T*)y, ldy, g.T0, C, k, stride, eps, act, g.run)))
+  if (g.nv == 2) { EMO_WC0(16, 64, 2); }
+  else if (g.lpr == 8) {
+    if (g.kp == 4) { EMO_WC0(4, 8, 1); } else if (g.kp == 10) { EMO_WC0(10, 8, 1); } else { EMO_WC0(16, 8, 1); }
+  } else {
+    if (g.kp == 4) { EMO_WC0(4, 64, 1); } else if (g.kp == 10) { EMO_WC0(10, 64, 1); } else { EMO_WC0(16, 64, 1); }
+  }
+#undef EMO_WC0
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}
+
+
 // -------------------------------------------------------------------------------------------------------------- audio resampling
 // y[n] = sum_j h[n*down - j*up] * x[j] over |n*down - j*up| <= half, x[j] = mean over channels of frame j (0 outside the utterance).
 // With t = n*down = T0*up + p the taps of output n are h[p + up*i] at j = T0 - i: row p of the phase table, column c = i + i0

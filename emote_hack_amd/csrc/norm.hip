@@ -1092,3 +1092,99 @@ extern "C" int emo_layernorm(const void* x, int ldx, const float* gamma, const f
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
+
+// ------------------------------------------------------------------------------------------ LayerNorm + activation
+// y = act(LayerNorm(x)) over the last dim in one read and one write: what sits behind every feature-encoder conv of the layer-norm
+// wav2vec2 family (Net.py:607-648 -> transformers Wav2Vec2LayerNormConvLayer: conv, LayerNorm over channels, GELU).  layernorm_kernel's
+// lane mapping, two-pass f32 statistics and output expression; the activation (emo_channelnorm's convention: 0 none, 1 erf-GELU) acts
+// on the f32 normalised value, which is rounded once.  No pe operand.  act = 0 is emo_layernorm(pe = NULL) bit for bit.
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void layernorm_act_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, T* __restrict__ y, int ldy, int64_t M, int C,
+                                                            float eps, int act) {
+  constexpr int V = TT<T>::VEC;
+  constexpr int RPW = 64 / LPR;  // rows per wavefront
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane % LPR, rsel = lane / LPR;
+  const int CV = C / V;
+  const float invC = 1.0f / (float)C;
+  for (int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * RPW; m0 < M; m0 += (int64_t)gridDim.x * 4 * RPW) {
+    const int64_t m = m0 + rsel;
+    const bool ok = m < M;
+    float f[LN_MAXV][V];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < LN_MAXV; j++) {
+      const int cv = sub + LPR * j;
+      if (ok && cv < CV) {
+        unpack16<T>(*(const uint4*)(x + m * ldx + cv * V), f[j]);
+#pragma unroll
+        for (int e = 0; e < V; e++) s += f[j][e];
+      }
+    }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const float mean = s * invC;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < LN_MAXV; j++) {
+      const int cv = sub + LPR * j;
+      if (ok && cv < CV) {
+#pragma unroll
+        for (int e = 0; e < V; e++) { float d = f[j][e] - mean; q += d * d; }
+      }
+    }
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+    const float rstd = rsqrtf(q * invC + eps);
+#pragma unroll
+    for (int j = 0; j < LN_MAXV; j++) {
+      const int cv = sub + LPR * j;
+      if (ok && cv < CV) {
+        float g[V], b[V], o[V];
+        *(float4*)&g[0] = *(const float4*)(gamma + cv * V);
+        *(float4*)&b[0] = *(const float4*)(beta + cv * V);
+        if constexpr (V == 8) {
+          *(float4*)&g[4] = *(const float4*)(gamma + cv * V + 4);
+          *(float4*)&b[4] = *(const float4*)(beta + cv * V + 4);
+        }
+#pragma unroll
+        for (int e = 0; e < V; e++) {
+          const float v = (f[j][e] - mean) * rstd * g[e] + b[e];
+          o[e] = act == 1 ? gelu_for<T>(v) : v;
+        }
+        *(uint4*)(y + m * ldy + cv * V) = pack16<T>(o);
+      }
+    }
+  }
+}
+
+template <typename T>
+static void launch_layernorm_act(const T* x, int ldx, const float* gamma, const float* beta, T* y, int ldy, int64_t M, int C, float eps,
+                                 int act, hipStream_t st) {
+  const LnGeom lg = ln_geom(M, C / TT<T>::VEC);
+#define EMO_LNA(L) layernorm_act_kernel<T, L><<<lg.grid, 256, 0, st>>>(x, ldx, gamma, beta, y, ldy, M, C, eps, act)
+  switch (lg.lpr) {
+    case 1: EMO_LNA(1); break;
+    case 2: EMO_LNA(2); break;
+    case 4: EMO_LNA(4); break;
+    case 8: EMO_LNA(8); break;
+    case 16: EMO_LNA(16); break;
+    case 32: EMO_LNA(32); break;
+    default: EMO_LNA(64); break;
+  }
+#undef EMO_LNA
+}
+
+extern "C" int emo_layernorm_act(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int64_t M, int C,
+                                 float eps, int act, int dtype, void* stream) {
+  EMO_CHECK(x && gamma && beta && y, EMO_ERR_NULL, "emo_layernorm_act: null pointer");
+  int rc = ln_check("emo_layernorm_act", M, C, ldx, ldy, dtype);
+  if (rc) return rc;
+  EMO_CHECK(act == 0 || act == 1, EMO_ERR_BAD_SHAPE, "emo_layernorm_act: act=%d (0 none | 1 erf-GELU)", act);
+  EMO_CHECK(((uintptr_t)gamma % 16) == 0 && ((uintptr_t)beta % 16) == 0, EMO_ERR_BAD_SHAPE, "emo_layernorm_act: gamma/beta alignment");
+  hipStream_t st = as_stream(stream);
+  EMO_DISPATCH(dtype, "emo_layernorm_act", (launch_layernorm_act<T>((const T*)x, ldx, gamma, beta, (T*)y, ldy, M, C, eps, act, st)));
+  EMO_LAUNCH_CHECK();
+  return EMO_OK;
+}

@@ -341,6 +341,20 @@ def layer_norm(x: torch.Tensor, gamma, beta, eps=1e-5, pe=None, rows_per_frame=0
     return y
 
 
+def layer_norm_act(x: torch.Tensor, gamma, beta, eps=1e-5, gelu=True, out=None) -> torch.Tensor:
+    """act(LayerNorm(x)) over the last dim in one pass, act = erf-GELU or none (emo_layernorm_act).  out: a rows view to write into."""
+    _need_cuda(x, out)
+    M, Cc = x.shape
+    px, ldx = _rows(x)
+    y = torch.empty(M, Cc, device=x.device, dtype=x.dtype) if out is None else out
+    assert y.shape == x.shape and y.dtype == x.dtype, (y.shape, y.dtype)
+    py, ldy = _rows(y)
+    _launch("layernorm_act", 0.0, x.element_size() * 2.0 * M * Cc,
+            lambda: check(_lib.load().emo_layernorm_act(px, ldx, _ptr(gamma), _ptr(beta), py, ldy, M, Cc, float(eps), int(bool(gelu)), dt(x),
+                                                        _stream()), "emo_layernorm_act"))
+    return y
+
+
 def layer_norm_stats(x: torch.Tensor, eps=1e-5) -> torch.Tensor:
     """(mean, rstd) per row, f32 (M, 2): the statistics pass of a LayerNorm folded into the consumer GEMM (gemm(ln=...))."""
     _need_cuda(x)
@@ -1238,6 +1252,31 @@ def channel_norm(x: torch.Tensor, gamma, beta, eps=1e-5, gelu=False) -> torch.Te
     _launch("channelnorm", 0.0, x.element_size() * 3.0 * S * Cc,
             lambda: check(lib.emo_channelnorm(px, ldx, _ptr(gamma), _ptr(beta), _ptr(y), Cc, S, Cc, float(eps), int(bool(gelu)), _ptr(ws), dt(x), _stream()),
                           "emo_channelnorm"))
+    return y
+
+
+def wav_conv0_ln_act_ok(n: int, Cc: int, k: int, stride: int) -> bool:
+    """whether emo_wav_conv0_ln_act serves this first-layer shape (host only; emo_wav_conv0_ln_act_plan)"""
+    plan = (C.c_int64 * 6)()
+    return _lib.load().emo_wav_conv0_ln_act_plan(int(n), int(Cc), int(k), int(stride), plan) == 0
+
+
+def wav_conv0_ln_act(wave: torch.Tensor, w: torch.Tensor, bias, gamma, beta, stride: int, eps=1e-5, gelu=True, dtype=torch.float32,
+                     out=None) -> torch.Tensor:
+    """Conv1d(1, C, k, stride) + bias -> LayerNorm(C) -> optional erf-GELU per time step, straight from the f32 waveform (n,): ->
+    ((n - k) // stride + 1, C) rows in `dtype` (emo_wav_conv0_ln_act).  w f32 (C, k); bias / gamma / beta f32 (C,).  out: a rows view
+    in `dtype` to write into."""
+    _need_cuda(wave, w, bias, gamma, beta, out)
+    assert wave.dtype == w.dtype == torch.float32 and wave.dim() == 1 and w.dim() == 2 and wave.is_contiguous() and w.is_contiguous()
+    n, (Cc, k) = wave.shape[0], w.shape
+    T0 = max((n - k) // stride + 1, 1)
+    y = torch.empty(T0, Cc, device=wave.device, dtype=dtype) if out is None else out
+    assert y.shape == (T0, Cc), (y.shape, T0, Cc)
+    py, ldy = _rows(y)
+    _launch("wav_conv0_ln_act", 2.0 * T0 * Cc * k, 4.0 * n + y.element_size() * 1.0 * T0 * Cc,
+            lambda: check(_lib.load().emo_wav_conv0_ln_act(_ptr(wave), n, _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), py, ldy, Cc, k, int(stride),
+                                                           float(eps), int(bool(gelu)), dt(y), _stream()), "emo_wav_conv0_ln_act"),
+            tag=f"n={n} C={Cc} k={k} s={stride}")
     return y
 
 

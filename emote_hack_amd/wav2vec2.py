@@ -11,11 +11,22 @@
                             positional conv   16 per-group GEMMs over the same kind of row view (k = 128), GELU, residual
                             12 layers         emo_gemm (q | k fused, V^T by the transposed store) + emo_attention (12 heads of 64) +
                                               emo_layernorm + GELU feed-forward
+                          The wav2vec2-large family (wav2vec2-large-960h-lv60, large-xlsr-53, XLS-R, large-robust: LARGE_CONFIG) differs
+                          by three config switches, each served on its own:
+                            feat_extract_norm "layer"   every conv is conv (+ bias) -> LayerNorm(C) -> GELU per time step: layer 0 by
+                                              emo_wav_conv0_ln_act straight from the waveform (or the window-matrix GEMM + emo_layernorm_act:
+                                              `conv0_route`), layers 1-6 a row-view GEMM + bias and emo_layernorm_act
+                            conv_bias         the bias rides in the GEMM epilogue
+                            do_stable_layer_norm   pre-LN layers = clip_layers.run_clip_layers (LayerNorms folded into the q | k, V^T and
+                                              fc1 GEMMs) over a key-renaming view of the master dict, encoder.layer_norm last
+                          and its processor returns an attention_mask: forward takes right-padded batches with one (see forward).
   Wav2VecFeatureExtractor extract_features_from_wav behind the file read (Net.py:636-667): utterance normalisation (what
                           `self.processor(...)` does), encoder, emo_audio_windows -> (T, (m + n + 1) * 768)
 
 Oracle: oracle/wav2vec2_ref.py, pinned by outputs of transformers' own model (tests/golden/wav2vec2.safetensors).
-Only the wav2vec2-base family is built (feat_extract_norm "group", post-LN encoder) - the one the reference names.
+Both checkpoint families are built: wav2vec2-base (feat_extract_norm "group", post-LN encoder - the one the reference names) and
+wav2vec2-large (feat_extract_norm "layer", conv biases, pre-LN encoder; goldens tests/golden/wav2vec2_large.safetensors from
+tools/oracle/gen_golden_wav2vec2_large.py).
 """
 from __future__ import annotations
 
@@ -25,6 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
+from .clip_layers import load_local_checkpoint, pack_clip_layers, run_clip_layers
 from .module import HipModule, round_up
 from .synth import synth_state_dict, synth_tensor
 
@@ -32,15 +44,25 @@ BASE_CONFIG = dict(hidden_size=768, num_hidden_layers=12, num_attention_heads=12
                    conv_dim=(512, 512, 512, 512, 512, 512, 512), conv_stride=(5, 2, 2, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 3, 2, 2),
                    conv_bias=False, feat_extract_norm="group", num_conv_pos_embeddings=128, num_conv_pos_embedding_groups=16,
                    do_stable_layer_norm=False, layer_norm_eps=1e-5)
+# wav2vec2-large-960h-lv60(-self), wav2vec2-large-xlsr-53, the XLS-R models, wav2vec2-large-robust
+LARGE_CONFIG = dict(BASE_CONFIG, hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096, conv_bias=True,
+                    feat_extract_norm="layer", do_stable_layer_norm=True)
 
 
 def wav2vec2_param_shapes(cfg=None):
-    """transformers' Wav2Vec2Model state-dict keys / shapes for a config of the base family (parametrised weight-norm spelling)."""
+    """transformers' Wav2Vec2Model state-dict keys / shapes for a config (parametrised weight-norm spelling): conv biases with
+    `conv_bias`, a LayerNorm behind every conv with feat_extract_norm "layer" (behind layer 0 only - a GroupNorm - with "group").  The
+    encoder's keys are the same for the post-LN and the pre-LN (`do_stable_layer_norm`) layers."""
     c = dict(BASE_CONFIG, **(cfg or {}))
     d, cin = {}, 1
     for i, (co, k) in enumerate(zip(c["conv_dim"], c["conv_kernel"])):
         d[f"feature_extractor.conv_layers.{i}.conv.weight"] = (co, cin, k)
-        if i == 0:
+        if c["conv_bias"]:
+            d[f"feature_extractor.conv_layers.{i}.conv.bias"] = (co,)
+        if c["feat_extract_norm"] == "layer":
+            d[f"feature_extractor.conv_layers.{i}.layer_norm.weight"] = (co,)
+            d[f"feature_extractor.conv_layers.{i}.layer_norm.bias"] = (co,)
+        elif i == 0:
             d["feature_extractor.conv_layers.0.layer_norm.weight"] = (co,)
             d["feature_extractor.conv_layers.0.layer_norm.bias"] = (co,)
         cin = co
@@ -80,27 +102,63 @@ def wav2vec2_synth_state_dict(cfg=None, prefix="wav2vec2.", device="cpu"):
     return sd
 
 
+class _ClipLayerKeys:
+    """The master dict under transformers' CLIPEncoderLayer key names, which clip_layers.pack_clip_layers reads: a pre-LN wav2vec2
+    layer is that layer with other names (a view - nothing is copied)."""
+    _RENAMES = (("self_attn.", "attention."), ("layer_norm1.", "layer_norm."), ("layer_norm2.", "final_layer_norm."),
+                ("mlp.fc1.", "feed_forward.intermediate_dense."), ("mlp.fc2.", "feed_forward.output_dense."))
+
+    def __init__(self, sd):
+        self._sd = sd
+
+    def __getitem__(self, key):
+        for clip, own in self._RENAMES:
+            if clip in key:
+                return self._sd[key.replace(clip, own)]
+        return self._sd[key]
+
+
 class Wav2Vec2Model(HipModule):
-    """forward(input_values (1, n_samples) f32) -> namespace(last_hidden_state=(1, T, hidden) f32), like the transformers class the
-    reference calls (Net.py:643-644)."""
+    """forward(input_values (B, n_samples) f32) -> namespace(last_hidden_state=(B, T, hidden) f32), like the transformers class the
+    reference calls (Net.py:643-644).  `conv0_route` ("fused" | "gemm") selects how layer 0 of a feat_extract_norm "layer" model runs:
+    emo_wav_conv0_ln_act straight from the waveform, or the window-matrix GEMM + emo_layernorm_act (also the fallback for a first
+    layer the fused kernel does not serve); forward(conv0_route=) overrides it for one call."""
     _tolerated = frozenset({"masked_spec_embed"})
+    # keys of the Wav2Vec2ForCTC / Wav2Vec2ForPreTraining files the encoder has no use for
+    _tolerated_prefixes = ("lm_head.", "quantizer.", "project_hid.", "project_q.")
+    CONV0_ROUTES = ("fused", "gemm")
 
     def __init__(self, config=None, **kwargs):
         cfg = dict(BASE_CONFIG)
         if config is not None:
             cfg.update({k: getattr(config, k) for k in BASE_CONFIG if hasattr(config, k)} if not isinstance(config, dict) else config)
         cfg.update(kwargs)
-        if cfg["feat_extract_norm"] != "group" or cfg["do_stable_layer_norm"] or cfg["conv_bias"]:
-            raise NotImplementedError("Wav2Vec2Model: only the wav2vec2-base family (feat_extract_norm='group', conv_bias=False, "
-                                      "do_stable_layer_norm=False) - the checkpoint the reference names (Net.py:608)")
+        if cfg["feat_extract_norm"] not in ("group", "layer"):
+            raise ValueError(f"Wav2Vec2Model: feat_extract_norm={cfg['feat_extract_norm']!r} must be 'group' or 'layer'")
         H, nh = cfg["hidden_size"], cfg["num_attention_heads"]
         if H % nh or (H // nh) % 8 or (H // cfg["num_conv_pos_embedding_groups"]) % 8 or any(c % 8 for c in cfg["conv_dim"]):
             raise ValueError("Wav2Vec2Model: head dim, positional-conv group width and conv channels must be multiples of 8")
         self.config = SimpleNamespace(**cfg)
         self._cfg = cfg
+        self.conv0_route = "fused"
         super().__init__(wav2vec2_param_shapes(cfg))
 
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path, subfolder=None, torch_dtype=None, **_ignored):
+        """A LOCAL checkpoint folder (`<path>[/<subfolder>]/config.json` + `model.safetensors` or `pytorch_model.bin`) - nothing is
+        fetched.  The family is read from config.json; Wav2Vec2ForCTC / ForPreTraining files load too (see _remap_keys)."""
+        config, sd = load_local_checkpoint(pretrained_model_path, subfolder)
+        model = cls({k: config[k] for k in BASE_CONFIG if k in config})
+        model.load_state_dict(sd)
+        if torch_dtype is not None:
+            model.to(dtype=torch_dtype)
+        return model
+
     def _remap_keys(self, sd):
+        if any(k.startswith("wav2vec2.") for k in sd):        # a task model's file: the encoder under `wav2vec2.`, heads beside it
+            sd = {(k[len("wav2vec2."):] if k.startswith("wav2vec2.") else k): v for k, v in sd.items()}
+        for k in [k for k in sd if k.startswith(self._tolerated_prefixes)]:
+            del sd[k]
         pc = "encoder.pos_conv_embed.conv."
         for old, new in ((pc + "weight_g", pc + "parametrizations.weight.original0"), (pc + "weight_v", pc + "parametrizations.weight.original1")):
             if old in sd and new not in sd:       # checkpoints written before torch's parametrised weight_norm
@@ -118,7 +176,16 @@ class Wav2Vec2Model(HipModule):
             if i == 0:       # Cin = 1: the k taps padded to a 16-byte multiple (the window matrix is padded alike)
                 t = torch.nn.functional.pad(t, (0, round_up(k, 8) - k))
             w[f"conv{i}"] = t.to(dev, dtp).contiguous()
-        w["gn.g"], w["gn.b"] = f32("feature_extractor.conv_layers.0.layer_norm.weight"), f32("feature_extractor.conv_layers.0.layer_norm.bias")
+            w[f"conv{i}.b"] = f32(f"feature_extractor.conv_layers.{i}.conv.bias") if c["conv_bias"] else None
+        if c["feat_extract_norm"] == "layer":
+            for i in range(len(c["conv_kernel"])):
+                w[f"cln{i}.g"] = f32(f"feature_extractor.conv_layers.{i}.layer_norm.weight")
+                w[f"cln{i}.b"] = f32(f"feature_extractor.conv_layers.{i}.layer_norm.bias")
+            # the fused first layer reads the f32 master taps (C, k), and a bias even where the checkpoint has none
+            w["conv0.f32"] = f32("feature_extractor.conv_layers.0.conv.weight").reshape(c["conv_dim"][0], -1).contiguous()
+            w["conv0.b32"] = w["conv0.b"] if c["conv_bias"] else torch.zeros(c["conv_dim"][0], device=dev, dtype=torch.float32)
+        else:
+            w["gn.g"], w["gn.b"] = f32("feature_extractor.conv_layers.0.layer_norm.weight"), f32("feature_extractor.conv_layers.0.layer_norm.bias")
         w["fp.ln.g"], w["fp.ln.b"] = f32("feature_projection.layer_norm.weight"), f32("feature_projection.layer_norm.bias")
         w["fp.w"], w["fp.b"] = lin("feature_projection.projection.weight"), f32("feature_projection.projection.bias")
         # weight_norm(dim=2): w = g * v / ||v||, the norm over every dim but 2 - formed once at load in f32
@@ -130,6 +197,9 @@ class Wav2Vec2Model(HipModule):
         w["pos.w"] = [wp[gi * cg:(gi + 1) * cg].permute(0, 2, 1).reshape(cg, -1).to(dev, dtp).contiguous() for gi in range(G)]
         w["pos.b"] = [f32("encoder.pos_conv_embed.conv.bias")[gi * cg:(gi + 1) * cg].contiguous() for gi in range(G)]
         w["enc.ln.g"], w["enc.ln.b"] = f32("encoder.layer_norm.weight"), f32("encoder.layer_norm.bias")
+        if c["do_stable_layer_norm"]:       # pre-LN: CLIP's layer under other key names
+            w["layers"] = pack_clip_layers(_ClipLayerKeys(sd), "encoder.layers", c["num_hidden_layers"], dev, dtp)
+            return w
         for i in range(c["num_hidden_layers"]):
             p = f"encoder.layers.{i}"
             w[f"{i}.qk.w"] = torch.cat([sd[f"{p}.attention.q_proj.weight"], sd[f"{p}.attention.k_proj.weight"]]).to(dev, dtp).contiguous()
@@ -149,33 +219,101 @@ class Wav2Vec2Model(HipModule):
         T, C = x.shape
         return torch.as_strided(x, ((T - k) // s + 1, k * C), (s * C, 1))
 
+    def _frames(self, n):
+        """frames the feature encoder makes of n samples (transformers' _get_feat_extract_output_lengths); 0 once a layer runs dry"""
+        for k, s in zip(self._cfg["conv_kernel"], self._cfg["conv_stride"]):
+            if n < k:
+                return 0
+            n = (n - k) // s + 1
+        return n
+
+    def _utterance_lengths(self, input_values, attention_mask):
+        """The valid sample count of every row of the batch, from the argument checks alone (no device work)."""
+        if input_values.dim() != 2:
+            raise ValueError("input_values must be (batch, n_samples)")
+        B, n = input_values.shape
+        if self._cfg["feat_extract_norm"] != "layer":
+            # GroupNorm runs over time, so a padded utterance is not the utterance run alone: this family is used unmasked, one at a time
+            if attention_mask is not None:
+                raise NotImplementedError("attention_mask: wav2vec2-base-960h is used unmasked (its processor returns no mask; Net.py:639-644)")
+            if B != 1:
+                raise ValueError("input_values must be (1, n_samples): one utterance per call (Net.py:639)")
+            return [n]
+        if B < 1:
+            raise ValueError("input_values must hold at least one utterance")
+        if attention_mask is None:
+            return [n] * B
+        mask = torch.as_tensor(attention_mask)
+        if tuple(mask.shape) != (B, n):
+            raise ValueError(f"attention_mask {tuple(mask.shape)} must have input_values' shape {(B, n)}")
+        mask = mask.cpu()
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError("attention_mask must hold 0 / 1")
+        lens = [int(v) for v in (mask != 0).sum(1)]
+        for b, ln in enumerate(lens):
+            if bool((mask[b, :ln] == 0).any()):
+                raise ValueError(f"attention_mask row {b} is not right-padded (ones, then zeros)")
+        return lens
+
     @torch.no_grad()
-    def forward(self, input_values, attention_mask=None, **_ignored):
-        self._need()
-        if attention_mask is not None:
-            raise NotImplementedError("attention_mask: wav2vec2-base-960h is used unmasked (its processor returns no mask; Net.py:639-644)")
-        if input_values.dim() != 2 or input_values.shape[0] != 1:
-            raise ValueError("input_values must be (1, n_samples): one utterance per call (Net.py:639)")
-        c, w, dtp, dev = self._cfg, self._w, self.dtype, self.device
-        eps = c["layer_norm_eps"]
-        k0, s0 = c["conv_kernel"][0], c["conv_stride"][0]
-        if input_values.shape[1] < k0:
-            raise ValueError("input_values shorter than the first convolution's kernel")
-        n_t = input_values.shape[1]        # every layer must keep at least one frame: refuse before the first launch, not at the layer that runs dry
-        for k, s in zip(c["conv_kernel"], c["conv_stride"]):
-            if n_t < k:
+    def forward(self, input_values, attention_mask=None, conv0_route=None, **_ignored):
+        """input_values (B, n) f32 [+ attention_mask (B, n) of 0 / 1, right-padded; feat_extract_norm "layer" models only] ->
+        last_hidden_state (B, T_max, H) f32 with T_max = frames(n).  Utterance b runs alone on its valid prefix input_values[b, :len_b] and
+        lands in rows [0, T_b), T_b = frames(len_b); rows from T_b on are ZERO.  At the valid rows that is what transformers computes for
+        the padded, masked batch - no normalisation of this family runs over time, transformers zeroes the padded frames in front of the
+        positional conv and masks the padded keys - while at the rows from T_b on transformers returns values that depend on the padding
+        and that no caller may use."""
+        route = self.conv0_route if conv0_route is None else conv0_route
+        if route not in self.CONV0_ROUTES:
+            raise ValueError(f"conv0_route={route!r} must be one of {self.CONV0_ROUTES}")
+        lens = self._utterance_lengths(input_values, attention_mask)
+        k0 = self._cfg["conv_kernel"][0]
+        for ln in lens:         # every layer must keep at least one frame: refuse before the first launch, not at the layer that runs dry
+            if ln < k0:
+                raise ValueError("input_values shorter than the first convolution's kernel")
+            if self._frames(ln) < 1:
                 raise ValueError("input_values too short for the feature encoder")
-            n_t = (n_t - k) // s + 1
-        wave = input_values[0].to(dev).float()
-        # layer 0 (Cin = 1): the (T0, k0) window matrix, padded to 16-byte rows (index / pad only)
+        self._need()
+        if len(lens) == 1 and lens[0] == input_values.shape[1]:
+            return SimpleNamespace(last_hidden_state=self._encode(input_values[0], route).unsqueeze(0))
+        out = torch.zeros(len(lens), self._frames(input_values.shape[1]), self._cfg["hidden_size"], device=self.device, dtype=torch.float32)
+        for b, ln in enumerate(lens):
+            y = self._encode(input_values[b, :ln], route)
+            out[b, :y.shape[0]] = y
+        return SimpleNamespace(last_hidden_state=out)
+
+    def _feature_encoder_layer0(self, wave, route):
+        """wave (n,) f32 on the device -> (T0, conv_dim[0]) rows in the compute dtype: conv 0 (+ bias), its norm, GELU"""
+        c, w, dtp = self._cfg, self._w, self.dtype
+        k0, s0 = c["conv_kernel"][0], c["conv_stride"][0]
+        layer = c["feat_extract_norm"] == "layer"
+        if layer and route == "fused" and ops.wav_conv0_ln_act_ok(wave.shape[0], c["conv_dim"][0], k0, s0):
+            return ops.wav_conv0_ln_act(wave, w["conv0.f32"], w["conv0.b32"], w["cln0.g"], w["cln0.b"], s0, 1e-5, gelu=True, dtype=dtp)
+        # Cin = 1: the (T0, k0) window matrix, padded to 16-byte rows (index / pad only)
         a0 = torch.nn.functional.pad(wave.unfold(0, k0, s0), (0, round_up(k0, 8) - k0)).contiguous()
-        h = ops.gemm(ops.convert(a0, dtp), w["conv0"])
-        h = ops.channel_norm(h, w["gn.g"], w["gn.b"], 1e-5, gelu=True)            # GroupNorm(C, C) over time, then GELU
+        h = ops.gemm(ops.convert(a0, dtp), w["conv0"], w["conv0.b"])
+        if layer:
+            return ops.layer_norm_act(h, w["cln0.g"], w["cln0.b"], 1e-5, gelu=True)
+        return ops.channel_norm(h, w["gn.g"], w["gn.b"], 1e-5, gelu=True)            # GroupNorm(C, C) over time, then GELU
+
+    def _feature_encoder(self, wave, route):
+        """wave (n,) f32 on the device -> (T, conv_dim[-1]) rows in the compute dtype"""
+        c, w = self._cfg, self._w
+        layer = c["feat_extract_norm"] == "layer"
+        h = self._feature_encoder_layer0(wave, route)
         for i in range(1, len(c["conv_kernel"])):
             k, s = c["conv_kernel"][i], c["conv_stride"][i]
             if h.shape[0] < k:
                 raise ValueError("input_values too short for the feature encoder")
-            h = ops.act(ops.gemm(self._windows(h, k, s), w[f"conv{i}"]), "gelu")
+            h = ops.gemm(self._windows(h, k, s), w[f"conv{i}"], w[f"conv{i}.b"])
+            h = ops.layer_norm_act(h, w[f"cln{i}.g"], w[f"cln{i}.b"], 1e-5, gelu=True) if layer else ops.act(h, "gelu")
+        return h
+
+    def _encode(self, wave, route):
+        """one utterance (n,) -> (T, H) f32"""
+        c, w, dtp, dev = self._cfg, self._w, self.dtype, self.device
+        eps = c["layer_norm_eps"]
+        h = self._feature_encoder(wave.to(dev).float().contiguous(), route)
         T = h.shape[0]
         h = ops.gemm(ops.layer_norm(h, w["fp.ln.g"], w["fp.ln.b"], eps), w["fp.w"], w["fp.b"])          # (T, H)
         H = h.shape[1]
@@ -188,8 +326,12 @@ class Wav2Vec2Model(HipModule):
         n_out = T          # (an even kernel yields T + 1 steps, the last one dropped; an odd one yields T)
         for gi in range(G):
             ops.gemm(torch.as_strided(xp[gi], (n_out, kp * cg), (cg, 1)), w["pos.w"][gi], w["pos.b"][gi], out=pos[:, gi * cg:(gi + 1) * cg])
-        h = ops.layer_norm(ops.add(h, ops.act(pos, "gelu")), w["enc.ln.g"], w["enc.ln.b"], eps)
+        h = ops.add(h, ops.act(pos, "gelu"))
         nh = c["num_attention_heads"]
+        if c["do_stable_layer_norm"]:       # pre-LN layers, encoder.layer_norm last
+            h = run_clip_layers(h, w["layers"], n_layers=c["num_hidden_layers"], B=1, L=T, H=H, heads=nh, eps=eps, act="gelu", causal=False)
+            return ops.convert(ops.layer_norm(h, w["enc.ln.g"], w["enc.ln.b"], eps), torch.float32)
+        h = ops.layer_norm(h, w["enc.ln.g"], w["enc.ln.b"], eps)
         d = H // nh
         for i in range(c["num_hidden_layers"]):
             qk = ops.gemm(h, w[f"{i}.qk.w"], w[f"{i}.qk.b"])
@@ -198,7 +340,7 @@ class Wav2Vec2Model(HipModule):
             h = ops.layer_norm(ops.gemm(att, w[f"{i}.o.w"], w[f"{i}.o.b"], residual=h), w[f"{i}.ln1.g"], w[f"{i}.ln1.b"], eps)
             f = ops.act(ops.gemm(h, w[f"{i}.f1.w"], w[f"{i}.f1.b"]), "gelu")
             h = ops.layer_norm(ops.gemm(f, w[f"{i}.f2.w"], w[f"{i}.f2.b"], residual=h), w[f"{i}.ln2.g"], w[f"{i}.ln2.b"], eps)
-        return SimpleNamespace(last_hidden_state=ops.convert(h, torch.float32).unsqueeze(0))
+        return ops.convert(h, torch.float32)
 
 
 def normalize_waveform(x: torch.Tensor) -> torch.Tensor:

@@ -186,7 +186,14 @@ int emo_layernorm(const void* x, int ldx, const float* gamma, const float* beta,
 /* the statistics half of it: stats[m] = (mean, 1 / sqrt(var + eps)) of row m (two-pass, f32) for the LayerNorm fold of
  * emo_gemm (emo_gemm_params.ln_stats) - a read-only pass over x. */
 int emo_layernorm_stats(const void* x, int ldx, float* stats, int64_t M, int C, float eps, int dtype, void* stream);
-/* What both would launch for (M, C, dtype), asked without a launch (host only): plan = lanes per row (1 .. 64), rows per
+/* y = act(LayerNorm(x)) over the last dim in one read and one write, act 0 none | 1 erf-GELU (emo_channelnorm's convention): the
+ * LayerNorm + GELU behind every feature-encoder conv of the layer-norm wav2vec2 family (Net.py:607-648 -> transformers
+ * Wav2Vec2LayerNormConvLayer: conv -> LayerNorm over channels -> GELU).  emo_layernorm's row geometry, checks and limits; two-pass
+ * f32 statistics, the activation on the f32 normalised value, one rounding to `dtype`.  No pe operand; act = 0 gives what
+ * emo_layernorm(pe = NULL) gives, bit for bit. */
+int emo_layernorm_act(const void* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int64_t M, int C, float eps,
+                      int act, int dtype, void* stream);
+/* What the three would launch for (M, C, dtype), asked without a launch (host only): plan = lanes per row (1 .. 64), rows per
  * wavefront, grid (blocks of 4 wavefronts, <= 4096), 1 if the rows need a second trip of the grid.  Returns what their shape
  * checks return for contiguous rows, and writes nothing on a refusal. */
 int emo_layernorm_plan(int64_t M, int C, int dtype, int plan[4]);
@@ -418,6 +425,19 @@ int emo_rows_to_video(const void* x, int64_t ld, float* y, int B, int C, int F, 
 size_t emo_channelnorm_workspace_bytes(int64_t S, int C);
 int emo_channelnorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, int64_t S, int C, float eps,
                     int act, void* workspace, int dtype, void* stream);
+/* emo_wav_conv0_ln_act: the whole first feature-encoder layer of the layer-norm wav2vec2 family behind Wav2VecFeatureExtractor
+ *   (Net.py:607-648 -> transformers Wav2Vec2LayerNormConvLayer with one input channel: Conv1d(1, C, k, stride, bias) -> LayerNorm(C)
+ *   -> GELU) straight from the waveform, with no window matrix and no pre-norm tensor in memory:
+ *       y[t][c] = act(LN_c(bias[c] + sum_{j<k} w[c][j] * wave[t * stride + j])),   t in [0, (n - k) / stride + 1)
+ *   wave f32 [n]; w f32 [C][k] and bias / gamma / beta f32 [C] (the f32 masters, never rounded to `dtype`); y rows [T0][ldy] in
+ *   `dtype`; act 0 none | 1 erf-GELU.  Taps accumulate in ascending j with fmaf from the bias, statistics are two-pass f32, the result
+ *   is rounded once.  Served: C % 8 == 0, C <= 1024, 1 <= k <= 16, stride >= 1, n >= k; anything else is EMO_ERR_UNSUPPORTED before
+ *   any launch.
+ * emo_wav_conv0_ln_act_plan (host only): that shape check without a launch, and on EMO_OK plan = rows T0, lanes per row, 8-channel
+ *   vectors per lane, compiled tap count, row groups per wavefront, grid.  Writes nothing on a refusal. */
+int emo_wav_conv0_ln_act_plan(int64_t n, int C, int k, int stride, int64_t plan[6]);
+int emo_wav_conv0_ln_act(const float* wave, int64_t n, const float* w, const float* bias, const float* gamma, const float* beta, void* y,
+                         int64_t ldy, int C, int k, int stride, float eps, int act, int dtype, void* stream);
 /* emo_audio_resample: the sf.read / librosa.resample / mean(axis=1) of Wav2VecFeatureExtractor.extract_features_from_wav (Net.py:627-640)
  *   as one pass - channel downmix + rational polyphase resampling, f32.  With g = gcd(in_rate, out_rate), up = out_rate / g,
  *   down = in_rate / g, half = 10 * max(up, down) and f32 taps h[-half .. half] (a Kaiser-windowed sinc designed on the host in f64,
