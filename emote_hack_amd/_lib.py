@@ -150,14 +150,10 @@ SIGNATURES = {
     "emo_gif_lzw_codes_per_strip": (_i64, [_i, _i, _i]),
     "emo_gif_lzw_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_gif_lzw_emit": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
-    "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _p]),
-    "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _p]),
-    "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "emo_jpeg_upsample_rgb": (_i, [_p, _p, _p, _i, _i, _i, _p]),
-    "emo_jpeg_layout_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "emo_jpeg_layout_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
-    "emo_jpeg_layout_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "emo_jpeg_layout_rgb": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
+    "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "emo_jpeg_rgb": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_progressive_scan": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "emo_image_resize_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i]),
     "emo_image_resize": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, C.c_size_t, _p]),

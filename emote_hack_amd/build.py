@@ -41,7 +41,7 @@ def _newer(a, b):
 def build_extension(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_api.h"), os.path.join(CSRC, "gemm_impl.h"), os.path.join(CSRC, "conv_halo_impl.h"),
-            os.path.join(os.path.dirname(HERE), "include", "emo_hip.h")]
+            os.path.join(CSRC, "jpeg_bits.h"),            os.path.join(os.path.dirname(HERE), "include", "emo_hip.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src, obj = os.path.join(CSRC, s), os.path.join(LIBDIR, s.replace(".hip", ".o"))

@@ -1,7 +1,7 @@
 // video_in.hip - baseline JPEG (ITU-T T.81) decoding of Motion-JPEG frames, the device half of the reader that stands in for
 // `VideoReader(path).read()` (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-185) and the reverse of
 // video_out.hip (emote_hack_amd/video_io.py is the host half: marker segments, byte unstuffing, the decoding tables):
-//   emo_jpeg_decode_bits  : Huffman decoding (T.81 F.2.2) of one interleaved 4:2:0 scan per frame.  A frame's stream is serial - where a
+//   emo_jpeg_decode_bits  : Huffman decoding (T.81 F.2.2) of one interleaved scan per frame.  A frame's stream is serial - where a
 //                           code starts depends on every code before it - and frames are independent: ONE workgroup per frame.  Its 256
 //                           lanes stage the stream through LDS a window at a time and flush the decoded coefficients as coalesced 16-byte
 //                           stores; lane 0 walks the codes in between.  Every loop is counted, every read is masked to the frame's bytes,
@@ -13,25 +13,19 @@
 //                           workgroup barrier is met, a wave synchronises with itself only.
 //   emo_jpeg_idct         : dequantisation and libjpeg's "islow" integer IDCT (jidctint.c); a wavefront takes eight whole blocks
 //                           (1024 contiguous bytes), one column and then one row per lane
-//   emo_jpeg_upsample_rgb : libjpeg's h2v2 "fancy" (triangle) chroma up-sampling on the real chroma plane and its 16-bit fixed-point
+//   emo_jpeg_rgb          : libjpeg's "fancy" (triangle) chroma up-sampling on the real chroma plane and its 16-bit fixed-point
 //                           YCbCr -> RGB (jdsample.c, jdcolor.c); every lane writes one whole dword of the packed frames
-// The four kernels are templates over the scan's layout - the number of components NC and the luminance sampling factors HS x VS (T.81
-// A.1.1, A.2.3), chrominance always 1 x 1 - so an MCU holds BPM = HS * VS + 2 blocks, or 1 when NC is 1:
+// Every entry takes the scan's layout as three small ints - the number of components NC and the luminance sampling factors HS x VS
+// (T.81 A.1.1, A.2.3), chrominance always 1 x 1 - and picks the instance of its kernel, a template over them; an MCU holds
+// BPM = HS * VS + 2 blocks, or 1 when NC is 1:
 //   4:2:0  NC 3, 2 x 2, MCU 16 x 16, blocks Y00 Y01 Y10 Y11 Cb Cr   h2v2_fancy_upsample (jdsample.c), ycc_rgb_convert (jdcolor.c)
 //   4:2:2  NC 3, 2 x 1, MCU 16 x 8,  blocks Y0 Y1 Cb Cr             h2v1_fancy_upsample (jdsample.c), ycc_rgb_convert
 //   4:4:4  NC 3, 1 x 1, MCU 8 x 8,   blocks Y Cb Cr                 fullsize_upsample: chroma as it is, ycc_rgb_convert
 //   grey   NC 1,        MCU 8 x 8,   one block (not interleaved, T.81 A.2.2)   gray_rgb_convert (jdcolor.c): the sample three times
-// The four entries above are the 4:2:0 instances; emo_jpeg_layout_decode_bits / _decode_segments / _idct / _rgb take the layout as
-// three small ints and pick the instance.
+// The bit reader, the symbol look-up and the staging window are in jpeg_bits.h, which video_in_progressive.hip shares.
 // Integer arithmetic throughout: the bytes are those libjpeg's default decoder gives.
-#include "common.h"
+#include "jpeg_bits.h"
 
-// blocks per MCU of a layout; 0 for one that is not built
-static inline int jpeg_layout_bpm(int ncomp, int hs, int vs) {
-  if (ncomp == 1) return (hs == 1 && vs == 1) ? 1 : 0;
-  if (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return hs * vs + 2;
-  return 0;
-}
 // the component of block k of an MCU of BPM blocks: the luminance blocks first, then Cb, then Cr
 template <int BPM>
 __device__ __forceinline__ int jd_component(int k) {
@@ -45,58 +39,8 @@ __device__ const uint8_t JPEG_NATURAL_OF[64] = {
 };
 
 // ------------------------------------------------------------------------------------------------------------ entropy decoding
-#define JD_TABLE_INTS EMO_JPEG_DECODE_TABLE_INTS   // per table: MINCODE[16] MAXCODE[16] VALPTR[16] 16 unused HUFFVAL[256]
-#define JD_STAGE_BYTES 4096                        // the window of the stream held in LDS
-#define JD_STAGE_SLACK 16                          // the reader runs at most 8 bytes ahead of the bits it has handed out
 #define JD_BLOCK_BYTES_MAX 216                     // a block is at most 27 + 63 * 26 = 1665 bits
 #define JD_BLOCKS 48                               // blocks decoded between two flushes (6 KiB of coefficients)
-
-// the bit reader of the walking lane: `acc` holds `cnt` unread bits at its top, `rp` is the next dword of the window
-struct jd_reader {
-  const uint32_t* win;
-  uint64_t acc;
-  int cnt, rp;
-  __device__ __forceinline__ void refill() {      // afterwards cnt >= 32
-    if (cnt < 32) {
-      const uint32_t w = win[min(rp, (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4 - 1)];
-      acc |= (uint64_t)__builtin_bswap32(w) << (32 - cnt);
-      cnt += 32;
-      rp++;
-    }
-  }
-  __device__ __forceinline__ uint32_t peek(int k) const { return k ? (uint32_t)(acc >> (64 - k)) : 0u; }   // k <= 32
-  __device__ __forceinline__ void skip(int k) { acc <<= k; cnt -= k; }
-  __device__ __forceinline__ int64_t used() const { return (int64_t)rp * 32 - cnt; }                         // bits since the window's start
-};
-
-// DECODE of T.81 figure F.16 behind an 8-bit look-up: the symbol, or -1 when no code of the table matches the next 16 bits (with fewer
-// than 16 bits left in the frame that is a code cut short, not an undefined one: the caller tells them apart)
-__device__ __forceinline__ int jd_symbol(jd_reader& r, const uint16_t* lut, const int32_t* tab) {
-  r.refill();
-  const uint32_t e = lut[r.peek(8)];
-  if (e) {
-    r.skip((int)(e >> 8));
-    return (int)(e & 255u);
-  }
-  const uint32_t bits16 = r.peek(16);
-  for (int l = 9; l <= 16; l++) {
-    const int code = (int)(bits16 >> (16 - l));
-    const int maxcode = tab[16 + l - 1];
-    if (code <= maxcode) {
-      r.skip(l);
-      return tab[64 + ((tab[32 + l - 1] + code - tab[l - 1]) & 255)];
-    }
-  }
-  return -1;
-}
-
-// RECEIVE + EXTEND (figures F.17, F.12): the s-bit magnitude, s <= 11
-__device__ __forceinline__ int jd_extend(jd_reader& r, int s) {
-  r.refill();
-  const int v = (int)r.peek(s);
-  r.skip(s);
-  return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v;
-}
 
 // the four tables into LDS and figure F.16 on every 8-bit prefix of each; all 256 lanes of the workgroup, which meet two barriers here
 __device__ __forceinline__ void jd_tables_to_lds(const int32_t* __restrict__ tables, int32_t* tab, uint16_t (*lut)[256], int t) {
@@ -154,21 +98,6 @@ __device__ __forceinline__ int jd_block(jd_reader& r, const int32_t* dc_tab, con
   return EMO_JPEG_OK;
 }
 
-// dword i of a window that starts at byte `first` of the buffer: bytes first + 4 i .. + 3, those at or behind `hi` as 0.  Aligned dword
-// loads of the buffer (scan_bytes is a multiple of 4), shifted into place
-__device__ __forceinline__ uint32_t jd_stage_dword(const uint8_t* __restrict__ scan, int64_t first, int i, int64_t hi) {
-  const int64_t g = first + 4 * (int64_t)i;                    // the first byte wanted
-  if (g >= hi) return 0u;
-  const int64_t a = g & ~(int64_t)3;
-  const int sh = (int)(g & 3) * 8;
-  const uint32_t w0 = *(const uint32_t*)(scan + a);            // a < hi <= scan_bytes, a % 4 == 0: inside the buffer
-  const uint32_t w1 = (sh && a + 4 < hi) ? *(const uint32_t*)(scan + a + 4) : 0u;
-  uint32_t v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
-  const int64_t left = hi - g;                                 // >= 1
-  if (left < 4) v &= (1u << (8 * (int)left)) - 1u;
-  return v;
-}
-
 template <int BPM>
 __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
                                                                const int64_t* __restrict__ offsets, const int32_t* __restrict__ tables,
@@ -207,9 +136,7 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
     __syncthreads();
     if (t == 0) {
       jd_reader r;
-      r.win = win; r.acc = 0; r.cnt = 0; r.rp = 0;
-      r.refill();
-      r.skip((int)(bit0 & 7));
+      r.open(win, (int)(bit0 & 7));
       const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
       int pred0 = sh_pred[0], pred1 = sh_pred[1], pred2 = sh_pred[2];
       int st = EMO_JPEG_OK, nb = 0;
@@ -248,8 +175,11 @@ __global__ __launch_bounds__(256) void jpeg_decode_bits_kernel(const uint8_t* __
   if (t == 0) status[frame] = sh_status != EMO_JPEG_OK ? sh_status : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
 }
 
-static int jpeg_decode_bits_launch(const char* who, const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables,
-                                   int16_t* coefs, int32_t* status, int n, int n_mcu, int bpm, void* stream) {
+extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
+                                    int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream) {
+  const char* who = "emo_jpeg_decode_bits";
+  const int bpm = jpeg_bpm(ncomp, hs, vs);
+  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, JPEG_LAYOUTS_BUILT, who, ncomp, hs, vs);
   EMO_CHECK(scan && offsets && tables && coefs && status, EMO_ERR_NULL, "%s: null pointer", who);
   EMO_CHECK(n > 0 && n_mcu > 0 && (int64_t)n * n_mcu * bpm < (int64_t)1 << 31 && (int64_t)n_mcu * bpm < (int64_t)1 << 24, EMO_ERR_BAD_SHAPE,
             "%s: n=%d n_mcu=%d", who, n, n_mcu);
@@ -267,31 +197,9 @@ static int jpeg_decode_bits_launch(const char* who, const uint8_t* scan, int64_t
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
-                                    int32_t* status, int n, int n_mcu, void* stream) {
-  return jpeg_decode_bits_launch("emo_jpeg_decode_bits", scan, scan_bytes, offsets, tables, coefs, status, n, n_mcu, 6, stream);
-}
-
-extern "C" int emo_jpeg_layout_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables,
-                                           int16_t* coefs, int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream) {
-  const int bpm = jpeg_layout_bpm(ncomp, hs, vs);
-  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_decode_bits: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built",
-            ncomp, hs, vs);
-  return jpeg_decode_bits_launch("emo_jpeg_layout_decode_bits", scan, scan_bytes, offsets, tables, coefs, status, n, n_mcu, bpm, stream);
-}
-
 // ------------------------------------------------------------------------------------------------------------ segments in parallel
 #define JS_WAVES 4                                 // segments (wavefronts) per workgroup
 static_assert(64 * JS_WAVES == 256, "jd_tables_to_lds strides by 256 lanes");
-
-// What a wave wrote to its part of LDS is read by other lanes of the SAME wave only: a wave's LDS accesses complete in order, so the
-// fences stop the compiler from moving them and the barrier is the wave's own.  No workgroup barrier: the waves of a workgroup walk
-// segments of different lengths.
-__device__ __forceinline__ void jd_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int BPM>
 __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(const uint8_t* __restrict__ scan, int64_t scan_bytes,
@@ -333,9 +241,7 @@ __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(con
     int nb = 0;
     if (lane == 0) {
       jd_reader r;
-      r.win = win; r.acc = 0; r.cnt = 0; r.rp = 0;
-      r.refill();
-      r.skip((int)(bitpos & 7));
+      r.open(win, (int)(bitpos & 7));
       const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
       for (; nb < JD_BLOCKS && done_blocks + nb < n_blocks; nb++) {
         if (!holds_end && (r.used() >> 3) + JD_BLOCK_BYTES_MAX > JD_STAGE_BYTES) break;    // the next block may leave the window
@@ -367,9 +273,12 @@ __global__ __launch_bounds__(64 * JS_WAVES) void jpeg_decode_segments_kernel(con
   if (lane == 0) status[seg] = st != EMO_JPEG_OK ? st : (done_blocks < n_blocks ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
 }
 
-static int jpeg_decode_segments_launch(const char* who, const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets,
-                                       const int32_t* seg_first_block, const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs,
-                                       int64_t coef_blocks, int32_t* status, int n_seg, int bpm, void* stream) {
+extern "C" int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
+                                        const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks,
+                                        int32_t* status, int n_seg, int ncomp, int hs, int vs, void* stream) {
+  const char* who = "emo_jpeg_decode_segments";
+  const int bpm = jpeg_bpm(ncomp, hs, vs);
+  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, JPEG_LAYOUTS_BUILT, who, ncomp, hs, vs);
   EMO_CHECK(scan && seg_offsets && seg_first_block && seg_blocks && tables && coefs && status, EMO_ERR_NULL, "%s: null pointer", who);
   EMO_CHECK(n_seg > 0 && n_seg <= (1 << 30) && coef_blocks > 0 && coef_blocks < (int64_t)1 << 31, EMO_ERR_BAD_SHAPE,
             "%s: n_seg=%d coef_blocks=%lld", who, n_seg, (long long)coef_blocks);
@@ -391,24 +300,6 @@ static int jpeg_decode_segments_launch(const char* who, const uint8_t* scan, int
 #undef JS_LAUNCH
   EMO_LAUNCH_CHECK();
   return EMO_OK;
-}
-
-extern "C" int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
-                                        const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks,
-                                        int32_t* status, int n_seg, void* stream) {
-  return jpeg_decode_segments_launch("emo_jpeg_decode_segments", scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables, coefs,
-                                     coef_blocks, status, n_seg, 6, stream);
-}
-
-extern "C" int emo_jpeg_layout_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets,
-                                               const int32_t* seg_first_block, const int32_t* seg_blocks, const int32_t* tables,
-                                               int16_t* coefs, int64_t coef_blocks, int32_t* status, int n_seg, int ncomp, int hs, int vs,
-                                               void* stream) {
-  const int bpm = jpeg_layout_bpm(ncomp, hs, vs);
-  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_decode_segments: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built",
-            ncomp, hs, vs);
-  return jpeg_decode_segments_launch("emo_jpeg_layout_decode_segments", scan, scan_bytes, seg_offsets, seg_first_block, seg_blocks, tables,
-                                     coefs, coef_blocks, status, n_seg, bpm, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------ dequantisation, IDCT
@@ -446,18 +337,18 @@ __device__ __forceinline__ void jpeg_idct_1d(const int32_t* in, int32_t* out) {
 
 // A wavefront takes 8 consecutive blocks (1024 contiguous bytes): lane = (block, eighth) loads 8 coefficients as one 16-byte vector,
 // then lane = (block, column) runs pass 1 and lane = (block, row) pass 2, and stores its 8 samples as one 8-byte vector.
-// NQ quantisers: 2 - luminance, chrominance - or one per component.  The planes are padded to whole MCUs: luminance rows of
+// One quantiser per component.  The planes are padded to whole MCUs: luminance rows of
 // mcu_cols * 8 * HS bytes, chrominance rows of mcu_cols * 8, multiples of 8, so the 8-byte store stays aligned.
-template <int NC, int HS, int VS, int NQ>
+template <int NC, int HS, int VS>
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coefs, const uint16_t* __restrict__ quant,
                                                         uint8_t* __restrict__ yp, uint8_t* __restrict__ cp, int64_t n_blocks, int n_mcu,
                                                         int mcu_cols, int mcu_rows) {
   __shared__ __attribute__((aligned(16))) int32_t ws[4][8 * JI_LD];
   constexpr int NY = NC == 1 ? 1 : HS * VS, BPM = NC == 1 ? 1 : NY + 2;      // luminance blocks, all blocks of an MCU
-  __shared__ uint16_t q[NQ][64];
+  __shared__ uint16_t q[NC][64];
   __shared__ uint8_t nat[64];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t < NQ * 64) q[t >> 6][t & 63] = quant[t];
+  if (t < NC * 64) q[t >> 6][t & 63] = quant[t];
   if (t < 64) nat[t] = JPEG_NATURAL_OF[t];
   __syncthreads();
   int32_t* w = ws[wave] + (lane >> 3) * JI_LD;              // this lane's block
@@ -471,7 +362,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
     if (live) {
       const uint4 v = *(const uint4*)(coefs + b * 64 + sub * 8);
       const uint32_t pk[4] = {v.x, v.y, v.z, v.w};
-      const uint16_t* qq = q[NQ == 2 ? (k >= NY) : (k < NY ? 0 : k - NY + 1)];
+      const uint16_t* qq = q[k < NY ? 0 : k - NY + 1];
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const int c = (int16_t)(pk[j >> 1] >> ((j & 1) * 16));
@@ -523,9 +414,9 @@ static int jpeg_geometry(const char* who, int n, int H, int W, int hs, int vs, i
   return EMO_OK;
 }
 
-template <int NC, int HS, int VS, int NQ>
-static int jpeg_idct_launch(const char* who, const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H,
-                            int W, void* stream) {
+template <int NC, int HS, int VS>
+static int jpeg_idct_launch(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream) {
+  const char* who = "emo_jpeg_idct";
   constexpr int BPM = NC == 1 ? 1 : HS * VS + 2;
   EMO_CHECK(coefs && quant && y_plane && (c_planes || NC == 1), EMO_ERR_NULL, "%s: null pointer", who);
   int mcu_rows = 0, mcu_cols = 0;
@@ -535,26 +426,21 @@ static int jpeg_idct_launch(const char* who, const int16_t* coefs, const uint16_
             "%s: coefs must be 16-byte aligned, the planes 8-byte aligned", who);
   const int n_mcu = mcu_rows * mcu_cols;
   const int64_t n_blocks = (int64_t)n * n_mcu * BPM, g = (n_blocks + 31) / 32;
-  jpeg_idct_kernel<NC, HS, VS, NQ><<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, quant, y_plane, c_planes, n_blocks, n_mcu,
-                                                                                               mcu_cols, mcu_rows);
+  jpeg_idct_kernel<NC, HS, VS><<<(int)(g < 4096 ? g : 4096), 256, 0, as_stream(stream)>>>(coefs, quant, y_plane, c_planes, n_blocks, n_mcu,
+                                                                                           mcu_cols, mcu_rows);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream) {
-  return jpeg_idct_launch<3, 2, 2, 2>("emo_jpeg_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
-}
-
-extern "C" int emo_jpeg_layout_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W,
-                                    int ncomp, int hs, int vs, void* stream) {
-  switch (jpeg_layout_bpm(ncomp, hs, vs)) {
-    case 1: return jpeg_idct_launch<1, 1, 1, 1>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
-    case 3: return jpeg_idct_launch<3, 1, 1, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
-    case 4: return jpeg_idct_launch<3, 2, 1, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
-    case 6: return jpeg_idct_launch<3, 2, 2, 3>("emo_jpeg_layout_idct", coefs, quant, y_plane, c_planes, n, H, W, stream);
+extern "C" int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, int ncomp,
+                             int hs, int vs, void* stream) {
+  switch (jpeg_bpm(ncomp, hs, vs)) {
+    case 1: return jpeg_idct_launch<1, 1, 1>(coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 3: return jpeg_idct_launch<3, 1, 1>(coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 4: return jpeg_idct_launch<3, 2, 1>(coefs, quant, y_plane, c_planes, n, H, W, stream);
+    case 6: return jpeg_idct_launch<3, 2, 2>(coefs, quant, y_plane, c_planes, n, H, W, stream);
   }
-  return emo_fail(EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_idct: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built", ncomp,
-                  hs, vs);
+  return emo_fail(EMO_ERR_BAD_SHAPE, JPEG_LAYOUTS_BUILT, "emo_jpeg_idct", ncomp, hs, vs);
 }
 
 // ------------------------------------------------------------------------------------------------------------ chroma up-sampling, colour
@@ -615,9 +501,8 @@ __device__ __forceinline__ uint32_t jpeg_pixel_rgb_full(const uint8_t* __restric
 
 // lane = one dword of the packed output: bytes 4 d .. 4 d + 3 belong to pixels (4 d) / 3 and the one behind it
 template <int NC, int HS, int VS>
-__global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp,
-                                                                uint8_t* __restrict__ rgb, int64_t total_bytes, int H, int W, int mcu_rows,
-                                                                int mcu_cols) {
+__global__ __launch_bounds__(256) void jpeg_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cp, uint8_t* __restrict__ rgb,
+                                                       int64_t total_bytes, int H, int W, int mcu_rows, int mcu_cols) {
   const int ch = (H + 1) / 2, cw = (W + 1) / 2;
   const int64_t y_ld = (int64_t)mcu_cols * (8 * HS), y_rows = (int64_t)mcu_rows * (8 * VS), c_ld = (int64_t)mcu_cols * 8, c_rows = (int64_t)mcu_rows * 8;
   const int64_t n_pix = total_bytes / 3, n_dwords = (total_bytes + 3) / 4;
@@ -650,31 +535,26 @@ __global__ __launch_bounds__(256) void jpeg_upsample_rgb_kernel(const uint8_t* _
 }
 
 template <int NC, int HS, int VS>
-static int jpeg_rgb_launch(const char* who, const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
+static int jpeg_rgb_launch(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
+  const char* who = "emo_jpeg_rgb";
   EMO_CHECK(y_plane && (c_planes || NC == 1) && rgb, EMO_ERR_NULL, "%s: null pointer", who);
   int mcu_rows = 0, mcu_cols = 0;
   const int rc = jpeg_geometry(who, n, H, W, HS, VS, NC == 1 ? 1 : HS * VS + 2, &mcu_rows, &mcu_cols);
   if (rc != EMO_OK) return rc;
   EMO_CHECK((uintptr_t)rgb % 4 == 0, EMO_ERR_BAD_SHAPE, "%s: rgb must be 4-byte aligned", who);
   const int64_t total = (int64_t)n * H * W * 3, g = ((total + 3) / 4 + 255) / 256;
-  jpeg_upsample_rgb_kernel<NC, HS, VS><<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(y_plane, c_planes, rgb, total, H, W, mcu_rows,
-                                                                                                     mcu_cols);
+  jpeg_rgb_kernel<NC, HS, VS><<<(int)(g < 65536 ? g : 65536), 256, 0, as_stream(stream)>>>(y_plane, c_planes, rgb, total, H, W, mcu_rows, mcu_cols);
   EMO_LAUNCH_CHECK();
   return EMO_OK;
 }
 
-extern "C" int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream) {
-  return jpeg_rgb_launch<3, 2, 2>("emo_jpeg_upsample_rgb", y_plane, c_planes, rgb, n, H, W, stream);
-}
-
-extern "C" int emo_jpeg_layout_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
-                                   void* stream) {
-  switch (jpeg_layout_bpm(ncomp, hs, vs)) {
-    case 1: return jpeg_rgb_launch<1, 1, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
-    case 3: return jpeg_rgb_launch<3, 1, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
-    case 4: return jpeg_rgb_launch<3, 2, 1>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
-    case 6: return jpeg_rgb_launch<3, 2, 2>("emo_jpeg_layout_rgb", y_plane, c_planes, rgb, n, H, W, stream);
+extern "C" int emo_jpeg_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
+                            void* stream) {
+  switch (jpeg_bpm(ncomp, hs, vs)) {
+    case 1: return jpeg_rgb_launch<1, 1, 1>(y_plane, c_planes, rgb, n, H, W, stream);
+    case 3: return jpeg_rgb_launch<3, 1, 1>(y_plane, c_planes, rgb, n, H, W, stream);
+    case 4: return jpeg_rgb_launch<3, 2, 1>(y_plane, c_planes, rgb, n, H, W, stream);
+    case 6: return jpeg_rgb_launch<3, 2, 2>(y_plane, c_planes, rgb, n, H, W, stream);
   }
-  return emo_fail(EMO_ERR_BAD_SHAPE, "emo_jpeg_layout_rgb: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built", ncomp, hs,
-                  vs);
+  return emo_fail(EMO_ERR_BAD_SHAPE, JPEG_LAYOUTS_BUILT, "emo_jpeg_rgb", ncomp, hs, vs);
 }

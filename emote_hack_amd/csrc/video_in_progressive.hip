@@ -2,97 +2,21 @@
 // of decode_mjpeg(progressive=True) (emote_hack_amd/video_io.py is the host half: it walks the scans of a file, keeps the Huffman
 // tables and the restart interval each scan saw, and refuses progressions that are not complete).
 //   emo_jpeg_progressive_scan : ONE scan of a progression, for many frames at once, into the [n][n_mcu][bpm][64] zig-zag coefficient
-//                               buffer that emo_jpeg_layout_idct (emo_jpeg_idct) reads.  Like emo_jpeg_layout_decode_segments: one
-//                               WAVEFRONT per segment - a restart interval of the scan in one frame, or the frame's whole scan - four
-//                               segments per workgroup.  A wave loads the tables its segment names into its own part of LDS, its 64 lanes
+//                               buffer that emo_jpeg_idct reads.  Like emo_jpeg_decode_segments: one WAVEFRONT per segment - a restart
+//                               interval of the scan in one frame, or the frame's whole scan - four segments per workgroup.  A wave loads the tables its segment names into its own part of LDS, its 64 lanes
 //                               stage the stream a window at a time and move blocks between the buffer and LDS (lane = coefficient), its
 //                               lane 0 walks the codes in between.  A scan writes positions Ss .. Se of the blocks of its units only; the
 //                               scans of a progression are launched one behind the other on a stream, which is their only ordering.
 // The four procedures are those of jdphuff.c: decode_mcu_DC_first, decode_mcu_DC_refine, decode_mcu_AC_first, decode_mcu_AC_refine
 // (T.81 G.1.2.1 - G.1.2.3, G.2).  Every loop is counted, every read of the stream is masked to the segment's bytes, the segment table
 // is clamped to the buffers, an error ends the segment.
-// The bit reader, the symbol look-up and the staging window are copies of those in video_in.hip, which stays as it is.
-#include "common.h"
+// The bit reader, the symbol look-up and the staging window are those of video_in.hip: jpeg_bits.h.
+#include "jpeg_bits.h"
 
-#define JP_TABLE_INTS EMO_JPEG_DECODE_TABLE_INTS   // per table: MINCODE[16] MAXCODE[16] VALPTR[16] 16 unused HUFFVAL[256]
-#define JP_STAGE_BYTES 4096                        // the window of the stream held in LDS
-#define JP_STAGE_SLACK 16                          // the reader runs at most 8 bytes ahead of the bits it has handed out
 #define JP_ITEM_BYTES_MAX 216                      // a block of a scan is at most 63 * 26 + 30 bits (AC first), 63 * 18 + 30 (AC refine)
 #define JP_BLOCKS 32                               // blocks walked between two flushes (4 KiB of coefficients per wave)
 #define JP_WAVES 4                                 // segments (wavefronts) per workgroup
 #define JP_TABLES 3                                // tables a segment can name: the DC tables of an interleaved scan's components
-
-// the bit reader of the walking lane: `acc` holds `cnt` unread bits at its top, `rp` is the next dword of the window
-struct jp_reader {
-  const uint32_t* win;
-  uint64_t acc;
-  int cnt, rp;
-  __device__ __forceinline__ void refill() {      // afterwards cnt >= 32
-    if (cnt < 32) {
-      const uint32_t w = win[min(rp, (JP_STAGE_BYTES + JP_STAGE_SLACK) / 4 - 1)];
-      acc |= (uint64_t)__builtin_bswap32(w) << (32 - cnt);
-      cnt += 32;
-      rp++;
-    }
-  }
-  __device__ __forceinline__ uint32_t peek(int k) const { return k ? (uint32_t)(acc >> (64 - k)) : 0u; }   // k <= 32
-  __device__ __forceinline__ void skip(int k) { acc <<= k; cnt -= k; }
-  __device__ __forceinline__ int64_t used() const { return (int64_t)rp * 32 - cnt; }                         // bits since the window's start
-  __device__ __forceinline__ int bits(int k) {    // RECEIVE (figure F.17), k <= 16
-    refill();
-    const int v = (int)peek(k);
-    skip(k);
-    return v;
-  }
-};
-
-// DECODE of T.81 figure F.16 behind an 8-bit look-up: the symbol, or -1 when no code of the table matches the next 16 bits
-__device__ __forceinline__ int jp_symbol(jp_reader& r, const uint16_t* lut, const int32_t* tab) {
-  r.refill();
-  const uint32_t e = lut[r.peek(8)];
-  if (e) {
-    r.skip((int)(e >> 8));
-    return (int)(e & 255u);
-  }
-  const uint32_t bits16 = r.peek(16);
-  for (int l = 9; l <= 16; l++) {
-    const int code = (int)(bits16 >> (16 - l));
-    const int maxcode = tab[16 + l - 1];
-    if (code <= maxcode) {
-      r.skip(l);
-      return tab[64 + ((tab[32 + l - 1] + code - tab[l - 1]) & 255)];
-    }
-  }
-  return -1;
-}
-
-// RECEIVE + EXTEND (figures F.17, F.12): the s-bit magnitude, s <= 11
-__device__ __forceinline__ int jp_extend(jp_reader& r, int s) {
-  const int v = r.bits(s);
-  return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v;
-}
-
-// dword i of a window that starts at byte `first` of the buffer: bytes first + 4 i .. + 3, those at or behind `hi` as 0.  Aligned dword
-// loads of the buffer (scan_bytes is a multiple of 4), shifted into place
-__device__ __forceinline__ uint32_t jp_stage_dword(const uint8_t* __restrict__ scan, int64_t first, int i, int64_t hi) {
-  const int64_t g = first + 4 * (int64_t)i;                    // the first byte wanted
-  if (g >= hi) return 0u;
-  const int64_t a = g & ~(int64_t)3;
-  const int sh = (int)(g & 3) * 8;
-  const uint32_t w0 = *(const uint32_t*)(scan + a);            // a < hi <= scan_bytes, a % 4 == 0: inside the buffer
-  const uint32_t w1 = (sh && a + 4 < hi) ? *(const uint32_t*)(scan + a + 4) : 0u;
-  uint32_t v = sh ? (w0 >> sh) | (w1 << (32 - sh)) : w0;
-  const int64_t left = hi - g;                                 // >= 1
-  if (left < 4) v &= (1u << (8 * (int)left)) - 1u;
-  return v;
-}
-
-// a wave synchronises with itself only (see video_in.hip): its LDS accesses complete in order
-__device__ __forceinline__ void jp_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // what a launch is constant in
 struct jp_scan {
@@ -122,13 +46,13 @@ enum { JP_DC_FIRST = 0, JP_DC_REFINE = 1, JP_AC_FIRST = 2, JP_AC_REFINE = 3 };
 // coefficients with a zero history in registers and reads b[k] only where a correction bit is 1).  Returns EMO_JPEG_OK or what ended the segment (the caller turns it into PAST_END when the
 // reader has left the segment's bits).
 template <int PROC>
-__device__ __forceinline__ int jp_item(jp_reader& r, const int32_t* tab, const uint16_t* lut, int& pred, int& eobrun, int16_t* b,
+__device__ __forceinline__ int jp_item(jd_reader& r, const int32_t* tab, const uint16_t* lut, int& pred, int& eobrun, int16_t* b,
                                        uint64_t history, const jp_scan& p, int items_left) {
   if (PROC == JP_DC_FIRST) {                                   // G.1.2.1, decode_mcu_DC_first: F.2.2.1, the value shifted left by Al
-    const int s = jp_symbol(r, lut, tab);
+    const int s = jd_symbol(r, lut, tab);
     if (s < 0) return JP_NO_CODE;
     if (s > 11) return EMO_JPEG_BAD_CODE;
-    pred = (int)((uint32_t)pred + (uint32_t)jp_extend(r, s));
+    pred = (int)((uint32_t)pred + (uint32_t)jd_extend(r, s));
     b[0] = (int16_t)((uint32_t)pred << p.Al);
     return EMO_JPEG_OK;
   }
@@ -144,12 +68,12 @@ __device__ __forceinline__ int jp_item(jp_reader& r, const int32_t* tab, const u
     }
     int k = Ss;
     for (int it = 0; it <= Se - Ss && k <= Se; it++) {         // every symbol moves k on by at least one
-      const int rs = jp_symbol(r, lut, tab);
+      const int rs = jd_symbol(r, lut, tab);
       if (rs < 0) return JP_NO_CODE;
       const int run = rs >> 4, s = rs & 15;
       if (s) {
         if (s > 10) return EMO_JPEG_BAD_CODE;
-        const int v = jp_extend(r, s);
+        const int v = jd_extend(r, s);
         k += run;
         if (k > Se) return EMO_JPEG_BAD_RUN;
         b[k++] = (int16_t)((uint32_t)v << p.Al);
@@ -170,7 +94,7 @@ __device__ __forceinline__ int jp_item(jp_reader& r, const int32_t* tab, const u
   int k = Ss;
   if (eobrun == 0) {
     for (int it = 0; it <= Se - Ss && k <= Se; it++) {
-      const int rs = jp_symbol(r, lut, tab);
+      const int rs = jd_symbol(r, lut, tab);
       if (rs < 0) return JP_NO_CODE;
       int run = rs >> 4, val = 0;
       const int s = rs & 15;
@@ -223,9 +147,9 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
                                                                                const int32_t* __restrict__ tables, int n_tables,
                                                                                int16_t* __restrict__ coefs, int n, int32_t* __restrict__ status,
                                                                                int n_seg, jp_scan p) {
-  __shared__ int32_t tabs[JP_WAVES][JP_TABLES][JP_TABLE_INTS];
+  __shared__ int32_t tabs[JP_WAVES][JP_TABLES][JD_TABLE_INTS];
   __shared__ uint16_t luts[JP_WAVES][JP_TABLES][256];        // length << 8 | symbol of the code that starts the 8 bits; 0: longer than 8
-  __shared__ uint32_t wins[JP_WAVES][(JP_STAGE_BYTES + JP_STAGE_SLACK) / 4];
+  __shared__ uint32_t wins[JP_WAVES][(JD_STAGE_BYTES + JD_STAGE_SLACK) / 4];
   __shared__ int16_t blks[JP_WAVES][JP_BLOCKS * 64];
   __shared__ uint64_t hists[JP_WAVES][JP_BLOCKS];            // per block of the round: which coefficients are not 0 (AC refinement)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -239,9 +163,9 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
   const int use_tables = PROC == JP_DC_REFINE ? 0 : (interleaved ? p.ncomp : 1);
   for (int s = 0; s < use_tables; s++) {
     const int which = min(max(seg_tables[seg * JP_TABLES + s], 0), n_tables - 1);
-    for (int i = lane; i < JP_TABLE_INTS; i += 64) tabs[wave][s][i] = tables[(int64_t)which * JP_TABLE_INTS + i];
+    for (int i = lane; i < JD_TABLE_INTS; i += 64) tabs[wave][s][i] = tables[(int64_t)which * JD_TABLE_INTS + i];
   }
-  jp_wave_sync();
+  jd_wave_sync();
   for (int s = 0; s < use_tables; s++) {
     const int32_t* tb = tabs[wave][s];
     for (int q = lane; q < 256; q += 64) {
@@ -256,7 +180,7 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
       luts[wave][s][q] = e;
     }
   }
-  jp_wave_sync();
+  jd_wave_sync();
 
   // the segment's own bytes, frame and units, clamped to the buffers: offsets that leave the scan or run backwards give an empty
   // segment, units that leave the frame's grid are not decoded
@@ -289,17 +213,15 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
       }
     }
     const int64_t byte0 = bitpos >> 3;                       // the window starts at this byte of the segment
-    for (int i = lane; i < (JP_STAGE_BYTES + JP_STAGE_SLACK) / 4; i += 64) win[i] = jp_stage_dword(scan, lo + byte0, i, hi);
-    jp_wave_sync();
+    for (int i = lane; i < (JD_STAGE_BYTES + JD_STAGE_SLACK) / 4; i += 64) win[i] = jd_stage_dword(scan, lo + byte0, i, hi);
+    jd_wave_sync();
     int nb = 0;
     if (lane == 0) {
-      jp_reader r;
-      r.win = win; r.acc = 0; r.cnt = 0; r.rp = 0;
-      r.refill();
-      r.skip((int)(bitpos & 7));
-      const bool holds_end = byte0 + JP_STAGE_BYTES >= hi - lo;
+      jd_reader r;
+      r.open(win, (int)(bitpos & 7));
+      const bool holds_end = byte0 + JD_STAGE_BYTES >= hi - lo;
       for (; nb < cnt; nb++) {
-        if (!holds_end && (r.used() >> 3) + JP_ITEM_BYTES_MAX > JP_STAGE_BYTES) break;     // the next block may leave the window
+        if (!holds_end && (r.used() >> 3) + JP_ITEM_BYTES_MAX > JD_STAGE_BYTES) break;     // the next block may leave the window
         int slot = 0;
         if (interleaved && p.bpm > 1) {                      // block k of an MCU: the luminance blocks first, then Cb, then Cr
           const int k = (item0 + done + nb) % p.bpm;
@@ -314,7 +236,7 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
       }
       bitpos = byte0 * 8 + r.used();
     }
-    jp_wave_sync();
+    jd_wave_sync();
     nb = __builtin_amdgcn_readfirstlane(nb);                 // lane 0's, in scalar registers: the loop stays uniform for the compiler too
     st = __builtin_amdgcn_readfirstlane(st);
     bitpos = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bitpos >> 32)) << 32 |
@@ -323,7 +245,7 @@ __global__ __launch_bounds__(64 * JP_WAVES) void jpeg_progressive_scan_kernel(co
     if (in_band)
       for (int j = 0; j < nb; j++) frame_coefs[(int64_t)jp_block_of(p, item0 + done + j) * 64 + lane] = blk[j * 64 + lane];
     done += nb;
-    jp_wave_sync();
+    jd_wave_sync();
     if (st != EMO_JPEG_OK || nb == 0) break;
   }
   if (lane == 0) status[seg] = st != EMO_JPEG_OK ? st : (done < n_items ? EMO_JPEG_PAST_END : EMO_JPEG_OK);
@@ -336,10 +258,8 @@ extern "C" int emo_jpeg_progressive_scan(const uint8_t* scan, int64_t scan_bytes
   const char* who = "emo_jpeg_progressive_scan";
   EMO_CHECK(scan && seg_offsets && seg_frame && seg_first_unit && seg_units && seg_tables && tables && coefs && status, EMO_ERR_NULL,
             "%s: null pointer", who);
-  int bpm = 0;
-  if (ncomp == 1) bpm = (hs == 1 && vs == 1) ? 1 : 0;
-  else if (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) bpm = hs * vs + 2;
-  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, "%s: %d component(s) with luminance at %dx%d: 4:2:0, 4:2:2, 4:4:4 and grey are built", who, ncomp, hs, vs);
+  const int bpm = jpeg_bpm(ncomp, hs, vs);
+  EMO_CHECK(bpm, EMO_ERR_BAD_SHAPE, JPEG_LAYOUTS_BUILT, who, ncomp, hs, vs);
   EMO_CHECK(n > 0 && H > 0 && W > 0 && H <= 65535 && W <= 65535, EMO_ERR_BAD_SHAPE, "%s: n=%d H=%d W=%d (1 .. 65535: SOF2 holds 16 bits)", who, n,
             H, W);
   const int mcu_cols = (W + 8 * hs - 1) / (8 * hs), mcu_rows = (H + 8 * vs - 1) / (8 * vs);

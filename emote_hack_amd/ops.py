@@ -796,9 +796,31 @@ def rows_to_frames_u8(x: torch.Tensor, B, Cc, F, H, W, mul=0.5, add=0.5, lo=0.0,
     return out
 
 
-def jpeg_mcus(H: int, W: int) -> int:
-    """16x16 MCUs of an (H, W) frame at 4:2:0"""
-    return ((int(H) + 15) // 16) * ((int(W) + 15) // 16)
+JPEG_LAYOUTS = {(3, 2, 2): "4:2:0", (3, 2, 1): "4:2:2", (3, 1, 1): "4:4:4", (1, 1, 1): "grey"}      # (components, luminance h, v)
+
+
+def _jpeg_layout(layout):
+    layout = tuple(int(v) for v in layout)
+    assert layout in JPEG_LAYOUTS, f"a layout is (components, luminance h, luminance v), one of {sorted(JPEG_LAYOUTS)}; got {layout}"
+    return layout
+
+
+def jpeg_bpm(layout) -> int:
+    """blocks per MCU: the luminance blocks, Cb, Cr; one for a grey scan, which is not interleaved (T.81 A.2.2, A.2.3)"""
+    nc, hs, vs = _jpeg_layout(layout)
+    return 1 if nc == 1 else hs * vs + 2
+
+
+def jpeg_grid(H: int, W: int, layout=(3, 2, 2)):
+    """(MCU rows, MCU columns) of an (H, W) frame: MCUs of 8 h x 8 v pixels"""
+    _, hs, vs = _jpeg_layout(layout)
+    return (int(H) + 8 * vs - 1) // (8 * vs), (int(W) + 8 * hs - 1) // (8 * hs)
+
+
+def jpeg_mcus(H: int, W: int, layout=(3, 2, 2)) -> int:
+    """MCUs of an (H, W) frame in `layout`: 16x16 ones at 4:2:0 (for grey, the 8x8 blocks of the frame)"""
+    mr, mc = jpeg_grid(H, W, layout)
+    return mr * mc
 
 
 def jpeg_blocks(frames: torch.Tensor, quant: torch.Tensor) -> torch.Tensor:
@@ -951,183 +973,89 @@ def _jpeg_out(out, shape, dtype, device, what):
     return out
 
 
-def jpeg_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Tensor, n_mcu: int, out=None, status=None):
-    """the unstuffed scans of n frames (uint8, a multiple of 4 bytes; frame i in bytes offsets[i] .. offsets[i + 1], int64 (n + 1)) ->
-    (coefficients int16 (n, n_mcu, 6, 64) in jpeg_blocks' layout, status int32 (n): a key of JPEG_STATUS) (emo_jpeg_decode_bits; T.81
-    F.2.2).  tables: device int32 (4, JPEG_DECODE_TABLE_INTS), video_io.huffman_decode_table of DC luma / AC luma / DC chroma / AC chroma."""
-    _need_cuda(scan, offsets, tables)
+def _jpeg_scan_args(scan, offsets, tables):
+    """what both entropy decoders check of their scan buffer, its offsets and the four decoding tables -> len(offsets) - 1"""
     assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
     assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
     assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
-    n, n_mcu = offsets.numel() - 1, int(n_mcu)
-    coefs = _jpeg_out(out, (n, n_mcu, 6, 64), torch.int16, scan.device, "coefs")
+    return offsets.numel() - 1
+
+
+def jpeg_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Tensor, n_mcu: int, layout=(3, 2, 2), out=None, status=None):
+    """the unstuffed scans of n frames in `layout`, a key of JPEG_LAYOUTS (uint8, a multiple of 4 bytes; frame i in bytes offsets[i] ..
+    offsets[i + 1], int64 (n + 1)) -> (coefficients int16 (n, n_mcu, bpm, 64) - at 4:2:0 jpeg_blocks' layout -, status int32 (n): a key
+    of JPEG_STATUS) (emo_jpeg_decode_bits; T.81 A.2.3, F.2.2).  tables: device int32 (4, JPEG_DECODE_TABLE_INTS),
+    video_io.huffman_decode_table of DC luma / AC luma / DC chroma / AC chroma: the first pair decodes component 0, the second Cb and Cr."""
+    _need_cuda(scan, offsets, tables)
+    nc, hs, vs = _jpeg_layout(layout)
+    n, n_mcu = _jpeg_scan_args(scan, offsets, tables), int(n_mcu)
+    coefs = _jpeg_out(out, (n, n_mcu, jpeg_bpm(layout), 64), torch.int16, scan.device, "coefs")
     status = _jpeg_out(status, (n,), torch.int32, scan.device, "status")
     _launch("jpeg_decode_bits", 0.0, float(scan.numel() + 2 * coefs.numel()),
             lambda: check(_lib.load().emo_jpeg_decode_bits(_ptr(scan), scan.numel(), _ptr(offsets), _ptr(tables), _ptr(coefs), _ptr(status), n, n_mcu,
-                                                           _stream()), "emo_jpeg_decode_bits"), tag=f"{n}x{n_mcu}")
-    return coefs, status
-
-
-def jpeg_decode_segments(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_first_block: torch.Tensor, seg_blocks: torch.Tensor,
-                         tables: torch.Tensor, n: int, n_mcu: int, out=None, status=None):
-    """unstuffed segments (restart intervals, or whole frames without restart markers; segment s in bytes seg_offsets[s] ..
-    seg_offsets[s + 1] of scan, int64 (n_seg + 1)) -> (coefficients int16 (n, n_mcu, 6, 64), status int32 (n_seg), a key of JPEG_STATUS
-    PER SEGMENT) (emo_jpeg_decode_segments; T.81 E.1.4, F.2.2).  Segment s fills seg_blocks[s] blocks from block seg_first_block[s] on of
-    the whole coefficient buffer (both int32 (n_seg)); blocks no segment names are not written.  scan and tables as in jpeg_decode_bits."""
-    _need_cuda(scan, seg_offsets, seg_first_block, seg_blocks, tables)
-    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
-    assert seg_offsets.dtype == torch.int64 and seg_offsets.dim() == 1 and seg_offsets.numel() >= 2 and seg_offsets.is_contiguous(), (seg_offsets.dtype, seg_offsets.shape)
-    n_seg = seg_offsets.numel() - 1
-    for tab in (seg_first_block, seg_blocks):
-        assert tab.dtype == torch.int32 and tuple(tab.shape) == (n_seg,) and tab.is_contiguous(), (tab.dtype, tab.shape, n_seg)
-    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
-    n, n_mcu = int(n), int(n_mcu)
-    coefs = _jpeg_out(out, (n, n_mcu, 6, 64), torch.int16, scan.device, "coefs")
-    status = _jpeg_out(status, (n_seg,), torch.int32, scan.device, "status")
-    _launch("jpeg_decode_segments", 0.0, float(scan.numel() + 2 * coefs.numel()),
-            lambda: check(_lib.load().emo_jpeg_decode_segments(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_first_block), _ptr(seg_blocks),
-                                                               _ptr(tables), _ptr(coefs), n * n_mcu * 6, _ptr(status), n_seg, _stream()),
-                          "emo_jpeg_decode_segments"), tag=f"{n_seg}/{n}x{n_mcu}")
-    return coefs, status
-
-
-def jpeg_idct(coefs: torch.Tensor, quant: torch.Tensor, H: int, W: int, out_y=None, out_c=None):
-    """coefficients int16 (n, MCUs, 6, 64) of (H, W) frames -> (Y plane uint8 (n, mr * 16, mc * 16), Cb / Cr planes uint8 (n, 2, mr * 8,
-    mc * 8)), mr, mc = ceil(H / 16), ceil(W / 16): dequantisation and libjpeg's integer IDCT (emo_jpeg_idct).  quant: device uint16
-    (2, 64), natural order."""
-    _need_cuda(coefs, quant)
-    H, W = int(H), int(W)
-    mr, mc = (H + 15) // 16, (W + 15) // 16
-    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[1:]) == (mr * mc, 6, 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
-    assert quant.dtype == torch.uint16 and quant.numel() == 128 and quant.is_contiguous(), (quant.dtype, quant.shape)
-    n = coefs.shape[0]
-    y = _jpeg_out(out_y, (n, mr * 16, mc * 16), torch.uint8, coefs.device, "y plane")
-    c = _jpeg_out(out_c, (n, 2, mr * 8, mc * 8), torch.uint8, coefs.device, "chroma planes")
-    _launch("jpeg_idct", 0.0, float(2 * coefs.numel() + y.numel() + c.numel()),
-            lambda: check(_lib.load().emo_jpeg_idct(_ptr(coefs), _ptr(quant), _ptr(y), _ptr(c), n, H, W, _stream()), "emo_jpeg_idct"),
-            tag=f"{n}x{H}x{W}")
-    return y, c
-
-
-def jpeg_upsample_rgb(y: torch.Tensor, c: torch.Tensor, H: int, W: int, out=None) -> torch.Tensor:
-    """jpeg_idct's planes -> packed uint8 RGB frames (n, H, W, 3): libjpeg's triangle chroma up-sampling and fixed-point colour
-    transform (emo_jpeg_upsample_rgb)."""
-    _need_cuda(y, c)
-    H, W = int(H), int(W)
-    mr, mc = (H + 15) // 16, (W + 15) // 16
-    n = y.shape[0]
-    assert y.dtype == torch.uint8 and tuple(y.shape) == (n, mr * 16, mc * 16) and y.is_contiguous(), (y.dtype, y.shape)
-    assert c.dtype == torch.uint8 and tuple(c.shape) == (n, 2, mr * 8, mc * 8) and c.is_contiguous(), (c.dtype, c.shape)
-    rgb = _jpeg_out(out, (n, H, W, 3), torch.uint8, y.device, "frames")
-    _launch("jpeg_upsample_rgb", 0.0, float(y.numel() + c.numel() + rgb.numel()),
-            lambda: check(_lib.load().emo_jpeg_upsample_rgb(_ptr(y), _ptr(c), _ptr(rgb), n, H, W, _stream()), "emo_jpeg_upsample_rgb"),
-            tag=f"{n}x{H}x{W}")
-    return rgb
-
-
-JPEG_LAYOUTS = {(3, 2, 2): "4:2:0", (3, 2, 1): "4:2:2", (3, 1, 1): "4:4:4", (1, 1, 1): "grey"}      # (components, luminance h, v)
-
-
-def _jpeg_layout(layout):
-    layout = tuple(int(v) for v in layout)
-    assert layout in JPEG_LAYOUTS, f"a layout is (components, luminance h, luminance v), one of {sorted(JPEG_LAYOUTS)}; got {layout}"
-    return layout
-
-
-def jpeg_layout_bpm(layout) -> int:
-    """blocks per MCU: the luminance blocks, Cb, Cr; one for a grey scan, which is not interleaved (T.81 A.2.2, A.2.3)"""
-    nc, hs, vs = _jpeg_layout(layout)
-    return 1 if nc == 1 else hs * vs + 2
-
-
-def jpeg_layout_grid(H: int, W: int, layout):
-    """(MCU rows, MCU columns) of an (H, W) frame: MCUs of 8 h x 8 v pixels"""
-    _, hs, vs = _jpeg_layout(layout)
-    return (int(H) + 8 * vs - 1) // (8 * vs), (int(W) + 8 * hs - 1) // (8 * hs)
-
-
-def jpeg_layout_mcus(H: int, W: int, layout) -> int:
-    """MCUs of an (H, W) frame in `layout`: jpeg_mcus for every layout (for grey, the 8x8 blocks of the frame)"""
-    mr, mc = jpeg_layout_grid(H, W, layout)
-    return mr * mc
-
-
-def jpeg_layout_decode_bits(scan: torch.Tensor, offsets: torch.Tensor, tables: torch.Tensor, n_mcu: int, layout, out=None, status=None):
-    """jpeg_decode_bits for a scan in `layout`, a key of JPEG_LAYOUTS -> (coefficients int16 (n, n_mcu, bpm, 64), status int32 (n))
-    (emo_jpeg_layout_decode_bits; T.81 A.2.3, F.2.2).  tables as there: the first pair decodes component 0, the second Cb and Cr."""
-    _need_cuda(scan, offsets, tables)
-    nc, hs, vs = _jpeg_layout(layout)
-    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
-    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
-    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
-    n, n_mcu = offsets.numel() - 1, int(n_mcu)
-    coefs = _jpeg_out(out, (n, n_mcu, jpeg_layout_bpm(layout), 64), torch.int16, scan.device, "coefs")
-    status = _jpeg_out(status, (n,), torch.int32, scan.device, "status")
-    _launch("jpeg_layout_decode_bits", 0.0, float(scan.numel() + 2 * coefs.numel()),
-            lambda: check(_lib.load().emo_jpeg_layout_decode_bits(_ptr(scan), scan.numel(), _ptr(offsets), _ptr(tables), _ptr(coefs), _ptr(status), n,
-                                                                  n_mcu, nc, hs, vs, _stream()), "emo_jpeg_layout_decode_bits"),
+                                                           nc, hs, vs, _stream()), "emo_jpeg_decode_bits"),
             tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{n_mcu}")
     return coefs, status
 
 
-def jpeg_layout_decode_segments(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_first_block: torch.Tensor, seg_blocks: torch.Tensor,
-                                tables: torch.Tensor, n: int, n_mcu: int, layout, out=None, status=None):
-    """jpeg_decode_segments for scans in `layout` -> (coefficients int16 (n, n_mcu, bpm, 64), status int32 (n_seg))
-    (emo_jpeg_layout_decode_segments).  The segment table counts blocks, bpm to an MCU."""
+def jpeg_decode_segments(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_first_block: torch.Tensor, seg_blocks: torch.Tensor,
+                         tables: torch.Tensor, n: int, n_mcu: int, layout=(3, 2, 2), out=None, status=None):
+    """unstuffed segments (restart intervals, or whole frames without restart markers; segment s in bytes seg_offsets[s] ..
+    seg_offsets[s + 1] of scan, int64 (n_seg + 1)) -> (coefficients int16 (n, n_mcu, bpm, 64), status int32 (n_seg), a key of JPEG_STATUS
+    PER SEGMENT) (emo_jpeg_decode_segments; T.81 E.1.4, F.2.2).  Segment s fills seg_blocks[s] blocks from block seg_first_block[s] on of
+    the whole coefficient buffer (both int32 (n_seg), in blocks, bpm to an MCU); blocks no segment names are not written.  scan, tables
+    and layout as in jpeg_decode_bits."""
     _need_cuda(scan, seg_offsets, seg_first_block, seg_blocks, tables)
     nc, hs, vs = _jpeg_layout(layout)
-    assert scan.dtype == torch.uint8 and scan.dim() == 1 and scan.is_contiguous(), (scan.dtype, scan.shape)
-    assert seg_offsets.dtype == torch.int64 and seg_offsets.dim() == 1 and seg_offsets.numel() >= 2 and seg_offsets.is_contiguous(), (seg_offsets.dtype, seg_offsets.shape)
-    n_seg = seg_offsets.numel() - 1
+    n_seg = _jpeg_scan_args(scan, seg_offsets, tables)
     for tab in (seg_first_block, seg_blocks):
         assert tab.dtype == torch.int32 and tuple(tab.shape) == (n_seg,) and tab.is_contiguous(), (tab.dtype, tab.shape, n_seg)
-    assert tables.dtype == torch.int32 and tuple(tables.shape) == (4, JPEG_DECODE_TABLE_INTS) and tables.is_contiguous(), (tables.dtype, tables.shape)
-    n, n_mcu, bpm = int(n), int(n_mcu), jpeg_layout_bpm(layout)
+    n, n_mcu, bpm = int(n), int(n_mcu), jpeg_bpm(layout)
     coefs = _jpeg_out(out, (n, n_mcu, bpm, 64), torch.int16, scan.device, "coefs")
     status = _jpeg_out(status, (n_seg,), torch.int32, scan.device, "status")
-    _launch("jpeg_layout_decode_segments", 0.0, float(scan.numel() + 2 * coefs.numel()),
-            lambda: check(_lib.load().emo_jpeg_layout_decode_segments(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_first_block),
-                                                                      _ptr(seg_blocks), _ptr(tables), _ptr(coefs), n * n_mcu * bpm, _ptr(status),
-                                                                      n_seg, nc, hs, vs, _stream()), "emo_jpeg_layout_decode_segments"),
+    _launch("jpeg_decode_segments", 0.0, float(scan.numel() + 2 * coefs.numel()),
+            lambda: check(_lib.load().emo_jpeg_decode_segments(_ptr(scan), scan.numel(), _ptr(seg_offsets), _ptr(seg_first_block), _ptr(seg_blocks),
+                                                               _ptr(tables), _ptr(coefs), n * n_mcu * bpm, _ptr(status), n_seg, nc, hs, vs,
+                                                               _stream()), "emo_jpeg_decode_segments"),
             tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n_seg}/{n}x{n_mcu}")
     return coefs, status
 
 
-def jpeg_layout_idct(coefs: torch.Tensor, quant: torch.Tensor, H: int, W: int, layout, out_y=None, out_c=None):
+def jpeg_idct(coefs: torch.Tensor, quant: torch.Tensor, H: int, W: int, layout=(3, 2, 2), out_y=None, out_c=None):
     """coefficients int16 (n, MCUs, bpm, 64) of (H, W) frames in `layout` -> (Y plane uint8 (n, mr * 8 v, mc * 8 h), Cb / Cr planes uint8
-    (n, 2, mr * 8, mc * 8); None for grey), mr, mc = jpeg_layout_grid(H, W, layout) (emo_jpeg_layout_idct).  quant: device uint16
-    (3, 64), one quantiser per component, natural order."""
+    (n, 2, mr * 8, mc * 8); None for grey), mr, mc = jpeg_grid(H, W, layout): dequantisation and libjpeg's integer IDCT (emo_jpeg_idct).
+    quant: device uint16 (3, 64), one quantiser per component, natural order (a grey frame: its one table three times)."""
     _need_cuda(coefs, quant)
     nc, hs, vs = _jpeg_layout(layout)
     H, W = int(H), int(W)
-    mr, mc = jpeg_layout_grid(H, W, layout)
-    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[1:]) == (mr * mc, jpeg_layout_bpm(layout), 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
+    mr, mc = jpeg_grid(H, W, layout)
+    assert coefs.dtype == torch.int16 and coefs.dim() == 4 and tuple(coefs.shape[1:]) == (mr * mc, jpeg_bpm(layout), 64) and coefs.is_contiguous(), (coefs.dtype, coefs.shape)
     assert quant.dtype == torch.uint16 and quant.numel() == 192 and quant.is_contiguous(), (quant.dtype, quant.shape)
     n = coefs.shape[0]
     y = _jpeg_out(out_y, (n, mr * 8 * vs, mc * 8 * hs), torch.uint8, coefs.device, "y plane")
     c = _jpeg_out(out_c, (n, 2, mr * 8, mc * 8), torch.uint8, coefs.device, "chroma planes") if nc == 3 else None
-    _launch("jpeg_layout_idct", 0.0, float(2 * coefs.numel() + y.numel() + (c.numel() if nc == 3 else 0)),
-            lambda: check(_lib.load().emo_jpeg_layout_idct(_ptr(coefs), _ptr(quant), _ptr(y), _ptr(c) if nc == 3 else None, n, H, W, nc, hs, vs,
-                                                           _stream()), "emo_jpeg_layout_idct"),
+    _launch("jpeg_idct", 0.0, float(2 * coefs.numel() + y.numel() + (c.numel() if nc == 3 else 0)),
+            lambda: check(_lib.load().emo_jpeg_idct(_ptr(coefs), _ptr(quant), _ptr(y), _ptr(c) if nc == 3 else None, n, H, W, nc, hs, vs, _stream()),
+                          "emo_jpeg_idct"),
             tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{H}x{W}")
     return y, c
 
 
-def jpeg_layout_rgb(y: torch.Tensor, c, H: int, W: int, layout, out=None) -> torch.Tensor:
-    """jpeg_layout_idct's planes -> packed uint8 RGB frames (n, H, W, 3): libjpeg's chroma up-sampling of the layout and its fixed-point
-    colour transform; a grey frame's sample in all three channels (emo_jpeg_layout_rgb).  c: None for grey."""
+def jpeg_rgb(y: torch.Tensor, c, H: int, W: int, layout=(3, 2, 2), out=None) -> torch.Tensor:
+    """jpeg_idct's planes -> packed uint8 RGB frames (n, H, W, 3): libjpeg's chroma up-sampling of the layout (triangle filters where
+    chroma is halved) and its fixed-point colour transform; a grey frame's sample in all three channels (emo_jpeg_rgb).  c: None for
+    grey."""
     nc, hs, vs = _jpeg_layout(layout)
     _need_cuda(*((y, c) if nc == 3 else (y,)))
     H, W = int(H), int(W)
-    mr, mc = jpeg_layout_grid(H, W, layout)
+    mr, mc = jpeg_grid(H, W, layout)
     n = y.shape[0]
     assert y.dtype == torch.uint8 and tuple(y.shape) == (n, mr * 8 * vs, mc * 8 * hs) and y.is_contiguous(), (y.dtype, y.shape)
     if nc == 3:
         assert c.dtype == torch.uint8 and tuple(c.shape) == (n, 2, mr * 8, mc * 8) and c.is_contiguous(), (c.dtype, c.shape)
     rgb = _jpeg_out(out, (n, H, W, 3), torch.uint8, y.device, "frames")
-    _launch("jpeg_layout_rgb", 0.0, float(y.numel() + (c.numel() if nc == 3 else 0) + rgb.numel()),
-            lambda: check(_lib.load().emo_jpeg_layout_rgb(_ptr(y), _ptr(c) if nc == 3 else None, _ptr(rgb), n, H, W, nc, hs, vs, _stream()),
-                          "emo_jpeg_layout_rgb"),
+    _launch("jpeg_rgb", 0.0, float(y.numel() + (c.numel() if nc == 3 else 0) + rgb.numel()),
+            lambda: check(_lib.load().emo_jpeg_rgb(_ptr(y), _ptr(c) if nc == 3 else None, _ptr(rgb), n, H, W, nc, hs, vs, _stream()), "emo_jpeg_rgb"),
             tag=f"{JPEG_LAYOUTS[(nc, hs, vs)]} {n}x{H}x{W}")
     return rgb
 
@@ -1139,7 +1067,7 @@ def jpeg_scan_units(H: int, W: int, layout, scan_comp: int) -> int:
     scan_comp = int(scan_comp)
     assert -1 <= scan_comp < nc, (scan_comp, nc)
     if scan_comp < 0 or nc == 1:
-        return jpeg_layout_mcus(H, W, layout)
+        return jpeg_mcus(H, W, layout)
     h, v = (hs, vs) if scan_comp == 0 else (1, 1)
     return (((int(W) * h + hs - 1) // hs + 7) // 8) * (((int(H) * v + vs - 1) // vs + 7) // 8)
 
@@ -1166,7 +1094,7 @@ def jpeg_progressive_scan(scan: torch.Tensor, seg_offsets: torch.Tensor, seg_fra
     assert seg_tables.dtype == torch.int32 and tuple(seg_tables.shape) == (n_seg, 3) and seg_tables.is_contiguous(), (seg_tables.dtype, seg_tables.shape)
     assert tables.dtype == torch.int32 and tables.dim() == 2 and tables.shape[0] >= 1 and tables.shape[1] == JPEG_DECODE_TABLE_INTS and tables.is_contiguous(), (tables.dtype, tables.shape)
     assert coefs.dtype == torch.int16 and coefs.dim() == 4 and coefs.shape[0] >= 1 and coefs.is_contiguous() and \
-        tuple(coefs.shape[1:]) == (jpeg_layout_mcus(H, W, layout), jpeg_layout_bpm(layout), 64), (coefs.dtype, coefs.shape)
+        tuple(coefs.shape[1:]) == (jpeg_mcus(H, W, layout), jpeg_bpm(layout), 64), (coefs.dtype, coefs.shape)
     assert -1 <= scan_comp < nc, f"scan_comp {scan_comp}: -1 (interleaved) or a component below {nc}"
     assert 0 <= Ss <= Se <= 63 and (Se == 0 if Ss == 0 else scan_comp >= 0), \
         f"a DC scan holds coefficient 0 alone, an AC scan a band inside 1 .. 63 of one component (T.81 G.1.1.1.1); got {Ss} .. {Se}, scan_comp {scan_comp}"

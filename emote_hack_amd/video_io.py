@@ -19,8 +19,7 @@
   decode_mjpeg      JPEG files (4:2:0, 4:2:2, 4:4:4, grey) -> packed uint8 frames on the device: per set of tables and layout ONE
                     host-to-device copy of the scans and the segment table, then emo_jpeg_decode_segments (one wavefront per restart
                     interval; emo_jpeg_decode_bits, one workgroup per frame, where no frame has restart intervals), emo_jpeg_idct,
-                    emo_jpeg_upsample_rgb - or their emo_jpeg_layout_* counterparts for everything but plain 4:2:0 -
-                    (csrc/video_in.hip) and one read of the segments' status - the bytes libjpeg's default decoder gives
+                    emo_jpeg_rgb (csrc/video_in.hip) and one read of the segments' status - the bytes libjpeg's default decoder gives
   read_image        one JPEG file -> an (H, W, 3) uint8 frame on the device through decode_mjpeg, resized there under size=
   read_video        read_avi + decode_mjpeg: what `VideoReader(path).read()` is to magicanimate/pipelines/animation.py:174-185
   resize_taps       the per-axis coefficient table of Pillow's `Image.resize` for 8-bit images (Resample.c), in 22-bit fixed point
@@ -305,7 +304,7 @@ class JpegLayout:
 
     @property
     def key(self):
-        """(components, luminance h, luminance v): what ops.JPEG_LAYOUTS names and the emo_jpeg_layout_* entries take"""
+        """(components, luminance h, luminance v): what ops.JPEG_LAYOUTS names and the emo_jpeg_* decode entries take"""
         return (self.components,) + tuple(self.factors[0])
 
     @property
@@ -314,7 +313,7 @@ class JpegLayout:
 
     @property
     def blocks_per_mcu(self):
-        return ops.jpeg_layout_bpm(self.key)
+        return ops.jpeg_bpm(self.key)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -345,7 +344,7 @@ class JpegScan:
 class ParsedJpeg:
     height: int
     width: int
-    quant: np.ndarray          # uint16 (2, 64): luminance, chrominance (Cb's), NATURAL order
+    quants: np.ndarray         # uint16 (3, 64): the quantiser of every component, NATURAL order (a grey file: its one table three times)
     specs: tuple               # four (BITS tuple, HUFFVAL bytes): DC luminance, AC luminance, DC chrominance, AC chrominance (a grey
     #                            file: the luminance pair twice)
     scan: np.ndarray           # uint8: the entropy-coded segment without the 0x00 behind every 0xFF, up to the marker that ends it
@@ -353,25 +352,22 @@ class ParsedJpeg:
     intervals: np.ndarray = None      # int64 (intervals + 1): restart interval k lies in scan[intervals[k]:intervals[k + 1]] (the RSTm
     #                                   markers are taken out); (0, len(scan)) for a file without restart intervals
     layout: JpegLayout = None
-    quants: np.ndarray = None  # uint16 (3, 64): the quantiser of every component, NATURAL order (a grey file: its one table three times)
     scans: tuple = None        # a progressive file (parse_jpeg(progressive=True)): one JpegScan per scan in file order; specs is then
     #                            empty, scan and intervals hold no bytes, restart is the interval in force at the first scan.  None: baseline
 
     @property
     def mcus(self):
         """MCUs of the frame in its own layout (the 8x8 blocks of a grey frame)"""
-        return ops.jpeg_layout_mcus(self.height, self.width, self.layout.key)
+        return ops.jpeg_mcus(self.height, self.width, self.layout.key)
 
     @property
-    def classic(self):
-        """4:2:0 with one chrominance quantiser: what emo_jpeg_decode_bits / _idct / _upsample_rgb take"""
-        return self.layout.key == (3, 2, 2) and np.array_equal(self.quants[1], self.quants[2])
+    def quant(self):
+        """uint16 (2, 64): luminance, chrominance (Cb's) - what jpeg_tables(quality).quant is for a file encode_mjpeg wrote"""
+        return self.quants[:2]
 
     def table_key(self):
         if self.scans is not None:      # Huffman tables and restart intervals may differ inside a group: libjpeg optimises tables per file
             return self.quants.tobytes(), self.layout.key, tuple(s.script for s in self.scans)
-        if self.classic:
-            return self.quant.tobytes(), self.specs
         return self.quants.tobytes(), self.specs, self.layout.key
 
 
@@ -386,9 +382,11 @@ _FACTOR_NAMES = {((1, 2), (1, 1), (1, 1)): " (4:4:0)", ((4, 1), (1, 1), (1, 1)):
                  ((2, 1), (1, 1), (1, 1)): " (4:2:2)", ((1, 1), (1, 1), (1, 1)): " (4:4:4)"}
 
 
-def _entropy_bytes(data: bytes, pos: int, units: int, ri: int, what: str):
+def _entropy_bytes(data: bytes, pos: int, units: int, ri: int, what: str, unit: str = "units", restart: bool = True, open_end: bool = False):
     """the entropy-coded bytes that start at data[pos] -> (unstuffed bytes without the RSTm markers, intervals as in ParsedJpeg, the
-    position of the marker that ends them); the markers must cut `units` units at a restart interval of `ri` into ceil(units / ri)"""
+    position of the marker that ends them); the markers must cut `units` units (called `unit` in messages) at a restart interval of
+    `ri` into ceil(units / ri).  restart=False refuses the first RSTm marker; open_end=True takes bytes that run to the end of the data
+    with no marker behind them, as the baseline path always has"""
     rst, end, at = [], None, pos                                                 # forward from pos to the first marker that is no RSTm:
     while True:                                                                  # a file of many scans is not searched to its end per scan
         at = data.find(b"\xFF", at)
@@ -397,13 +395,17 @@ def _entropy_bytes(data: bytes, pos: int, units: int, ri: int, what: str):
         if data[at + 1] == 0x00:                                                 # a stuffed byte
             at += 2
         elif 0xD0 <= data[at + 1] <= 0xD7:
+            if not restart:
+                raise ValueError(f"parse_jpeg: a restart marker inside {what}; restart markers are not built; {_ONLY}")
             rst.append(at - pos)
             at += 2
         else:
             end = at - pos
             break
     if end is None:
-        raise ValueError(f"parse_jpeg: {what} runs to the end of the file: no marker ends it (a cut file)")
+        if not open_end:
+            raise ValueError(f"parse_jpeg: {what} runs to the end of the file: no marker ends it (a cut file)")
+        end = len(data) - pos
     a = np.frombuffer(data, np.uint8, count=end, offset=pos)
     if rst or ri:
         if not ri:
@@ -418,7 +420,7 @@ def _entropy_bytes(data: bytes, pos: int, units: int, ri: int, what: str):
                              "not built)")
         want = -(-units // ri)
         if len(rst) + 1 != want:
-            raise ValueError(f"parse_jpeg: {len(rst) + 1} restart interval{'s' if rst else ''} in {what}, {units} units at a restart interval "
+            raise ValueError(f"parse_jpeg: {len(rst) + 1} restart interval{'s' if rst else ''} in {what}, {units} {unit} at a restart interval "
                              f"of {ri} make {want} (a damaged file; resynchronisation is not built)")
     keep = np.ones(len(a), bool)
     if len(a) > 1:
@@ -665,13 +667,12 @@ def parse_jpeg(data, restart: bool = False, layouts: bool = False, progressive: 
         if not huff:
             huff = dict(zip(HUFFMAN_IDS, HUFFMAN_SPECS))
         scans, quant = _progressive_scans(data, pos, body, frame, quant, huff, ri)
-        q = np.stack([quant[comps[0][3]], quant[comps[min(1, nf - 1)][3]]])
         quants = np.stack([quant[comps[min(k, nf - 1)][3]] for k in range(3)])
         empty, none = np.zeros(0, np.uint8), np.zeros(2, np.int64)
-        for arr in (q, quants, empty, none):
+        for arr in (quants, empty, none):
             arr.setflags(write=False)
-        return ParsedJpeg(int(height), int(width), q, (), empty, scans[0].restart, none, JpegLayout(nf, factors, tuple(c[3] for c in comps), ()),
-                          quants, scans)
+        return ParsedJpeg(int(height), int(width), quants, (), empty, scans[0].restart, none, JpegLayout(nf, factors, tuple(c[3] for c in comps), ()),
+                          scans)
     if len(body) != 4 + 2 * nf or body[0] != nf:
         raise ValueError(f"parse_jpeg: a scan of {body[0] if body else 0} of the frame's {nf} components (not interleaved); {_ONLY}")
     sel = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(nf)]
@@ -694,51 +695,18 @@ def parse_jpeg(data, restart: bool = False, layouts: bool = False, progressive: 
         if key not in huff:
             raise ValueError(f"parse_jpeg: Huffman table (class {key[0]}, destination {key[1]}) is used and never defined")
         specs.append(huff[key])
-    a = np.frombuffer(data, np.uint8, offset=pos)
-    ends = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0x00)) if len(a) > 1 else np.zeros(0, np.int64)
-    rst = []                                                                     # where the RSTm markers start
-    for e in ends:                                                               # up to the first other marker: EOI in a whole file
-        if not 0xD0 <= a[e + 1] <= 0xD7:
-            a = a[:e]
-            break
-        if not restart:
-            raise ValueError(f"parse_jpeg: a restart marker inside the scan; restart markers are not built; {_ONLY}")
-        rst.append(int(e))
-    if rst or ri:
-        n_mcu = ops.jpeg_layout_mcus(height, width, (nf,) + factors[0])
-        if not ri:
-            raise ValueError(f"parse_jpeg: {len(rst)} restart marker{'s' if len(rst) != 1 else ''} in the scan (the first at byte {pos + rst[0]}) "
-                             "and no restart interval defined by a DRI segment")
-        found = [int(a[e + 1]) - 0xD0 for e in rst]
-        wrong = [k for k, m in enumerate(found) if m != k % 8]
-        if wrong:
-            k = wrong[0]
-            raise ValueError(f"parse_jpeg: restart marker {k} of the scan is RST{found[k]} (FF{0xD0 + found[k]:02X} at byte {pos + rst[k]}), RST{k % 8} "
-                             "is expected there: the markers count 0 .. 7 and round again (a damaged file; resynchronisation is not built)")
-        want = -(-n_mcu // ri)
-        if len(rst) + 1 != want:
-            raise ValueError(f"parse_jpeg: {len(rst) + 1} restart interval{'s' if rst else ''} in the scan, {n_mcu} MCUs at a restart interval of "
-                             f"{ri} make {want} (a damaged file; resynchronisation is not built)")
-    keep = np.ones(len(a), bool)
-    if len(a) > 1:
-        keep[np.flatnonzero((a[:-1] == 0xFF) & (a[1:] == 0x00)) + 1] = False       # the stuffed bytes
-    if rst:
-        keep[np.array(rst)] = keep[np.array(rst) + 1] = False                    # the markers
-    before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)            # bytes of the scan in front of byte i of a
-    scan = a[keep]
-    intervals = before[[0] + rst + [len(a)]]
-    q = np.stack([quant[comps[0][3]], quant[comps[min(1, nf - 1)][3]]])
+    scan, intervals, _ = _entropy_bytes(data, pos, ops.jpeg_mcus(height, width, (nf,) + factors[0]), ri, "the scan", unit="MCUs", restart=restart,
+                                        open_end=True)
     quants = np.stack([quant[comps[min(k, nf - 1)][3]] for k in range(3)])
-    for arr in (q, quants, scan, intervals):
-        arr.setflags(write=False)
+    quants.setflags(write=False)
     layout = JpegLayout(nf, factors, tuple(c[3] for c in comps), tuple((td, ta) for _, td, ta in sel))
-    return ParsedJpeg(int(height), int(width), q, tuple(specs), scan, int(ri), intervals, layout, quants)
+    return ParsedJpeg(int(height), int(width), quants, tuple(specs), scan, int(ri), intervals, layout)
 
 
 @functools.lru_cache(maxsize=16)
 def _decode_header(quant_bytes: bytes, specs: tuple) -> np.ndarray:
-    """what a group of frames shares, as bytes: the four decoding tables (int32 (4, 320)) and the quantisers (uint16 (2, 64); (3, 64),
-    one per component, for a group that goes through the emo_jpeg_layout_* entries)"""
+    """what a group of frames shares, as bytes: the four decoding tables (int32 (4, 320)) and the quantisers (uint16 (3, 64), one per
+    component)"""
     tables = np.stack([huffman_decode_table(*spec) for spec in specs])
     return np.concatenate([tables.view(np.uint8).reshape(-1), np.frombuffer(quant_bytes, np.uint8)])
 
@@ -756,8 +724,8 @@ def _progressive_group_plan(parsed, members, device) -> dict:
     frame, scan and restart interval a status belongs to"""
     first = parsed[members[0]]
     n, H, W = len(members), first.height, first.width
-    classic, layout = first.classic, first.layout.key
-    n_mcu, bpm, nf = first.mcus, ops.jpeg_layout_bpm(layout), first.layout.components
+    layout = first.layout.key
+    n_mcu, bpm, nf = first.mcus, ops.jpeg_bpm(layout), first.layout.components
     table_of, table_bytes = {}, []                                               # the decoding tables the group uses, each once
 
     def table(spec):
@@ -794,7 +762,7 @@ def _progressive_group_plan(parsed, members, device) -> dict:
     seg_offsets = np.concatenate(seg_offsets + [np.array([at], np.int64)]).astype(np.int64)
     seg_frame, seg_first, seg_units, seg_tables, seg_scan, seg_interval = (np.concatenate(x) for x in (seg_frame, seg_first, seg_units, seg_tables,
                                                                                                        seg_scan, seg_interval))
-    quant_bytes = (first.quant if classic else first.quants).tobytes()
+    quant_bytes = first.quants.tobytes()
     pad = -at % 4 or (4 if at == 0 else 0)
     ints = [x.astype(np.int32).reshape(-1).view(np.uint8) for x in (seg_frame, seg_first, seg_units, seg_tables)]
     host = np.concatenate([np.frombuffer(b"".join(table_bytes), np.uint8), np.frombuffer(quant_bytes, np.uint8), seg_offsets.view(np.uint8)]
@@ -804,7 +772,7 @@ def _progressive_group_plan(parsed, members, device) -> dict:
     q_end = t_end + len(quant_bytes)
     o_end = q_end + 8 * (n_seg + 1)                                              # every part is a multiple of 8 bytes up to here
     tables = dev[:t_end].view(torch.int32).view(-1, ops.JPEG_DECODE_TABLE_INTS)
-    quant = dev[t_end:q_end].view(torch.uint16).view(-1, 64)
+    quant = dev[t_end:q_end].view(torch.uint16).view(3, 64)
     d_off = dev[q_end:o_end].view(torch.int64)
     d_frame, d_first, d_units = (dev[o_end + 4 * j * n_seg:o_end + 4 * (j + 1) * n_seg].view(torch.int32) for j in range(3))
     d_tabs = dev[o_end + 12 * n_seg:o_end + 24 * n_seg].view(torch.int32).view(n_seg, 3)
@@ -819,23 +787,33 @@ def _progressive_group_plan(parsed, members, device) -> dict:
                 seg_frame=seg_frame, seg_scan=seg_scan, seg_interval=seg_interval)
 
 
-def _decode_progressive_group(parsed, members, out, whole: bool):
-    """_progressive_group_plan's group decoded into out (all of it when `whole`, else a new tensor): the coefficient buffer zeroed once,
-    one emo_jpeg_progressive_scan launch per scan of the script in file order, the baseline IDCT and colour launches, one read of every
-    segment's status"""
+def _coefs_to_frames(coefs, quant, H, W, layout, out, members) -> None:
+    """the tail every group shares: emo_jpeg_idct and emo_jpeg_rgb on the group's coefficients, into frames `members` of out - straight
+    into out where the group is all of it, else through a tensor of its own, copied as one slice where the members are consecutive and
+    scattered by index where they are not"""
+    n = len(members)
+    whole = n == out.shape[0]
+    y, c = ops.jpeg_idct(coefs, quant, H, W, layout)
+    rgb = ops.jpeg_rgb(y, c, H, W, layout, out=out if whole else None)
+    if whole:
+        return
+    if members == list(range(members[0], members[0] + n)):
+        out[members[0]:members[0] + n] = rgb
+    else:
+        out[torch.tensor(members, device=out.device)] = rgb
+
+
+def _decode_progressive_group(parsed, members, out) -> None:
+    """_progressive_group_plan's group decoded into its frames of out: the coefficient buffer zeroed once, one emo_jpeg_progressive_scan
+    launch per scan of the script in file order, the baseline IDCT and colour launches, one read of every segment's status"""
     first = parsed[members[0]]
-    H, W, classic, layout = first.height, first.width, first.classic, first.layout.key
+    H, W, layout = first.height, first.width, first.layout.key
     plan = _progressive_group_plan(parsed, members, out.device)
     coefs, status, quant, seg_frame, seg_scan, seg_interval = (plan[k] for k in ("coefs", "status", "quant", "seg_frame", "seg_scan", "seg_interval"))
     coefs.zero_()                                                                # once: every scan adds to it
     for _, run in plan["launches"]:                                              # file order on one stream is the only synchronisation
         run()
-    if classic:
-        y, c = ops.jpeg_idct(coefs, quant, H, W)
-        rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
-    else:
-        y, c = ops.jpeg_layout_idct(coefs, quant, H, W, layout)
-        rgb = ops.jpeg_layout_rgb(y, c, H, W, layout, out=out if whole else None)
+    _coefs_to_frames(coefs, quant, H, W, layout, out, members)
     st = status.cpu().numpy()                                                    # the one read, for all scans
     if st.any():
         bad = np.flatnonzero(st)
@@ -845,7 +823,6 @@ def _decode_progressive_group(parsed, members, out, whole: bool):
         where = f" in restart interval {int(seg_interval[bad])} of {len(s.intervals) - 1}" if s.restart else ""
         raise ValueError(f"decode_mjpeg: frame {members[f]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')} in scan "
                          f"{k} of {len(first.scans)} ({s}){where} (emo_jpeg_progressive_scan status {int(st[bad])})")
-    return rgb
 
 
 def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
@@ -854,13 +831,11 @@ def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
     libjpeg's default decoder (Pillow's `Image.open(f).convert("RGB")`) gives; a grey frame comes back with R = G = B.  The host only
     parses markers and takes the stuffed bytes out; frames that share their tables and their layout go up in ONE copy (tables,
     quantisers, the segment table, scans) and through one set of three launches (emo_jpeg_decode_segments, emo_jpeg_idct,
-    emo_jpeg_upsample_rgb for 4:2:0 frames with one chrominance quantiser; emo_jpeg_layout_decode_segments, emo_jpeg_layout_idct,
-    emo_jpeg_layout_rgb for the rest), followed by one read of the segments' status.  A segment is a restart interval, or a whole
-    frame that has none: frames with different restart intervals and frames without share a launch, and a frame decodes as many
-    wavefronts wide as it has intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits /
-    emo_jpeg_layout_decode_bits, one workgroup per frame.)  ValueError naming the frame for a file parse_jpeg refuses, a frame of
-    another size, or a scan that does not decode (naming the restart interval too when the frame has them).  There is no host decoder
-    behind this.
+    emo_jpeg_rgb), followed by one read of the segments' status.  A segment is a restart interval, or a whole frame that has none:
+    frames with different restart intervals and frames without share a launch, and a frame decodes as many wavefronts wide as it has
+    intervals.  (A group in which no frame is cut into intervals goes through emo_jpeg_decode_bits, one workgroup per frame.)
+    ValueError naming the frame for a file parse_jpeg refuses, a frame of another size, or a scan that does not decode (naming the
+    restart interval too when the frame has them).  There is no host decoder behind this.
     progressive=True also takes Huffman-coded progressive files (SOF2) with a complete progression, mixed freely with baseline ones
     (parse_jpeg(progressive=True) says what is refused).  Progressive frames that share layout, quantisers and scan script - the
     (components, Ss, Se, Ah, Al) of every scan; Huffman tables and restart intervals may differ from frame to frame - go up in one copy
@@ -891,13 +866,11 @@ def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
     for key, members in groups.items():
         n = len(members)
         if parsed[members[0]].scans is not None:
-            rgb = _decode_progressive_group(parsed, members, out, n == len(parsed))
-            if n != len(parsed):
-                out[torch.tensor(members, device=device)] = rgb
+            _decode_progressive_group(parsed, members, out)
             continue
         head = _decode_header(*key[:2])
-        classic, layout = parsed[members[0]].classic, parsed[members[0]].layout.key
-        n_mcu, bpm = parsed[members[0]].mcus, ops.jpeg_layout_bpm(layout)
+        layout = parsed[members[0]].layout.key
+        n_mcu, bpm = parsed[members[0]].mcus, ops.jpeg_bpm(layout)
         # the segment table: one segment per restart interval, one for a frame without; frame f of the group owns blocks f * n_mcu * bpm ..
         sizes = np.array([len(parsed[i].scan) for i in members], np.int64)
         frame_start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
@@ -917,31 +890,18 @@ def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
                               + [parsed[i].scan for i in members] + [np.zeros(pad, np.uint8)])
         dev = torch.from_numpy(host).to(device)                                  # the one copy
         t_end, q_end = 16 * ops.JPEG_DECODE_TABLE_INTS, len(head)
-        o_end = q_end + 8 * (n_seg + 1)                                          # head is t_end + 256 or 384 bytes: every table stays 8-byte aligned
+        o_end = q_end + 8 * (n_seg + 1)                                          # head is t_end + 384 bytes: every table stays 8-byte aligned
         tables = dev[:t_end].view(torch.int32).view(4, ops.JPEG_DECODE_TABLE_INTS)
-        quant = dev[t_end:q_end].view(torch.uint16).view(-1, 64)
+        quant = dev[t_end:q_end].view(torch.uint16).view(3, 64)
         scans, seg_off = dev[o_end + 8 * n_seg:], dev[q_end:o_end].view(torch.int64)
-        whole = n == len(parsed)
         if n_seg > n:
             seg_tabs = dev[o_end:o_end + 4 * n_seg].view(torch.int32), dev[o_end + 4 * n_seg:o_end + 8 * n_seg].view(torch.int32)
-            if classic:
-                entry = "emo_jpeg_decode_segments"
-                coefs, status = ops.jpeg_decode_segments(scans, seg_off, *seg_tabs, tables, n, n_mcu)
-            else:
-                entry = "emo_jpeg_layout_decode_segments"
-                coefs, status = ops.jpeg_layout_decode_segments(scans, seg_off, *seg_tabs, tables, n, n_mcu, layout)
-        elif classic:       # no frame of the group is cut into intervals: a segment is a frame, which a workgroup of its own decodes faster
+            entry = "emo_jpeg_decode_segments"
+            coefs, status = ops.jpeg_decode_segments(scans, seg_off, *seg_tabs, tables, n, n_mcu, layout)
+        else:               # no frame of the group is cut into intervals: a segment is a frame, which a workgroup of its own decodes faster
             entry = "emo_jpeg_decode_bits"
-            coefs, status = ops.jpeg_decode_bits(scans, seg_off, tables, n_mcu)
-        else:
-            entry = "emo_jpeg_layout_decode_bits"
-            coefs, status = ops.jpeg_layout_decode_bits(scans, seg_off, tables, n_mcu, layout)
-        if classic:
-            y, c = ops.jpeg_idct(coefs, quant, H, W)
-            rgb = ops.jpeg_upsample_rgb(y, c, H, W, out=out if whole else None)
-        else:
-            y, c = ops.jpeg_layout_idct(coefs, quant, H, W, layout)
-            rgb = ops.jpeg_layout_rgb(y, c, H, W, layout, out=out if whole else None)
+            coefs, status = ops.jpeg_decode_bits(scans, seg_off, tables, n_mcu, layout)
+        _coefs_to_frames(coefs, quant, H, W, layout, out, members)
         st = status.cpu().numpy()                                                # the one read
         if st.any():
             bad = int(np.flatnonzero(st)[0])                                     # the first in frame order, whichever wave ended first
@@ -950,11 +910,6 @@ def decode_mjpeg(jpegs, device=None, progressive: bool = False) -> torch.Tensor:
             where = f" in restart interval {bad - int(np.searchsorted(seg_frame, f))} of {len(p.intervals) - 1}" if p.restart else ""
             raise ValueError(f"decode_mjpeg: frame {members[f]} does not decode: {ops.JPEG_STATUS.get(int(st[bad]), f'status {int(st[bad])}')}"
                              f"{where} ({entry} status {int(st[bad])})")
-        if not whole:
-            if members == list(range(members[0], members[0] + n)):
-                out[members[0]:members[0] + n] = rgb
-            else:
-                out[torch.tensor(members, device=device)] = rgb
     return out
 
 

@@ -565,16 +565,27 @@ int emo_gif_lzw_emit(const uint16_t* codes, const int32_t* n_codes, const int64_
 
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
- * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, three components at 2x2 / 1x1 / 1x1 in one interleaved
- * scan; the host half (marker segments of Annex B, the removal of the stuffed 0x00 bytes, the decoding tables of Annex C / F.2.2.3,
- * the AVI container) is emote_hack_amd/video_io.py.  The three kernels give the bytes libjpeg's default decoder gives (jidctint.c
- * islow, jdsample.c h2v2 fancy up-sampling, jdcolor.c); they live in csrc/video_in.hip.
+ * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, one scan; the host half (marker segments of Annex B, the
+ * removal of the stuffed 0x00 bytes, the decoding tables of Annex C / F.2.2.3, the AVI container) is emote_hack_amd/video_io.py.  The
+ * kernels give the bytes libjpeg's default decoder gives (jidctint.c islow, jdsample.c fancy up-sampling, jdcolor.c); they live in
+ * csrc/video_in.hip.
+ * Every entry takes the scan's LAYOUT as three small ints: ncomp, the number of components, and hs x vs, the sampling factors of the
+ * first (luminance) component; chrominance is always 1 x 1 (T.81 A.1.1).  An MCU of an interleaved scan holds hs * vs luminance blocks,
+ * row by row, then one Cb and one Cr block (T.81 A.2.3); a one-component scan is not interleaved and its MCU is one block, whatever
+ * factors the frame header states (T.81 A.2.2):
+ *     ncomp hs vs   MCU       blocks per MCU (bpm)           chroma step, colour (libjpeg)
+ *     3     2  2    16 x 16   6: Y00 Y01 Y10 Y11 Cb Cr      jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert
+ *     3     2  1    16 x 8    4: Y0 Y1 Cb Cr                jdsample.c h2v1_fancy_upsample, ycc_rgb_convert
+ *     3     1  1    8 x 8     3: Y Cb Cr                    jdsample.c fullsize_upsample (chroma as it is), ycc_rgb_convert
+ *     1     1  1    8 x 8     1                             jdcolor.c gray_rgb_convert: R = G = B = the sample
+ *   Anything else (4:4:0, 4:1:1, four components) is EMO_ERR_BAD_SHAPE.  mcu_cols = ceil(W / (8 hs)), mcu_rows = ceil(H / (8 vs)),
+ *   n_mcu their product; H, W in 1 .. 65535 as in emo_jpeg_blocks; n * n_mcu * bpm < 2^31.
  * emo_jpeg_decode_bits (T.81 F.2.2 Huffman decoding procedures: F.2.2.1 DC, F.2.2.2 AC, F.2.2.3 DECODE, F.2.2.4 RECEIVE, figure F.12
- *   EXTEND): the UNSTUFFED scans of n frames lie in `scan` (scan_bytes bytes, a multiple of 4, 4-byte aligned; bytes behind the last
- *   frame are never used), frame i in bytes offsets[i] .. offsets[i + 1] (int64 [n + 1]).  Output: coefs int16 [n][n_mcu][6][64] in the
- *   layout emo_jpeg_blocks writes (16x16 MCUs in raster order, blocks Y00 Y01 Y10 Y11 Cb Cr, zig-zag order, the DC term UNDIFFERENCED:
- *   the differences are summed per component from 0 at every frame's first MCU), 16-byte aligned, and status int32 [n]:
- *     EMO_JPEG_OK        the frame decoded: n_mcu * 6 blocks inside its bytes (what is left of them - the 1-bits that fill the last
+ *   EXTEND; A.2.3 the order of blocks in an MCU): the UNSTUFFED scans of n frames lie in `scan` (scan_bytes bytes, a multiple of 4,
+ *   4-byte aligned; bytes behind the last frame are never used), frame i in bytes offsets[i] .. offsets[i + 1] (int64 [n + 1]).
+ *   Output: coefs int16 [n][n_mcu][bpm][64] (MCUs in raster order, zig-zag order, the DC term UNDIFFERENCED: the differences are summed
+ *   per component from 0 at every frame's first MCU; at 4:2:0 the layout emo_jpeg_blocks writes), 16-byte aligned, and status int32 [n]:
+ *     EMO_JPEG_OK        the frame decoded: n_mcu * bpm blocks inside its bytes (what is left of them - the 1-bits that fill the last
  *                        byte, anything else - is not looked at)
  *     EMO_JPEG_BAD_CODE  the next 16 bits start with no code of the table, or with the code of a symbol a baseline scan of 8-bit samples
  *                        cannot hold: a DC category above 11, an AC category above 10, a run with category 0 other than EOB / ZRL
@@ -582,20 +593,22 @@ int emo_gif_lzw_emit(const uint16_t* codes, const int32_t* n_codes, const int64_
  *                        backwards or leave the buffer are taken as an empty frame)
  *     EMO_JPEG_BAD_RUN   a zero run carries the position past coefficient 63
  *   A frame with an error stops there: its blocks up to the faulty one are written, the rest of ITS coefficients are zeroed, other
- *   frames are not touched.  One workgroup per frame; every loop is counted by n_mcu * 6 blocks and 64 coefficients, every read of the
- *   stream is masked to the frame's own bytes.
- *   tables: device int32 [4][EMO_JPEG_DECODE_TABLE_INTS] in the order DC luma, AC luma, DC chroma, AC chroma (Cb and Cr share theirs),
- *   each table = MINCODE[16] | MAXCODE[16] | VALPTR[16] | 16 unused | HUFFVAL[256] of T.81 F.2.2.3 / figure F.15, entry l - 1 for code
+ *   frames are not touched.  One workgroup per frame; every loop is counted by n_mcu * bpm blocks and 64 coefficients, every read of
+ *   the stream is masked to the frame's own bytes.
+ *   Block k % bpm of an MCU belongs to component 0 for k < bpm - 2 (all of them when bpm is 1), then to Cb, then to Cr; the component
+ *   selects the DC prediction and the table pair.  tables: device int32 [4][EMO_JPEG_DECODE_TABLE_INTS] in the order DC luma, AC luma,
+ *   DC chroma, AC chroma - [0], [1] for component 0, [2], [3] for Cb and Cr, which share theirs (a grey scan never reads those) - each
+ *   table = MINCODE[16] | MAXCODE[16] | VALPTR[16] | 16 unused | HUFFVAL[256] of T.81 F.2.2.3 / figure F.15, entry l - 1 for code
  *   length l, MAXCODE -1 where no code has that length.  (The kernel expands them into an 8-bit look-up in LDS.)
  * emo_jpeg_decode_segments (T.81 B.2.4.4 DRI, E.1.4 restart intervals, F.1.1.5.1 / F.2.1.3.1 the DC predictions return to 0 at every
  *   restart; the decoding procedures of F.2.2 as above): the same decoding, one wavefront per SEGMENT.  A segment is a run of whole MCUs
  *   that starts on a byte with DC predictions 0: one restart interval (the bytes between two RSTm markers, the markers themselves and
  *   the stuffed 0x00 bytes taken out by the host), or a whole frame that has no restart markers.  Segment s lies in bytes
  *   seg_offsets[s] .. seg_offsets[s + 1] of `scan` (int64 [n_seg + 1], 8-byte aligned; scan as above) and fills seg_blocks[s] blocks (a
- *   multiple of 6: whole MCUs) from block seg_first_block[s] on of coefs, blocks counted over the whole buffer of coef_blocks blocks of
- *   64 int16 - for interval k of frame f with restart interval Ri: (f * n_mcu + k * Ri) * 6 and (min((k + 1) * Ri, n_mcu) - k * Ri) * 6,
- *   so the buffer is the [n][n_mcu][6][64] emo_jpeg_decode_bits fills and emo_jpeg_idct reads.  Frames with different Ri, and frames
- *   without markers, may share a launch.  Blocks no segment names are not written.  status int32 [n_seg], PER SEGMENT, the values
+ *   multiple of bpm: whole MCUs) from block seg_first_block[s] on of coefs, blocks counted over the whole buffer of coef_blocks blocks
+ *   of 64 int16 - for interval k of frame f with restart interval Ri: (f * n_mcu + k * Ri) * bpm and (min((k + 1) * Ri, n_mcu) - k * Ri)
+ *   * bpm, so the buffer is the [n][n_mcu][bpm][64] emo_jpeg_decode_bits fills and emo_jpeg_idct reads.  Frames with different Ri, and
+ *   frames without markers, may share a launch.  Blocks no segment names are not written.  status int32 [n_seg], PER SEGMENT, the values
  *   above with "segment" for "frame"; a segment with an error stops there, its blocks from the faulty one on are zeroed, other segments
  *   are not touched.  seg_first_block and seg_blocks are clamped to coef_blocks (a segment that reaches past the buffer decodes the
  *   blocks that fit and reports on those), seg_offsets to 0 .. scan_bytes and to run forwards: a bad table decodes wrong data or reports
@@ -603,75 +616,42 @@ int emo_gif_lzw_emit(const uint16_t* codes, const int32_t* n_codes, const int64_
  *   the set-up of the shared tables the waves of a workgroup meet no common barrier.
  * emo_jpeg_idct (T.81 A.3.4 dequantisation, A.3.3 IDCT in libjpeg's integer form jidctint.c jpeg_idct_islow): coefficient * quantiser,
  *   an 8-point pass over columns descaled by 11 bits, the same pass over rows descaled by 18, sample = clamp(value + 128, 0, 255).
- *   quant: device uint16 [2][64], luma then chroma, NATURAL order.  Output: y_plane uint8 [n][mcu_rows * 16][mcu_cols * 16] and c_planes
- *   uint8 [n][2][mcu_rows * 8][mcu_cols * 8] (Cb, Cr), mcu_rows = ceil(H / 16), mcu_cols = ceil(W / 16), both 8-byte aligned.  32-bit
- *   sums that coefficients of no 8-bit image reach wrap.
- * emo_jpeg_upsample_rgb (jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert): the planes above -> packed uint8 RGB
- *   [n][H][W][3], 4-byte aligned.  Chroma: the plane of ceil(H / 2) x ceil(W / 2) real samples (the padded samples behind it are not
+ *   quant: device uint16 [3][64], one quantiser PER COMPONENT, NATURAL order (a grey frame reads the first only; its caller passes the
+ *   one table three times).  Output, planes padded to whole MCUs: y_plane uint8 [n][mcu_rows * 8 vs][mcu_cols * 8 hs] and c_planes
+ *   uint8 [n][2][mcu_rows * 8][mcu_cols * 8] (Cb, Cr; not touched and may be NULL when ncomp is 1), both 8-byte aligned.  32-bit sums
+ *   that coefficients of no 8-bit image reach wrap.
+ * emo_jpeg_rgb (jdsample.c, jdcolor.c): the planes above -> packed uint8 RGB [n][H][W][3], 4-byte aligned.
+ *   4:2:0 (h2v2_fancy_upsample): the chroma plane of ceil(H / 2) x ceil(W / 2) real samples (the padded samples behind it are not
  *   read), s = 3 * c(r) + c(r -+ 1) down the rows for output rows 2 r / 2 r + 1, o(2 x) = (3 s(x) + s(x - 1) + 8) >> 4 and o(2 x + 1) =
- *   (3 s(x) + s(x + 1) + 7) >> 4 along them, neighbours clamped to the plane.  Colour, cb and cr less 128: R = y + ((91881 cr + 32768)
- *   >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  (libjpeg
- *   replicates samples instead when the chroma plane is at most 2 wide, W <= 4: the host refuses such frames.)
- * H, W in 1 .. 65535 as in emo_jpeg_blocks.
- *
- * The emo_jpeg_layout_* entries do the same for the four common baseline layouts.  A layout is three small ints: ncomp, the number of
- * components, and hs x vs, the sampling factors of the first (luminance) component; chrominance is always 1 x 1 (T.81 A.1.1).  An MCU of
- * an interleaved scan holds hs * vs luminance blocks, row by row, then one Cb and one Cr block (T.81 A.2.3); a one-component scan is not
- * interleaved and its MCU is one block, whatever factors the frame header states (T.81 A.2.2):
- *     ncomp hs vs   MCU       blocks per MCU (bpm)           chroma step, colour (libjpeg)
- *     3     2  2    16 x 16   6: Y00 Y01 Y10 Y11 Cb Cr      jdsample.c h2v2_fancy_upsample, jdcolor.c ycc_rgb_convert (as emo_jpeg_upsample_rgb)
- *     3     2  1    16 x 8    4: Y0 Y1 Cb Cr                jdsample.c h2v1_fancy_upsample, ycc_rgb_convert
- *     3     1  1    8 x 8     3: Y Cb Cr                    jdsample.c fullsize_upsample (chroma as it is), ycc_rgb_convert
- *     1     1  1    8 x 8     1                             jdcolor.c gray_rgb_convert: R = G = B = the sample
- *   Anything else (4:4:0, 4:1:1, four components) is EMO_ERR_BAD_SHAPE.  mcu_cols = ceil(W / (8 hs)), mcu_rows = ceil(H / (8 vs)),
- *   n_mcu their product.
- * emo_jpeg_layout_decode_bits / emo_jpeg_layout_decode_segments (T.81 F.2.2, A.2.3 the order of blocks in an MCU, E.1.4): as
- *   emo_jpeg_decode_bits / emo_jpeg_decode_segments with bpm for 6.  Block k % bpm of an MCU belongs to component 0 for k < bpm - 2 (all
- *   of them when bpm is 1), then to Cb, then to Cr; the component selects the DC prediction and the table pair - tables [0], [1] for
- *   component 0, [2], [3] for Cb and Cr (a grey scan never reads those).  coefs int16 [n][n_mcu][bpm][64], zig-zag order, DC
- *   undifferenced; the segment table stays in blocks (seg_blocks a multiple of bpm).  Status values, clamping and "a frame (segment) that
- *   ended early has its remaining coefficients zeroed" as above; n * n_mcu * bpm < 2^31.
- * emo_jpeg_layout_idct (T.81 A.3.4, jidctint.c jpeg_idct_islow): as emo_jpeg_idct, with one quantiser PER COMPONENT, quant uint16
- *   [3][64] in natural order (a grey frame reads the first only), into planes padded to whole MCUs: y_plane uint8
- *   [n][mcu_rows * 8 vs][mcu_cols * 8 hs], c_planes uint8 [n][2][mcu_rows * 8][mcu_cols * 8] (Cb, Cr; not touched and may be NULL when
- *   ncomp is 1), both 8-byte aligned.
- * emo_jpeg_layout_rgb: those planes -> packed uint8 RGB [n][H][W][3], 4-byte aligned.  4:2:0 as emo_jpeg_upsample_rgb.  4:2:2
- *   (h2v1_fancy_upsample): no filter down the columns; along a row of cw = ceil(W / 2) real chroma samples, p the sample at column
- *   x >> 1, o(x) = (3 p + p(left) + 1) >> 2 for even x and (3 p + p(right) + 2) >> 2 for odd x, the neighbour clamped to 0 .. cw - 1 -
- *   which is libjpeg's special case for the first and the last column; the padded samples behind cw are not read.  (As above, libjpeg
- *   replicates instead when cw <= 2, W <= 4: the host refuses such frames at 4:2:2 and 4:2:0.)  4:4:4 (fullsize_upsample): the chroma
- *   sample of the pixel itself.  Then ycc_rgb_convert's fixed-point transform as above.  Grey (gray_rgb_convert): the sample in all
- *   three channels, no transform; c_planes is not read and may be NULL.  Any W from 1 at 4:4:4 and grey. */
+ *   (3 s(x) + s(x + 1) + 7) >> 4 along them, neighbours clamped to the plane.  4:2:2 (h2v1_fancy_upsample): no filter down the columns;
+ *   along a row of cw = ceil(W / 2) real chroma samples, p the sample at column x >> 1, o(x) = (3 p + p(left) + 1) >> 2 for even x and
+ *   (3 p + p(right) + 2) >> 2 for odd x, the neighbour clamped to 0 .. cw - 1 - which is libjpeg's special case for the first and the
+ *   last column; the padded samples behind cw are not read.  (libjpeg replicates samples instead when the chroma plane is at most 2
+ *   wide, W <= 4: the host refuses such frames at 4:2:2 and 4:2:0.)  4:4:4 (fullsize_upsample): the chroma sample of the pixel itself.
+ *   Colour (ycc_rgb_convert), cb and cr less 128: R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *   B = y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255.  Grey (gray_rgb_convert): the sample in all three channels, no
+ *   transform; c_planes is not read and may be NULL.  Any W from 1 at 4:4:4 and grey. */
 #define EMO_JPEG_DECODE_TABLE_INTS 320
 enum { EMO_JPEG_OK = 0, EMO_JPEG_BAD_CODE = 1, EMO_JPEG_PAST_END = 2, EMO_JPEG_BAD_RUN = 3 };
 int emo_jpeg_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
-                         int32_t* status, int n, int n_mcu, void* stream);
+                         int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream);
 int emo_jpeg_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
                              const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks, int32_t* status,
-                             int n_seg, void* stream);
-int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, void* stream);
-int emo_jpeg_upsample_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, void* stream);
-int emo_jpeg_layout_decode_bits(const uint8_t* scan, int64_t scan_bytes, const int64_t* offsets, const int32_t* tables, int16_t* coefs,
-                                int32_t* status, int n, int n_mcu, int ncomp, int hs, int vs, void* stream);
-int emo_jpeg_layout_decode_segments(const uint8_t* scan, int64_t scan_bytes, const int64_t* seg_offsets, const int32_t* seg_first_block,
-                                    const int32_t* seg_blocks, const int32_t* tables, int16_t* coefs, int64_t coef_blocks, int32_t* status,
-                                    int n_seg, int ncomp, int hs, int vs, void* stream);
-int emo_jpeg_layout_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, int ncomp,
-                         int hs, int vs, void* stream);
-int emo_jpeg_layout_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs,
-                        void* stream);
+                             int n_seg, int ncomp, int hs, int vs, void* stream);
+int emo_jpeg_idct(const int16_t* coefs, const uint16_t* quant, uint8_t* y_plane, uint8_t* c_planes, int n, int H, int W, int ncomp, int hs,
+                  int vs, void* stream);
+int emo_jpeg_rgb(const uint8_t* y_plane, const uint8_t* c_planes, uint8_t* rgb, int n, int H, int W, int ncomp, int hs, int vs, void* stream);
 
 /* ---- Progressive JPEG input (T.81 Annex G, SOF2, Huffman coding): the entropy decoder behind decode_mjpeg(progressive=True);
  * csrc/video_in_progressive.hip.  A progressive file codes its coefficients in several scans - spectral selection (a scan holds the
  * band Ss .. Se of the zig-zag sequence) and successive approximation (a scan holds the bits down to Al, a later one refines by one
  * bit) - and the host (emote_hack_amd/video_io.py parse_jpeg(progressive=True)) walks them, keeps the tables and the restart interval
  * each scan saw, and takes only COMPLETE progressions, which libjpeg decodes without inter-block smoothing (jdcoefct.c smoothing_ok):
- * the coefficients are then those of the baseline file, and emo_jpeg_layout_idct / emo_jpeg_layout_rgb (emo_jpeg_idct /
- * emo_jpeg_upsample_rgb) give libjpeg's bytes from them.
+ * the coefficients are then those of the baseline file, and emo_jpeg_idct / emo_jpeg_rgb give libjpeg's bytes from them.
  * emo_jpeg_progressive_scan (T.81 G.1.1.1.1 the scans of a progression, G.1.2 / G.2 the Huffman procedures, A.2.2 / A.2.3 the order of
  *   the units, E.1.4 restart intervals; jdphuff.c decode_mcu_DC_first, decode_mcu_DC_refine, decode_mcu_AC_first, decode_mcu_AC_refine):
- *   ONE scan of a progression for many frames at once, into coefs int16 [n][n_mcu][bpm][64] (zig-zag order, the layout of the
- *   emo_jpeg_layout_* entries), which the caller zeroes before the first scan.  One wavefront per segment, a restart interval of the
+ *   ONE scan of a progression for many frames at once, into coefs int16 [n][n_mcu][bpm][64] (zig-zag order, the buffer
+ *   emo_jpeg_decode_bits fills), which the caller zeroes before the first scan.  One wavefront per segment, a restart interval of the
  *   scan in one frame or the frame's whole scan: segment s holds bytes seg_offsets[s] .. seg_offsets[s + 1] of scan (int64 [n_seg + 1];
  *   unstuffed, markers taken out, scan_bytes a multiple of 4), belongs to frame seg_frame[s] and codes seg_units[s] units from unit
  *   seg_first_unit[s] on (int32 [n_seg] each).  ncomp, hs, vs: the layout; H, W: the frame.  Ss, Se, Ah, Al: the scan header's; Ss = 0

@@ -138,7 +138,7 @@ def idct(coefs, quant, H, W):
     return y, c
 
 
-def upsample_rgb(y, c, H, W):
+def h2v2_rgb(y, c, H, W):
     """the planes -> (n, H, W, 3) uint8: h2v2 fancy up-sampling on the real chroma plane, then the fixed-point colour transform"""
     ch, cw = (H + 1) // 2, (W + 1) // 2
     p = np.asarray(c)[:, :, :ch, :cw].astype(np.int64)
@@ -178,7 +178,7 @@ def decode(data):
     H, W, quant, specs, scan = split_file(data)
     mr, mc = R.n_mcus(H, W)
     coefs = huffman_decode(scan, specs, mr * mc)[None]
-    return upsample_rgb(*idct(coefs, quant, H, W), H, W)[0]
+    return h2v2_rgb(*idct(coefs, quant, H, W), H, W)[0]
 
 
 def pillow_file(frame, quality, optimize):

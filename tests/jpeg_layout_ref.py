@@ -1,5 +1,5 @@
 """Test infrastructure, not product: a numpy restatement of the layout-aware kernels of emote_hack_amd/csrc/video_in.hip
-(emo_jpeg_layout_decode_bits / _decode_segments / _idct / _rgb) for 4:2:0, 4:2:2, 4:4:4 and grey baseline files, in the arithmetic
+(emo_jpeg_decode_bits / _decode_segments / _idct / _rgb) for 4:2:0, 4:2:2, 4:4:4 and grey baseline files, in the arithmetic
 include/emo_hip.h fixes for them, which is libjpeg's default decoder's.  It builds on tests/jpeg_decode_ref.py - the standard's serial
 Huffman decoder (code_tables, _Reader) and the jidctint.c butterfly (_idct_pass) - and has a marker walk of its own, so that nothing here
 is shared with emote_hack_amd.video_io.  tests/test_jpeg_layouts_host.py holds it to Pillow's decoder byte for byte; the GPU tests hold
@@ -43,12 +43,12 @@ def pillow_file(picture, name, quality, optimize, **kw):
     return buf.getvalue()
 
 
-def three_quantiser_file(picture, name="4:4:4", optimize=False):
+def three_quantiser_file(picture, name="4:4:4", optimize=False, **kw):
     """a file whose three components use three different quantisation tables (Pillow's qtables=)"""
     tabs = [[min(255, 2 + k + (i % 8) + (i // 8)) for i in range(64)] for k in (0, 5, 11)]
     from PIL import Image
     buf = io.BytesIO()
-    Image.fromarray(picture).save(buf, format="JPEG", qtables=tabs, subsampling=SUBSAMPLING[name], optimize=optimize)
+    Image.fromarray(picture).save(buf, format="JPEG", qtables=tabs, subsampling=SUBSAMPLING[name], optimize=optimize, **kw)
     return buf.getvalue()
 
 
@@ -168,7 +168,7 @@ def idct(coefs, quant, H, W, layout):
 
 
 def to_rgb(y, c, H, W, layout):
-    """the planes -> (n, H, W, 3) uint8.  4:2:0: h2v2 fancy up-sampling (D.upsample_rgb).  4:2:2: h2v1_fancy_upsample on the ceil(W / 2)
+    """the planes -> (n, H, W, 3) uint8.  4:2:0: h2v2 fancy up-sampling (D.h2v2_rgb).  4:2:2: h2v1_fancy_upsample on the ceil(W / 2)
     real chroma samples of a row - even columns (3 p + left + 1) >> 2, odd ones (3 p + right + 2) >> 2, neighbours clamped to the plane -
     and no filter down the columns.  4:4:4: chroma as it is.  Then jdcolor.c's fixed-point transform.  Grey: the sample three times."""
     nc, hs, vs = layout
@@ -176,7 +176,7 @@ def to_rgb(y, c, H, W, layout):
     if nc == 1:
         return np.repeat(lum[..., None], 3, -1).astype(np.uint8)
     if (hs, vs) == (2, 2):
-        return D.upsample_rgb(y, c, H, W)
+        return D.h2v2_rgb(y, c, H, W)
     if (hs, vs) == (2, 1):
         cw = (W + 1) // 2
         p = np.asarray(c)[:, :, :H, :cw].astype(np.int64)

@@ -3,7 +3,7 @@ and of parse_jpeg / decode_mjpeg(progressive=True).  Three parts, none of which 
   - pillow_progressive: Pillow's own writer, which gives libjpeg's default script (10 scans in colour, 6 in grey, spectral selection and
     successive approximation both);
   - split_progressive / decode_coefficients: a marker walk and a serial decoder written from T.81 G.1.2 (figures G.3 - G.7 read as
-    decoding procedures, G.2), into the coefficient buffer (n_mcu, bpm, 64) of the emo_jpeg_layout_* entries;
+    decoding procedures, G.2), into the coefficient buffer (n_mcu, bpm, 64) the emo_jpeg_idct entry reads;
   - write_progressive: a writer that codes such a buffer under a GIVEN script, with fixed canonical Huffman tables (size does not matter
     here), because Pillow cannot choose scripts.
 tests/test_jpeg_progressive_host.py holds the decoder (plus the IDCT and colour restatements of tests/jpeg_layout_ref.py) to Pillow byte

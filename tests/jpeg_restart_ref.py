@@ -87,7 +87,7 @@ def decode(data):
     H, W, quant, specs, ri, parts, _ = split_restart_file(data)
     mr, mc = R.n_mcus(H, W)
     coefs = decode_intervals(parts, specs, mr * mc, ri)[None]
-    return D.upsample_rgb(*D.idct(coefs, quant, H, W), H, W)[0]
+    return D.h2v2_rgb(*D.idct(coefs, quant, H, W), H, W)[0]
 
 
 def entropy_intervals(coefs, huff, ri):

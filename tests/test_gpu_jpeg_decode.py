@@ -1,4 +1,4 @@
-"""GPU tests of the Motion-JPEG reader: emo_jpeg_decode_bits / emo_jpeg_idct / emo_jpeg_upsample_rgb (csrc/video_in.hip) against the
+"""GPU tests of the Motion-JPEG reader: emo_jpeg_decode_bits / emo_jpeg_idct / emo_jpeg_rgb (csrc/video_in.hip) at 4:2:0 against the
 numpy restatement in tests/jpeg_decode_ref.py (which tests/test_jpeg_decode_host.py holds to Pillow's decoder byte for byte), decode_mjpeg
 and read_video against Pillow's decoder itself, and the pipeline taking its control frames and its source image from a clip.
 
@@ -164,26 +164,26 @@ def test_pixel_kernels_equal_the_restatement(n, H, W):
             coefs, _ = R.blocks(R.make_frames(content, n, H, W), t.quant)
             yb, y = poisoned((n, mr * 16, mc * 16), torch.uint8)
             cb, c = poisoned((n, 2, mr * 8, mc * 8), torch.uint8)
-            o.jpeg_idct(torch.from_numpy(np.ascontiguousarray(coefs)).to(DEV), torch.from_numpy(t.quant.copy()).to(DEV), H, W, out_y=y, out_c=c)
+            o.jpeg_idct(torch.from_numpy(np.ascontiguousarray(coefs)).to(DEV), torch.from_numpy(t.quant[[0, 1, 1]]).to(DEV), H, W, out_y=y, out_c=c)
             want_y, want_c = D.idct(coefs, t.quant, H, W)
             assert np.array_equal(y.cpu().numpy(), want_y) and np.array_equal(c.cpu().numpy(), want_c), (content, quality)
             fb, frames = poisoned((n, H, W, 3), torch.uint8)
-            o.jpeg_upsample_rgb(y, c, H, W, out=frames)
-            assert np.array_equal(frames.cpu().numpy(), D.upsample_rgb(want_y, want_c, H, W)), (content, quality)
+            o.jpeg_rgb(y, c, H, W, out=frames)
+            assert np.array_equal(frames.cpu().numpy(), D.h2v2_rgb(want_y, want_c, H, W)), (content, quality)
             assert intact((yb, y), (cb, c), (fb, frames))
     # planes of independent bytes: every filter tap and colour clamp at full range, and padded samples that must not be read
     rng = np.random.default_rng(H * W)
     y_host, c_host = rng.integers(0, 256, (n, mr * 16, mc * 16), dtype=np.uint8), rng.integers(0, 256, (n, 2, mr * 8, mc * 8), dtype=np.uint8)
-    got = o.jpeg_upsample_rgb(torch.from_numpy(y_host).to(DEV), torch.from_numpy(c_host).to(DEV), H, W).cpu().numpy()
-    assert np.array_equal(got, D.upsample_rgb(y_host, c_host, H, W))
+    got = o.jpeg_rgb(torch.from_numpy(y_host).to(DEV), torch.from_numpy(c_host).to(DEV), H, W).cpu().numpy()
+    assert np.array_equal(got, D.h2v2_rgb(y_host, c_host, H, W))
     ch, cw = (H + 1) // 2, (W + 1) // 2
     c_host[:, :, ch:], c_host[:, :, :, cw:] = 0, 0
-    again = o.jpeg_upsample_rgb(torch.from_numpy(y_host).to(DEV), torch.from_numpy(c_host).to(DEV), H, W).cpu().numpy()
+    again = o.jpeg_rgb(torch.from_numpy(y_host).to(DEV), torch.from_numpy(c_host).to(DEV), H, W).cpu().numpy()
     assert np.array_equal(again, got)
     # coefficients no encoder makes: some byte comes out, the same one the wrapping restatement gives
     wild = rng.integers(-32768, 32768, (n, mr * mc, 6, 64)).astype(np.int16)
     quant = np.full((2, 64), 255, np.uint16)
-    y, c = o.jpeg_idct(torch.from_numpy(wild).to(DEV), torch.from_numpy(quant).to(DEV), H, W)
+    y, c = o.jpeg_idct(torch.from_numpy(wild).to(DEV), torch.from_numpy(quant[[0, 1, 1]]).to(DEV), H, W)
     want_y, want_c = D.idct(wild, quant, H, W)
     assert np.array_equal(y.cpu().numpy(), want_y) and np.array_equal(c.cpu().numpy(), want_c)
 
@@ -200,8 +200,8 @@ def test_entry_point_refusals():
     lib = o._lib.load()
     z = torch.zeros(4096, device=DEV, dtype=torch.uint8)
     for H, W in ((8, 70000), (70000, 8), (0, 8)):                                # SOF0 holds 16 bits
-        assert lib.emo_jpeg_idct(o._ptr(z), o._ptr(z), o._ptr(z), o._ptr(z), 1, H, W, o._stream()) != 0
-        assert lib.emo_jpeg_upsample_rgb(o._ptr(z), o._ptr(z), o._ptr(z), 1, H, W, o._stream()) != 0
+        assert lib.emo_jpeg_idct(o._ptr(z), o._ptr(z), o._ptr(z), o._ptr(z), 1, H, W, 3, 2, 2, o._stream()) != 0
+        assert lib.emo_jpeg_rgb(o._ptr(z), o._ptr(z), o._ptr(z), 1, H, W, 3, 2, 2, o._stream()) != 0
     with pytest.raises(EmoHipError):
         V.decode_mjpeg([V.jpeg_header(16, 16, 90) + b"\xFF\xD9"], device="cpu")   # no host decoder
 

@@ -1,5 +1,5 @@
-"""GPU tests of the JPEG layouts: emo_jpeg_layout_decode_bits / _decode_segments / _idct / _rgb (csrc/video_in.hip) through their
-ops wrappers against the numpy restatement in tests/jpeg_layout_ref.py (which tests/test_jpeg_layouts_host.py holds to Pillow's decoder
+"""GPU tests of the JPEG layouts: emo_jpeg_decode_bits / _decode_segments / _idct / _rgb (csrc/video_in.hip) in every layout through
+their ops wrappers against the numpy restatement in tests/jpeg_layout_ref.py (which tests/test_jpeg_layouts_host.py holds to Pillow's decoder
 byte for byte), decode_mjpeg and read_image against Pillow's decoder itself - 4:4:4, 4:2:2, 4:2:0 and grey files, with and without
 restart intervals, mixed in one call - and the pipeline taking its source image from a still JPEG file on the device.
 
@@ -43,18 +43,18 @@ def packed_scans(parts):
 
 
 def decode_bits(o, parts, specs, n_mcu, layout):
-    """ops.jpeg_layout_decode_bits on one whole scan per frame, into poisoned buffers -> (coefficients, status) on the host"""
+    """ops.jpeg_decode_bits on one whole scan per frame, into poisoned buffers -> (coefficients, status) on the host"""
     scan, offsets = packed_scans(parts)
     cb, coefs = poisoned((len(parts), n_mcu, L.bpm(layout), 64), torch.int16)
     sb, status = poisoned((len(parts),), torch.int32)
-    o.jpeg_layout_decode_bits(scan, to_dev(offsets), device_decode_tables(specs), n_mcu, layout, out=coefs, status=status)
+    o.jpeg_decode_bits(scan, to_dev(offsets), device_decode_tables(specs), n_mcu, layout=layout, out=coefs, status=status)
     torch.cuda.synchronize()
     assert intact((cb, coefs), (sb, status))
     return coefs.cpu().numpy(), status.cpu().numpy()
 
 
 def decode_segments(o, frames, specs, n_mcu, layout):
-    """ops.jpeg_layout_decode_segments on frames = [(ri, parts)], into poisoned buffers -> (coefficients, status per segment)"""
+    """ops.jpeg_decode_segments on frames = [(ri, parts)], into poisoned buffers -> (coefficients, status per segment)"""
     b, parts, first, blocks = L.bpm(layout), [], [], []
     for f, (ri, fparts) in enumerate(frames):
         spans = [(m0, min(m0 + (ri or n_mcu), n_mcu)) for m0 in range(0, n_mcu, ri or n_mcu)]
@@ -65,8 +65,8 @@ def decode_segments(o, frames, specs, n_mcu, layout):
     scan, offsets = packed_scans(parts)
     cb, coefs = poisoned((len(frames), n_mcu, b, 64), torch.int16)
     sb, status = poisoned((len(parts),), torch.int32)
-    o.jpeg_layout_decode_segments(scan, to_dev(offsets), to_dev(first, np.int32), to_dev(blocks, np.int32), device_decode_tables(specs),
-                                  len(frames), n_mcu, layout, out=coefs, status=status)
+    o.jpeg_decode_segments(scan, to_dev(offsets), to_dev(first, np.int32), to_dev(blocks, np.int32), device_decode_tables(specs),
+                           len(frames), n_mcu, layout=layout, out=coefs, status=status)
     torch.cuda.synchronize()
     assert intact((cb, coefs), (sb, status))
     return coefs.cpu().numpy(), status.cpu().numpy()
@@ -78,7 +78,7 @@ def test_kernels_equal_the_restatement(name, H, W):
     o, layout = ops(), L.LAYOUTS[name]
     mr, mc = L.grid(H, W, layout)
     n_mcu, (nc, hs, vs) = mr * mc, layout
-    assert o.jpeg_layout_grid(H, W, layout) == (mr, mc) and o.jpeg_layout_bpm(layout) == L.bpm(layout)
+    assert o.jpeg_grid(H, W, layout) == (mr, mc) and o.jpeg_bpm(layout) == L.bpm(layout)
     for quality in L.QUALITIES:
         for optimize in (False, True):
             _, (f, want, want_y, want_c, want_rgb) = case(name, H, W, quality, optimize)
@@ -90,12 +90,12 @@ def test_kernels_equal_the_restatement(name, H, W):
             # the planes
             yb, y = poisoned((1, mr * 8 * vs, mc * 8 * hs), torch.uint8)
             cb, c = poisoned((1, 2, mr * 8, mc * 8), torch.uint8) if nc == 3 else (None, None)
-            o.jpeg_layout_idct(to_dev(want[None]), to_dev(f["quant"], np.uint16), H, W, layout, out_y=y, out_c=c)
+            o.jpeg_idct(to_dev(want[None]), to_dev(f["quant"], np.uint16), H, W, layout=layout, out_y=y, out_c=c)
             assert np.array_equal(y.cpu().numpy()[0], want_y), (quality, optimize)
             assert nc == 1 or np.array_equal(c.cpu().numpy()[0], want_c), (quality, optimize)
             # the pixels
             fb, frames = poisoned((1, H, W, 3), torch.uint8)
-            o.jpeg_layout_rgb(y, c, H, W, layout, out=frames)
+            o.jpeg_rgb(y, c, H, W, layout=layout, out=frames)
             assert np.array_equal(frames.cpu().numpy()[0], want_rgb), (quality, optimize)
             assert intact((yb, y), (fb, frames)) and (nc == 1 or intact((cb, c)))
 
@@ -123,14 +123,14 @@ def test_pixel_kernels_on_planes_of_independent_bytes(name):
     y_host = rng.integers(0, 256, (n, mr * 8 * vs, mc * 8 * hs), dtype=np.uint8)
     c_host = rng.integers(0, 256, (n, 2, mr * 8, mc * 8), dtype=np.uint8) if nc == 3 else None
     dev_c = lambda: to_dev(c_host) if nc == 3 else None
-    got = o.jpeg_layout_rgb(to_dev(y_host), dev_c(), H, W, layout).cpu().numpy()
+    got = o.jpeg_rgb(to_dev(y_host), dev_c(), H, W, layout=layout).cpu().numpy()
     assert np.array_equal(got, L.to_rgb(y_host, c_host, H, W, layout))
     if nc == 3:
         c_host[:, :, -(-H // vs):], c_host[:, :, :, -(-W // hs):] = 0, 0         # behind the real chroma samples
-        assert np.array_equal(o.jpeg_layout_rgb(to_dev(y_host), dev_c(), H, W, layout).cpu().numpy(), got)
+        assert np.array_equal(o.jpeg_rgb(to_dev(y_host), dev_c(), H, W, layout=layout).cpu().numpy(), got)
     wild = rng.integers(-32768, 32768, (n, mr * mc, L.bpm(layout), 64)).astype(np.int16)
     quant = np.stack([np.full(64, v, np.uint16) for v in (255, 254, 253)])
-    y, c = o.jpeg_layout_idct(to_dev(wild), to_dev(quant), H, W, layout)
+    y, c = o.jpeg_idct(to_dev(wild), to_dev(quant), H, W, layout=layout)
     want_y, want_c = L.idct(wild, quant, H, W, layout)
     assert np.array_equal(y.cpu().numpy(), want_y) and (nc == 1 or np.array_equal(c.cpu().numpy(), want_c))
 
@@ -141,15 +141,15 @@ def test_layout_entries_refuse_what_is_not_built():
     z = torch.zeros(4096, device=DEV, dtype=torch.uint8)
     p = o._ptr(z)
     for nc, hs, vs in ((3, 1, 2), (3, 4, 1), (4, 1, 1), (1, 2, 2), (2, 1, 1)):   # 4:4:0, 4:1:1, four components, ...
-        assert lib.emo_jpeg_layout_decode_bits(p, 4096, p, p, p, p, 1, 1, nc, hs, vs, o._stream()) != 0
-        assert lib.emo_jpeg_layout_decode_segments(p, 4096, p, p, p, p, p, 1, p, 1, nc, hs, vs, o._stream()) != 0
-        assert lib.emo_jpeg_layout_idct(p, p, p, p, 1, 8, 8, nc, hs, vs, o._stream()) != 0
-        assert lib.emo_jpeg_layout_rgb(p, p, p, 1, 8, 8, nc, hs, vs, o._stream()) != 0
+        assert lib.emo_jpeg_decode_bits(p, 4096, p, p, p, p, 1, 1, nc, hs, vs, o._stream()) != 0
+        assert lib.emo_jpeg_decode_segments(p, 4096, p, p, p, p, p, 1, p, 1, nc, hs, vs, o._stream()) != 0
+        assert lib.emo_jpeg_idct(p, p, p, p, 1, 8, 8, nc, hs, vs, o._stream()) != 0
+        assert lib.emo_jpeg_rgb(p, p, p, 1, 8, 8, nc, hs, vs, o._stream()) != 0
     for H, W in ((8, 70000), (0, 8)):                                            # SOF0 holds 16 bits
-        assert lib.emo_jpeg_layout_idct(p, p, p, p, 1, H, W, 3, 2, 1, o._stream()) != 0
-        assert lib.emo_jpeg_layout_rgb(p, p, p, 1, H, W, 3, 2, 1, o._stream()) != 0
+        assert lib.emo_jpeg_idct(p, p, p, p, 1, H, W, 3, 2, 1, o._stream()) != 0
+        assert lib.emo_jpeg_rgb(p, p, p, 1, H, W, 3, 2, 1, o._stream()) != 0
     with pytest.raises(AssertionError):
-        o.jpeg_layout_bpm((3, 1, 2))
+        o.jpeg_bpm((3, 1, 2))
 
 
 # ------------------------------------------------------------------------------------------------------------------- truncated scans
@@ -222,6 +222,25 @@ def test_decode_mjpeg_with_three_quantisers():
         for optimize in (False, True):
             data = L.three_quantiser_file(pic, name, optimize)
             assert np.array_equal(V.decode_mjpeg([data]).cpu().numpy()[0], L.pillow_decode(data)), (name, optimize)
+
+
+def test_decode_mjpeg_420_with_one_and_with_two_chrominance_quantisers():
+    """4:2:0 with Cb and Cr on one quantiser had entries of its own once; it and 4:2:0 with three quantisers now share them.  Two groups
+    of 2 x 24 x 40 frames (one and a half MCU rows, two and a half MCU columns: the padded edge and the chroma clamp) in one call, un-cut
+    (emo_jpeg_decode_bits; consecutive members, a slice copy) and cut every 2 MCUs (emo_jpeg_decode_segments; alternating members, an
+    index scatter), against the restatement byte for byte"""
+    H, W = 24, 40
+    pics = [D.picture(H, W, seed) for seed in (3, 4)]
+    for kw, order in ((dict(), (0, 1, 2, 3)), (dict(restart_marker_blocks=2), (0, 2, 1, 3))):
+        files = [L.pillow_file(p, "4:2:0", 90, False, **kw) for p in pics] + [L.three_quantiser_file(p, "4:2:0", False, **kw) for p in pics]
+        files = [files[i] for i in order]
+        parsed = [V.parse_jpeg(d, restart=True, layouts=True) for d in files]
+        assert all(p.layout.key == (3, 2, 2) and (p.height, p.width, p.mcus) == (H, W, 6) and p.restart == (2 if kw else 0) for p in parsed)
+        equal = [np.array_equal(p.quants[1], p.quants[2]) for p in parsed]
+        assert equal == [i < 2 for i in order] and len({p.table_key() for p in parsed}) == 2
+        got = V.decode_mjpeg(files)
+        assert tuple(got.shape) == (4, H, W, 3)
+        assert np.array_equal(got.cpu().numpy(), np.stack([L.decode(d) for d in files])), kw
 
 
 # ------------------------------------------------------------------------------------------------------------------- still images

@@ -1,6 +1,6 @@
 """CPU tests of the Motion-JPEG reader's host half and of the restatement the GPU tests lean on.
 
-tests/jpeg_decode_ref.py restates emo_jpeg_decode_bits / emo_jpeg_idct / emo_jpeg_upsample_rgb in numpy (the standard's serial Huffman
+tests/jpeg_decode_ref.py restates emo_jpeg_decode_bits / emo_jpeg_idct / emo_jpeg_rgb in numpy (the standard's serial Huffman
 decoder, libjpeg's integer IDCT, its triangle chroma filter and fixed-point colour transform).  Every step is integer arithmetic, so it is
 held to Pillow's decoder (libjpeg-turbo, default settings) by EQUALITY: on files framed from known coefficients and on Pillow's own files,
 with the standard Huffman tables and with optimised ones.  emote_hack_amd.video_io.parse_jpeg is then checked against jpeg_header /
@@ -121,6 +121,27 @@ def test_parse_jpeg_on_a_scan_of_ff_bytes():
     assert np.array_equal(V.parse_jpeg(data).scan, stream)
     assert np.array_equal(V.parse_jpeg(data[:-2]).scan, stream)                  # a file that lost its EOI
     assert len(V.parse_jpeg(V.jpeg_header(16, 16, 90) + b"\xFF\xD9").scan) == 0
+
+
+def test_parse_jpeg_on_a_baseline_file_without_its_eoi():
+    """a baseline scan that runs to the end of the data, no marker behind it, parses to the scan bytes of the whole file - with and
+    without restart intervals - while a progressive scan cut like that stays refused"""
+    from PIL import Image
+    pic = D.picture(24, 40, 6)
+    for kw in (dict(), dict(restart_marker_blocks=2)):
+        buf = io.BytesIO()
+        Image.fromarray(pic).save(buf, format="JPEG", quality=90, subsampling=2, **kw)
+        data = buf.getvalue()
+        assert data.endswith(b"\xFF\xD9")
+        whole, cut = (V.parse_jpeg(d, restart=True) for d in (data, data[:-2]))
+        assert len(whole.scan) > 0 and np.array_equal(cut.scan, whole.scan) and np.array_equal(cut.intervals, whole.intervals)
+        assert cut.restart == whole.restart == (2 if kw else 0) and len(cut.intervals) - 1 == (3 if kw else 1)
+    buf = io.BytesIO()
+    Image.fromarray(pic).save(buf, format="JPEG", quality=90, progressive=True)
+    data = buf.getvalue()
+    assert len(V.parse_jpeg(data, progressive=True).scans) > 1
+    with pytest.raises(ValueError, match="no marker"):
+        V.parse_jpeg(data[:-2], progressive=True)
 
 
 def test_parse_jpeg_fills_in_the_standard_tables_when_dht_is_absent():

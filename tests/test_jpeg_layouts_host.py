@@ -49,25 +49,26 @@ def test_parse_jpeg_returns_the_layout(name):
         assert p.layout.factors == (((hs, vs), (1, 1), (1, 1)) if nc == 3 else ((1, 1),))
         assert p.layout.blocks_per_mcu == L.bpm(L.LAYOUTS[name]) == {"4:4:4": 3, "4:2:2": 4, "4:2:0": 6, "grey": 1}[name]
         mr, mc = L.grid(H, W, L.LAYOUTS[name])
-        assert p.mcus == mr * mc == V.ops.jpeg_layout_mcus(H, W, p.layout.key) == {"4:4:4": 45, "4:2:2": 25, "4:2:0": 15, "grey": 45}[name]
+        assert p.mcus == mr * mc == V.ops.jpeg_mcus(H, W, p.layout.key) == {"4:4:4": 45, "4:2:2": 25, "4:2:0": 15, "grey": 45}[name]
         assert p.layout.quant == f["tq"] == ((0, 1, 1) if nc == 3 else (0,))
         assert p.layout.huffman == f["tables"] == (((0, 0), (1, 1), (1, 1)) if nc == 3 else ((0, 0),))
         assert p.quants.dtype == np.uint16 and np.array_equal(p.quants, f["quant"]) and np.array_equal(p.quant, f["quant"][:2])
         assert list(p.specs) == f["specs"] and np.array_equal(p.scan, f["parts"][0]) and p.restart == 0
-        assert p.classic == (name == "4:2:0")
-    assert V.ops.jpeg_mcus(H, W) == V.ops.jpeg_layout_mcus(H, W, (3, 2, 2))      # jpeg_mcus keeps its meaning
+        assert (p.layout.key == (3, 2, 2) and np.array_equal(p.quants[1], p.quants[2])) == (name == "4:2:0")
+    assert V.ops.jpeg_mcus(H, W) == V.ops.jpeg_mcus(H, W, (3, 2, 2)) == 15       # jpeg_mcus keeps its meaning: 4:2:0 unless told
 
 
 def test_parse_jpeg_on_three_quantisers_and_a_restart_file():
     pic = D.picture(17, 33, 3)
     data = L.three_quantiser_file(pic)
     p, f = V.parse_jpeg(data, layouts=True), L.split_file(data)
-    assert p.layout.name == "4:4:4" and p.layout.quant == (0, 1, 2) and np.array_equal(p.quants, f["quant"]) and not p.classic
+    assert p.layout.name == "4:4:4" and p.layout.quant == (0, 1, 2) and np.array_equal(p.quants, f["quant"]) and p.layout.key != (3, 2, 2)
     assert len({p.quants[k].tobytes() for k in range(3)}) == 3
     with pytest.raises(ValueError, match="Cb and Cr use different quantisation tables"):
         V.parse_jpeg(L.three_quantiser_file(pic, "4:2:0"))                       # without the keyword: as before
     p420 = V.parse_jpeg(L.three_quantiser_file(pic, "4:2:0"), layouts=True)
-    assert p420.layout.name == "4:2:0" and not p420.classic and p420.layout.quant == (0, 1, 2)
+    assert p420.layout.name == "4:2:0" and p420.layout.key == (3, 2, 2) and not np.array_equal(p420.quants[1], p420.quants[2])
+    assert p420.layout.quant == (0, 1, 2)
     # 33 x 17 at 4:2:2: MCUs of 16 x 8, 3 x 3 = 9 of them; a restart interval of 2 makes 5 intervals, the last of one MCU
     data = L.pillow_file(pic, "4:2:2", 90, False, restart_marker_blocks=2)
     p, f = V.parse_jpeg(data, restart=True, layouts=True), L.split_file(data)
@@ -153,4 +154,4 @@ def test_without_the_keyword_parse_jpeg_takes_what_it_took():
         with pytest.raises(ValueError, match=says):
             V.parse_jpeg(L.pillow_file(pic, name, 90, False))
     p = V.parse_jpeg(L.pillow_file(pic, "4:2:0", 90, False))
-    assert p.classic and p.layout.key == (3, 2, 2) and p.mcus == V.ops.jpeg_mcus(16, 24)
+    assert p.layout.key == (3, 2, 2) and np.array_equal(p.quants[1], p.quants[2]) and p.mcus == V.ops.jpeg_mcus(16, 24)

@@ -2,8 +2,8 @@
 MCU row, device path against what a user had before it (profiles/jpeg_layouts.md):
 
   new   emote_hack_amd.video_io.decode_mjpeg([file]): marker parsing and byte unstuffing on the host, ONE host-to-device copy, three
-        launches (emo_jpeg_decode_bits / emo_jpeg_decode_segments, emo_jpeg_idct, emo_jpeg_upsample_rgb for plain 4:2:0; their
-        emo_jpeg_layout_* counterparts for the rest), one read of the status; the frame ends on the device
+        launches (emo_jpeg_decode_bits / emo_jpeg_decode_segments, emo_jpeg_idct, emo_jpeg_rgb), one read of the status; the frame ends
+        on the device
   old   PIL.Image.open(...).convert("RGB") (libjpeg, one host thread), then the host-to-device copy of the uint8 frame
 
 on the same files, which Pillow writes from tools/bench/mjpeg.py's picture-like frame.  Host clock around work that ends in a device

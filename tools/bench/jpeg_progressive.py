@@ -1,7 +1,7 @@
 """Times the decoding of progressive JPEG files on the device (profiles/jpeg_progressive.md):
 
   progressive    Pillow's progressive file (libjpeg's default script: 10 scans at 4:2:0) through emo_jpeg_progressive_scan, one launch per
-                 scan, then emo_jpeg_idct and emo_jpeg_upsample_rgb - without restart markers (a scan of a frame is ONE lane's walk) and
+                 scan, then emo_jpeg_idct and emo_jpeg_rgb - without restart markers (a scan of a frame is ONE lane's walk) and
                  with restart_marker_rows=1 (one wavefront per row of units of every scan)
   baseline       Pillow's baseline file of the same picture through emo_jpeg_decode_bits / emo_jpeg_decode_segments and the same two
   pillow         PIL.Image.open(...).convert("RGB") of the progressive file (libjpeg, one host thread), host clock
@@ -75,7 +75,7 @@ def pillow_decode(data):
 def progressive_decode(files, dev):
     """(a function that decodes the progressive files on buffers uploaded once: zero, one launch per scan, IDCT, colour; the plan)"""
     parsed = [V.parse_jpeg(d, progressive=True) for d in files]
-    assert len({p.table_key() for p in parsed}) == 1 and parsed[0].classic
+    assert len({p.table_key() for p in parsed}) == 1 and parsed[0].layout.key == (3, 2, 2) and np.array_equal(parsed[0].quants[1], parsed[0].quants[2])
     plan = V._progressive_group_plan(parsed, list(range(len(parsed))), dev)
     H, W = parsed[0].height, parsed[0].width
 
@@ -83,7 +83,7 @@ def progressive_decode(files, dev):
         plan["coefs"].zero_()
         for _, launch in plan["launches"]:
             launch()
-        return ops.jpeg_upsample_rgb(*ops.jpeg_idct(plan["coefs"], plan["quant"], H, W), H, W)
+        return ops.jpeg_rgb(*ops.jpeg_idct(plan["coefs"], plan["quant"], H, W), H, W)
     return run, plan
 
 
@@ -96,7 +96,7 @@ def baseline_decode(files, dev):
     start = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     scan = torch.from_numpy(np.concatenate([p.scan for p in parsed] + [np.zeros(-int(sizes.sum()) % 4, np.uint8)])).to(dev)
     tables = torch.from_numpy(np.stack([V.huffman_decode_table(*s) for s in parsed[0].specs])).to(dev)
-    quant = torch.from_numpy(parsed[0].quant.copy()).to(dev)
+    quant = torch.from_numpy(parsed[0].quants.copy()).to(dev)
     assert all(p.specs == parsed[0].specs for p in parsed), "baseline files written without optimize= share the Annex K tables"
     if any(p.restart for p in parsed):
         off, first, blocks = [], [], []
@@ -111,7 +111,7 @@ def baseline_decode(files, dev):
     else:
         off = torch.from_numpy(start).to(dev)
         entropy = lambda: ops.jpeg_decode_bits(scan, off, tables, n_mcu)
-    return (lambda: ops.jpeg_upsample_rgb(*ops.jpeg_idct(entropy()[0], quant, H, W), H, W)), entropy
+    return (lambda: ops.jpeg_rgb(*ops.jpeg_idct(entropy()[0], quant, H, W), H, W)), entropy
 
 
 def main():

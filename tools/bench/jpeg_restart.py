@@ -1,7 +1,7 @@
 """Times the decoding of Motion-JPEG frames with and without restart intervals (profiles/jpeg_restart.md):
 
   by hand    a file without restart markers on the frame-serial path, called launch by launch: parse_jpeg, one copy, emo_jpeg_decode_bits
-             (one workgroup per frame, one lane walks the frame), emo_jpeg_idct, emo_jpeg_upsample_rgb, one status read
+             (one workgroup per frame, one lane walks the frame), emo_jpeg_idct, emo_jpeg_rgb, one status read
   plain      the same file through decode_mjpeg (the same launches: a clip without restart intervals keeps that path)
   row        encode_mjpeg(restart_interval="row") through decode_mjpeg: one wavefront per row of MCUs
   4          encode_mjpeg(restart_interval=4) through decode_mjpeg: one wavefront per 4 MCUs
@@ -37,7 +37,7 @@ def upload(parsed):
     offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)).to(DEV)
     scan = torch.from_numpy(np.concatenate([p.scan for p in parsed] + [np.zeros(-int(sizes.sum()) % 4, np.uint8)])).to(DEV)
     tables = torch.from_numpy(np.stack([V.huffman_decode_table(*s) for s in parsed[0].specs])).to(DEV)
-    return scan, offsets, tables, torch.from_numpy(parsed[0].quant.copy()).to(DEV)
+    return scan, offsets, tables, torch.from_numpy(parsed[0].quants.copy()).to(DEV)
 
 
 def decode_frame_serial(jpegs):
@@ -46,7 +46,7 @@ def decode_frame_serial(jpegs):
     H, W = parsed[0].height, parsed[0].width
     scan, offsets, tables, quant = upload(parsed)
     coefs, status = ops.jpeg_decode_bits(scan, offsets, tables, ops.jpeg_mcus(H, W))
-    rgb = ops.jpeg_upsample_rgb(*ops.jpeg_idct(coefs, quant, H, W), H, W)
+    rgb = ops.jpeg_rgb(*ops.jpeg_idct(coefs, quant, H, W), H, W)
     assert not status.cpu().numpy().any()
     return rgb
 

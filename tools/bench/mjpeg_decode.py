@@ -1,7 +1,7 @@
 """Times the decoding of a Motion-JPEG clip's frames, device path against what a user had before it (profiles/mjpeg_decode.md):
 
   new   emote_hack_amd.video_io.decode_mjpeg: marker parsing and byte unstuffing on the host, ONE host-to-device copy of the scans,
-        emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_upsample_rgb, one read of the frames' status; the frames end on the device
+        emo_jpeg_decode_bits, emo_jpeg_idct, emo_jpeg_rgb, one read of the frames' status; the frames end on the device
   old   PIL.Image.open(...).convert("RGB") per frame (libjpeg, one host thread), then the host-to-device copy of the uint8 frames
 
 on the same files: a clip of 512 x 512 frames (the size the pipeline is benchmarked at) encoded by encode_mjpeg, then one frame of it.
@@ -42,13 +42,13 @@ def kernel_split(jpegs, reps):
     scan = np.concatenate([p.scan for p in parsed] + [np.zeros(-int(sizes.sum()) % 4, np.uint8)])
     scan = torch.from_numpy(scan).to(DEV)
     tables = torch.from_numpy(np.stack([V.huffman_decode_table(*s) for s in parsed[0].specs])).to(DEV)
-    quant = torch.from_numpy(parsed[0].quant.copy()).to(DEV)
+    quant = torch.from_numpy(parsed[0].quants.copy()).to(DEV)
     n_mcu = ops.jpeg_mcus(H, W)
     coefs, _ = ops.jpeg_decode_bits(scan, offsets, tables, n_mcu)
     y, c = ops.jpeg_idct(coefs, quant, H, W)
     steps = {"emo_jpeg_decode_bits": lambda: ops.jpeg_decode_bits(scan, offsets, tables, n_mcu),
              "emo_jpeg_idct": lambda: ops.jpeg_idct(coefs, quant, H, W),
-             "emo_jpeg_upsample_rgb": lambda: ops.jpeg_upsample_rgb(y, c, H, W)}
+             "emo_jpeg_rgb": lambda: ops.jpeg_rgb(y, c, H, W)}
     out = {}
     for name, fn in steps.items():
         for _ in range(2):
