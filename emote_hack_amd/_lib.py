@@ -150,6 +150,11 @@ SIGNATURES = {
     "emo_gif_lzw_codes_per_strip": (_i64, [_i, _i, _i]),
     "emo_gif_lzw_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_gif_lzw_emit": (_i, [_p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "emo_png_filter": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "emo_png_tokens_per_strip": (_i64, [_i, _i, _i, _i]),
+    "emo_png_lz_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "emo_png_deflate_bits": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "emo_png_deflate_emit": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

@@ -960,6 +960,91 @@ def gif_lzw_emit(codes: torch.Tensor, n_codes: torch.Tensor, bit_offsets: torch.
     return out
 
 
+PNG_SYMBOLS = 320                                # slots 0 .. 285: literal / length symbols, 288 .. 317: distance symbols
+PNG_MAX_STRIP_BYTES = 65535
+PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+
+
+def _png_frames(frames):
+    _need_cuda(frames)
+    assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.is_contiguous(), (frames.dtype, frames.shape)
+    return tuple(int(s) for s in frames.shape)
+
+
+def png_filter(frames: torch.Tensor, filter: int = 5):
+    """packed uint8 frames (n, H, W, C), C in 1 | 3 | 4 -> (filtered uint8 (n, H, 1 + W * C): per scanline the filter type and the
+    filtered bytes, adler int32 (n, H, 2): the Adler-32 pair of every filtered row) (emo_png_filter).  filter 0 .. 4: None, Sub, Up,
+    Average, Paeth for all rows; 5: per row the type with the smallest sum of min(v, 256 - v)."""
+    n, H, W, C = _png_frames(frames)
+    filtered = torch.empty(n, H, 1 + W * C, device=frames.device, dtype=torch.uint8)
+    adler = torch.empty(n, H, 2, device=frames.device, dtype=torch.int32)
+    _launch("png_filter", 0.0, 2.0 * frames.numel(),
+            lambda: check(_lib.load().emo_png_filter(_ptr(frames), _ptr(filtered), _ptr(adler), n, H, W, C, int(filter), _stream()), "emo_png_filter"),
+            tag=f"{n}x{H}x{W}x{C}")
+    return filtered, adler
+
+
+def _png_strips(filtered, channels, strip_rows):
+    _need_cuda(filtered)
+    assert filtered.dtype == torch.uint8 and filtered.dim() == 3 and filtered.is_contiguous(), (filtered.dtype, filtered.shape)
+    n, H, R = (int(s) for s in filtered.shape)
+    assert isinstance(channels, int) and channels >= 1 and (R - 1) % channels == 0 and R > 1, (R, channels)
+    assert isinstance(strip_rows, int) and not isinstance(strip_rows, bool) and strip_rows >= 1, strip_rows
+    strip_rows = min(strip_rows, H)
+    return n, H, (R - 1) // channels, strip_rows, -(-H // strip_rows)
+
+
+def png_lz_count(filtered: torch.Tensor, channels: int, strip_rows: int):
+    """filtered scanlines uint8 (n, H, 1 + W * channels) -> (tokens int32 (n, strips, cap), n_tokens int32 (n, strips), hist int32
+    (n, 320)): every strip of strip_rows scanlines tokenised on its own by the greedy single-probe LZ77 of emo_png_lz_count; hist counts
+    the frame's literal / length and distance symbols and its one end-of-block."""
+    n, H, W, strip_rows, strips = _png_strips(filtered, channels, strip_rows)
+    cap = int(_lib.load().emo_png_tokens_per_strip(H, W, channels, strip_rows))
+    tokens = torch.empty(n, strips, cap, device=filtered.device, dtype=torch.int32)
+    n_tokens = torch.empty(n, strips, device=filtered.device, dtype=torch.int32)
+    hist = torch.zeros(n, PNG_SYMBOLS, device=filtered.device, dtype=torch.int32)
+    _launch("png_lz_count", 0.0, float(filtered.numel()),
+            lambda: check(_lib.load().emo_png_lz_count(_ptr(filtered), _ptr(tokens), _ptr(n_tokens), _ptr(hist), n, H, W, channels, strip_rows,
+                                                       _stream()), "emo_png_lz_count"), tag=f"{n}x{H}x{W}x{channels}/{strip_rows}")
+    return tokens, n_tokens, hist
+
+
+def _png_coded(tokens, n_tokens, codes, H, W, channels, strip_rows):
+    _need_cuda(tokens, n_tokens, codes)
+    n, strips, cap = (int(s) for s in tokens.shape)
+    assert tokens.dtype == torch.int32 and tokens.is_contiguous() and strip_rows >= 1 and strips == -(-H // min(strip_rows, H)) \
+        and cap == int(_lib.load().emo_png_tokens_per_strip(H, W, channels, strip_rows)), (tokens.dtype, tokens.shape, H, W, channels, strip_rows)
+    assert n_tokens.dtype == torch.int32 and tuple(n_tokens.shape) == (n, strips) and n_tokens.is_contiguous(), (n_tokens.dtype, n_tokens.shape)
+    assert codes.dtype == torch.int32 and tuple(codes.shape) == (n, PNG_SYMBOLS) and codes.is_contiguous(), (codes.dtype, codes.shape)
+    return n, strips
+
+
+def png_deflate_bits(tokens: torch.Tensor, n_tokens: torch.Tensor, codes: torch.Tensor, H: int, W: int, channels: int, strip_rows: int):
+    """-> int32 (n, strips): the bits of every strip's tokens under its frame's table, codes int32 (n, 320) of `length << 16 | the
+    bit-reversed code` (emo_png_deflate_bits)."""
+    n, strips = _png_coded(tokens, n_tokens, codes, H, W, channels, strip_rows)
+    bits = torch.empty(n, strips, device=tokens.device, dtype=torch.int32)
+    _launch("png_deflate_bits", 0.0, 4.0 * tokens.numel(),
+            lambda: check(_lib.load().emo_png_deflate_bits(_ptr(tokens), _ptr(n_tokens), _ptr(codes), _ptr(bits), n, H, W, channels, strip_rows,
+                                                           _stream()), "emo_png_deflate_bits"), tag=f"{n}x{H}x{W}x{channels}/{strip_rows}")
+    return bits
+
+
+def png_deflate_emit(tokens: torch.Tensor, n_tokens: torch.Tensor, codes: torch.Tensor, bit_offsets: torch.Tensor, out: torch.Tensor, H: int,
+                     W: int, channels: int, strip_rows: int):
+    """writes every strip's tokens, least significant bit first, at its bit offset (int64 (n, strips), from out's first bit) into out, a
+    ZEROED uint8 buffer of a multiple of 4 bytes (emo_png_deflate_emit)."""
+    n, strips = _png_coded(tokens, n_tokens, codes, H, W, channels, strip_rows)
+    _need_cuda(bit_offsets, out)
+    assert bit_offsets.dtype == torch.int64 and tuple(bit_offsets.shape) == (n, strips) and bit_offsets.is_contiguous(), (bit_offsets.dtype, bit_offsets.shape)
+    assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous(), (out.dtype, out.shape)
+    _launch("png_deflate_emit", 0.0, 4.0 * tokens.numel() + out.numel(),
+            lambda: check(_lib.load().emo_png_deflate_emit(_ptr(tokens), _ptr(n_tokens), _ptr(codes), _ptr(bit_offsets), _ptr(out), out.numel(), n,
+                                                           H, W, channels, strip_rows, _stream()), "emo_png_deflate_emit"),
+            tag=f"{n}x{H}x{W}x{channels}/{strip_rows}")
+    return out
+
+
 JPEG_DECODE_TABLE_INTS = 320                     # EMO_JPEG_DECODE_TABLE_INTS
 JPEG_STATUS = {0: "ok", 1: "a code the Huffman table does not define", 2: "the scan ends before the frame's last block",
                3: "a zero run leaves its block"}   # EMO_JPEG_OK / _BAD_CODE / _PAST_END / _BAD_RUN

@@ -32,8 +32,13 @@
                     -> emo_gif_lzw_count / emo_gif_lzw_emit (csrc/gif_out.hip; strips of rows coded independently between Clear codes),
                     ONE device-to-host copy of the code streams, then the header, the colour tables, the extensions and the sub-blocks
                     of at most 255 bytes on the host
-  save_videos_grid, images2video, video2images      the reference surface: `.avi`, and with format="gif" a `.gif` (mp4 needs an encoder
-                    that is not here)
+  deflate_tables, png_zlib_streams, encode_png, encode_apng, write_png, write_apng      the lossless files: PNG stills and animated PNG
+                    (ISO 15948, RFC 1950 / 1951): emo_png_filter -> emo_png_lz_count (csrc/png_out.hip; strips of scanlines matched
+                    independently) -> ONE small read of the frames' symbol counts -> the Huffman code lengths, the canonical codes and
+                    the header of one dynamic block per frame on the host (table building, like median cut) -> emo_png_deflate_bits /
+                    emo_png_deflate_emit, one copy of the streams, then header, end-of-block, Adler-32 and the chunks on the host
+  save_videos_grid, images2video, video2images, save_images_grid      the reference surface: `.avi`, with format="gif" a `.gif`, with
+                    format="apng" an `.apng` (mp4 needs an encoder that is not here); the image grid as `.png` or `.jpg`
 
 File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
 assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line; the resize tables hold
@@ -1426,6 +1431,448 @@ def write_gif(frames_u8: torch.Tensor, path, fps, **options) -> None:
         fh.write(data)
 
 
+# ---------------------------------------------------------------------------------------------------------------------- PNG / APNG
+PNG_STRIP_ROWS = 1      # scanlines per independently tokenised strip: one row gave the smallest files AND the shortest walk (profiles/png_encode.md)
+PNG_OPTIONS = ("filter", "strip_rows", "loop")
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_COLOUR_TYPES = {1: 0, 3: 2, 4: 6}      # channels -> IHDR colour type: grey, RGB, RGBA
+ADLER = 65521
+DEFLATE_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)      # RFC 1951 3.2.7
+# extra bits behind every slot of the device's histogram (RFC 1951 3.2.5): length symbols 265 .. 284, distance symbols 4 .. 29 at 288 +
+DEFLATE_EXTRA_BITS = np.zeros(ops.PNG_SYMBOLS, np.int64)
+DEFLATE_EXTRA_BITS[265:285] = (np.arange(265, 285) - 261) // 4
+DEFLATE_EXTRA_BITS[288 + 4:288 + 30] = np.arange(4, 30) // 2 - 1
+DEFLATE_EXTRA_BITS.setflags(write=False)
+
+
+def huffman_code_lengths(freq, limit: int, complete: bool = False) -> list:
+    """Code lengths of at most `limit` bits for the symbols with freq > 0 (0 for the others) that minimise sum(freq * length): a plain
+    Huffman tree where its deepest leaf fits, else package-merge (Larmore / Hirschberg), which is optimal under the limit.  Two or more
+    used symbols always give a complete code (Kraft sum exactly 1).  One used symbol gets length 1, no used symbol no code at all (RFC
+    1951 3.2.7 for the distance alphabet); complete=True - the code-length alphabet, which inflate wants complete - then gives a second,
+    unused symbol length 1 too.  Ties are broken by symbol index, so the same histogram gives the same lengths everywhere."""
+    import heapq
+    freq = [int(f) for f in freq]
+    used = [i for i, f in enumerate(freq) if f > 0]
+    lengths = [0] * len(freq)
+    if len(used) > (1 << limit):
+        raise ValueError(f"{len(used)} symbols do not fit codes of {limit} bits")
+    if len(used) < 2:
+        for i in used:
+            lengths[i] = 1
+        for i in range(len(freq) if complete else 0):                            # a second code of one bit, never used
+            if sum(lengths) < 2 and lengths[i] == 0:
+                lengths[i] = 1
+        return lengths
+    heap = [(freq[i], i, k) for k, i in enumerate(used)]                          # (weight, tie-break, node); nodes 0 .. n - 1 are the leaves
+    heapq.heapify(heap)
+    children = []                                                                # of node n + j
+    while len(heap) > 1:
+        a, b = heapq.heappop(heap), heapq.heappop(heap)
+        heapq.heappush(heap, (a[0] + b[0], min(a[1], b[1]), len(used) + len(children)))
+        children.append((a[2], b[2]))
+    below = [0] * (len(used) + len(children))                                    # depth of every node, from the root (the last one made) down
+    for j in range(len(children) - 1, -1, -1):
+        for c in children[j]:
+            below[c] = below[len(used) + j] + 1
+    depth = dict(zip(used, below))
+    if max(depth.values()) > limit:
+        leaves = sorted((freq[i], i) for i in used)
+        n = len(leaves)
+        leaf_w, leaf_m = np.array([w for w, _ in leaves], np.int64), np.eye(n, dtype=np.uint8)      # a row: how often each leaf is in the item
+        level_w, level_m = leaf_w, leaf_m
+        for _ in range(limit - 1):                                               # packages of the level below, merged with the leaves
+            k = len(level_w) // 2
+            both_w = np.concatenate([leaf_w, level_w[0:2 * k:2] + level_w[1:2 * k:2]])
+            both_m = np.concatenate([leaf_m, level_m[0:2 * k:2] + level_m[1:2 * k:2]])
+            order = np.argsort(both_w, kind="stable")                            # stable: leaves in front of packages of equal weight
+            level_w, level_m = both_w[order], both_m[order]
+        depth = {i: int(d) for (_, i), d in zip(leaves, level_m[:2 * n - 2].sum(axis=0, dtype=np.int64))}
+    for i, d in depth.items():
+        lengths[i] = d
+    return lengths
+
+
+def canonical_codes(lengths) -> list:
+    """RFC 1951 3.2.2: code lengths -> the codes, as integers read most significant bit first; 0 where the length is 0"""
+    lengths = [int(l) for l in lengths]
+    top = max(lengths, default=0)
+    count = [0] * (top + 2)
+    for l in lengths:
+        if l:
+            count[l] += 1
+    nxt, code = [0] * (top + 2), 0
+    for l in range(1, top + 1):
+        code = (code + count[l - 1]) << 1
+        nxt[l] = code
+    out = []
+    for l in lengths:
+        out.append(nxt[l] if l else 0)
+        if l:
+            nxt[l] += 1
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _reversed16() -> np.ndarray:
+    v = np.arange(65536, dtype=np.uint32)
+    out = np.zeros(65536, np.uint32)
+    for k in range(16):
+        out |= ((v >> k) & 1) << (15 - k)
+    return out
+
+
+def _reversed_bits(code: int, n: int) -> int:
+    """the n-bit code with its bits in reverse order: deflate packs from bit 0 up and wants a Huffman code's first bit first"""
+    return int(_reversed16()[code]) >> (16 - n) if n else 0
+
+
+def deflate_length_runs(lengths) -> list:
+    """The code lengths of a dynamic block as (code-length symbol, extra bits, their value) (RFC 1951 3.2.7), greedily: a run of zeros
+    goes out as 18 (11 .. 138 zeros) while 11 or more are left, then as 17 (3 .. 10), then one by one; a run of another length as the
+    length itself once, then 16 (repeat the previous 3 .. 6 times) while 3 or more are left, then one by one."""
+    out, i, n = [], 0, len(lengths)
+    while i < n:
+        v, j = lengths[i], i
+        while j < n and lengths[j] == v:
+            j += 1
+        run = j - i
+        if v == 0:
+            while run >= 11:
+                k = min(run, 138)
+                out.append((18, 7, k - 11))
+                run -= k
+            if run >= 3:
+                out.append((17, 3, run - 3))
+                run = 0
+        else:
+            out.append((v, 0, 0))
+            run -= 1
+            while run >= 3:
+                k = min(run, 6)
+                out.append((16, 2, k - 3))
+                run -= k
+        out.extend([(v, 0, 0)] * run)
+        i = j
+    return out
+
+
+@dataclasses.dataclass(frozen=True)
+class DeflateTables:
+    """One frame's dynamic Huffman block (RFC 1951 3.2.7), from the histogram emo_png_lz_count leaves."""
+    lengths: np.ndarray        # int64 (320): the code length of every slot of the histogram (0 .. 285 literal / length, 288 .. 317 distance)
+    codes: np.ndarray          # uint32 (320): length << 16 | the canonical code with its bits reversed - what emo_png_deflate_* read
+    header: int                # BFINAL .. the last code length, the first bit on the wire in bit 0
+    header_bits: int
+
+    @property
+    def end_of_block(self):
+        """(the bit-reversed code of symbol 256, its length)"""
+        return int(self.codes[256] & 0xFFFF), int(self.lengths[256])
+
+    def token_bits(self, hist) -> int:
+        """the bits of all the tokens a histogram counts, its end-of-block symbols left out"""
+        h = np.asarray(hist).astype(np.int64)
+        return int((h * (self.lengths + DEFLATE_EXTRA_BITS)).sum()) - int(h[256]) * int(self.lengths[256])
+
+
+def deflate_tables(hist) -> DeflateTables:
+    """A frame's symbol counts (320 integers as emo_png_lz_count adds them: literal / length symbols at 0 .. 285 with the end-of-block
+    at 256, distance symbols at 288 .. 317) -> its Huffman codes, at most 15 bits each, and the header of its one dynamic block:
+    BFINAL = 1, BTYPE = 2, HLIT, HDIST, HCLEN, the code-length code's lengths (at most 7 bits, in the order of 3.2.7) and the run-length
+    coded lengths of both alphabets as one sequence (deflate_length_runs).  No distance symbol used: one distance code of length 0; one
+    used: length 1."""
+    h = np.asarray(hist)
+    if h.shape != (ops.PNG_SYMBOLS,) or h.dtype.kind not in "iu":
+        raise ValueError(f"deflate_tables takes {ops.PNG_SYMBOLS} integer counts, got {h.dtype} {h.shape}")
+    h = h.astype(np.int64)
+    if h[256] < 1:
+        raise ValueError("deflate_tables: the histogram counts no end-of-block symbol")
+    lit = huffman_code_lengths(h[:286], 15)
+    dist = huffman_code_lengths(h[288:318], 15)
+    n_lit = max(257, max(i for i, l in enumerate(lit) if l) + 1)
+    n_dist = max([1] + [i + 1 for i, l in enumerate(dist) if l])
+    runs = deflate_length_runs(lit[:n_lit] + dist[:n_dist])
+    cl_freq = [0] * 19
+    for sym, _, _ in runs:
+        cl_freq[sym] += 1
+    cl = huffman_code_lengths(cl_freq, 7, complete=True)
+    cl_codes = canonical_codes(cl)
+    n_cl = max(4, max(k for k, sym in enumerate(DEFLATE_CL_ORDER) if cl[sym]) + 1)
+    value = nbits = 0
+
+    def put(v, n):
+        nonlocal value, nbits
+        value |= v << nbits
+        nbits += n
+
+    put(1, 1)
+    put(2, 2)
+    put(n_lit - 257, 5)
+    put(n_dist - 1, 5)
+    put(n_cl - 4, 4)
+    for sym in DEFLATE_CL_ORDER[:n_cl]:
+        put(cl[sym], 3)
+    for sym, nx, x in runs:
+        put(_reversed_bits(cl_codes[sym], cl[sym]), cl[sym])
+        put(x, nx)
+    lengths = np.zeros(ops.PNG_SYMBOLS, np.int64)
+    lengths[:286], lengths[288:318] = lit, dist
+    plain = np.zeros(ops.PNG_SYMBOLS, np.int64)
+    plain[:286], plain[288:318] = canonical_codes(lit), canonical_codes(dist)
+    codes = (lengths << 16 | (_reversed16()[plain] >> np.where(lengths, 16 - lengths, 0))).astype(np.uint32)
+    lengths.setflags(write=False)
+    codes.setflags(write=False)
+    return DeflateTables(lengths, codes, value, nbits)
+
+
+def adler32_combine(pairs, nbytes) -> int:
+    """The Adler-32 (RFC 1950 8.2) of consecutive pieces from the (s1, s2) each has on its own (the state after its bytes from (1, 0),
+    as emo_png_filter leaves per row) and their lengths in bytes (one int for all, or one per piece): a stream in state (s1, s2)
+    followed by a piece (r1, r2) of R bytes is in (s1 + r1 - 1, s2 + r2 + R (s1 - 1)), both mod 65521.  -> s2 << 16 | s1"""
+    p = np.asarray(pairs).astype(np.int64).reshape(-1, 2)
+    if len(p) < 1:
+        return 1
+    lens = np.broadcast_to(np.asarray(nbytes, np.int64), (len(p),)) % ADLER
+    before = np.concatenate([[0], np.cumsum((p[:-1, 0] - 1) % ADLER)]) % ADLER    # s1 - 1 in front of every piece
+    s1 = (1 + int(((p[:, 0] - 1) % ADLER).sum())) % ADLER
+    s2 = int(((p[:, 1] + lens * before) % ADLER).sum()) % ADLER
+    return s2 << 16 | s1
+
+
+def _or_bits(buf: np.ndarray, at: int, value: int, nbits: int) -> None:
+    """ORs nbits bits of value into the uint8 array, least significant bit first from bit `at`"""
+    if nbits:
+        raw = np.frombuffer((value << (at & 7)).to_bytes(((at & 7) + nbits + 7) // 8, "little"), np.uint8)
+        buf[at >> 3:(at >> 3) + len(raw)] |= raw
+
+
+def zlib_stream(tokens_at_their_bits: np.ndarray, tables: DeflateTables, token_bits: int, adler: int) -> bytes:
+    """What the host adds to a frame's bytes as emo_png_deflate_emit leaves them (uint8, the tokens in place from bit 16 +
+    tables.header_bits on, zero elsewhere): the zlib header 78 01 (deflate, 32 KiB window, no dictionary, fastest-level flag), the block
+    header, the end-of-block code behind the tokens, and the Adler-32 big-endian behind the block's last byte"""
+    buf = np.array(tokens_at_their_bits, dtype=np.uint8)
+    end = 16 + tables.header_bits + int(token_bits)
+    code, length = tables.end_of_block
+    if len(buf) != (end + length + 7) // 8 + 4:
+        raise ValueError(f"zlib_stream: {len(buf)} bytes for a block of {end + length} bits behind the 2-byte header")
+    buf[0], buf[1] = 0x78, 0x01
+    _or_bits(buf, 16, tables.header, tables.header_bits)
+    _or_bits(buf, end, code, length)
+    buf[-4:] = np.frombuffer(struct.pack(">I", adler), np.uint8)
+    return buf.tobytes()
+
+
+def png_chunk(kind: bytes, body: bytes) -> bytes:
+    import zlib
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body))
+
+
+def _png_ihdr(width: int, height: int, channels: int) -> bytes:
+    if channels not in PNG_COLOUR_TYPES or not (1 <= int(width) < 2 ** 31 and 1 <= int(height) < 2 ** 31):
+        raise ValueError(f"a PNG frame is 1 .. 2^31 - 1 pixels each way with 1 (grey), 3 (RGB) or 4 (RGBA) channels, got {height} x {width} x {channels}")
+    return png_chunk(b"IHDR", struct.pack(">IIBBBBB", int(width), int(height), 8, PNG_COLOUR_TYPES[channels], 0, 0, 0))
+
+
+def png_container(width: int, height: int, channels: int, stream: bytes) -> bytes:
+    """One still around its zlib stream (PNG section 5): signature, IHDR (bit depth 8, colour type 0 / 2 / 6, no interlace), one IDAT, IEND"""
+    return PNG_SIGNATURE + _png_ihdr(width, height, channels) + png_chunk(b"IDAT", bytes(stream)) + png_chunk(b"IEND", b"")
+
+
+def apng_delay(fps):
+    """the (numerator, denominator) of a frame's delay in seconds, 1 / fps exactly (fps as fps_fraction takes it); ValueError when a
+    term of the reduced fraction passes the 16 bits fcTL holds"""
+    f = fps_fraction(fps)
+    if f.denominator > 65535 or f.numerator > 65535:
+        raise ValueError(f"an APNG frame's delay is a fraction of two 16-bit numbers: 1 / fps = {f.denominator} / {f.numerator} for fps = {fps!r} "
+                         "does not fit 65535")
+    return f.denominator, f.numerator
+
+
+def apng_container(width: int, height: int, channels: int, streams, fps, loop: int = 0) -> bytes:
+    """An animated PNG (APNG 1.0) around the frames' zlib streams: IHDR, acTL (frames, plays; 0: forever), then per frame an fcTL - the
+    whole frame at (0, 0), the delay apng_delay(fps), dispose 0 (none), blend 0 (source) - and the stream, frame 0's in IDAT (the still
+    a plain PNG reader shows), the others' in fdAT; fcTL and fdAT share one running sequence number.  IEND."""
+    num, den = apng_delay(fps)
+    loop = _int_in(loop, 0, 2 ** 31 - 1, "loop= (0: forever)")
+    if len(streams) < 1:
+        raise ValueError("apng_container: no frames")
+    out, seq = [PNG_SIGNATURE, _png_ihdr(width, height, channels), png_chunk(b"acTL", struct.pack(">II", len(streams), loop))], 0
+    for i, stream in enumerate(streams):
+        out.append(png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, int(width), int(height), 0, 0, num, den, 0, 0)))
+        seq += 1
+        if i == 0:
+            out.append(png_chunk(b"IDAT", bytes(stream)))
+        else:
+            out.append(png_chunk(b"fdAT", struct.pack(">I", seq) + bytes(stream)))
+            seq += 1
+    out.append(png_chunk(b"IEND", b""))
+    return b"".join(out)
+
+
+def _png_frames(frames_u8, who):
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (3, 4, 5) or frames_u8.shape[-1] not in PNG_COLOUR_TYPES:
+        raise ValueError(f"{who} takes packed uint8 frames with 1 (grey), 3 (RGB) or 4 (RGBA) channels, (H, W, C), (n, H, W, C) or the "
+                         f"(1, n, H, W, C) of output_type=\"uint8\", got {getattr(frames_u8, 'dtype', type(frames_u8))} "
+                         f"{tuple(getattr(frames_u8, 'shape', ()))}")
+    if frames_u8.dim() == 3:
+        frames_u8 = frames_u8[None]
+    elif frames_u8.dim() == 5:
+        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
+    n, height, width = (int(s) for s in frames_u8.shape[:3])
+    if n < 1:
+        raise ValueError(f"{who}: no frames")
+    if height < 1 or width < 1:
+        raise ValueError(f"{who}: a PNG frame is at least 1 pixel each way, got {height} x {width}")
+    return frames_u8
+
+
+def _png_filter(filter):
+    if not isinstance(filter, str) or filter not in ops.PNG_FILTERS:
+        raise ValueError(f"filter= takes one of {', '.join(repr(k) for k in ops.PNG_FILTERS)}, got {filter!r}")
+    return ops.PNG_FILTERS[filter]
+
+
+def png_strip_rows(strip_rows, height: int, width: int, channels: int) -> int:
+    """strip_rows= as the PNG writers take it (None: the frame as one strip) -> the scanlines per strip the kernels get: lowered to the
+    frame's height and to what fits the 65535 bytes a strip may hold; ValueError where one scanline (1 + width * channels bytes) does not"""
+    rows = int(height) if strip_rows is None else _int_in(strip_rows, 1, 2 ** 31 - 1, "strip_rows= (None: the frame as one strip)")
+    row = 1 + int(width) * int(channels)
+    if row > ops.PNG_MAX_STRIP_BYTES:
+        raise ValueError(f"a scanline of {width} pixels of {channels} bytes is {row} bytes with its filter byte: above the "
+                         f"{ops.PNG_MAX_STRIP_BYTES} bytes of a strip (the match table holds 16-bit offsets)")
+    return max(1, min(rows, int(height), ops.PNG_MAX_STRIP_BYTES // row))
+
+
+def png_zlib_streams(frames_u8: torch.Tensor, filter: str = "adaptive", strip_rows=PNG_STRIP_ROWS) -> list:
+    """The device part of encode_png: (n, H, W, C) uint8 device frames -> the n zlib streams (bytes) an IDAT chunk holds.  Five
+    launches - emo_png_filter, emo_png_lz_count, [the tables], emo_png_deflate_bits, a scan, emo_png_deflate_emit - around ONE small
+    read (the n histograms and the rows' Adler-32 pairs) and the copy of the streams.  The sizes of all frames follow from the
+    histograms and the code lengths, so the buffer is sized without a second read."""
+    frames_u8 = _png_frames(frames_u8, "png_zlib_streams").contiguous()
+    n, height, width, channels = (int(s) for s in frames_u8.shape)
+    rows = png_strip_rows(strip_rows, height, width, channels)
+    filtered, adler = ops.png_filter(frames_u8, _png_filter(filter))
+    tokens, n_tokens, hist = ops.png_lz_count(filtered, channels, rows)
+    hist_host, adler_host = hist.cpu().numpy(), adler.cpu().numpy()              # the one small read
+    tables = [deflate_tables(h) for h in hist_host]
+    codes = torch.from_numpy(np.stack([t.codes for t in tables]).view(np.int32)).to(frames_u8.device)
+    bits = ops.png_deflate_bits(tokens, n_tokens, codes, height, width, channels, rows)
+    token_bits = np.array([t.token_bits(h) for t, h in zip(tables, hist_host)], np.int64)
+    head = np.array([16 + t.header_bits for t in tables], np.int64)
+    nbytes = (head + token_bits + np.array([t.end_of_block[1] for t in tables], np.int64) + 7) // 8 + 4
+    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+    ends = torch.cumsum(bits, dim=1, dtype=torch.int64)
+    offsets = (ends - bits + torch.from_numpy(starts * 8 + head).to(ends.device)[:, None]).contiguous()
+    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
+    ops.png_deflate_emit(tokens, n_tokens, codes, offsets, out, height, width, channels, rows)
+    host = out.cpu().numpy()
+    return [zlib_stream(host[s:s + b], t, tb, adler32_combine(a, 1 + width * channels))
+            for s, b, t, tb, a in zip(starts, nbytes, tables, token_bits, adler_host)]
+
+
+def encode_png(frames_u8: torch.Tensor, filter: str = "adaptive", strip_rows=PNG_STRIP_ROWS) -> list:
+    """Packed uint8 frames on the device, (n, H, W, C) or (H, W, C) (or the (1, n, H, W, 3) of output_type="uint8") with C = 1 (grey),
+    3 (RGB) or 4 (RGBA) -> n PNG files (bytes), lossless: the filtering, the LZ77 matching and the Huffman coding run on the device
+    (png_zlib_streams), the host builds each frame's code tables from its histogram and wraps the stream in signature, IHDR, one IDAT
+    and IEND.  filter="adaptive" picks per scanline the filter type with the smallest sum of absolute differences (libpng's
+    heuristic); "none" | "sub" | "up" | "average" | "paeth" forces one.  strip_rows scanlines form a strip whose matches stay inside
+    it (None: the whole frame; lowered where a strip would pass 65535 bytes); one dynamic Huffman block per frame either way."""
+    frames_u8 = _png_frames(frames_u8, "encode_png")
+    height, width, channels = (int(s) for s in frames_u8.shape[1:])
+    _png_filter(filter)
+    png_strip_rows(strip_rows, height, width, channels)
+    return [png_container(width, height, channels, s) for s in png_zlib_streams(frames_u8, filter, strip_rows)]
+
+
+def encode_apng(frames_u8: torch.Tensor, fps, loop: int = 0, filter: str = "adaptive", strip_rows=PNG_STRIP_ROWS) -> bytes:
+    """The same frames -> one animated PNG as bytes, playing at exactly fps (apng_delay: the reduced fraction's terms must fit 16
+    bits) and repeating `loop` times (0: forever).  Every frame is a whole frame (dispose 0, blend 0): no differences between frames.
+    All arguments are checked before the first launch."""
+    frames_u8 = _png_frames(frames_u8, "encode_apng")
+    height, width, channels = (int(s) for s in frames_u8.shape[1:])
+    apng_delay(fps)
+    _int_in(loop, 0, 2 ** 31 - 1, "loop= (0: forever)")
+    _png_filter(filter)
+    png_strip_rows(strip_rows, height, width, channels)
+    return apng_container(width, height, channels, png_zlib_streams(frames_u8, filter, strip_rows), fps, loop)
+
+
+def _png_pattern(path, who):
+    """a `.png` path -> (path, whether its file name holds one %d-style field for the frame's number)"""
+    import re
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() != ".png":
+        raise ValueError(f"{who} writes PNG stills: name the file `.png`, or with a field for the frame's number as in `frame_%04d.png`, got {path!r}")
+    name = os.path.basename(path).replace("%%", "")
+    numbered = re.findall(r"%0?\d*d", name)
+    if name.count("%") != len(numbered) or len(numbered) > 1 or "%" in os.path.dirname(path):
+        raise ValueError(f"{who}: a pattern holds one field for the frame's number in the file's name, as in `frame_%04d.png`, got {path!r}")
+    return path, bool(numbered)
+
+
+def write_png(frames_u8: torch.Tensor, path, filter: str = "adaptive", strip_rows=PNG_STRIP_ROWS) -> list:
+    """encode_png into files: a path whose name holds a %d-style field (`frames/frame_%04d.png`) takes any number of frames as numbered
+    stills, counted from 0; a plain `.png` path takes exactly one frame.  -> the paths written"""
+    path, numbered = _png_pattern(path, "write_png")
+    frames_u8 = _png_frames(frames_u8, "write_png")
+    n = int(frames_u8.shape[0])
+    if n > 1 and not numbered:
+        raise ValueError(f"write_png: {n} frames and one file name {path!r}: put a field for the frame's number into it, as in `frame_%04d.png`, "
+                         "for numbered stills, or write an animated `.apng` (encode_apng, write_video(format=\"apng\"))")
+    files = encode_png(frames_u8, filter, strip_rows)
+    paths = [path % i for i in range(n)] if numbered else [path]
+    _makedirs_for(paths[0])
+    for p, data in zip(paths, files):
+        with open(p, "wb") as fh:
+            fh.write(data)
+    return paths
+
+
+def _apng_path(path, who):
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() != ".apng":
+        raise ValueError(f"{who} writes an animated PNG: name the file `.apng`, got {path!r}")
+    return path
+
+
+def write_apng(frames_u8: torch.Tensor, path, fps, **options) -> None:
+    """encode_apng (with its options) into the `.apng` file at path"""
+    path = _apng_path(path, "write_apng")
+    unknown = sorted(set(options) - set(PNG_OPTIONS))
+    if unknown:
+        raise ValueError(f"write_apng: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; an APNG takes {', '.join(PNG_OPTIONS)}")
+    data = encode_apng(frames_u8, fps, **options)
+    _makedirs_for(path)
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
+def save_images_grid(images: torch.Tensor, path: str, quality: int = 90):
+    """magicanimate/utils/util.py:35-41: (b, c, 1, h, w) in [0, 1] -> one image file of the grid `torchvision.utils.make_grid(images)`
+    lays out with its defaults (8 per row, 2 pixels of padding; make_grid_u8), `* 255` truncated to uint8 as :39 does.  `.png` is written
+    lossless (encode_png), `.jpg` / `.jpeg` as one baseline JPEG frame at `quality` (the frame encode_mjpeg makes).  The file is
+    encoded on the HIP device: images held on the host are uploaded."""
+    path = os.fspath(path)
+    ext = os.path.splitext(path)[1].lower()
+    if ext not in (".png", ".jpg", ".jpeg"):
+        raise ValueError(f"save_images_grid writes `.png` (lossless) or `.jpg` / `.jpeg` files, got {path!r}")
+    if not torch.is_tensor(images) or images.dim() != 5 or images.shape[2] != 1:
+        raise ValueError(f"save_images_grid takes a float (b, c, 1, h, w) tensor, got {tuple(getattr(images, 'shape', ()))}")
+    _check_quality(quality)
+    if not images.is_cuda:
+        images = images.to("cuda")
+    grid = make_grid_u8(images, n_rows=8)                                        # (1, Hg, Wg, 3)
+    if ext == ".png":
+        data = encode_png(grid)[0]
+    else:
+        out, starts, bits = encode_streams(grid, quality)
+        data = jpeg_header(int(grid.shape[1]), int(grid.shape[2]), int(quality)) + finish_scan(out.cpu().numpy()[int(starts[0]):], int(bits[0]))
+    _makedirs_for(path)
+    with open(path, "wb") as fh:
+        fh.write(data)
+
+
 # ---------------------------------------------------------------------------------------------------------------------- reference surface
 def _avi_path(path, who, gif_hint="pass format=\"gif\" with a `.gif` path for an animated GIF"):
     path = os.fspath(path)
@@ -1436,20 +1883,30 @@ def _avi_path(path, who, gif_hint="pass format=\"gif\" with a `.gif` path for an
 
 
 def _output_path(path, who, format, quality, restart_interval, gif_options):
-    """what the writers of the reference surface check before anything runs -> (path, is it a GIF)"""
+    """what the writers of the reference surface check before anything runs -> (path, the format: None, "gif" or "apng")"""
     if format is None:
         if gif_options:
-            raise ValueError(f"{who}: {', '.join(sorted(gif_options))} belong{'s' if len(gif_options) == 1 else ''} to format=\"gif\"")
-        return _avi_path(path, who), False
-    if format != "gif":
-        raise ValueError(f"{who}: format= takes None (a Motion-JPEG `.avi` file) or \"gif\", got {format!r}")
+            owner = "apng" if set(gif_options) - set(GIF_OPTIONS) and not set(gif_options) - set(PNG_OPTIONS) else "gif"
+            raise ValueError(f"{who}: {', '.join(sorted(gif_options))} belong{'s' if len(gif_options) == 1 else ''} to format=\"{owner}\"")
+        return _avi_path(path, who), None
+    if isinstance(format, str) and format == "apng":
+        path = _apng_path(path, f"{who} with format=\"apng\"")
+        unknown = sorted(set(gif_options) - set(PNG_OPTIONS))
+        if unknown:
+            raise ValueError(f"{who}: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; an APNG takes {', '.join(PNG_OPTIONS)}")
+        if quality != 90 or restart_interval is not None:
+            raise ValueError(f"{who}: quality= and restart_interval= belong to the JPEG frames of an `.avi` file; an APNG is lossless and takes "
+                             f"{', '.join(PNG_OPTIONS)}")
+        return path, "apng"
+    if not isinstance(format, str) or format != "gif":
+        raise ValueError(f"{who}: format= takes None (a Motion-JPEG `.avi` file), \"gif\" or \"apng\", got {format!r}")
     path = _gif_path(path, f"{who} with format=\"gif\"")
     unknown = sorted(set(gif_options) - set(GIF_OPTIONS))
     if unknown:
         raise ValueError(f"{who}: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; a GIF takes {', '.join(GIF_OPTIONS)}")
     if quality != 90 or restart_interval is not None:
         raise ValueError(f"{who}: quality= and restart_interval= belong to the JPEG frames of an `.avi` file; a GIF takes {', '.join(GIF_OPTIONS)}")
-    return path, True
+    return path, "gif"
 
 
 def _makedirs_for(path):
@@ -1461,12 +1918,17 @@ def _makedirs_for(path):
 def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None, format=None, **gif_options) -> None:
     """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + write_avi.  With format="gif" and a
     `.gif` path: an animated GIF instead (write_gif; its options - loop, colors, palette, dither, dither_strength, strip_rows - as
-    keywords; quality=, restart_interval= and audio= have no place in one and are refused)."""
-    path, gif = _output_path(path, "write_video", format, quality, restart_interval, gif_options)
-    if gif:
+    keywords; quality=, restart_interval= and audio= have no place in one and are refused).  With format="apng" and an `.apng` path:
+    a lossless animated PNG (write_apng; its options are filter, strip_rows and loop; the same three keywords are refused)."""
+    path, kind = _output_path(path, "write_video", format, quality, restart_interval, gif_options)
+    if kind == "gif":
         if audio is not None:
             raise ValueError("write_video: a GIF holds no sound; write an `.avi` file for audio=")
         return write_gif(frames_u8, path, fps, **gif_options)
+    if kind == "apng":
+        if audio is not None:
+            raise ValueError("write_video: an APNG holds no sound: audio= has no place in one; write an `.avi` file for audio=")
+        return write_apng(frames_u8, path, fps, **gif_options)
     if frames_u8.dim() == 5:
         frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
     jpegs = encode_mjpeg(frames_u8, quality, restart_interval)
@@ -1504,7 +1966,7 @@ def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, f
                      **gif_options):
     """magicanimate/utils/util.py:21-33 with a Motion-JPEG `.avi` in place of imageio.mimsave.  The frames are encoded on the HIP device:
     videos held on the host are uploaded.  restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes the animated GIF
-    mimsave would (write_video)."""
+    mimsave would, format="apng" with an `.apng` path a lossless animated PNG (write_video)."""
     path, _ = _output_path(path, "save_videos_grid", format, quality, restart_interval, gif_options)
     if torch.is_tensor(videos) and not videos.is_cuda:
         videos = videos.to("cuda")
@@ -1513,7 +1975,8 @@ def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, f
 
 def images2video(video, path, fps=8, quality: int = 90, restart_interval=None, format=None, **gif_options):
     """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file.
-    restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes an animated GIF (write_video)."""
+    restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes an animated GIF, format="apng" with an `.apng` path a
+    lossless animated PNG (write_video)."""
     path, _ = _output_path(path, "images2video", format, quality, restart_interval, gif_options)
     frames = video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))
     write_video(frames.to("cuda"), path, fps, quality, restart_interval=restart_interval, format=format, **gif_options)

@@ -563,6 +563,56 @@ int emo_gif_lzw_count(const uint8_t* indices, uint16_t* codes, int32_t* n_codes,
 int emo_gif_lzw_emit(const uint16_t* codes, const int32_t* n_codes, const int64_t* bit_offsets, uint8_t* out, int64_t out_bytes, int n,
                      int H, int W, int strip_rows, void* stream);
 
+/* ---- PNG / APNG output: the device half of the lossless writer, what `save_images_grid` (magicanimate/utils/util.py:35-41,
+ * `Image.fromarray(grid).save(path)`) and the numbered stills of ExtractFrames.py:51 ask Pillow for.  PNG is ISO/IEC 15948 (RFC 2083;
+ * filtering: its section 6), the image data a zlib stream (RFC 1950) holding ONE deflate block with dynamic Huffman codes (RFC 1951
+ * 3.2.7) per frame.  The host half (the Huffman tables and the block header, the combination of the rows' checksums, the chunks and
+ * their CRCs) is emote_hack_amd/video_io.py.  The kernels live in csrc/png_out.hip.  Shapes common to all entries: n, H, W >= 1, C in
+ * {1, 3, 4} (grey, RGB, RGBA at bit depth 8), a filtered scanline has R = 1 + W * C bytes, and H * R <= 2^31 - 1.
+ * emo_png_filter (PNG section 6): packed uint8 frames [n][H][W][C] -> filtered uint8 [n][H][R]: per scanline the filter type byte t and
+ *   then, for byte j = 0 .. W * C - 1 of the raw row, (x - pred_t) mod 256 with x = raw[y][j], a = raw[y][j - C] (0 where j < C),
+ *   b = raw[y - 1][j] (0 in the frame's row 0), c = raw[y - 1][j - C] (0 where either is) and pred_0 = 0 (None), pred_1 = a (Sub),
+ *   pred_2 = b (Up), pred_3 = floor((a + b) / 2) (Average), pred_4 = Paeth: with p = a + b - c, pa = |p - a|, pb = |p - b|,
+ *   pc = |p - c|, it is a if pa <= pb and pa <= pc, else b if pb <= pc, else c.  Every row is computed from the RAW rows.  filter 0 .. 4
+ *   forces t for all rows; filter 5 picks per row the t with the smallest sum over the row's W * C filtered bytes v of min(v, 256 - v)
+ *   (libpng's heuristic), the LOWEST t on a tie.  adler uint32 [n][H][2] takes per row (s1, s2) = the Adler-32 state (RFC 1950 8.2)
+ *   after the row's R filtered bytes d_0 .. d_(R-1) from the state (1, 0): s1 = (1 + sum d_i) mod 65521, s2 = (R + sum (R - i) d_i)
+ *   mod 65521.  The host chains them: a stream in state (s1, s2) followed by a row (r1, r2) of R bytes is in
+ *   ((s1 + r1 - 1) mod 65521, (s2 + r2 + R (s1 - 1)) mod 65521).
+ * emo_png_lz_count: a frame's filtered bytes are cut into strips of strip_rows scanlines (the last may be shorter; strip_rows > H
+ *   counts as H); a strip holds at most 65535 bytes, more is refused.  Each strip, a byte string s of P bytes, is tokenised on its own
+ *   by a deterministic greedy LZ77 over a table T of 4096 strip offsets, all empty at the strip's start.  From pos = 0, while pos < P:
+ *   if pos + 3 <= P, then h = ((s[pos] | s[pos + 1] << 8 | s[pos + 2] << 16) * 0x9E3779B1 mod 2^32) >> 20, cand = T[h], T[h] = pos; if
+ *   cand is not empty and pos - cand <= 32768, L = the number of leading bytes on which s[cand ..] and s[pos ..] agree, counted up to
+ *   min(258, P - pos) (the two ranges may overlap); if L >= 3 the token is the match (length L, distance pos - cand) and pos += L.  In
+ *   every other case the token is the literal s[pos] and pos += 1.  The table is read and written at token starts only, and one slot
+ *   is probed: a slot taken by another triple with the same hash gives L < 3 and a literal.
+ *   tokens uint32 [n * strips][emo_png_tokens_per_strip(H, W, C, strip_rows)] (= the bytes of a full strip: one token per byte at
+ *   worst) takes them packed as length << 16 | distance for a match (3 .. 258, 1 .. 32768) and as the byte alone for a literal (bits
+ *   16 .. 31 zero); entries behind a strip's tokens are not written.  n_tokens int32 [n * strips] their number.  hist uint32 [n][320]:
+ *   the symbols of RFC 1951 3.2.5 are ADDED with integer atomics (the caller zeroes it): slot v for a literal v, slot 257 .. 285 for a
+ *   match's length symbol, slot 288 + d for its distance symbol d = 0 .. 29, and slot 256 once per frame, the end-of-block.
+ * emo_png_deflate_bits: codes uint32 [n][320] holds per frame and per slot of hist `code length << 16 | the canonical code with its
+ *   bits reversed` (length 1 .. 15; packed least significant bit first, a reversed code is on the wire most significant bit first as
+ *   RFC 1951 3.1.1 wants).  bits int32 [n * strips] = the exact size of every strip's tokens: per literal its code's length, per match
+ *   the length symbol's code, its extra bits, the distance symbol's code, its extra bits.  Block header and end-of-block are not in it.
+ * emo_png_deflate_emit ORs every strip's tokens in that order - codes, then extra bits as plain integers above them - into out from
+ *   bit_offsets[strip] (int64 [n * strips], from the first bit of out) on, least significant bit first.  out must be zeroed, 4-byte
+ *   aligned, out_bytes a multiple of 4: 32-bit atomicOr, since strips and frames share words; a word is touched only where a token
+ *   has a 1-bit in it and never at or beyond out_bytes.  A strip whose n_tokens is outside 0 .. the buffer's entries writes nothing.
+ *   THE HOST places everything else after the one copy back: per frame, starting on a byte, the zlib header 78 01, the block header
+ *   (BFINAL = 1, BTYPE = 2, HLIT, HDIST, HCLEN, the code lengths) right behind it, the strips' tokens end to end behind that (the
+ *   caller's bit_offsets leave exactly that room), the end-of-block code, zero bits up to the next byte and the Adler-32 as s2 << 16 |
+ *   s1, big-endian. */
+int emo_png_filter(const uint8_t* frames, uint8_t* filtered, uint32_t* adler, int n, int H, int W, int C, int filter, void* stream);
+int64_t emo_png_tokens_per_strip(int H, int W, int C, int strip_rows);
+int emo_png_lz_count(const uint8_t* filtered, uint32_t* tokens, int32_t* n_tokens, uint32_t* hist, int n, int H, int W, int C,
+                     int strip_rows, void* stream);
+int emo_png_deflate_bits(const uint32_t* tokens, const int32_t* n_tokens, const uint32_t* codes, int32_t* bits, int n, int H, int W, int C,
+                         int strip_rows, void* stream);
+int emo_png_deflate_emit(const uint32_t* tokens, const int32_t* n_tokens, const uint32_t* codes, const int64_t* bit_offsets, uint8_t* out,
+                         int64_t out_bytes, int n, int H, int W, int C, int strip_rows, void* stream);
+
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
  * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, one scan; the host half (marker segments of Annex B, the
