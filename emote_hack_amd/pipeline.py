@@ -1224,27 +1224,6 @@ class EMOAnimationPipeline:
         return out
 
     @staticmethod
-    def _png_save_options(video_io, save_path, ext, n_frames, kwargs):
-        """the checks of a `.png` / `.apng` save_path, before anything runs -> the keywords of write_png / write_apng, and the path"""
-        if kwargs.get("save_restart_interval") is not None or kwargs.get("save_quality", 90) != 90:
-            raise ValueError(f"save_restart_interval= and save_quality= belong to the JPEG frames of an `.avi` file, not to a lossless `{ext}`")
-        if any(kwargs.get(k) is not None for k in ("save_palette", "save_dither", "save_dither_strength")):
-            raise ValueError(f"save_palette=, save_dither= and save_dither_strength= belong to a `.gif` save_path, not to a `{ext}`")
-        out = dict(filter="adaptive" if kwargs.get("save_png_filter") is None else kwargs["save_png_filter"])
-        video_io._png_filter(out["filter"])
-        if ext == ".png":
-            if kwargs.get("save_loop") is not None:
-                raise ValueError("save_loop= belongs to a `.gif` or an `.apng` save_path; numbered `.png` stills do not play")
-            out["path"], numbered = video_io._png_pattern(save_path, "save_path=")
-            if n_frames > 1 and not numbered:
-                raise ValueError(f"save_path={out['path']!r} names one `.png` file for {n_frames} frames: put a field for the frame's number "
-                                 "into the name, as in `frames/f_%04d.png`, or name the file `.apng` for an animated PNG")
-        else:
-            out["path"] = os.fspath(save_path)
-            out["loop"] = video_io._int_in(0 if kwargs.get("save_loop") is None else kwargs["save_loop"], 0, 2 ** 31 - 1, "save_loop= (0: forever)")
-        return out
-
-    @staticmethod
     def _audio_for_file(audio):
         """the samples save_path= puts beside the frames: audio= as a `.wav` path or a (samples, rate) pair, at its own rate and with its
         own channels -> (float samples (n, channels), rate); anything else (a bare waveform, a container this build cannot demux) -> None"""
@@ -1310,8 +1289,9 @@ class EMOAnimationPipeline:
         quantised to 256 colours, mapped and LZW-coded on the device (emote_hack_amd.video_io.encode_gif) and play at fps *
         interpolation_factor, which may not pass 50.  save_palette="global" | "frame" (one colour table for the clip, the default, or one
         per frame), save_dither=None | "bayer" with save_dither_strength=1 .. 128 (default 32) and save_loop=0 .. 65535 (0, the
-        default: forever) are its options; save_quality= and save_restart_interval= are refused with it.  A GIF has no sound: audio=
-        still drives the model and is not in the file.
+        default: forever) are its options.  A GIF has no sound: audio= still drives the model and is not in the file.  A save_* keyword
+        that belongs to another format than save_path's is refused by the name of that format, whichever the formats
+        (emote_hack_amd.video_io.save_plan checks the call against the one table of formats, video_io.FORMATS, before anything runs).
         save_path="clip.apng" writes a lossless animated PNG of the same 8-bit frames, filtered, matched and Huffman-coded on the device
         (emote_hack_amd.video_io.encode_apng), playing at exactly fps * interpolation_factor (the reduced fraction's terms must fit 16
         bits); save_path="frames/f_%04d.png" - a `.png` name with one %d-style field - writes every frame as a numbered PNG still,
@@ -1344,47 +1324,20 @@ class EMOAnimationPipeline:
         if output_type == "uint8" and self.vae is None:
             raise ValueError("output_type=\"uint8\" decodes the latents into 8-bit frames: it needs a VAE on the pipeline "
                              "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor); output_type=\"latent\" returns the latents")
-        save_path, save_quality, save_fps, save_audio = kwargs.get("save_path"), kwargs.get("save_quality", 90), None, None
-        if save_path is not None:
+        plan = save_audio = None
+        if kwargs.get("save_path") is not None:      # what the path and the save_* keywords can be refused for, before anything runs
             from . import video_io
-            save_ext = os.path.splitext(os.fspath(save_path))[1].lower()
-            save_gif = save_ext == ".gif"
-            save_png = save_ext in (".png", ".apng")
-            if save_png:      # lossless: numbered `.png` stills (no frame rate) or one animated `.apng`
-                n_out = (int(video_length) - 1) * int(interp_k) + 1 if video_length else 1
-                save_png = self._png_save_options(video_io, save_path, save_ext, n_out, kwargs)
-                save_path = save_png.pop("path")
-            elif not save_gif:
-                save_path = video_io._avi_path(save_path, "save_path=", "`.gif` for an animated GIF")
-                if any(kwargs.get(k) is not None for k in ("save_palette", "save_dither", "save_dither_strength", "save_loop")):
-                    raise ValueError("save_palette=, save_dither=, save_dither_strength= and save_loop= belong to a `.gif` save_path")
-            video_io.jpeg_tables(save_quality)      # quality 1 .. 100
-            video_io.restart_mcus(kwargs.get("save_restart_interval"), 16)      # None, "row" or 1 .. 65535 MCUs
-            if save_gif:
-                save_path = os.fspath(save_path)
-                if kwargs.get("save_restart_interval") is not None or save_quality != 90:
-                    raise ValueError("save_restart_interval= and save_quality= belong to the JPEG frames of an `.avi` file, not to a `.gif`")
-                save_gif = dict(palette=kwargs.get("save_palette") or "global", dither=kwargs.get("save_dither"),
-                                dither_strength=32 if kwargs.get("save_dither_strength") is None else kwargs["save_dither_strength"],
-                                loop=0 if kwargs.get("save_loop") is None else kwargs["save_loop"])
-                video_io._gif_quantize_options(256, save_gif["palette"], save_gif["dither"], save_gif["dither_strength"])
-                video_io._int_in(save_gif["loop"], 0, 65535, "save_loop= (0: forever)")
-            stills = save_png and save_ext == ".png"
-            if kwargs.get("fps") is None and not stills:
+            from .conditioning import _as_fraction
+            plan = video_io.save_plan(kwargs["save_path"], (int(video_length) - 1) * int(interp_k) + 1 if video_length else 1,
+                                      None if kwargs.get("fps") is None else _as_fraction(kwargs["fps"], "fps"), interp_k,
+                                      {name: kwargs.get(keyword) for name, keyword in video_io.SAVE_KEYWORDS.items()})
+            if plan.record.plays and plan.rate is None:
                 raise ValueError("save_path= writes a video file and a file has a frame rate: pass fps= (an int, a Fraction or a (num, den) "
                                  "pair; the file plays at fps * interpolation_factor)")
-            from .conditioning import _as_fraction
-            if save_png and not stills:      # the delay's terms fit 16 bits
-                video_io.apng_delay(video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k)))
-            if save_gif:      # at most 50 frames a second
-                video_io.gif_delays(video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k)),
-                                    (int(video_length) - 1) * int(interp_k) + 1 if video_length else 1)
             if self.vae is None:
                 raise ValueError("save_path= decodes the latents into 8-bit frames, as output_type=\"uint8\" does: it needs a VAE on the pipeline "
                                  "(emote_hack_amd.vae.AutoencoderKL, vae= of the constructor)")
-            if not stills:
-                save_fps = video_io.fps_fraction(_as_fraction(kwargs["fps"], "fps") * int(interp_k))
-            if not save_gif and not save_png:
+            if plan.record.sound:
                 save_audio = self._audio_for_file(audio)
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
@@ -1549,24 +1502,14 @@ class EMOAnimationPipeline:
         if interp_k >= 2:      # :824, between the loop and the decode
             method = {"slerp": slerp, "linear": linear}.get(interp) or get_tensor_interpolation_method() or slerp
             lat = self._interpolate_latents(lat, int(interp_k), lat.device, method)
-        frames_u8 = self.vae.decode_video(lat, output="uint8") if output_type == "uint8" or save_path is not None else None
-        if save_path is not None:      # the end of every reference run: save_videos_grid (magicanimate/utils/util.py:21-33)
-            from . import video_io
-            n_frames = frames_u8.shape[0] * frames_u8.shape[1]
+        frames_u8 = self.vae.decode_video(lat, output="uint8") if output_type == "uint8" or plan is not None else None
+        if plan is not None:      # the end of every reference run: save_videos_grid (magicanimate/utils/util.py:21-33)
             if save_audio is not None:
                 samples, rate = save_audio
                 first = math.floor(_as_fraction(kwargs.get("audio_start", 0), "audio_start") * rate)
-                count = math.floor(n_frames * rate / save_fps + Fraction(1, 2))
+                count = math.floor(frames_u8.shape[0] * frames_u8.shape[1] * rate / plan.rate + Fraction(1, 2))
                 save_audio = (samples[first:first + count], rate) if first < len(samples) else None      # cut where the audio ends
-            if save_gif:
-                video_io.write_gif(frames_u8, save_path, save_fps, **save_gif)
-            elif save_png and save_fps is None:
-                video_io.write_png(frames_u8, save_path, **save_png)
-            elif save_png:
-                video_io.write_apng(frames_u8, save_path, save_fps, **save_png)
-            else:
-                video_io.write_video(frames_u8, save_path, save_fps, save_quality, audio=save_audio,
-                                     restart_interval=kwargs.get("save_restart_interval"))
+            plan.write(frames_u8, save_audio)
         if output_type == "uint8":
             video = frames_u8
         elif self.vae is not None and output_type != "latent":

@@ -9,7 +9,7 @@
                     restart_interval= (MCUs, or "row") the scan is cut into restart intervals (T.81 E.1.4): a DRI segment, every interval
                     coded from DC predictions 0 (emo_jpeg_count_bits_ri, emo_jpeg_emit_bits_ri), padded and stuffed on its own, RSTm
                     markers between them - a file whose intervals decode_mjpeg decodes in parallel
-  write_avi         a classic RIFF `AVI ` file: hdrl (avih, a vids / MJPG stream, optionally an auds / PCM stream), movi with the 00dc and
+  avi_container, write_avi      a classic RIFF `AVI ` file: hdrl (avih, a vids / MJPG stream, optionally an auds / PCM stream), movi with the 00dc and
                     01wb chunks interleaved per frame, idx1.  Below 2^31 bytes (OpenDML is not written)
   read_avi          the reverse, for files write_avi made
   parse_jpeg        one baseline 4:2:0 file -> its size, tables and scan with the stuffed 0x00 bytes taken out (the reverse of jpeg_header
@@ -37,8 +37,12 @@
                     independently) -> ONE small read of the frames' symbol counts -> the Huffman code lengths, the canonical codes and
                     the header of one dynamic block per frame on the host (table building, like median cut) -> emo_png_deflate_bits /
                     emo_png_deflate_emit, one copy of the streams, then header, end-of-block, Adler-32 and the chunks on the host
-  save_videos_grid, images2video, video2images, save_images_grid      the reference surface: `.avi`, with format="gif" a `.gif`, with
-                    format="apng" an `.apng` (mp4 needs an encoder that is not here); the image grid as `.png` or `.jpg`
+  FORMATS           the one table of the files a clip is written as - avi, gif, apng, numbered png stills: per format its extension,
+                    the keywords it owns, whether it plays and holds sound, the checks of its options and of its rate, its encoder.
+                    Every writer of a clip runs one sequence over its record (_write_clip), and save_plan does for the pipeline's
+                    save_path= what the writers do for format=; all of them lay their streams out with _stream_layout
+  write_video, save_videos_grid, images2video, video2images, save_images_grid      the reference surface: `.avi`, with format="gif" a
+                    `.gif`, with format="apng" an `.apng` (mp4 needs an encoder that is not here); the image grid as `.png` or `.jpg`
 
 File IO and byte framing live here, on the host, like audio_io.read_wav; no arithmetic on pixels does (the grid of save_videos_grid is
 assembled by torch copies on the device; its `(x * 255)` truncated to uint8 is the reference's own line; the resize tables hold
@@ -212,44 +216,65 @@ def _device_tables(quality: int, device: str):
     return (torch.from_numpy(t.quant.copy()).to(device), torch.from_numpy(t.huff.astype(np.int64).astype(np.int32)).to(device))
 
 
+def _frames_u8(frames_u8, who, channels=(3,), dims=(4, 5), limit=None):
+    """The one check of the frames an encoder is handed, before any launch -> them as (n, H, W, C): a uint8 tensor of one of `dims`
+    dimensions ((H, W, C) is one frame, (1, n, H, W, C) is folded) whose last is one of `channels`, at least one frame.  limit=(name,
+    most) also holds every side to 1 .. most pixels (None: only to at least 1) and names the file format in the refusal."""
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in dims or frames_u8.shape[-1] not in channels:
+        c, what = ("3", "RGB frames") if tuple(channels) == (3,) else ("C", "frames with 1 (grey), 3 (RGB) or 4 (RGBA) channels")
+        shapes = {3: f"(H, W, {c})", 4: f"(n, H, W, {c})", 5: f"(1, n, H, W, {c}) as output_type=\"uint8\" returns them"}
+        raise ValueError(f"{who} takes packed uint8 {what}, {' or '.join(shapes[d] for d in dims)}, got "
+                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
+    if frames_u8.dim() != 4:
+        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[-3:])
+    n, height, width = (int(s) for s in frames_u8.shape[:3])
+    if n < 1:
+        raise ValueError(f"{who}: no frames")
+    if limit is not None and not (1 <= height <= (limit[1] or height) and 1 <= width <= (limit[1] or width)):
+        raise ValueError(f"{who}: a {limit[0]} frame is {f'1 .. {limit[1]} pixels' if limit[1] else 'at least 1 pixel'} each way, got {height} x {width}")
+    return frames_u8
+
+
+def _stream_layout(bits, head_bits=None, tail_bytes=0, totals=None):
+    """Where every unit's bits go in one buffer of streams.  bits: integer device tensor (rows, units), the bits of every unit (a JPEG
+    block, a GIF or PNG strip); a row - a frame, or one restart interval - is whatever must start on a byte, and inside it the units
+    follow each other bit by bit.  -> (offsets, starts, nbytes, out, totals): the bit offset of every unit in the buffer (int64,
+    contiguous, on bits' device), the byte start and the bytes of every row (int64 numpy), the zeroed uint8 buffer on that device, its
+    length rounded up to a multiple of 4 (the kernels OR whole dwords), and the rows' bit totals.  head_bits (per row, host) are left
+    free in front of a row's first unit, tail_bytes behind every row's last byte; totals= are the rows' bit totals behind the head
+    where the host knows them (they may count bits the caller adds behind the units) - without them they are read from the device,
+    the one read of a layout."""
+    ends = torch.cumsum(bits, dim=1, dtype=torch.int64)                         # bits, inside each row
+    totals = ends[:, -1].cpu().numpy() if totals is None else np.asarray(totals, np.int64)
+    head = np.zeros(len(totals), np.int64) if head_bits is None else np.asarray(head_bits, np.int64)
+    nbytes = (head + totals + 7) // 8 + int(tail_bytes)
+    starts = np.cumsum(nbytes) - nbytes
+    offsets = (ends - bits + torch.from_numpy(starts * 8 + head).to(ends.device)[:, None]).contiguous()
+    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=bits.device, dtype=torch.uint8)
+    return offsets, starts, nbytes, out, totals
+
+
 def encode_streams(frames_u8: torch.Tensor, quality: int = 90, restart_interval=None):
     """The device part of encode_mjpeg: (n, H, W, 3) uint8 device frames -> (streams uint8 device buffer, byte start of every frame, bits
     of every frame); three launches, one read of the n frame totals.  With restart_interval (restart_mcus) every restart interval starts
     on a byte: the starts and the bits come per interval, int64 (n, ceil(MCUs / interval)), from one read of as many totals."""
     quality = _check_quality(quality)
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
-        raise ValueError("encode_mjpeg takes packed uint8 RGB frames, (n, H, W, 3) or (1, n, H, W, 3) as output_type=\"uint8\" returns them, got "
-                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-    if frames_u8.dim() == 5:
-        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
-    if frames_u8.shape[0] < 1:
-        raise ValueError("encode_mjpeg: no frames")
+    frames_u8 = _frames_u8(frames_u8, "encode_mjpeg")
     ri = restart_mcus(restart_interval, frames_u8.shape[2])
     frames_u8 = frames_u8.contiguous()
     quant, huff = _device_tables(quality, str(frames_u8.device))
     coefs = ops.jpeg_blocks(frames_u8, quant)
-    if ri is not None:
-        n, n_mcu = int(coefs.shape[0]), int(coefs.shape[1])
-        ri = min(ri, n_mcu)
-        k = -(-n_mcu // ri)                                                      # intervals per frame; the last may be short
-        counts = ops.jpeg_count_bits(coefs, huff, restart_mcus=ri)
-        per = torch.nn.functional.pad(counts.to(torch.int64), (0, (k * ri - n_mcu) * 6)).view(n, k, ri * 6)
-        ends = torch.cumsum(per, dim=2)                                          # bits, inside each interval
-        bits = ends[:, :, -1].cpu().numpy()                                      # the one read: n * k totals
-        nbytes = (bits + 7) // 8
-        starts = (np.cumsum(nbytes.reshape(-1)) - nbytes.reshape(-1)).reshape(n, k).astype(np.int64)
-        offsets = (ends - per + torch.from_numpy(starts * 8).to(ends.device)[:, :, None]).view(n, k * ri * 6)[:, :n_mcu * 6].contiguous()
-        out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
-        ops.jpeg_emit_bits(coefs, huff, offsets, out, restart_mcus=ri)
-        return out, starts, bits
-    counts = ops.jpeg_count_bits(coefs, huff)
-    ends = torch.cumsum(counts, dim=1, dtype=torch.int64)                       # bits, inside each frame
-    bits = ends[:, -1].cpu().numpy()                                            # the one read before the streams themselves
-    nbytes = (bits + 7) // 8
-    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
-    offsets = (ends - counts + torch.from_numpy(starts * 8).to(ends.device)[:, None]).contiguous()
-    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
-    ops.jpeg_emit_bits(coefs, huff, offsets, out)
+    n, n_mcu = int(coefs.shape[0]), int(coefs.shape[1])
+    ri = None if ri is None else min(ri, n_mcu)
+    counts = ops.jpeg_count_bits(coefs, huff, restart_mcus=ri)
+    if ri is None:
+        offsets, starts, _, out, bits = _stream_layout(counts)
+    else:      # a row of the layout is one restart interval: k per frame, the last padded with blocks of no bits where it is short
+        k = -(-n_mcu // ri)
+        per = torch.nn.functional.pad(counts.to(torch.int64), (0, (k * ri - n_mcu) * 6)).view(n * k, ri * 6)
+        offsets, starts, _, out, bits = _stream_layout(per)
+        offsets, starts, bits = offsets.view(n, k * ri * 6)[:, :n_mcu * 6].contiguous(), starts.reshape(n, k), bits.reshape(n, k)
+    ops.jpeg_emit_bits(coefs, huff, offsets, out, restart_mcus=ri)
     return out, starts, bits
 
 
@@ -1089,8 +1114,8 @@ def _chunk(cid: bytes, body: bytes) -> bytes:
     return cid + struct.pack("<I", len(body)) + body + (b"\x00" if len(body) & 1 else b"")
 
 
-def write_avi(path, jpegs, width: int, height: int, fps, audio=None) -> None:
-    """JPEG frames (bytes each) -> a RIFF `AVI ` file at `path`: one vids / MJPG stream at fps = dwRate / dwScale and, with
+def avi_container(jpegs, width: int, height: int, fps, audio=None) -> bytes:
+    """JPEG frames (bytes each) -> a RIFF `AVI ` file as bytes: one vids / MJPG stream at fps = dwRate / dwScale and, with
     audio=(float samples (n,) | (n, channels), rate), one auds stream of 16-bit PCM.  movi holds, per frame, the 00dc chunk followed by
     the 01wb chunk of that frame's samples: sample boundaries are round(i * rate / fps), so no sample is lost or repeated, and whatever
     the audio has beyond the last frame goes with the last frame.  ValueError when the file would pass 2^31 - 1 bytes."""
@@ -1147,8 +1172,12 @@ def write_avi(path, jpegs, width: int, height: int, fps, audio=None) -> None:
     assert pos == movi_size, (pos, movi_size)
     body = b"AVI " + b"LIST" + struct.pack("<I", hdrl_size) + hdrl + b"LIST" + struct.pack("<I", movi_size) + b"".join(movi) + _chunk(b"idx1", b"".join(index))
     assert len(body) + 8 == total, (len(body) + 8, total)
-    with open(os.fspath(path), "wb") as fh:
-        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+def write_avi(path, jpegs, width: int, height: int, fps, audio=None) -> None:
+    """avi_container into the file at path"""
+    _write_file(path, avi_container(jpegs, width, height, fps, audio=audio))
 
 
 def _chunks(raw: bytes, pos: int, end: int):
@@ -1289,20 +1318,6 @@ def median_cut(hist, colors: int = 256):
     return palette, len(boxes)
 
 
-def _gif_frames(frames_u8, who):
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (4, 5) or frames_u8.shape[-1] != 3:
-        raise ValueError(f"{who} takes packed uint8 RGB frames, (n, H, W, 3) or (1, n, H, W, 3) as output_type=\"uint8\" returns them, got "
-                         f"{getattr(frames_u8, 'dtype', type(frames_u8))} {tuple(getattr(frames_u8, 'shape', ()))}")
-    if frames_u8.dim() == 5:
-        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
-    n, height, width = (int(s) for s in frames_u8.shape[:3])
-    if n < 1:
-        raise ValueError(f"{who}: no frames")
-    if not (1 <= height <= 65535 and 1 <= width <= 65535):
-        raise ValueError(f"{who}: a GIF frame is 1 .. 65535 pixels each way, got {height} x {width}")
-    return frames_u8
-
-
 def _gif_quantize_options(colors, palette, dither, dither_strength):
     colors = _int_in(colors, 2, 256, "colors=")
     if palette not in ("global", "frame"):
@@ -1321,7 +1336,7 @@ def quantize_frames(frames_u8: torch.Tensor, colors: int = 256, palette: str = "
     of its table (squared distance on the 8-bit values, the lowest index on a tie), after the ordered dither when dither="bayer":
     v + floor((2 B8[y & 7][x & 7] - 63) * dither_strength / 128) clamped to 0 .. 255, dither_strength 1 .. 128."""
     colors, palette, strength = _gif_quantize_options(colors, palette, dither, dither_strength)
-    frames_u8 = _gif_frames(frames_u8, "quantize_frames").contiguous()
+    frames_u8 = _frames_u8(frames_u8, "quantize_frames", limit=("GIF", 65535)).contiguous()
     n = int(frames_u8.shape[0])
     hist = ops.gif_histogram(frames_u8, per_frame=palette == "frame").cpu().numpy()
     palettes = np.zeros((hist.shape[0], 256, 3), np.uint8)
@@ -1342,17 +1357,20 @@ def _gif_strip_rows(strip_rows, height):
     return int(height) if strip_rows is None else _int_in(strip_rows, 1, 65535, "strip_rows= (None: the frame as one stream)")
 
 
+def _gif_check(loop=0, colors=256, palette="global", dither=None, dither_strength=32, strip_rows=GIF_STRIP_ROWS, prefix=""):
+    """the values of a GIF's options (prefix: how the caller spells loop=), before any launch"""
+    _int_in(loop, 0, 65535, f"{prefix}loop= (0: forever)")
+    _gif_quantize_options(colors, palette, dither, dither_strength)
+    _gif_strip_rows(strip_rows, 1)
+
+
 def gif_code_streams(indices: torch.Tensor, strip_rows=GIF_STRIP_ROWS):
     """The device part of the LZW coding: palette indices uint8 (n, H, W) on the device -> (streams uint8 device buffer, byte start of
     every frame, bytes of every frame); two launches and one read of the n frame totals between them.  Every frame starts on a byte;
     inside a frame the strips follow each other bit by bit."""
     rows = _gif_strip_rows(strip_rows, indices.shape[1])
     codes, n_codes, bits = ops.gif_lzw_count(indices, rows)
-    ends = torch.cumsum(bits, dim=1, dtype=torch.int64)
-    nbytes = (ends[:, -1].cpu().numpy() + 7) // 8                                # the one read before the streams themselves
-    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
-    offsets = (ends - bits + torch.from_numpy(starts * 8).to(ends.device)[:, None]).contiguous()
-    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=indices.device, dtype=torch.uint8)
+    offsets, starts, nbytes, out, _ = _stream_layout(bits)                       # the one read before the streams themselves
     ops.gif_lzw_emit(codes, n_codes, offsets, out, int(indices.shape[1]), int(indices.shape[2]), rows)
     return out, starts, nbytes
 
@@ -1400,35 +1418,19 @@ def encode_gif(frames_u8: torch.Tensor, fps, loop: int = 0, colors: int = 256, p
     cut into strips of strip_rows rows that are coded independently between Clear codes (None: one stream per frame), and the code
     streams come back in one copy.  Every frame is a whole frame: no differences between frames, no transparency.  All arguments are
     checked before the first launch."""
-    frames_u8 = _gif_frames(frames_u8, "encode_gif")
+    frames_u8 = _frames_u8(frames_u8, "encode_gif", limit=("GIF", 65535))
     n, height, width = (int(s) for s in frames_u8.shape[:3])
     delays = gif_delays(fps, n)
-    loop = _int_in(loop, 0, 65535, "loop= (0: forever)")
-    _gif_quantize_options(colors, palette, dither, dither_strength)
-    _gif_strip_rows(strip_rows, height)
+    _gif_check(loop, colors, palette, dither, dither_strength, strip_rows)
     indices, palettes, _ = quantize_frames(frames_u8, colors, palette, dither, dither_strength)
     out, starts, nbytes = gif_code_streams(indices, strip_rows)
     host = out.cpu().numpy()
     return gif_container(width, height, palettes, [host[s:s + b] for s, b in zip(starts, nbytes)], delays, loop)
 
 
-def _gif_path(path, who):
-    path = os.fspath(path)
-    if os.path.splitext(path)[1].lower() != ".gif":
-        raise ValueError(f"{who} writes an animated GIF: name the file `.gif`, got {path!r}")
-    return path
-
-
 def write_gif(frames_u8: torch.Tensor, path, fps, **options) -> None:
     """encode_gif (with its options) into the `.gif` file at path"""
-    path = _gif_path(path, "write_gif")
-    unknown = sorted(set(options) - set(GIF_OPTIONS))
-    if unknown:
-        raise ValueError(f"write_gif: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; a GIF takes {', '.join(GIF_OPTIONS)}")
-    data = encode_gif(frames_u8, fps, **options)
-    _makedirs_for(path)
-    with open(path, "wb") as fh:
-        fh.write(data)
+    _write_clip("write_gif", lambda: frames_u8, path, fps, FORMATS["gif"], None, options)
 
 
 # ---------------------------------------------------------------------------------------------------------------------- PNG / APNG
@@ -1710,21 +1712,11 @@ def apng_container(width: int, height: int, channels: int, streams, fps, loop: i
     return b"".join(out)
 
 
-def _png_frames(frames_u8, who):
-    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (3, 4, 5) or frames_u8.shape[-1] not in PNG_COLOUR_TYPES:
-        raise ValueError(f"{who} takes packed uint8 frames with 1 (grey), 3 (RGB) or 4 (RGBA) channels, (H, W, C), (n, H, W, C) or the "
-                         f"(1, n, H, W, C) of output_type=\"uint8\", got {getattr(frames_u8, 'dtype', type(frames_u8))} "
-                         f"{tuple(getattr(frames_u8, 'shape', ()))}")
-    if frames_u8.dim() == 3:
-        frames_u8 = frames_u8[None]
-    elif frames_u8.dim() == 5:
-        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
-    n, height, width = (int(s) for s in frames_u8.shape[:3])
-    if n < 1:
-        raise ValueError(f"{who}: no frames")
-    if height < 1 or width < 1:
-        raise ValueError(f"{who}: a PNG frame is at least 1 pixel each way, got {height} x {width}")
-    return frames_u8
+def _png_check(filter="adaptive", strip_rows=PNG_STRIP_ROWS, loop=0, prefix=""):
+    """the values of the PNG writers' options (prefix: how the caller spells loop=), before any launch"""
+    _int_in(loop, 0, 2 ** 31 - 1, f"{prefix}loop= (0: forever)")
+    _png_filter(filter)
+    png_strip_rows(strip_rows, 1, 1, 1)
 
 
 def _png_filter(filter):
@@ -1749,7 +1741,7 @@ def png_zlib_streams(frames_u8: torch.Tensor, filter: str = "adaptive", strip_ro
     launches - emo_png_filter, emo_png_lz_count, [the tables], emo_png_deflate_bits, a scan, emo_png_deflate_emit - around ONE small
     read (the n histograms and the rows' Adler-32 pairs) and the copy of the streams.  The sizes of all frames follow from the
     histograms and the code lengths, so the buffer is sized without a second read."""
-    frames_u8 = _png_frames(frames_u8, "png_zlib_streams").contiguous()
+    frames_u8 = _frames_u8(frames_u8, "png_zlib_streams", tuple(PNG_COLOUR_TYPES), (3, 4, 5), ("PNG", None)).contiguous()
     n, height, width, channels = (int(s) for s in frames_u8.shape)
     rows = png_strip_rows(strip_rows, height, width, channels)
     filtered, adler = ops.png_filter(frames_u8, _png_filter(filter))
@@ -1760,11 +1752,8 @@ def png_zlib_streams(frames_u8: torch.Tensor, filter: str = "adaptive", strip_ro
     bits = ops.png_deflate_bits(tokens, n_tokens, codes, height, width, channels, rows)
     token_bits = np.array([t.token_bits(h) for t, h in zip(tables, hist_host)], np.int64)
     head = np.array([16 + t.header_bits for t in tables], np.int64)
-    nbytes = (head + token_bits + np.array([t.end_of_block[1] for t in tables], np.int64) + 7) // 8 + 4
-    starts = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
-    ends = torch.cumsum(bits, dim=1, dtype=torch.int64)
-    offsets = (ends - bits + torch.from_numpy(starts * 8 + head).to(ends.device)[:, None]).contiguous()
-    out = torch.zeros((int(nbytes.sum()) + 3) // 4 * 4, device=frames_u8.device, dtype=torch.uint8)
+    # in front of a frame's tokens the zlib and block headers, behind them the end-of-block code, then 4 bytes of Adler-32
+    offsets, starts, nbytes, out, _ = _stream_layout(bits, head, 4, token_bits + np.array([t.end_of_block[1] for t in tables], np.int64))
     ops.png_deflate_emit(tokens, n_tokens, codes, offsets, out, height, width, channels, rows)
     host = out.cpu().numpy()
     return [zlib_stream(host[s:s + b], t, tb, adler32_combine(a, 1 + width * channels))
@@ -1778,9 +1767,9 @@ def encode_png(frames_u8: torch.Tensor, filter: str = "adaptive", strip_rows=PNG
     and IEND.  filter="adaptive" picks per scanline the filter type with the smallest sum of absolute differences (libpng's
     heuristic); "none" | "sub" | "up" | "average" | "paeth" forces one.  strip_rows scanlines form a strip whose matches stay inside
     it (None: the whole frame; lowered where a strip would pass 65535 bytes); one dynamic Huffman block per frame either way."""
-    frames_u8 = _png_frames(frames_u8, "encode_png")
+    frames_u8 = _frames_u8(frames_u8, "encode_png", tuple(PNG_COLOUR_TYPES), (3, 4, 5), ("PNG", None))
     height, width, channels = (int(s) for s in frames_u8.shape[1:])
-    _png_filter(filter)
+    _png_check(filter, strip_rows)
     png_strip_rows(strip_rows, height, width, channels)
     return [png_container(width, height, channels, s) for s in png_zlib_streams(frames_u8, filter, strip_rows)]
 
@@ -1789,11 +1778,10 @@ def encode_apng(frames_u8: torch.Tensor, fps, loop: int = 0, filter: str = "adap
     """The same frames -> one animated PNG as bytes, playing at exactly fps (apng_delay: the reduced fraction's terms must fit 16
     bits) and repeating `loop` times (0: forever).  Every frame is a whole frame (dispose 0, blend 0): no differences between frames.
     All arguments are checked before the first launch."""
-    frames_u8 = _png_frames(frames_u8, "encode_apng")
+    frames_u8 = _frames_u8(frames_u8, "encode_apng", tuple(PNG_COLOUR_TYPES), (3, 4, 5), ("PNG", None))
     height, width, channels = (int(s) for s in frames_u8.shape[1:])
     apng_delay(fps)
-    _int_in(loop, 0, 2 ** 31 - 1, "loop= (0: forever)")
-    _png_filter(filter)
+    _png_check(filter, strip_rows, loop)
     png_strip_rows(strip_rows, height, width, channels)
     return apng_container(width, height, channels, png_zlib_streams(frames_u8, filter, strip_rows), fps, loop)
 
@@ -1801,9 +1789,7 @@ def encode_apng(frames_u8: torch.Tensor, fps, loop: int = 0, filter: str = "adap
 def _png_pattern(path, who):
     """a `.png` path -> (path, whether its file name holds one %d-style field for the frame's number)"""
     import re
-    path = os.fspath(path)
-    if os.path.splitext(path)[1].lower() != ".png":
-        raise ValueError(f"{who} writes PNG stills: name the file `.png`, or with a field for the frame's number as in `frame_%04d.png`, got {path!r}")
+    path = _path_with(path, who, (".png",), "PNG stills (one, or numbered ones with a field for the frame's number as in `frame_%04d.png`)")
     name = os.path.basename(path).replace("%%", "")
     numbered = re.findall(r"%0?\d*d", name)
     if name.count("%") != len(numbered) or len(numbered) > 1 or "%" in os.path.dirname(path):
@@ -1815,37 +1801,21 @@ def write_png(frames_u8: torch.Tensor, path, filter: str = "adaptive", strip_row
     """encode_png into files: a path whose name holds a %d-style field (`frames/frame_%04d.png`) takes any number of frames as numbered
     stills, counted from 0; a plain `.png` path takes exactly one frame.  -> the paths written"""
     path, numbered = _png_pattern(path, "write_png")
-    frames_u8 = _png_frames(frames_u8, "write_png")
+    frames_u8 = _frames_u8(frames_u8, "write_png", tuple(PNG_COLOUR_TYPES), (3, 4, 5), ("PNG", None))
     n = int(frames_u8.shape[0])
     if n > 1 and not numbered:
         raise ValueError(f"write_png: {n} frames and one file name {path!r}: put a field for the frame's number into it, as in `frame_%04d.png`, "
                          "for numbered stills, or write an animated `.apng` (encode_apng, write_video(format=\"apng\"))")
     files = encode_png(frames_u8, filter, strip_rows)
     paths = [path % i for i in range(n)] if numbered else [path]
-    _makedirs_for(paths[0])
     for p, data in zip(paths, files):
-        with open(p, "wb") as fh:
-            fh.write(data)
+        _write_file(p, data)
     return paths
-
-
-def _apng_path(path, who):
-    path = os.fspath(path)
-    if os.path.splitext(path)[1].lower() != ".apng":
-        raise ValueError(f"{who} writes an animated PNG: name the file `.apng`, got {path!r}")
-    return path
 
 
 def write_apng(frames_u8: torch.Tensor, path, fps, **options) -> None:
     """encode_apng (with its options) into the `.apng` file at path"""
-    path = _apng_path(path, "write_apng")
-    unknown = sorted(set(options) - set(PNG_OPTIONS))
-    if unknown:
-        raise ValueError(f"write_apng: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; an APNG takes {', '.join(PNG_OPTIONS)}")
-    data = encode_apng(frames_u8, fps, **options)
-    _makedirs_for(path)
-    with open(path, "wb") as fh:
-        fh.write(data)
+    _write_clip("write_apng", lambda: frames_u8, path, fps, FORMATS["apng"], None, options)
 
 
 def save_images_grid(images: torch.Tensor, path: str, quality: int = 90):
@@ -1853,87 +1823,163 @@ def save_images_grid(images: torch.Tensor, path: str, quality: int = 90):
     lays out with its defaults (8 per row, 2 pixels of padding; make_grid_u8), `* 255` truncated to uint8 as :39 does.  `.png` is written
     lossless (encode_png), `.jpg` / `.jpeg` as one baseline JPEG frame at `quality` (the frame encode_mjpeg makes).  The file is
     encoded on the HIP device: images held on the host are uploaded."""
-    path = os.fspath(path)
-    ext = os.path.splitext(path)[1].lower()
-    if ext not in (".png", ".jpg", ".jpeg"):
-        raise ValueError(f"save_images_grid writes `.png` (lossless) or `.jpg` / `.jpeg` files, got {path!r}")
+    path = _path_with(path, "save_images_grid", (".png", ".jpg", ".jpeg"), "one image, lossless as PNG or as a baseline JPEG")
     if not torch.is_tensor(images) or images.dim() != 5 or images.shape[2] != 1:
         raise ValueError(f"save_images_grid takes a float (b, c, 1, h, w) tensor, got {tuple(getattr(images, 'shape', ()))}")
     _check_quality(quality)
     if not images.is_cuda:
         images = images.to("cuda")
     grid = make_grid_u8(images, n_rows=8)                                        # (1, Hg, Wg, 3)
-    if ext == ".png":
+    if path.lower().endswith(".png"):
         data = encode_png(grid)[0]
     else:
         out, starts, bits = encode_streams(grid, quality)
         data = jpeg_header(int(grid.shape[1]), int(grid.shape[2]), int(quality)) + finish_scan(out.cpu().numpy()[int(starts[0]):], int(bits[0]))
-    _makedirs_for(path)
+    _write_file(path, data)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- reference surface
+def encode_avi(frames_u8: torch.Tensor, fps, quality: int = 90, restart_interval=None, audio=None) -> bytes:
+    """(n, H, W, 3) uint8 device frames -> a Motion-JPEG `.avi` file as bytes: encode_mjpeg (with its restart_interval) + avi_container"""
+    jpegs = encode_mjpeg(frames_u8, quality, restart_interval)                   # (checks the arguments)
+    return avi_container(jpegs, int(frames_u8.shape[-2]), int(frames_u8.shape[-3]), fps, audio=audio)
+
+
+def _avi_check(quality=90, restart_interval=None, prefix=""):
+    _check_quality(quality)
+    restart_mcus(restart_interval, 16)
+
+
+@dataclasses.dataclass(frozen=True)
+class OutputFormat:
+    """One file format of the writers.  FORMATS holds them all, and what a writer or the pipeline's save_path= decides per format is
+    read from it: the path it takes, the keywords it takes and whose the others are, whether fps= and audio= mean anything to it."""
+    format: object      # the format= of write_video, save_videos_grid and images2video that selects it; save_path= goes by ext
+    ext: str
+    noun: str           # what the refusals call it
+    options: tuple      # the keywords it owns
+    check: object       # (**options, prefix=): refuses a bad value of one, before any launch
+    encode: object      # (frames_u8, fps, **options) -> the file's bytes; stills, which write_png numbers: no fps, one file per frame
+    plays: bool = True  # it has a frame rate, so fps= is needed
+    rate: object = None     # (fps, n_frames): refuses a rate such a file cannot hold, where there is one
+    sound: bool = False     # it holds audio=
+
+
+FORMATS = {
+    "avi": OutputFormat(None, ".avi", "a Motion-JPEG `.avi` file", ("quality", "restart_interval"), _avi_check, encode_avi, sound=True),
+    "gif": OutputFormat("gif", ".gif", "an animated GIF", GIF_OPTIONS, _gif_check, encode_gif, rate=gif_delays),
+    "apng": OutputFormat("apng", ".apng", "an animated PNG", PNG_OPTIONS, _png_check, encode_apng, rate=lambda fps, n: apng_delay(fps)),
+    "png": OutputFormat("png", ".png", "numbered PNG stills", PNG_OPTIONS[:2], _png_check, encode_png, plays=False),
+}
+# option -> the keyword of the pipeline call that carries it
+SAVE_KEYWORDS = {"quality": "save_quality", "restart_interval": "save_restart_interval", "palette": "save_palette", "dither": "save_dither",
+                 "dither_strength": "save_dither_strength", "loop": "save_loop", "filter": "save_png_filter"}
+
+
+def _listed(words, last="and") -> str:
+    words = list(words)
+    return words[0] if len(words) == 1 else f"{', '.join(words[:-1])} {last} {words[-1]}"
+
+
+def _path_with(path, who, exts, hint):
+    """path as a str where it ends in one of exts, in either case; the refusal says what `who` writes - hint - and names exts"""
+    path = os.fspath(path)
+    if os.path.splitext(path)[1].lower() not in exts:
+        raise ValueError(f"{who} writes {hint}: name the file {_listed((f'`{e}`' for e in exts), 'or')}, got {path!r}")
+    return path
+
+
+def _write_file(path, data) -> None:
+    d = os.path.dirname(os.fspath(path))
+    if d:
+        os.makedirs(d, exist_ok=True)            # util.py:32
     with open(path, "wb") as fh:
         fh.write(data)
 
 
-# ---------------------------------------------------------------------------------------------------------------------- reference surface
-def _avi_path(path, who, gif_hint="pass format=\"gif\" with a `.gif` path for an animated GIF"):
-    path = os.fspath(path)
-    if os.path.splitext(path)[1].lower() != ".avi":
-        raise ValueError(f"{who} writes Motion-JPEG `.avi` files, got {path!r}: name the file `.avi`, or {gif_hint} (mp4 needs an encoder "
-                         "that is not part of this build)")
-    return path
+def _given(options) -> dict:
+    """the options that were set: not None, and not the quality the writers have as their default"""
+    return {k: v for k, v in options.items() if v is not None and (k != "quality" or v != 90)}
 
 
-def _output_path(path, who, format, quality, restart_interval, gif_options):
-    """what the writers of the reference surface check before anything runs -> (path, the format: None, "gif" or "apng")"""
-    if format is None:
-        if gif_options:
-            owner = "apng" if set(gif_options) - set(GIF_OPTIONS) and not set(gif_options) - set(PNG_OPTIONS) else "gif"
-            raise ValueError(f"{who}: {', '.join(sorted(gif_options))} belong{'s' if len(gif_options) == 1 else ''} to format=\"{owner}\"")
-        return _avi_path(path, who), None
-    if isinstance(format, str) and format == "apng":
-        path = _apng_path(path, f"{who} with format=\"apng\"")
-        unknown = sorted(set(gif_options) - set(PNG_OPTIONS))
-        if unknown:
-            raise ValueError(f"{who}: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; an APNG takes {', '.join(PNG_OPTIONS)}")
-        if quality != 90 or restart_interval is not None:
-            raise ValueError(f"{who}: quality= and restart_interval= belong to the JPEG frames of an `.avi` file; an APNG is lossless and takes "
-                             f"{', '.join(PNG_OPTIONS)}")
-        return path, "apng"
-    if not isinstance(format, str) or format != "gif":
-        raise ValueError(f"{who}: format= takes None (a Motion-JPEG `.avi` file), \"gif\" or \"apng\", got {format!r}")
-    path = _gif_path(path, f"{who} with format=\"gif\"")
-    unknown = sorted(set(gif_options) - set(GIF_OPTIONS))
-    if unknown:
-        raise ValueError(f"{who}: unknown option{'s' if len(unknown) > 1 else ''} {', '.join(unknown)}; a GIF takes {', '.join(GIF_OPTIONS)}")
-    if quality != 90 or restart_interval is not None:
-        raise ValueError(f"{who}: quality= and restart_interval= belong to the JPEG frames of an `.avi` file; a GIF takes {', '.join(GIF_OPTIONS)}")
-    return path, "gif"
+def _own_options(record, options, who, save=False) -> None:
+    """Refuses the options `record` does not own, before anything runs, and says which format owns them.  save: the caller is the
+    pipeline call, which spells the options as SAVE_KEYWORDS does, knows no others, and selects a format by save_path's extension."""
+    def names(options):
+        return _listed([f"{SAVE_KEYWORDS[k]}=" for k in options if k in SAVE_KEYWORDS] if save else [f"{k}=" for k in options])
+    foreign = sorted(set(options) - set(record.options))
+    if foreign:
+        owners = dict.fromkeys(next((r for r in FORMATS.values() if k in r.options), None) for k in foreign)      # the first that owns it
+        how = (lambda r: f"`{r.ext}` save_path") if save else (lambda r: f"format=\"{r.format}\", `{r.ext}` path" if r.format else f"`{r.ext}` path, no format=")
+        raise ValueError(f"{who}: unknown option{'s' if len(foreign) > 1 else ''} {names(foreign)} for {record.noun}, which takes {names(record.options)}"
+                         + "".join(f"; {names(r.options)} belong to {r.noun} ({how(r)})" for r in owners if r is not None))
 
 
-def _makedirs_for(path):
-    d = os.path.dirname(path)
-    if d:
-        os.makedirs(d, exist_ok=True)            # util.py:32
+def _write_clip(who, frames, path, fps, record, audio, options, hint=None) -> None:
+    """The one sequence behind every writer of a clip: the path has the format's extension, the options are the format's own, audio=
+    comes only where the format holds sound - all before frames() is asked for the frames, so before anything is uploaded or
+    launched; then encode, which checks the frames and the options' values before its first launch, and write."""
+    path = _path_with(path, who, (record.ext,), hint or record.noun)
+    _own_options(record, options, who)
+    if audio is not None and not record.sound:
+        raise ValueError(f"{who}: {record.noun} holds no sound: audio= has no place in one; write an `.avi` file for audio=")
+    _write_file(path, record.encode(frames(), fps, **options, **({} if audio is None else {"audio": audio})))
 
 
-def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None, format=None, **gif_options) -> None:
-    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + write_avi.  With format="gif" and a
-    `.gif` path: an animated GIF instead (write_gif; its options - loop, colors, palette, dither, dither_strength, strip_rows - as
-    keywords; quality=, restart_interval= and audio= have no place in one and are refused).  With format="apng" and an `.apng` path:
-    a lossless animated PNG (write_apng; its options are filter, strip_rows and loop; the same three keywords are refused)."""
-    path, kind = _output_path(path, "write_video", format, quality, restart_interval, gif_options)
-    if kind == "gif":
-        if audio is not None:
-            raise ValueError("write_video: a GIF holds no sound; write an `.avi` file for audio=")
-        return write_gif(frames_u8, path, fps, **gif_options)
-    if kind == "apng":
-        if audio is not None:
-            raise ValueError("write_video: an APNG holds no sound: audio= has no place in one; write an `.avi` file for audio=")
-        return write_apng(frames_u8, path, fps, **gif_options)
-    if frames_u8.dim() == 5:
-        frames_u8 = frames_u8.reshape(-1, *frames_u8.shape[2:])
-    jpegs = encode_mjpeg(frames_u8, quality, restart_interval)
-    _makedirs_for(path)
-    write_avi(path, jpegs, int(frames_u8.shape[2]), int(frames_u8.shape[1]), fps, audio=audio)
+def _write_video(who, frames, path, fps, quality, audio, restart_interval, format, options) -> None:
+    """write_video, for it and for the two entries of the reference surface, which hand over frames() they make only once nothing is refused"""
+    named = {r.format: r for r in FORMATS.values() if r.plays}
+    if not isinstance(format, (str, type(None))) or format not in named:
+        raise ValueError(f"{who}: format= takes {_listed((f'{f!r} for {r.noun}' for f, r in named.items()), 'or')}, got {format!r}")
+    hint = None if format is not None else named[None].noun + " (" + ", ".join(
+        f"format=\"{f}\" with a `{r.ext}` path writes {r.noun}" for f, r in named.items() if f) + "; mp4 needs an encoder that is not part of this build)"
+    _write_clip(who if format is None else f"{who} with format=\"{format}\"", frames, path, fps, named[format], audio,
+                {**_given(dict(quality=quality, restart_interval=restart_interval)), **options}, hint)
+
+
+def write_video(frames_u8: torch.Tensor, path, fps, quality: int = 90, audio=None, restart_interval=None, format=None, **options) -> None:
+    """(n, H, W, 3) uint8 device frames -> an `.avi` file: encode_mjpeg (with its restart_interval) + avi_container.  With format="gif"
+    and a `.gif` path: an animated GIF instead (encode_gif; its options - loop, colors, palette, dither, dither_strength, strip_rows -
+    as keywords).  With format="apng" and an `.apng` path: a lossless animated PNG (encode_apng; its options are filter, strip_rows
+    and loop).  FORMATS says which keywords a format owns; another format's are refused by its name, and so is audio= where the format
+    holds no sound."""
+    _write_video("write_video", lambda: frames_u8, path, fps, quality, audio, restart_interval, format, options)
+
+
+@dataclasses.dataclass(frozen=True)
+class SavePlan:
+    """What save_path= of the pipeline call writes once the frames exist (save_plan): the file's format, its path, the rate it plays at
+    (None: stills) and the options that were set."""
+    record: OutputFormat
+    path: str
+    rate: object
+    options: dict
+
+    def write(self, frames_u8, audio=None):
+        if not self.record.plays:
+            return write_png(frames_u8, self.path, **self.options)
+        _write_clip("save_path=", lambda: frames_u8, self.path, self.rate, self.record, audio, self.options)
+
+
+def save_plan(save_path, n_frames: int, fps, interpolation_factor: int, options: dict) -> SavePlan:
+    """Everything save_path= of the pipeline call can be refused for before the denoising loop, in one place: the extension names a
+    format of FORMATS; `options` - the call's save_* keywords by the option they carry (SAVE_KEYWORDS), None where not given - are
+    that format's own and hold values it takes; n_frames stills have a numbered name; the rate, fps * interpolation_factor, is one
+    the file can hold.  fps=None leaves the rate open, which only stills may (SavePlan.rate stays None)."""
+    path = _path_with(save_path, "save_path=", tuple(r.ext for r in FORMATS.values()), _listed((r.noun for r in FORMATS.values()), "or"))
+    record = next(r for r in FORMATS.values() if r.ext == os.path.splitext(path)[1].lower())
+    options = _given(options)
+    _own_options(record, options, "save_path=", save=True)
+    record.check(**options, prefix="save_")
+    if not record.plays and not _png_pattern(path, "save_path=")[1] and n_frames > 1:
+        raise ValueError(f"save_path={path!r} names one `.png` file for {n_frames} frames: put a field for the frame's number "
+                         "into the name, as in `frames/f_%04d.png`, or name the file `.apng` for an animated PNG")
+    rate = None
+    if record.plays and fps is not None:
+        rate = fps_fraction(fps * int(interpolation_factor))
+        if record.rate is not None:
+            record.rate(rate, n_frames)
+    return SavePlan(record, path, rate, options)
 
 
 def make_grid_u8(videos: torch.Tensor, rescale=False, n_rows=6) -> torch.Tensor:
@@ -1963,23 +2009,20 @@ def make_grid_u8(videos: torch.Tensor, rescale=False, n_rows=6) -> torch.Tensor:
 
 
 def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=6, fps=25, quality: int = 90, restart_interval=None, format=None,
-                     **gif_options):
+                     **options):
     """magicanimate/utils/util.py:21-33 with a Motion-JPEG `.avi` in place of imageio.mimsave.  The frames are encoded on the HIP device:
     videos held on the host are uploaded.  restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes the animated GIF
     mimsave would, format="apng" with an `.apng` path a lossless animated PNG (write_video)."""
-    path, _ = _output_path(path, "save_videos_grid", format, quality, restart_interval, gif_options)
-    if torch.is_tensor(videos) and not videos.is_cuda:
-        videos = videos.to("cuda")
-    write_video(make_grid_u8(videos, rescale, n_rows), path, fps, quality, restart_interval=restart_interval, format=format, **gif_options)
+    frames = lambda: make_grid_u8(videos if not torch.is_tensor(videos) or videos.is_cuda else videos.to("cuda"), rescale, n_rows)
+    _write_video("save_videos_grid", frames, path, fps, quality, None, restart_interval, format, options)
 
 
-def images2video(video, path, fps=8, quality: int = 90, restart_interval=None, format=None, **gif_options):
+def images2video(video, path, fps=8, quality: int = 90, restart_interval=None, format=None, **options):
     """util.py:111-113: a sequence of (H, W, 3) uint8 frames (arrays, or one (t, H, W, 3) array / tensor) -> an `.avi` file.
     restart_interval as in encode_mjpeg.  format="gif" with a `.gif` path writes an animated GIF, format="apng" with an `.apng` path a
     lossless animated PNG (write_video)."""
-    path, _ = _output_path(path, "images2video", format, quality, restart_interval, gif_options)
-    frames = video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))
-    write_video(frames.to("cuda"), path, fps, quality, restart_interval=restart_interval, format=format, **gif_options)
+    frames = lambda: (video if torch.is_tensor(video) else torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(f) for f in video])))).to("cuda")
+    _write_video("images2video", frames, path, fps, quality, None, restart_interval, format, options)
 
 
 def decode_jpeg(data: bytes) -> np.ndarray:
