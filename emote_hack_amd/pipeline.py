@@ -1,21 +1,6 @@
 """EMOAnimationPipeline - the sampling loop of the reference (EMOAnimationPipeline.py:543-840) on
-MI355X.  Same `__call__` signature; the hot loop (`:698-823`) is re-designed:
-
-  * per step: Backbone read passes over this rank's work units -> (all_gather of the eps slices) -> window average + CFG +
-    scheduler step fused in ONE HIP kernel (emo_sched_step) on f32 master latents;
-  * the ReferenceNet banks depend on the timestep only (never on the latents), so the write pass is hoisted out of the
-    step: T timesteps (reference_group, default 10) go through ONE batched pass (M is T times larger: the batch-1 pass of
-    the reference is a small-M, launch-bound workload), their K / V^T projections with the Backbone's attn1 weights are
-    computed once, kept resident in HBM (2 groups x 28 MB x T at 512^2) and selected per step by a device-side row index;
-    the pass of group g+1 runs on a second HIP stream while the Backbone works through group g.  With world_size > 1 the
-    ranks deal a group's timesteps among themselves and swap the banks with one RCCL all_gather (north_star: "all-gather
-    over xGMI to broadcast ReferenceNet features");
-  * work units are (context window x CFG branch): rank r owns U[r::world_size]; a UNet call batches the
-    rank's next 2*context_batch_size units, uncond first - at world_size 1 exactly the reference's batch (:759-763).  The
-    reference's gather-to-root + broadcast (:796-821) is replaced by ONE all_gather of the eps slices, after which every rank
-    accumulates all units in the same order and runs the (deterministic, counter-based-noise) sampler step redundantly -
-    no broadcast, bit-identical latents on all ranks;
-  * the attn2 K / V^T projections of the text / audio context are computed once per clip, not per step.
+MI355X.  Same `__call__` signature; the hot loop (`:698-823`) is re-designed and lives in emote_hack_amd/denoise_loop.py (DenoiseLoop, the
+base class: prepare_denoise, denoise_step, denoise, reset_denoise, denoise_chained); this module keeps the reference-named surface.
 
 Prompts are encoded by `_encode_prompt` (:202-289) with the caller's tokenizer and a text encoder on the pipeline - on these kernels
 emote_hack_amd.clip_text.CLIPTextModel; `text_embeddings=` still takes precedence.
@@ -24,21 +9,18 @@ wav2vec (`audio_features=`, windowed by emote_hack_amd.conditioning.audio_window
 """
 from __future__ import annotations
 
-import copy
 import logging
 import math
 import numbers
 import os
 from dataclasses import dataclass
 from fractions import Fraction
-from types import SimpleNamespace
 from typing import Callable, List, Optional, Union
 
 import torch
 
 from . import ops
-from .context import get_context_scheduler
-from .reference_control import ReferenceAttentionControl
+from .denoise_loop import DenoiseLoop
 
 logger = logging.getLogger(__name__)
 
@@ -46,10 +28,6 @@ logger = logging.getLogger(__name__)
 @dataclass
 class AnimationPipelineOutput:  # EMOAnimationPipeline.py:79-81
     videos: Union[torch.Tensor, "object"]
-
-
-def _default(v, d):
-    return d if v is None else v
 
 
 # ---- magicanimate/utils/util.py:116-140 (the frame interpolation `interpolate_latents` uses)
@@ -78,7 +56,7 @@ def slerp(v0: torch.Tensor, v1: torch.Tensor, t: float, DOT_THRESHOLD: float = 0
     return (((1.0 - t) * omega).sin() * v0 + (t * omega).sin() * v1) / omega.sin()
 
 
-class EMOAnimationPipeline:
+class EMOAnimationPipeline(DenoiseLoop):
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, controlnet=None, scheduler=None, image_encoder=None,
                  image_processor=None, speed_encoder=None, face_region_controller=None, face_locator=None):
         """EMOAnimationPipeline.py:87-130.  The ctor forces steps_offset=1 / clip_sample=False on the
@@ -185,804 +163,6 @@ class EMOAnimationPipeline:
         cond = enc(pixel_values.to(device)).image_embeds.unsqueeze(1)                          # (b, 1, D)
         cond = cond.repeat(1, num_videos_per_prompt, 1).view(cond.shape[0] * num_videos_per_prompt, 1, -1)
         return torch.cat([torch.zeros_like(cond), cond]) if do_classifier_free_guidance else cond
-
-    # ------------------------------------------------------------------ the hot loop
-    @torch.no_grad()
-    def prepare_denoise(self, latents, ref_image_latents, text_embeddings, *, appearance_encoder, num_inference_steps=50,
-                        guidance_scale=7.5, eta=0.0, context_frames=16, context_stride=1, context_overlap=4,
-                        context_batch_size=1, context_schedule="uniform", audio_features=None, speed_embeddings=None, seed=0,
-                        fusion_blocks="midup", dist=False, rank=0, world_size=1, return_eps=False, use_graphs=None,
-                        controlnet=None, controlnet_cond=None, controlnet_conditioning_scale=1.0, reference_group=10,
-                        reference_lookahead=None, motion_latents=None, text_pairing="reference", _emulate_rank=None, face_mask=None,
-                        face_mask_threshold=None):
-        """Set up the loop state (EMOAnimationPipeline.py:628-696).  latents f32 (1,4,F_tot,h,w);
-        ref_image_latents (1,4,h,w); text_embeddings (2,L,D) = [uncond, cond].
-        reference_group = T: ReferenceNet timesteps computed per batched pass (1 = the reference's per-step order).
-        use_graphs: None (default) = HIP-graph replay of the UNet / ReferenceNet passes whenever the model lives on a HIP device
-        (the path bench.py measures; ~1700 launches per step leave the host), False = every kernel launched from Python.
-        The state splits into a PLAN (geometry, buffers, captured graphs - everything above `_bind_inputs`) and the INPUTS
-        (latents, reference image, text / audio / speed conditioning, ControlNet images, guidance scale, seed), which are copied
-        into the plan's buffers in place: `reset_denoise` re-arms a prepared state for another clip of the same geometry.
-        motion_latents (n_m, 4, h, w): latents of the previous clip's last frames - they go through the ReferenceNet next to the
-        reference image and their LN1 features join the banks as extra tokens (see denoise_chained).
-        text_pairing (matters at context_batch_size > 1 only): "reference" = the upstream row pairing, literally (see `unit_tv`
-        below: odd windows of a batch run their uncond row under the cond text and vice versa, which cancels guidance for them);
-        "branch" = the evidently intended one, every uncond row under the uncond text, every cond row under the cond text and the
-        cond-text bank - the same function as context_batch_size 1, batched.
-        _emulate_rank=(r, n): MEASUREMENT aid (bench.py --emulate-rank): the work of rank r of an n-rank job - its units, its share of every
-        ReferenceNet group, the projection of the whole group - in ONE process without collectives (the other ranks' eps slices are
-        missing, so the latents are not a sample of anything): a rank's critical path per step on an otherwise idle GPU.
-        speed_embeddings (1 | 2, 4*C0) is one embedding per clip, (1 | 2, F_tot, 4*C0) one per frame: every UNet call gathers its
-        windows' rows with the indices the audio context uses.  face_mask: an (H, W) / (1, 1, H, W) map at pixel or latent size (see
-        `__call__`); the pipeline's FaceRegionController turns it into (h*w, C0) rows ONCE per clip and every UNet call adds them behind
-        conv_in.  face_mask_threshold=t pools (mask > t) instead of the mask (FaceLocator logits: t = 0).  Both inputs are replicated
-        on every rank."""
-        if text_pairing not in ("reference", "branch"):
-            raise ValueError(f"text_pairing must be 'reference' or 'branch', got {text_pairing!r}")
-        unet, sch = self.unet, self.scheduler
-        dev = unet.device
-        if face_mask is not None:      # (argument errors before anything is allocated or launched)
-            self._check_face_mask(face_mask, latents.shape[3] * self.vae_scale_factor, latents.shape[4] * self.vae_scale_factor)
-        self._check_speed_embeddings(speed_embeddings, latents.shape[2])
-        # `do_classifier_free_guidance = guidance_scale > 1.0` (:622).  Without it the UNet batch is the window batch (:759-763
-        # `.repeat(1)`), the text is the cond embedding alone, every row reads the bank and eps = noise_pred / counter.  (The
-        # reference's own lines do not run in that mode: `pred_uc, pred_c = pred.chunk(2)` (:790) unpacks a one-row batch, and its
-        # reader is built with do_classifier_free_guidance=True (:634), which would mask half of the FRAMES off the bank; this
-        # follows the evident intent, pinned by the `ddim_nocfg` loop golden.)
-        cfg = self._do_cfg(guidance_scale)
-        if latents.shape[0] != 1:
-            raise ValueError("batch_size must be 1 (EMOAnimationPipeline.py:641-642); run clips as separate calls")
-        text_embeddings = self._text_rows(text_embeddings, cfg)
-        st = SimpleNamespace()
-        st.cfg = cfg
-        st.cbs = cbs = int(context_batch_size)
-        if cbs < 1:
-            raise ValueError("context_batch_size must be >= 1")
-        st.latents = torch.empty(tuple(latents.shape), device=dev, dtype=torch.float32)
-        _, st.C4, st.f_tot, st.h, st.w = st.latents.shape
-        st.HW = st.h * st.w
-        # text rows indexed by VARIANT: 0 = uncond, 1 = cond (without guidance both name the cond row)
-        st.text = torch.empty(2, *text_embeddings.shape[1:], device=dev, dtype=torch.float32)
-        st.appearance_encoder = appearance_encoder
-        st.writer = ReferenceAttentionControl(appearance_encoder, do_classifier_free_guidance=True, mode="write",
-                                              batch_size=cbs, fusion_blocks=fusion_blocks)      # :633
-        st.reader = ReferenceAttentionControl(unet, do_classifier_free_guidance=cfg, mode="read", batch_size=cbs,
-                                              fusion_blocks=fusion_blocks)                        # :634
-        st.num_inference_steps = num_inference_steps
-        st.timesteps = list(sch.set_timesteps(num_inference_steps))
-        # every step is emo_sched_step with a per-step plan.  The state keeps its own copy of the scheduler's tables (the object is
-        # shared: another set_timesteps must not move a state still being stepped), a ring of earlier model outputs and the model
-        # input of the next step, `lat_in`, which the step kernel writes - the UNet / ControlNet passes gather from it, so no
-        # step-dependent input scale is baked into a captured graph
-        st.t_dtype = torch.float32 if getattr(sch, "float_timesteps", False) else torch.int64
-        st.sched_frozen = copy.deepcopy(sch)
-        st.lat_in = torch.empty_like(st.latents)
-        st.ring = int(sch.history)
-        st.history = torch.empty(st.ring, st.latents.numel(), device=dev, dtype=torch.float32) if st.ring else None
-        st.plans = {}
-        n_steps = len(st.timesteps)
-        # ReferenceNet images = [reference, motion frames] (Net.py:56-72 intent; junk/EMo-write-up.txt:104-110)
-        st.n_ref_images = 1 + (0 if motion_latents is None else self._motion_rows(motion_latents).shape[0])
-        st.ref_lat = torch.empty(st.n_ref_images, st.C4, st.h, st.w, device=dev, dtype=torch.float32)
-        scheduler_fn = get_context_scheduler(context_schedule)
-        # the reference recomputes the (step-independent: step arg is always 0) window list every step (:748-755)
-        st.windows = [list(map(int, c)) for c in scheduler_fn(0, num_inference_steps, st.f_tot, context_frames, context_stride, context_overlap)]
-        nf = len(st.windows[0])
-        if any(len(c) != nf for c in st.windows):
-            raise ValueError("context windows of unequal length")
-        st.nf = nf
-        nb = math.ceil(len(st.windows) / cbs)
-        st.global_context = [st.windows[i * cbs:(i + 1) * cbs] for i in range(nb)]      # the reference's window batches (:752-755)
-        # `noise_pred[:, :, c] = noise_pred[:, :, c] + pred` (:792-794) with a frame listed twice in c (wrapped windows at
-        # context_stride > 1) keeps ONE occurrence (the last write wins): positions of earlier duplicates are marked -1
-        st.frame_idx = []
-        for c in st.windows:
-            last = {k: j for j, k in enumerate(c)}
-            st.frame_idx.append(torch.tensor([k if last[k] == j else -1 for j, k in enumerate(c)], dtype=torch.int32, device=dev))
-        # ---- work units (SURVEY 8e): U = [(window, branch)], branch 0 = uncond, 1 = cond; rank r owns U[r::world].  A UNet
-        # call batches up to 2*cbs of the rank's units, uncond units first (they skip the reference banks, :243-256) - at
-        # world_size 1 that is exactly the reference's [uc x cbs, c x cbs] batch (:759-763).
-        st.dist = bool(dist)
-        st.rank, st.world_size = (int(rank), int(world_size)) if st.dist else (0, 1)
-        st.emulate = _emulate_rank is not None
-        if st.emulate:
-            if st.dist:
-                raise ValueError("_emulate_rank replaces dist=True")
-            st.rank, st.world_size = int(_emulate_rank[0]), int(_emulate_rank[1])
-        # (branch-major order: with as many windows as ranks a rank owns BOTH branches of one window - balanced, the cond
-        # branch costs ~8 % more - and with twice as many ranks as windows, BASELINE configs[3], every rank owns one unit)
-        st.branches = (0, 1) if cfg else (1,)
-        st.np_slot = {br: i for i, br in enumerate(st.branches)}           # branch -> plane of the noise_pred accumulator
-        st.units = [(w, br) for br in st.branches for w in range(len(st.windows))]
-        # Text / bank VARIANT of a unit.  The reference stacks `torch.cat([text_embeddings] * context_batch_size)` (:631) =
-        # [uc, c, uc, c, ..] against latent rows [w0, w1, .., w0, w1, ..] (:759-763) and a uc mask [1, .., 0, ..]
-        # (mutual_self_attention.py:186-197): row r = branch * n + j of a batch of n windows is paired with text row r % 2, and a
-        # cond row reads bank row r - written by the ReferenceNet under text row r % 2 as well (:711-716).  At
-        # context_batch_size 1 that is variant = branch; at context_batch_size > 1 it is NOT (window 0's cond row runs under the
-        # uncond text and the uncond-text bank) - reference behaviour, reproduced (golden `ddim_cbs2`); text_pairing="branch"
-        # pairs by branch instead.
-        st.unit_tv = {}
-        pos = 0
-        for wb in st.global_context:
-            n = len(wb)
-            for j in range(n):
-                for br in st.branches:
-                    st.unit_tv[(pos + j, br)] = (br if text_pairing == "branch" else (br * n + j) % 2) if cfg else 1
-            pos += n
-        st.bank_variants = sorted({st.unit_tv[u] for u in st.units if u[1] == 1})   # the same on every rank
-        mine = st.units[st.rank::st.world_size]
-        st.n_slots = -(-len(st.units) // st.world_size)                    # units per rank, padded
-        st.calls = []
-        # which of the rank's units share a UNet call (a unit's SLOT - its place in the exchange buffer - stays its index in
-        # `mine`).  context_batch_size 1: the two branches of a window go together, [uncond, cond] - the reference's batch
-        # (:759-763), and the one whose halves share their prefix (unet._begin); units whose sibling lives on another rank are
-        # batched in pairs.  context_batch_size > 1: consecutive units, 2 * cbs per call.
-        if cbs == 1 and cfg:
-            byw = {}
-            for k, (w_, br) in enumerate(mine):
-                byw.setdefault(w_, {})[br] = k
-            chunks = [[byw[w_][0], byw[w_][1]] for w_ in sorted(byw) if len(byw[w_]) == 2]
-            singles = sorted((k for w_ in byw if len(byw[w_]) == 1 for k in byw[w_].values()), key=lambda k: (mine[k][1], k))
-            chunks += [singles[i:i + 2] for i in range(0, len(singles), 2)]
-        else:
-            n_per = len(st.branches) * cbs
-            chunks = [list(range(i, min(i + n_per, len(mine)))) for i in range(0, len(mine), n_per)]
-        for idxs in chunks:
-            chunk = [mine[k] for k in idxs]
-            uc = [k for k, u in enumerate(chunk) if u[1] == 0]
-            # one UNet call reads ONE bank (the row named by a device word): cond units are batched per bank variant
-            for n_call, tv in enumerate(sorted({st.unit_tv[u] for u in chunk if u[1] == 1}, reverse=True) or [None]):
-                order = (uc if n_call == 0 else []) + [k for k, u in enumerate(chunk) if u[1] == 1 and st.unit_tv[u] == tv]
-                call = SimpleNamespace(units=[chunk[k] for k in order], slots=[idxs[k] for k in order], bank_tv=tv)
-                call.n_uc = sum(1 for u in call.units if u[1] == 0)
-                # [uncond windows..., cond windows...] over the SAME windows in the same order: the two halves of the UNet batch
-                # carry identical latents and differ only from the first cross-attention on (unet._begin shares that prefix)
-                call.halves_identical = (call.n_uc * 2 == len(call.units) and call.n_uc > 0 and
-                                         [u[0] for u in call.units[:call.n_uc]] == [u[0] for u in call.units[call.n_uc:]])
-                call.idx = [torch.tensor(st.windows[w], dtype=torch.int64, device=dev) for w, _ in call.units]
-                st.calls.append(call)
-        if st.emulate:          # no exchange: the accumulators see this rank's units only
-            st.units = mine
-        st.t_table = torch.tensor(st.timesteps, dtype=st.t_dtype, device=dev)   # INT timestep table, bit-exact (f32: Euler / LMS)
-        st.t_buf = torch.zeros(1, dtype=st.t_dtype, device=dev)
-        if use_graphs is None:      # the measured path is the default one on a HIP device
-            use_graphs = dev.type == "cuda"
-        st.use_graphs, st.graphs = bool(use_graphs) and dev.type == "cuda", {}
-        st.graph_pool = st.writer_pool = None
-        if st.use_graphs:
-            st.graph_pool = torch.cuda.graph_pool_handle()
-            st.writer_pool = torch.cuda.graph_pool_handle()   # own pool: the ReferenceNet pass runs concurrently with the Backbone
-        # ---- contexts of the attn2 layers: their K / V^T projections depend on the context only -> once per clip (_bind_inputs)
-        st.audio_features = None if audio_features is None else torch.empty(tuple(audio_features.shape), device=dev, dtype=torch.float32)
-        st.speed = None if speed_embeddings is None else torch.empty(tuple(speed_embeddings.shape), device=dev, dtype=torch.float32)
-        # the face-region rows every UNet call adds behind conv_in: ONE buffer, rewritten per clip (captured graphs keep its address)
-        st.face_rows = None if face_mask is None else torch.empty(st.HW, unet.config.block_out_channels[0], device=dev, dtype=unet.dtype)
-        for call in st.calls:
-            call.ctx = call.ctx_kv = call.speed = None
-        st.text_c = st.text[1:2]
-        st.ref_ctx_kv = {}
-        # ---- eps hand-off: every unit's rows (nf*HW, C4); slot = position in the rank's unit list
-        st.send = torch.zeros(st.n_slots, nf * st.HW, st.C4, device=dev, dtype=unet.dtype)
-        st.recv = torch.zeros(st.world_size, st.n_slots, nf * st.HW, st.C4, device=dev, dtype=unet.dtype) if st.dist else None
-        st.noise_pred = torch.empty(len(st.branches), st.C4, st.f_tot, st.HW, device=dev, dtype=torch.float32)
-        st.counter = torch.empty(st.f_tot, device=dev, dtype=torch.float32)
-        st.return_eps, st.eps_trace = return_eps, []
-        # ---- ReferenceNet groups: the banks depend on the timestep only (never on the latents): T timesteps per pass
-        st.T = T = self.reference_group_size(reference_group, n_steps, st.world_size if (st.dist or st.emulate) else 1)
-        st.groups = [list(range(i, min(i + T, n_steps))) for i in range(0, n_steps, T)]
-        st.ref_t = torch.zeros(T, dtype=st.t_dtype, device=dev)
-        st.row_table = torch.tensor([((s_ // T) % 2) * T + s_ % T for s_ in range(n_steps)], dtype=torch.int32, device=dev)
-        st.bank_idx = torch.zeros(1, dtype=torch.int32, device=dev)
-        st.kv_all, st.group_ready, st.group_pending, st.groups_launched = {}, -1, -1, 0
-        st.ref_sel, st.ref_recv, st.ref_gath = {}, {}, {}
-        st.bank_pack, st.stage = {}, {}
-        spec_r = appearance_encoder.spec
-        chan = {a.prefix: a.channels for blk in spec_r.down + [spec_r.mid] + spec_r.up for a in blk.attentions if a is not None}
-        st.bank_C = [chan[p] for p in st.writer.order]
-        # look-ahead = group g+1's ReferenceNet pass on a second stream under group g's Backbone steps.  With world_size > 1 the
-        # side stream carries the WRITE passes only; the bank all_gather stays on the main stream and on the communicator of the
-        # per-step eps all_gather (see _ensure_group): one program order of collectives on every rank, so the overlap is safe
-        # at any world size and on by default.
-        if reference_lookahead is None:
-            reference_lookahead = True
-        st.lookahead = bool(reference_lookahead) and dev.type == "cuda"
-        st.side = torch.cuda.Stream() if st.lookahead else None
-        # ControlNet branch (EMOAnimationPipeline.py:643-650,678-679,718-746): (F_tot,3,H,W) conditioning images in [0,1]
-        st.controlnet = controlnet
-        if controlnet is not None:
-            if controlnet_cond is None or controlnet_cond.shape[0] != st.f_tot:
-                raise ValueError("controlnet_cond must hold one (3,H,W) conditioning image per frame")
-            st.cn_cond = torch.empty(tuple(controlnet_cond.shape), device=dev, dtype=torch.float32)
-            # the frames this rank's units touch; residuals are computed once per frame and step, in chunks of
-            # context_frames (the reference caches them per frame from overlap-0 windows: the network is per-frame, so
-            # the chunking does not enter the result)
-            need = sorted({k for call in st.calls for w, _ in call.units for k in st.windows[w]})
-            st.cn_pos = {k: i for i, k in enumerate(need)}
-            st.cn_chunks = [torch.tensor(need[i:i + context_frames], dtype=torch.int64, device=dev) for i in range(0, len(need), context_frames)]
-            st.cn_text = st.text_c                                   # cond text embedding (:678-679)
-            for call in st.calls:
-                call.cn_sel = torch.tensor([st.cn_pos[k] for w, _ in call.units for k in st.windows[w]], dtype=torch.int64, device=dev)
-            st.cn_down, st.cn_mid, st.cn_embed = None, None, None
-        self._bind_inputs(st, latents, ref_image_latents, text_embeddings, audio_features=audio_features, speed_embeddings=speed_embeddings,
-                          face_mask=face_mask, face_mask_threshold=face_mask_threshold, motion_latents=motion_latents, controlnet_cond=controlnet_cond,
-                          controlnet_conditioning_scale=controlnet_conditioning_scale, guidance_scale=guidance_scale, eta=eta, seed=seed)
-        return st
-
-    @staticmethod
-    def reference_group_size(reference_group, n_steps, world_size=1):
-        """ReferenceNet timesteps per batched pass: at least 1, never more than the loop has steps; with world_size > 1 the ranks
-        deal a group's timesteps among themselves, and a size that is not a multiple of world_size would pad every rank to
-        ceil(T / world) timesteps (10 over 8 ranks: 16 computed and shipped, 10 used) - rounded up to a multiple instead, still
-        capped by the step count."""
-        T = max(1, min(int(reference_group), int(n_steps)))
-        if world_size > 1:
-            T = min(-(-T // world_size) * world_size, int(n_steps))
-        return T
-
-    # ---- the INPUTS of a prepared loop state, copied into its buffers in place (the captured graphs keep reading them)
-    @staticmethod
-    def _do_cfg(guidance_scale):
-        """`do_classifier_free_guidance = guidance_scale > 1.0` (:622), decided on the f32 value emo_sched_step receives: a scale
-        in (1, 1 + 2^-24] would otherwise allocate two noise_pred planes for a kernel that reads one."""
-        import numpy as np
-        return bool(np.float32(guidance_scale) > np.float32(1.0))
-
-    @staticmethod
-    def _text_rows(text_embeddings, cfg):
-        if text_embeddings.shape[0] == 2 and not cfg:
-            text_embeddings = text_embeddings[1:]          # [uncond, cond] handed over anyway: the cond row is the prompt
-        if text_embeddings.shape[0] != (2 if cfg else 1):
-            raise ValueError("text_embeddings must be (2, L, D) = [uncond, cond] (:631), or (1, L, D) = [cond] without guidance")
-        return text_embeddings
-
-    @staticmethod
-    def _motion_rows(motion_latents):
-        ml = motion_latents
-        if ml.dim() == 5:
-            ml = ml[0].permute(1, 0, 2, 3)
-        return ml
-
-    @staticmethod
-    def _check_speed_embeddings(speed_embeddings, video_length):
-        """(1 | 2, 4*C0): one embedding per clip, shared or [uncond, cond]; (1 | 2, video_length, 4*C0): one per frame"""
-        se = speed_embeddings
-        if se is None:
-            return
-        if se.dim() not in (2, 3) or se.shape[0] not in (1, 2):
-            raise ValueError("speed_embeddings must have 1 row (shared) or 2 rows [uncond, cond]: (1 | 2, 4*C0) per clip or "
-                             f"(1 | 2, video_length, 4*C0) per frame, got {tuple(se.shape)}")
-        if se.dim() == 3 and se.shape[1] != video_length:
-            raise ValueError(f"per-frame speed_embeddings hold {se.shape[1]} frames, the clip has {video_length}")
-
-    def _check_face_mask(self, face_mask, height, width, locate_ok=False):
-        """The argument checks of `face_mask=` (nothing is launched): a FaceRegionController(1, block_out_channels[0]) on the pipeline,
-        and an (H, W) / (1, 1, H, W) map at pixel size (height, width) or at latent size (height / 8, width / 8).
-        Returns "pixel" or "latent" (or "locate" for that string where the caller resolves it)."""
-        ctl = getattr(self, "face_region_controller", None)
-        C0 = self.unet.config.block_out_channels[0]
-        if ctl is None:
-            raise ValueError("face_mask= needs a face_region_controller on the pipeline (emote_hack_amd.conditioning.FaceRegionController(1, "
-                             f"{C0}) with loaded weights: pass face_region_controller= to the constructor or assign pipe.face_region_controller)")
-        if ctl.in_channels != 1 or ctl.out_channels != C0:
-            raise ValueError(f"the face_region_controller maps {ctl.in_channels} -> {ctl.out_channels} channels; the mask has 1 and conv_in's "
-                             f"output {C0}: build FaceRegionController(1, {C0})")
-        if isinstance(face_mask, str):
-            if face_mask == "locate" and locate_ok:
-                return "locate"
-            raise ValueError(f"face_mask={face_mask!r}: a map, or \"locate\" in the pipeline call")
-        m = torch.as_tensor(face_mask)
-        f = self.vae_scale_factor
-        hw = tuple(m.shape) if m.dim() == 2 else tuple(m.shape[2:]) if (m.dim() == 4 and tuple(m.shape[:2]) == (1, 1)) else None
-        if hw == (height, width):
-            return "pixel"
-        if hw == (height // f, width // f):
-            return "latent"
-        raise ValueError(f"face_mask must be an (H, W) or (1, 1, H, W) map at pixel size ({height}, {width}) or at latent size "
-                         f"({height // f}, {width // f}), got {tuple(m.shape)}")
-
-    def _face_feature_rows(self, st, face_mask, threshold=None):
-        """face mask -> FaceRegionController input rows (h*w, 8) -> (h*w, C0) rows (train_stage_3_speedlayers.py:57-76).  A pixel-size
-        map is pooled 8 x 8 (ops.mask_pool, after the optional threshold); a latent-size one goes in as it is."""
-        f = self.vae_scale_factor
-        kind = self._check_face_mask(face_mask, st.h * f, st.w * f)
-        dev, dtp = st.latents.device, self.unet.dtype
-        m = torch.as_tensor(face_mask).to(dev).float()
-        m = m.reshape(m.shape[-2], m.shape[-1]).contiguous()
-        if kind == "pixel":
-            rows = ops.mask_pool(m, dtp, threshold=threshold)
-        else:
-            if threshold is not None:
-                m = (m > threshold).float()
-            rows = ops.ncfhw_to_rows(m.reshape(1, 1, 1, st.h, st.w), dtp, cpad=8)
-        return self.face_region_controller.forward_rows(rows, 1, st.h, st.w)
-
-    def _bind_inputs(self, st, latents, ref_image_latents=None, text_embeddings=None, *, audio_features=None, speed_embeddings=None,
-                     motion_latents=None, controlnet_cond=None, controlnet_conditioning_scale=None, guidance_scale=None, eta=None,
-                     seed=None, face_mask=None, face_mask_threshold=None):
-        """Copy a clip's inputs into the buffers of a prepared state (None = keep what is bound).  Everything derived from them -
-        the attn2 K / V^T of the text / audio context per UNet call, the ReferenceNet's text K / V^T - is recomputed INTO the
-        tensors the captured graphs already read; the ReferenceNet groups are marked stale (the reference image and the motion
-        frames enter them)."""
-        unet, dev = self.unet, st.latents.device
-
-        def put(dst, src, what):
-            src = src.to(dev).float()
-            if tuple(src.shape) != tuple(dst.shape):
-                raise ValueError(f"{what} {tuple(src.shape)} != prepared {tuple(dst.shape)}")
-            dst.copy_(src)
-        if st.side is not None:   # nothing of the previous clip may still be writing the bank cache
-            torch.cuda.current_stream().wait_stream(st.side)
-        put(st.latents, latents, "latents")
-        if ref_image_latents is not None:
-            put(st.ref_lat[:1], ref_image_latents.reshape(1, st.C4, st.h, st.w), "ref_image_latents")
-        if motion_latents is not None:
-            ml = self._motion_rows(motion_latents)
-            if st.n_ref_images == 1 or tuple(ml.shape) != (st.n_ref_images - 1, st.C4, st.h, st.w):
-                raise ValueError(f"motion_latents must be ({st.n_ref_images - 1}, {st.C4}, {st.h}, {st.w}), got {tuple(ml.shape)}")
-            put(st.ref_lat[1:], ml, "motion_latents")
-        elif st.n_ref_images != 1 and ref_image_latents is not None:
-            raise ValueError("the state was prepared with motion frames: pass motion_latents")
-        if guidance_scale is not None:
-            if self._do_cfg(guidance_scale) != st.cfg:
-                raise ValueError("guidance_scale crosses 1.0: classifier-free guidance on / off is part of the plan (prepare again)")
-            st.guidance_scale = float(guidance_scale)
-        if eta is not None:
-            st.eta = eta
-            if hasattr(st.sched_frozen, "eta"):   # DDIM: the plans read it, so none of the previous clip's may be kept
-                st.sched_frozen.eta = eta
-                st.plans = {}
-        if seed is not None:
-            st.seed = seed
-        ctx_stale = False
-        if text_embeddings is not None:
-            t = self._text_rows(text_embeddings, st.cfg).to(dev).float()
-            put(st.text, t if st.cfg else t.expand(2, -1, -1), "text_embeddings")
-            ctx_stale = True
-            for tv in st.bank_variants:
-                for pr, kv in st.appearance_encoder.context_kv(st.text[tv:tv + 1]).items():
-                    self._put_kv(st.ref_ctx_kv.setdefault(tv, {}), pr, kv)
-        if audio_features is not None:
-            if st.audio_features is None:
-                raise ValueError("the state was prepared without audio_features")
-            put(st.audio_features, audio_features, "audio_features")
-            ctx_stale = True
-        if speed_embeddings is not None:
-            if st.speed is None:
-                raise ValueError("the state was prepared without speed_embeddings")
-            if speed_embeddings.dim() != st.speed.dim():
-                raise ValueError(f"the state was prepared with {'per-frame' if st.speed.dim() == 3 else 'per-clip'} speed_embeddings "
-                                 f"{tuple(st.speed.shape)}, got {tuple(speed_embeddings.shape)}")
-            put(st.speed, speed_embeddings, "speed_embeddings")
-        if face_mask is not None:
-            if st.face_rows is None:
-                raise ValueError("the state was prepared without face_mask")
-            st.face_rows.copy_(self._face_feature_rows(st, face_mask, face_mask_threshold))
-        for call in st.calls:
-            if ctx_stale:
-                if st.audio_features is None:
-                    ctx = torch.cat([st.text[st.unit_tv[u]:st.unit_tv[u] + 1] for u in call.units])    # (n, L, D)
-                else:   # per-frame audio context; uncond units get a zero context (design choice, SURVEY A17)
-                    parts = []
-                    for (w, br), ix in zip(call.units, call.idx):
-                        a = st.audio_features.index_select(0, ix)
-                        parts.append(a if br == 1 else torch.zeros_like(a))
-                    ctx = torch.cat(parts)                                                              # (n*F, L_a, D)
-                if call.ctx is None:
-                    call.ctx = ctx
-                else:
-                    call.ctx.copy_(ctx)
-                if call.ctx_kv is None:
-                    call.ctx_kv = {}
-                for pr, kv in unet.context_kv(call.ctx).items():
-                    self._put_kv(call.ctx_kv, pr, kv)
-            if speed_embeddings is not None:
-                se = st.speed
-                if se.dim() == 3:   # per frame: the rows of each unit's window, gathered like the audio context -> (n, nf, 4*C0)
-                    sp = torch.stack([se[br if se.shape[0] == 2 else 0].index_select(0, ix) for (_, br), ix in zip(call.units, call.idx)])
-                else:
-                    sp = torch.cat([se[(br if se.shape[0] == 2 else 0):(br if se.shape[0] == 2 else 0) + 1] for _, br in call.units])
-                if call.speed is None:
-                    call.speed = sp
-                else:
-                    call.speed.copy_(sp)
-        if controlnet_cond is not None:
-            if st.controlnet is None:
-                raise ValueError("the state was prepared without a ControlNet")
-            put(st.cn_cond, controlnet_cond, "controlnet_cond")
-            # the conditioning embedding (controlnet.py:523) depends on the conditioning images only: once per clip, not per step
-            embeds = [st.controlnet.cond_embedding(st.cn_cond.index_select(0, idx)) for idx in st.cn_chunks]
-            if getattr(st, "cn_embed", None) is None:
-                st.cn_embed = embeds
-            else:
-                for (dst, _, _), (src, _, _) in zip(st.cn_embed, embeds):
-                    dst.copy_(src)
-        if controlnet_conditioning_scale is not None and st.controlnet is not None:
-            scale = float(controlnet_conditioning_scale)
-            if getattr(st, "cn_scale", scale) != scale and st.graphs.get("controlnet") not in (None, "warm"):
-                raise ValueError("controlnet_conditioning_scale is baked into the captured ControlNet pass (prepare again)")
-            st.cn_scale = scale
-        st.group_ready, st.group_pending, st.eps_trace = -1, -1, []
-        st.sched_first = None      # the multistep warm-up and lat_in restart at the next step that runs
-
-    @staticmethod
-    def _put_kv(store, key, kv):
-        """store[key] = (K rows, V^T) - into the tensors already there, if any (captured graphs hold their addresses)"""
-        if key in store:
-            for dst, src in zip((store[key],) if torch.is_tensor(store[key]) else store[key], (kv,) if torch.is_tensor(kv) else kv):
-                dst.copy_(src)
-        else:
-            store[key] = kv
-
-    # ---- ReferenceNet: one batched write pass per GROUP of timesteps, one group ahead of the Backbone on a second stream
-    def _ref_sel(self, st, Tg):
-        """group-local timestep indices this rank computes (rank r: r, r+world, ...; padded by repeating the last one)"""
-        if Tg not in st.ref_sel:
-            n = -(-Tg // st.world_size)
-            mine = [min(st.rank + i * st.world_size, Tg - 1) for i in range(n)]
-            st.ref_sel[Tg] = torch.tensor(mine, dtype=torch.int64, device=st.ref_t.device)
-        return st.ref_sel[Tg]
-
-    def _part_reference_write(self, st, Tg, tv):
-        """ReferenceNet write pass (:711-716) under text variant tv (1 = the cond text) for this rank's share of the group's
-        timesteps, batched: (n,4,h,w) with one timestep per row.  The reference runs [uncond-text, cond-text] copies every
-        step, but at context_batch_size 1 the reader never uses the uncond bank row (for the uc rows `hidden_states_c` is
-        overwritten by the bank-free uc attention, mutual_self_attention.py:243-256) and the ReferenceNet is batch-independent:
-        only the variants some cond unit reads (st.bank_variants) are computed.  Banks are rounded through fp16 like
-        reader.update() does (:588) and packed for the exchange."""
-        t = st.ref_t[:Tg] if st.world_size == 1 else st.ref_t.index_select(0, self._ref_sel(st, Tg))
-        n, k = t.numel(), st.n_ref_images
-        st.appearance_encoder._reference_control = st.writer   # (another prepared state on the same models may have attached its own)
-        st.writer.clear()
-        # batch rows timestep-major: (t0: reference image, motion frames...), (t1: ...) - the k images of one timestep are
-        # consecutive, so their LN1 rows (k, L, C) read as ONE bank of k*L tokens (the reference concatenates several bank
-        # entries along tokens the same way, mutual_self_attention.py:239)
-        imgs = st.ref_lat.expand(n, -1, -1, -1) if k == 1 else st.ref_lat.repeat(n, 1, 1, 1)
-        tt = t if k == 1 else t.repeat_interleave(k)
-        st.appearance_encoder(imgs, tt, encoder_hidden_states=st.text[tv:tv + 1], return_dict=False, _ctx_kv=st.ref_ctx_kv[tv])
-        tgt = self.unet.dtype
-        st.bank_L = [k * st.writer.bank[p][0].shape[1] for p in st.writer.order]
-        banks = [ops.convert(st.writer.bank[p][0], tgt, fp16_round=True).reshape(n, -1) for p in st.writer.order]
-        st.writer.clear()                                                                      # :823
-        # (keyed by the group size as well: a replayed graph of another group size writes ITS tensors, not the last ones bound here)
-        st.bank_pack[(Tg, tv)] = banks if st.world_size == 1 else torch.cat(banks, dim=1)      # (n, total) plumbing copy
-
-    def _part_reference_project(self, st, Tg, tv):
-        """K / V^T projections of the group's banks with the BACKBONE's attn1.to_k / to_v (the read side of
-        mutual_self_attention.py:238-241), once per group instead of once per step."""
-        st.stage[(Tg, tv)] = {}
-        off = 0
-        for i, (pr, L, C_) in enumerate(zip(st.reader.order, st.bank_L, st.bank_C)):
-            if st.world_size == 1:
-                rows = st.bank_pack[(Tg, tv)][i]
-            else:   # bank i occupies columns [off, off + L*C) of every gathered row (rows in group order)
-                rows = st.ref_gath[(Tg, tv)][:Tg, off:off + L * C_].contiguous()
-                off += L * C_
-            k, vt = self.unet.bank_kv(pr, rows.reshape(-1, C_), L)
-            st.stage[(Tg, tv)][pr] = (k, vt, L)
-
-    def _reference_write(self, st, g):
-        """Phase 1 of group g: this rank's share of the group's ReferenceNet write passes (no communication) on the CURRENT stream."""
-        steps = st.groups[g]
-        Tg = len(steps)
-        st.groups_launched += 1
-        st.ref_t[:Tg].copy_(st.t_table[steps[0]:steps[0] + Tg], non_blocking=True)
-        for tv in st.bank_variants:
-            self._run(st, ("ref_write", Tg, tv), lambda tv=tv: self._part_reference_write(st, Tg, tv), pool=st.writer_pool)
-
-    def _reference_finish(self, st, g):
-        """Phase 2 of group g on the CURRENT stream: the bank exchange (world_size > 1), the K / V^T projection of the whole group
-        with the Backbone's weights, and the copy into slot g % 2 of the resident cache."""
-        steps = st.groups[g]
-        Tg, T, slot = len(steps), st.T, g % 2
-        for tv in st.bank_variants:
-            if st.world_size > 1:
-                # north_star: "RCCL all-gather over xGMI to broadcast ReferenceNet features" - rank r computed timesteps
-                # r, r+world, ... of the group; ONE all_gather hands every rank every timestep's banks.  Same communicator and same
-                # stream as the per-step eps all_gather: every rank issues its collectives in ONE program order (eps of the group's
-                # last step, banks of the next group, eps of its first step, ...), so no start-order hazard exists by construction
-                import torch.distributed as td
-                send = st.bank_pack[(Tg, tv)]
-                n = send.shape[0]
-                if (Tg, tv) not in st.ref_gath:
-                    st.ref_recv[(Tg, tv)] = torch.empty(st.world_size * n, send.shape[1], device=send.device, dtype=send.dtype)
-                    st.ref_gath[(Tg, tv)] = torch.empty(st.world_size * n, send.shape[1], device=send.device, dtype=send.dtype)
-                if st.emulate:      # (stands in for the gathered rows: this rank's banks, repeated)
-                    st.ref_recv[(Tg, tv)].view(st.world_size, -1).copy_(send.contiguous().view(1, -1).expand(st.world_size, -1))
-                else:
-                    td.all_gather_into_tensor(st.ref_recv[(Tg, tv)].view(-1), send.contiguous().view(-1))
-                # row (rank r, slot i) is group-local timestep i*world + r -> group order
-                st.ref_gath[(Tg, tv)].view(n, st.world_size, -1).copy_(st.ref_recv[(Tg, tv)].view(st.world_size, n, -1).transpose(0, 1))
-            self._run(st, ("ref_project", Tg, tv), lambda tv=tv: self._part_reference_project(st, Tg, tv), pool=st.writer_pool)
-            if tv not in st.kv_all:   # resident cache: two groups of T timesteps per block
-                st.kv_all[tv] = {}
-                for pr, (k, vt, L) in st.stage[(Tg, tv)].items():
-                    st.kv_all[tv][pr] = (torch.zeros(2 * T * L, k.shape[1], device=k.device, dtype=k.dtype),
-                                         torch.zeros(2 * T, vt.shape[1], vt.shape[2], device=vt.device, dtype=vt.dtype), L)
-            dsts, srcs = [], []
-            for pr, (k, vt, L) in st.stage[(Tg, tv)].items():
-                ka, va, _ = st.kv_all[tv][pr]
-                dsts += [ka[slot * T * L:slot * T * L + Tg * L], va[slot * T:slot * T + Tg]]
-                srcs += [k[:Tg * L], vt[:Tg]]
-            torch._foreach_copy_(dsts, srcs)
-
-    def _reference_group(self, st, g):
-        """Compute group g's projected banks on the CURRENT stream and store them in slot g % 2 of the resident cache."""
-        self._reference_write(st, g)
-        self._reference_finish(st, g)
-
-    def _ensure_group(self, st, si):
-        """Group of step si resident (waiting for / computing it if needed), the NEXT group launched on the side stream.
-        world_size 1: the whole pass of group g+1 (write, projection, cache copy) rides the side stream.  world_size > 1: only its
-        WRITE pass does (the ReferenceNet forwards - the expensive, communication-free part); the bank all_gather and the projection are
-        issued on the MAIN stream when the loop reaches the group - in program order with the per-step eps all_gather, on the one
-        communicator both use (EMOAnimationPipeline.py:796-821 is the exchange this replaces)."""
-        g = si // st.T
-        cuda = self.unet.device.type == "cuda"
-        main = torch.cuda.current_stream() if cuda else None
-        split = st.world_size > 1
-        if st.group_ready != g:
-            if st.group_pending == g:
-                main.wait_stream(st.side)
-                if split:
-                    self._reference_finish(st, g)
-            else:
-                if st.group_pending >= 0 and cuda:   # a look-ahead pass for ANOTHER group is in flight (the caller jumped): it shares the
-                    main.wait_stream(st.side)        # timestep buffer and the captured write graphs with the pass below
-                self._reference_group(st, g)
-            st.group_ready, st.group_pending = g, -1
-            if g + 1 < len(st.groups) and st.lookahead:
-                # slot (g+1) % 2 held group g-1: every step of it is already enqueued on the main stream
-                st.side.wait_stream(main)
-                with torch.cuda.stream(st.side):
-                    if split:
-                        self._reference_write(st, g + 1)
-                    else:
-                        self._reference_group(st, g + 1)
-                st.group_pending = g + 1
-
-    # ---- ControlNet (per-frame residual cache of the step, :718-746)
-    def _part_controlnet(self, st):
-        downs, mids = [], []
-        for i, idx in enumerate(st.cn_chunks):
-            x = st.lat_in.index_select(2, idx)[0].permute(1, 0, 2, 3).contiguous()     # the scaled model input, written by the step kernel
-            d, m = st.controlnet(x, st.t_buf, encoder_hidden_states=st.cn_text.repeat(idx.numel(), 1, 1), controlnet_cond=None,
-                                 conditioning_scale=st.cn_scale, return_dict=False, _cond_rows=st.cn_embed[i])
-            downs.append(d)
-            mids.append(m)
-        st.cn_down = [torch.cat([d[i] for d in downs]) for i in range(len(downs[0]))]
-        st.cn_mid = torch.cat(mids)
-
-    def _controlnet_residuals(self, st, call):
-        """select_controlnet_res_samples (:514-540): frames of the call's units, '(b f) c h w -> b c f h w' (the CFG repeat of
-        the reference is the uncond and the cond unit of a window selecting the same frames)."""
-        if st.controlnet is None:
-            return {}
-        n, nf = len(call.units), st.nf
-
-        def to5(t):
-            y = t.index_select(0, call.cn_sel)
-            return y.reshape(n, nf, *y.shape[1:]).permute(0, 2, 1, 3, 4)
-        return dict(down_block_additional_residuals=tuple(to5(t) for t in st.cn_down), mid_block_additional_residual=to5(st.cn_mid))
-
-    # ---- one UNet call = the rank's next <= 2*cbs units; reads the timestep from the device buffer st.t_buf and the bank row
-    #      from st.bank_idx, so it is captured once into a HIP graph and replayed for the other steps
-    def _part_unet(self, st, ci):
-        call = st.calls[ci]
-        x = torch.cat([st.lat_in.index_select(2, ix) for ix in call.idx])   # :759-763; the scaled model input, written by the step kernel
-        # (a call of uncond units only names any resident cache: every one of its batches skips the bank segment)
-        bank_tv = call.bank_tv if call.bank_tv is not None else st.bank_variants[0]
-        self.unet._reference_control = st.reader
-        st.reader.set_projected_banks(st.kv_all[bank_tv], st.bank_idx, call.n_uc)               # replaces reader.update (:774)
-        face = {} if st.face_rows is None else dict(face_features=st.face_rows)      # (a call without one launches what it always did)
-        rows = self.unet(x, st.t_buf, encoder_hidden_states=call.ctx, speed_embeddings=call.speed, return_dict=False,
-                         _return_rows=True, _ctx_kv=call.ctx_kv, _halves_identical=call.halves_identical,
-                         **self._controlnet_residuals(st, call), **face)   # :777-786
-        n_rows = st.nf * st.HW
-        for k, slot in enumerate(call.slots):
-            st.send[slot].copy_(rows[k * n_rows:(k + 1) * n_rows])
-
-    def _accumulate_all(self, st):
-        """noise_pred[:, :, c] += pred; counter[:, :, c] += 1 (:790-794) over EVERY unit in global order - each rank does this
-        redundantly on the gathered rows, so the accumulators (and the latents) are bit-identical on all ranks."""
-        for i, (w, br) in enumerate(st.units):
-            rows = st.send[i] if not st.dist else st.recv[i % st.world_size, i // st.world_size]
-            ops.accumulate_window(rows, st.noise_pred[st.np_slot[br]], st.counter, st.frame_idx[w], C_=st.C4, F=st.f_tot, HW=st.HW,
-                                  add_counter=(br == st.branches[0]))
-
-    def _run(self, st, key, fn, pool=None):
-        """Eager on first use (warm-up: lazy kernel attributes, allocator), HIP-graph capture on the second, replay after.
-        Launch-bound host code (~1700 kernel launches per step from Python) disappears from the critical path."""
-        if not st.use_graphs or ops.PROFILER is not None:
-            return fn()
-        state = st.graphs.get(key)
-        if state is None:
-            fn()
-            st.graphs[key] = "warm"
-            return
-        if state == "warm":
-            g = torch.cuda.CUDAGraph()
-            # thread_local: only this thread's calls are checked during capture - the RCCL watchdog thread of a multi-GPU
-            # run polls events concurrently and must not invalidate the capture
-            with torch.cuda.graph(g, pool=pool if pool is not None else st.graph_pool, capture_error_mode="thread_local"):
-                fn()
-            st.graphs[key] = g
-            state = g
-        state.replay()
-
-    @torch.no_grad()
-    def denoise_step(self, st, si):
-        """One iteration of the hot loop (EMOAnimationPipeline.py:698-823)."""
-        dev = self.unet.device
-        if st.sched_first is None:    # the first step that runs: its model input, one scale-only launch
-            st.sched_first = si
-            ops.sched_scale(st.latents, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW, s=st.sched_frozen.input_scale(si))
-        self._ensure_group(st, si)                                     # :711-716, hoisted: banks of T timesteps per pass
-        st.t_buf.copy_(st.t_table[si:si + 1], non_blocking=True)       # device-to-device: the INT timestep of this step
-        st.bank_idx.copy_(st.row_table[si:si + 1], non_blocking=True)  # ... and its row in the resident bank cache
-        st.noise_pred.zero_()
-        st.counter.zero_()
-        if st.emulate:
-            st.counter.add_(1e-6)       # frames of the other ranks' windows: 0 / 1e-6 instead of 0 / 0
-        if st.controlnet is not None and st.calls:   # per-frame residual cache of this step (:718-746)
-            self._run(st, "controlnet", lambda: self._part_controlnet(st))
-        for ci in range(len(st.calls)):                                                        # :757
-            self._run(st, ("unet", ci), lambda ci=ci: self._part_unet(st, ci))
-        if st.dist:   # replaces gather-to-root (:796-809) + broadcast (:819-821): ONE all_gather of the eps slices
-            import torch.distributed as td
-            td.all_gather_into_tensor(st.recv.view(-1), st.send.view(-1))
-        self._accumulate_all(st)
-        eps_out = torch.empty(st.C4 * st.f_tot * st.HW, device=dev, dtype=torch.float32) if st.return_eps else None
-        p, slot = self._step_plan(st, si)   # :812-817 fused
-        ops.sched_step(st.noise_pred, st.counter, st.latents, st.history, st.lat_in, C_=st.C4, F=st.f_tot, HW=st.HW,
-                       guidance_scale=st.guidance_scale, a=p.a, b=p.b, c_x=p.c_x, c=p.c, slot=slot, c_noise=p.c_noise,
-                       s_next=p.s_next, seed=st.seed, step=si, eps_out=eps_out)
-        if st.return_eps:
-            st.eps_trace.append(eps_out.view(1, st.C4, st.f_tot, st.h, st.w))
-
-    @staticmethod
-    def _step_plan(st, si):
-        """(StepPlan, ring slots) of step si: d_n goes to slot (si - first) % ring, d_{n-k} is read from slot (si - first - k) % ring
-        - the ring restarts with the first step that runs."""
-        key = (st.sched_first, si)
-        if key not in st.plans:
-            p = st.sched_frozen.step_plan(si, st.sched_first)
-            j = si - st.sched_first
-            slot = [j % st.ring if st.ring else -1]
-            for k in range(1, 4):
-                if p.c[k] != 0.0:
-                    if k > j or k >= st.ring:
-                        raise RuntimeError(f"step plan of step {si} reads d_(n-{k}), which the ring does not hold")
-                    slot.append((j - k) % st.ring)
-                else:
-                    slot.append(-1)
-            st.plans[key] = (p, tuple(slot))
-        return st.plans[key]
-
-    def _run_loop(self, st, num_actual_inference_steps=None, callback=None, callback_steps=1):
-        n = st.num_inference_steps
-        for si, t in enumerate(st.timesteps):
-            if num_actual_inference_steps is not None and si < n - num_actual_inference_steps:   # :699-700
-                continue
-            self.denoise_step(st, si)
-            if callback is not None and si % callback_steps == 0:
-                callback(si, t, st.latents)
-        return (st.latents, st.eps_trace) if st.return_eps else st.latents
-
-    @torch.no_grad()
-    def denoise(self, latents, ref_image_latents, text_embeddings, *, num_actual_inference_steps=None, callback=None,
-                callback_steps=1, reuse_state=False, **kw):
-        """The whole loop; returns the denoised latents f32 (1,4,F_tot,h,w) (and the eps trace if asked).
-        reuse_state: keep the prepared state (plan + captured HIP graphs) on the pipeline and re-arm it when the next call has the
-        same plan - same shapes, step count, window / guidance / distribution settings and the same loaded weights; only the
-        inputs are copied in (`_bind_inputs`).  `__call__` turns it on: a second clip costs the loop and nothing else."""
-        if not reuse_state:
-            st = self.prepare_denoise(latents, ref_image_latents, text_embeddings, **kw)
-            return self._run_loop(st, num_actual_inference_steps, callback, callback_steps)
-        key = self._plan_key(latents, ref_image_latents, text_embeddings, kw)
-        cached = self._plan_cache
-        if cached is not None and cached[0] == key:
-            st = cached[1]
-            bind = {k: kw[k] for k in ("audio_features", "speed_embeddings", "motion_latents", "controlnet_cond",
-                                       "controlnet_conditioning_scale", "face_mask", "face_mask_threshold") if kw.get(k) is not None}
-            # an omitted guidance_scale / eta / seed means the documented DEFAULT, not "what the previous clip used" (they are not
-            # part of the plan key, so the hit happens either way; "None = keep" is reset_denoise's contract, not this one's)
-            bind.update(guidance_scale=_default(kw.get("guidance_scale"), 7.5), eta=_default(kw.get("eta"), 0.0), seed=_default(kw.get("seed"), 0))
-            self._bind_inputs(st, latents, ref_image_latents, text_embeddings, **bind)
-        else:
-            self._plan_cache = None          # drop the old graphs before the new plan allocates
-            st = self.prepare_denoise(latents, ref_image_latents, text_embeddings, **kw)
-            self._plan_cache = (key, st)
-        res = self._run_loop(st, num_actual_inference_steps, callback, callback_steps)
-        # (the state's latents are overwritten by the next clip)
-        return (res[0].clone(), list(res[1])) if isinstance(res, tuple) else res.clone()
-
-    def clear_plan_cache(self):
-        """Release the prepared state `denoise(reuse_state=True)` / `__call__` keep (buffers, captured HIP graphs, bank cache)."""
-        self._plan_cache = None
-
-    def _plan_key(self, latents, ref_image_latents, text_embeddings, kw):
-        """Everything a prepared state's PLAN depends on (prepare_denoise above `_bind_inputs`): tensor shapes, the settings that
-        shape windows / units / groups / graphs, and the identity of the packed weights the graphs were captured over."""
-        from . import unet as unet_mod
-
-        def shp(t):
-            return None if t is None else tuple(t.shape)
-
-        def wid(m):   # a re-pack (load_state_dict / .to) builds a new dict of packed tensors: captured graphs are stale
-            return None if m is None else (id(m), id(getattr(m, "_w", None)), str(getattr(m, "dtype", None)))
-        def sched_id(s):   # the scheduler OBJECT the state steps with and everything its tables depend on
-            c = s.config   # (a user-supplied scheduler may carry a leaner config: absent fields key as None)
-            return (id(s), type(s).__name__) + tuple(getattr(c, f, None) for f in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule",
-                                                                                   "steps_offset", "set_alpha_to_one", "timestep_spacing",
-                                                                                   "solver_order", "use_karras_sigmas", "final_sigmas_type",
-                                                                                   "lower_order_final", "lms_order"))
-
-        def pg_id():       # a state prepared with dist=True holds communicators of the default group it was made under
-            if not kw.get("dist"):
-                return None
-            import torch.distributed as td
-            return id(td.group.WORLD) if td.is_initialized() else None     # (the public handle of the default group)
-        plan = {k: v for k, v in kw.items() if k not in ("audio_features", "speed_embeddings", "motion_latents", "controlnet_cond",
-                                                            "controlnet_conditioning_scale", "guidance_scale", "eta", "seed",
-                                                            "appearance_encoder", "controlnet", "face_mask", "face_mask_threshold")}
-        # (a face mask enters the plan by presence: either size ends in the same (h*w, C0) buffer; the speed embeddings by shape - per clip or
-        # per frame)
-        return (shp(latents), shp(ref_image_latents), shp(text_embeddings), shp(kw.get("audio_features")), shp(kw.get("speed_embeddings")),
-                kw.get("face_mask") is not None,
-                shp(kw.get("motion_latents")), shp(kw.get("controlnet_cond")), kw.get("controlnet_conditioning_scale", 1.0),
-                self._do_cfg(kw.get("guidance_scale", 7.5)), wid(self.unet), wid(kw.get("appearance_encoder")), wid(kw.get("controlnet")),
-                sched_id(self.scheduler), pg_id(), unet_mod.SHARE_CFG_PREFIX, unet_mod.GN_FOLD_MIN_HW, unet_mod.GN_CONV_MIN_HW, unet_mod.MERGE_QKV,
-                tuple(sorted((k, repr(v)) for k, v in plan.items())))
-
-    def reset_denoise(self, st, latents, motion_latents=None, **inputs):
-        """Re-arm a prepared loop state for another clip of the SAME geometry: new noisy latents (and motion frames; optionally
-        ref_image_latents / text_embeddings / audio_features / speed_embeddings / face_mask (+ face_mask_threshold) / controlnet_cond /
-        guidance_scale / eta / seed; per-frame speeds and a face mask for a state prepared with them, refused otherwise)
-        are copied IN PLACE, so the captured HIP graphs, the resident bank cache and the communicators are reused - only the
-        context K / V^T and the ReferenceNet groups are recomputed (the reference image and the motion frames enter them)."""
-        if tuple(latents.shape) != tuple(st.latents.shape):
-            raise ValueError(f"reset_denoise: latents {tuple(latents.shape)} != prepared {tuple(st.latents.shape)}")
-        if motion_latents is None and st.n_ref_images != 1:
-            raise ValueError("reset_denoise: the state was prepared with motion frames")
-        if motion_latents is not None:
-            ml = self._motion_rows(motion_latents)
-            if ml.shape[0] != st.n_ref_images - 1 or tuple(ml.shape[1:]) != (st.C4, st.h, st.w):
-                raise ValueError(f"reset_denoise: motion_latents must be ({st.n_ref_images - 1}, {st.C4}, {st.h}, {st.w}), got {tuple(ml.shape)}")
-        self._bind_inputs(st, latents, motion_latents=motion_latents, **inputs)
-        return st
-
-    @torch.no_grad()
-    def denoise_chained(self, clips, ref_image_latents, text_embeddings, *, n_motion_frames=4, **kw):
-        """Long-video generation by clip chaining (intent of Net.py:56-72 `pre_extract_motion_features` and
-        junk/EMo-write-up.txt:104-110 - the reference never wires it): clip k+1 is denoised with the LAST n_motion_frames
-        latent frames of the denoised clip k as motion frames; the first clip gets zero maps.  The motion frames pass through
-        the ReferenceNet together with the reference image at every timestep and their LN1 features are appended to the
-        reference banks as extra tokens, i.e. every spatial self-attention of the Backbone's mid / up path also attends to
-        the previous clip's tail (same bank mechanism, Lk1 = (1 + n_motion_frames) * L).  `clips`: list of noisy latents
-        (1, 4, F, h, w), each with F >= n_motion_frames.  Clips of one geometry share ONE prepared state (graphs, bank cache,
-        context K/V); a clip of another shape prepares afresh.  Returns the list of denoised latents.  Design choice - no
-        reference behaviour to match."""
-        out, prev, st = [], None, None
-        run_kw = {k: kw.pop(k) for k in ("num_actual_inference_steps", "callback", "callback_steps") if k in kw}
-        for lat in clips:
-            _, c4, f, h, w = lat.shape
-            if n_motion_frames > 0:
-                if f < n_motion_frames:
-                    raise ValueError(f"denoise_chained: a clip of {f} frames cannot hand over {n_motion_frames} motion frames")
-                motion = torch.zeros(n_motion_frames, c4, h, w) if prev is None else prev[0, :, -n_motion_frames:].permute(1, 0, 2, 3)
-                if motion.shape[0] != n_motion_frames or tuple(motion.shape[2:]) != (h, w):
-                    raise ValueError("denoise_chained: consecutive clips must share the latent size")
-            else:
-                motion = None
-            if st is not None and tuple(st.latents.shape) == tuple(lat.shape):
-                # (same conditioning for every clip of the chain: the face mask, per-frame speeds and the rest stay bound)
-                self.reset_denoise(st, lat, motion)
-            else:
-                st = self.prepare_denoise(lat, ref_image_latents, text_embeddings, motion_latents=motion, **kw)
-            res = self._run_loop(st, **run_kw)
-            prev = (res[0] if isinstance(res, tuple) else res).clone()   # (the state's latents are overwritten by the next clip)
-            out.append(prev)
-        return out
 
     @torch.no_grad()
     def images2latents(self, images, dtype=None):
@@ -1237,6 +417,27 @@ class EMOAnimationPipeline:
             return (x.reshape(len(x), -1).float().numpy(), int(audio[1]))
         return None
 
+    def _encode_head_speeds(self, speeds, video_length=None):
+        """head speeds through the pipeline's SpeedEncoder: ONE per clip (head_rotation_speeds=) -> (1, 4*C0), or with video_length one per
+        frame (head_speeds_per_frame=) -> (1, video_length, 4*C0)"""
+        keyword, shape = ("head_rotation_speeds", "1, ") if video_length is None else ("head_speeds_per_frame", "1, video_length, ")
+        enc = getattr(self, "speed_encoder", None)
+        if enc is None:
+            raise ValueError(f"{keyword}= needs a speed_encoder on the pipeline (emote_hack_amd.conditioning.SpeedEncoder(9, "
+                             "4 * block_out_channels[0]) with loaded weights: pass speed_encoder= to the constructor or assign "
+                             f"pipe.speed_encoder), or pass speed_embeddings=({shape}4 * block_out_channels[0])")
+        v = torch.as_tensor(speeds, dtype=torch.float32).reshape(-1)
+        if video_length is not None and v.numel() != video_length:
+            raise ValueError(f"head_speeds_per_frame= takes one speed per frame: got {v.numel()} values for video_length {video_length}")
+        if video_length is None and v.numel() != 1:
+            raise ValueError(f"head_rotation_speeds= takes ONE speed per clip (a float or a one-element tensor), got {v.numel()} values: "
+                             "per-frame speeds would need a per-frame time embedding - run one clip per speed, or pass speed_embeddings=")
+        width_e = 4 * self.unet.config.block_out_channels[0]      # (the UNet's time-embedding width)
+        if enc.speed_embedding_dim != width_e:
+            raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width_e}: "
+                             f"build SpeedEncoder(9, {width_e})")
+        return enc(v) if video_length is None else enc(v).reshape(1, video_length, width_e)
+
     # ------------------------------------------------------------------ reference-compatible entry point
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]], video_length: Optional[int], height: Optional[int] = None,
@@ -1374,13 +575,13 @@ class EMOAnimationPipeline:
                 raise ValueError("clip_image= and text_embeddings= both name the cross-attention context: pass one")
             if prompt not in ("", [""]):
                 raise ValueError("clip_image= replaces the prompt as the cross-attention context: call with prompt \"\"")
-            text_embeddings = self._encode_image(clip_image, self._execution_device, num_videos_per_prompt, guidance_scale > 1.0)
+            text_embeddings = self._encode_image(clip_image, self._execution_device, num_videos_per_prompt, self._do_cfg(guidance_scale))
         if text_embeddings is None:
             if self.text_encoder is None:
                 raise ValueError("pass text_embeddings=(2,L,D) [uncond, cond], or put a tokenizer + text_encoder "
                                  "(emote_hack_amd.clip_text.CLIPTextModel) on the pipeline")
             if self.tokenizer is not None:     # :628-630
-                text_embeddings = self._encode_prompt(prompt, self._execution_device, num_videos_per_prompt, guidance_scale > 1.0,
+                text_embeddings = self._encode_prompt(prompt, self._execution_device, num_videos_per_prompt, self._do_cfg(guidance_scale),
                                                       negative_prompt)
             else:
                 text_embeddings = self.text_encoder(prompt, negative_prompt)
@@ -1422,36 +623,11 @@ class EMOAnimationPipeline:
             if head_rotation_speeds is not None:
                 raise ValueError("head_rotation_speeds= (ONE speed per clip) and head_speeds_per_frame= both name the head speed: pass one")
             if kwargs.get("speed_embeddings") is None:
-                enc = getattr(self, "speed_encoder", None)
-                if enc is None:
-                    raise ValueError("head_speeds_per_frame= needs a speed_encoder on the pipeline (emote_hack_amd.conditioning.SpeedEncoder(9, "
-                                     "4 * block_out_channels[0]) with loaded weights: pass speed_encoder= to the constructor or assign "
-                                     "pipe.speed_encoder), or pass speed_embeddings=(1, video_length, 4 * block_out_channels[0])")
-                v = torch.as_tensor(kwargs["head_speeds_per_frame"], dtype=torch.float32).reshape(-1)
-                if v.numel() != video_length:
-                    raise ValueError(f"head_speeds_per_frame= takes one speed per frame: got {v.numel()} values for video_length {video_length}")
-                width_e = 4 * self.unet.config.block_out_channels[0]
-                if enc.speed_embedding_dim != width_e:
-                    raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width_e}: "
-                                     f"build SpeedEncoder(9, {width_e})")
-                kwargs["speed_embeddings"] = enc(v).reshape(1, video_length, width_e)
+                kwargs["speed_embeddings"] = self._encode_head_speeds(kwargs["head_speeds_per_frame"], video_length)
         if head_rotation_speeds is not None and kwargs.get("speed_embeddings") is None:
             # :783-784 hands `head_rotation_speeds` to a UNet that rejects it; here ONE speed per clip goes through the pipeline's
             # SpeedEncoder (Net.py:198-258) into the UNet's class-embedding slot, one row shared by the CFG halves
-            enc = getattr(self, "speed_encoder", None)
-            if enc is None:
-                raise ValueError("head_rotation_speeds= needs a speed_encoder on the pipeline (emote_hack_amd.conditioning.SpeedEncoder(9, "
-                                 "4 * block_out_channels[0]) with loaded weights: pass speed_encoder= to the constructor or assign "
-                                 "pipe.speed_encoder), or pass speed_embeddings=(1, 4 * block_out_channels[0])")
-            v = torch.as_tensor(head_rotation_speeds, dtype=torch.float32).reshape(-1)
-            if v.numel() != 1:
-                raise ValueError(f"head_rotation_speeds= takes ONE speed per clip (a float or a one-element tensor), got {v.numel()} values: "
-                                 "per-frame speeds would need a per-frame time embedding - run one clip per speed, or pass speed_embeddings=")
-            width_e = 4 * self.unet.config.block_out_channels[0]      # (not `width`: that is the frame's, read again below)
-            if enc.speed_embedding_dim != width_e:
-                raise ValueError(f"the speed_encoder embeds to {enc.speed_embedding_dim} values, the UNet's time embedding has {width_e}: "
-                                 f"build SpeedEncoder(9, {width_e})")
-            kwargs["speed_embeddings"] = enc(v)
+            kwargs["speed_embeddings"] = self._encode_head_speeds(head_rotation_speeds)
         self._check_speed_embeddings(kwargs.get("speed_embeddings"), video_length)
         face_mask, face_thr = kwargs.get("face_mask"), kwargs.get("face_mask_threshold")
         if face_mask is not None:

@@ -1,5 +1,5 @@
 """N>1 path on CPU: multi-process `gloo` runs of the product pipeline's sharded sampling loop
-(emote_hack_amd/pipeline.py: (window x CFG-branch) units dealt `U[rank::world_size]`, a group's ReferenceNet timesteps dealt
+(emote_hack_amd/denoise_loop.py: (window x CFG-branch) units dealt `U[rank::world_size]`, a group's ReferenceNet timesteps dealt
 over ranks + all_gather of the packed banks, ONE all_gather of the eps slices per step, redundant deterministic
 accumulate + sampler step).
 

@@ -94,8 +94,12 @@ def test_reference_group_size_never_exceeds_the_step_count():
 def test_strong_mode_deals_one_unit_per_rank_at_eight_gpus():
     """bench.py --mode strong = BASELINE configs[3]: one 48-frame clip = 4 windows x 2 CFG branches = 8 units; U[r::8] hands every
     rank exactly one, U[r::4] a [uncond, cond] pair of ONE window (shared prefix), U[r::2] two such pairs."""
-    units = [(w, br) for br in (0, 1) for w in range(4)]
+    from emote_hack_amd.denoise_loop import loop_plan
+    plan = lambda world, r: loop_plan(48, 50, 50, context_frames=12, context_stride=1, context_overlap=0, dist=world > 1, rank=r, world_size=world)
+    units = plan(1, 0).units
+    assert len(units) == 8 and all(plan(8, r).units == units for r in range(8))
     assert all(len(units[r::8]) == 1 for r in range(8))
+    assert all([c.units for c in plan(8, r).calls] == [units[r::8]] for r in range(8))
     for world in (4, 2, 1):
         for r in range(world):
             mine = units[r::world]
@@ -103,6 +107,9 @@ def test_strong_mode_deals_one_unit_per_rank_at_eight_gpus():
             for w, br in mine:
                 byw.setdefault(w, set()).add(br)
             assert all(v == {0, 1} for v in byw.values()), (world, r, mine)
+            calls = plan(world, r).calls
+            assert sorted(u for c in calls for u in c.units) == sorted(mine)
+            assert all(c.units == [(c.units[0][0], 0), (c.units[0][0], 1)] and c.halves_identical for c in calls), (world, r)
 
 
 def test_groupnorm_one_launch_plan():
