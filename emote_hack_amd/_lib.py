@@ -155,6 +155,8 @@ SIGNATURES = {
     "emo_png_lz_count": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_png_deflate_bits": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_png_deflate_emit": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p]),
+    "emo_png_inflate": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "emo_png_unfilter": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

@@ -1045,6 +1045,48 @@ def png_deflate_emit(tokens: torch.Tensor, n_tokens: torch.Tensor, codes: torch.
     return out
 
 
+PNG_STATUS = {0: "ok", 1: "a block of type 3", 2: "a stored block whose NLEN is not the complement of its LEN",
+              3: "a set of code lengths that makes no Huffman code", 4: "a symbol or bits that the block's codes do not define",
+              5: "a distance that reaches in front of the frame's first byte", 6: "the stream ends inside a block",
+              7: "more bytes than the frame's scanlines hold", 8: "the last block ends before the frame's last scanline",
+              9: "a scanline with a filter type above 4"}   # EMO_PNG_OK / _BAD_BLOCK / _BAD_STORED / _BAD_LENGTHS / _BAD_SYMBOL / _BAD_DISTANCE /
+#                                                             _PAST_END / _OVERFLOW / _SHORT / _BAD_FILTER
+
+
+def png_inflate(streams: torch.Tensor, offsets: torch.Tensor, H: int, W: int, channels: int, out=None, produced=None, status=None):
+    """the raw deflate streams of n frames (uint8, a multiple of 4 bytes; frame i in bytes offsets[i] .. offsets[i + 1], int64 (n + 1);
+    zlib header and Adler-32 taken off) -> (filtered uint8 (n, H, 1 + W * channels), produced int32 (n), status int32 (n): a key of
+    PNG_STATUS) (emo_png_inflate; RFC 1951).  channels 1 .. 4."""
+    _need_cuda(streams, offsets)
+    assert streams.dtype == torch.uint8 and streams.dim() == 1 and streams.is_contiguous(), (streams.dtype, streams.shape)
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
+    n, H, W, channels = offsets.numel() - 1, int(H), int(W), int(channels)
+    filtered = _jpeg_out(out, (n, H, 1 + W * channels), torch.uint8, streams.device, "filtered")
+    produced = _jpeg_out(produced, (n,), torch.int32, streams.device, "produced")
+    status = _jpeg_out(status, (n,), torch.int32, streams.device, "status")
+    _launch("png_inflate", 0.0, float(streams.numel() + filtered.numel()),
+            lambda: check(_lib.load().emo_png_inflate(_ptr(streams), streams.numel(), _ptr(offsets), _ptr(filtered), _ptr(produced), _ptr(status), n,
+                                                      H, W, channels, _stream()), "emo_png_inflate"), tag=f"{n}x{H}x{W}x{channels}")
+    return filtered, produced, status
+
+
+def png_unfilter(filtered: torch.Tensor, channels: int, out=None, adler=None, status=None):
+    """filtered scanlines uint8 (n, H, 1 + W * channels) -> (frames uint8 (n, H, W, channels), adler int32 (n, H, 2): the Adler-32 pair
+    of every filtered row as png_filter gives it, status int32 (n): 0 or 9 of PNG_STATUS) (emo_png_unfilter; PNG 9.2 - 9.4)."""
+    _need_cuda(filtered)
+    assert filtered.dtype == torch.uint8 and filtered.dim() == 3 and filtered.is_contiguous(), (filtered.dtype, filtered.shape)
+    n, H, R = (int(s) for s in filtered.shape)
+    assert isinstance(channels, int) and channels >= 1 and (R - 1) % channels == 0 and R > 1, (R, channels)
+    W = (R - 1) // channels
+    frames = _jpeg_out(out, (n, H, W, channels), torch.uint8, filtered.device, "frames")
+    adler = _jpeg_out(adler, (n, H, 2), torch.int32, filtered.device, "adler")
+    status = _jpeg_out(status, (n,), torch.int32, filtered.device, "status")
+    _launch("png_unfilter", 0.0, 2.0 * filtered.numel(),
+            lambda: check(_lib.load().emo_png_unfilter(_ptr(filtered), _ptr(frames), _ptr(adler), _ptr(status), n, H, W, channels, _stream()),
+                          "emo_png_unfilter"), tag=f"{n}x{H}x{W}x{channels}")
+    return frames, adler, status
+
+
 JPEG_DECODE_TABLE_INTS = 320                     # EMO_JPEG_DECODE_TABLE_INTS
 JPEG_STATUS = {0: "ok", 1: "a code the Huffman table does not define", 2: "the scan ends before the frame's last block",
                3: "a zero run leaves its block"}   # EMO_JPEG_OK / _BAD_CODE / _PAST_END / _BAD_RUN

@@ -37,6 +37,11 @@
                     independently) -> ONE small read of the frames' symbol counts -> the Huffman code lengths, the canonical codes and
                     the header of one dynamic block per frame on the host (table building, like median cut) -> emo_png_deflate_bits /
                     emo_png_deflate_emit, one copy of the streams, then header, end-of-block, Adler-32 and the chunks on the host
+  parse_png, decode_png, decode_apng      the reverse: the chunks, CRCs, sequence numbers and zlib headers of a PNG / APNG file on the host,
+                    then ONE copy of all frames' deflate streams, emo_png_inflate (one wavefront per frame: stored, fixed and dynamic
+                    blocks, the 32 KiB window a ring in LDS) and emo_png_unfilter (a skewed wavefront over bands of 64 rows;
+                    csrc/png_in.hip), one small read of the statuses and the rows' Adler-32 pairs - the bytes Pillow gives.  read_image
+                    takes a `.png`, read_video an `.apng`, an animated `.png` and a numbered pattern through them
   FORMATS           the one table of the files a clip is written as - avi, gif, apng, numbered png stills: per format its extension,
                     the keywords it owns, whether it plays and holds sound, the checks of its options and of its rate, its encoder.
                     Every writer of a clip runs one sequence over its record (_write_clip), and save_plan does for the pipeline's
@@ -1818,6 +1823,263 @@ def write_apng(frames_u8: torch.Tensor, path, fps, **options) -> None:
     _write_clip("write_apng", lambda: frames_u8, path, fps, FORMATS["apng"], None, options)
 
 
+# ---------------------------------------------------------------------------------------------------------------------- reading PNG / APNG
+PNG_CHANNELS = {0: 1, 4: 2, 2: 3, 6: 4}      # IHDR colour type -> channels at bit depth 8: grey, grey + alpha, RGB, RGBA
+_PNG_ONLY = ("decode_png reads PNG and APNG files at bit depth 8 without interlace: grey, grey + alpha, RGB or RGBA; APNG frames that "
+             "cover the whole canvas and replace it (blend_op 0)")
+
+
+@dataclasses.dataclass(frozen=True)
+class ParsedPng:
+    """What parse_png takes from a PNG / APNG file: everything but the pixels."""
+    width: int
+    height: int
+    channels: int              # 1 grey, 2 grey + alpha, 3 RGB, 4 RGBA
+    still: bytes               # the raw deflate stream (RFC 1951) of the IDAT image: zlib header and Adler-32 taken off
+    still_adler: int           # the Adler-32 its zlib stream ends with
+    frames: tuple              # the animation's frames as (raw deflate stream, Adler-32); for a file without acTL the still alone
+    delays: tuple              # a Fraction of a second per frame of the animation; () for a file without acTL
+    loop: int                  # acTL num_plays (0: forever); 0 for a still
+    animated: bool             # the file holds acTL
+    still_in_animation: bool   # the IDAT image is the animation's first frame (an fcTL stands in front of it)
+
+
+def _zlib_body(stream: bytes, what: str):
+    """a zlib stream (RFC 1950) -> (the deflate stream inside, the Adler-32 behind it); the header is checked here"""
+    if len(stream) < 6:
+        raise ValueError(f"{what}: a zlib stream of {len(stream)} bytes holds no header and checksum")
+    cmf, flg = stream[0], stream[1]
+    if cmf & 15 != 8:
+        raise ValueError(f"{what}: zlib compression method {cmf & 15}, PNG takes 8 (deflate)")
+    if cmf >> 4 > 7:
+        raise ValueError(f"{what}: a zlib window of 2^{(cmf >> 4) + 8} bytes, deflate stops at 32 KiB")
+    if (cmf << 8 | flg) % 31:
+        raise ValueError(f"{what}: the zlib header's check bits (FCHECK) are wrong")
+    if flg & 0x20:
+        raise ValueError(f"{what}: a zlib stream with a preset dictionary, which PNG does not allow")
+    return bytes(stream[2:-4]), struct.unpack(">I", stream[-4:])[0]
+
+
+def parse_png(data) -> ParsedPng:
+    """A PNG (ISO/IEC 15948) or APNG 1.0 file's bytes -> ParsedPng.  The signature, every chunk's CRC, the order IHDR .. IDAT .. IEND, the
+    sequence numbers of fcTL / fdAT and the zlib header of every frame are checked; the bodies of a frame's IDAT (or fdAT, less their
+    sequence numbers) chunks are joined.  ValueError, naming what, for: a bit depth other than 8, a palette image (colour type 3), an
+    interlaced (Adam7) file, an APNG frame that does not cover the whole canvas or blends over the one before (blend_op 1), a CRC
+    mismatch, a missing IEND, an unknown critical chunk - and for a damaged structure.  Ancillary chunks are skipped; so is tRNS on
+    grey and RGB files, as Pillow's `np.asarray(Image.open(f))` and `.convert("RGB")` leave the samples of such a file as they are."""
+    import zlib
+    data = bytes(data)
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError("not a PNG file: the signature is missing")
+    pos, ihdr, seq, ended = 8, None, 0, False
+    n_frames = loop = None
+    idat, groups, control = [], [], []      # groups: per fcTL the list its data chunks join; control: per fcTL (num, den)
+    current, idat_state = None, 0           # idat_state: 0 in front of the IDAT chunks, 1 among them, 2 behind them
+    while pos < len(data):
+        if pos + 12 > len(data):
+            raise ValueError(f"a chunk header at byte {pos} runs past the file's end ({_PNG_ONLY}: no IEND)")
+        size, kind = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
+        if pos + 12 + size > len(data):
+            raise ValueError(f"chunk {kind!r} at byte {pos} runs past the file's end: no IEND")
+        body = data[pos + 8:pos + 8 + size]
+        if zlib.crc32(kind + body) != struct.unpack(">I", data[pos + 8 + size:pos + 12 + size])[0]:
+            raise ValueError(f"chunk {kind!r} at byte {pos}: CRC mismatch")
+        pos += 12 + size
+        if kind != b"IDAT" and idat_state == 1:
+            idat_state = 2
+        if ihdr is None and kind != b"IHDR":
+            raise ValueError(f"the first chunk is {kind!r}, not IHDR")
+        if kind == b"IHDR":
+            if ihdr is not None or size != 13:
+                raise ValueError("a second or malformed IHDR")
+            ihdr = struct.unpack(">IIBBBBB", body)
+            width, height, depth, colour, comp, filt, lace = ihdr
+            if colour == 3:
+                raise ValueError(f"a palette image (colour type 3): {_PNG_ONLY}")
+            if colour not in PNG_CHANNELS:
+                raise ValueError(f"colour type {colour}: {_PNG_ONLY}")
+            if depth != 8:
+                raise ValueError(f"bit depth {depth}: {_PNG_ONLY}")
+            if lace:
+                raise ValueError(f"an interlaced (Adam7) file: {_PNG_ONLY}")
+            if comp or filt or not width or not height or width >= 2 ** 31 or height >= 2 ** 31:
+                raise ValueError(f"IHDR: {width} x {height}, compression method {comp}, filter method {filt}")
+        elif kind == b"IDAT":
+            if idat_state == 2:
+                raise ValueError("IDAT chunks are not consecutive")
+            idat_state = 1
+            idat.append(body)
+        elif kind == b"IEND":
+            ended = True
+            break
+        elif kind == b"acTL":
+            if n_frames is not None or idat_state or size != 8:
+                raise ValueError("a second, late or malformed acTL")
+            n_frames, loop = struct.unpack(">II", body)
+        elif kind == b"fcTL":
+            if size != 26 or n_frames is None:
+                raise ValueError("an fcTL of the wrong size or without acTL")
+            s, w, h, x, y, num, den, dispose, blend = struct.unpack(">IIIIIHHBB", body)
+            if s != seq:
+                raise ValueError(f"fcTL sequence number {s}, {seq} is next")
+            seq += 1
+            if (w, h, x, y) != (width, height, 0, 0):
+                raise ValueError(f"an APNG frame of {w} x {h} at ({x}, {y}) on a canvas of {width} x {height}, a partial frame: {_PNG_ONLY}")
+            if blend != 0:
+                raise ValueError(f"an APNG frame that blends over the one before (blend_op {blend}): {_PNG_ONLY}")
+            if idat_state == 0 and groups:
+                raise ValueError("two fcTL chunks in front of IDAT")
+            current = idat if idat_state == 0 else []
+            groups.append(current)
+            control.append(Fraction(num, den or 100))
+        elif kind == b"fdAT":
+            if size < 4 or current is None or current is idat:
+                raise ValueError("an fdAT without its fcTL")
+            s = struct.unpack(">I", body[:4])[0]
+            if s != seq:
+                raise ValueError(f"fdAT sequence number {s}, {seq} is next")
+            seq += 1
+            current.append(body[4:])
+        elif not kind[0] & 0x20 and kind != b"PLTE":
+            raise ValueError(f"unknown critical chunk {kind!r}")
+    if not ended:
+        raise ValueError("no IEND chunk: the file is cut")
+    if ihdr is None or not idat:
+        raise ValueError("no IDAT chunk")
+    channels = PNG_CHANNELS[colour]
+    still, still_adler = _zlib_body(b"".join(idat), "IDAT")
+    if n_frames is None:
+        return ParsedPng(width, height, channels, still, still_adler, ((still, still_adler),), (), 0, False, True)
+    if len(groups) != n_frames or n_frames < 1:
+        raise ValueError(f"acTL counts {n_frames} frames, the file holds {len(groups)} fcTL chunks")
+    frames = []
+    for i, g in enumerate(groups):
+        if not g:
+            raise ValueError(f"APNG frame {i} has no data")
+        frames.append((still, still_adler) if g is idat else _zlib_body(b"".join(g), f"APNG frame {i}"))
+    return ParsedPng(width, height, channels, still, still_adler, tuple(frames), tuple(control), int(loop), True, groups[0] is idat)
+
+
+def _png_device(device, who):
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ops._lib.EmoHipError(f"{who} decodes on the HIP device, got device {device} (there is no host decoder here)")
+    return device
+
+
+def _decode_png_streams(streams, height: int, width: int, channels: int, device, who: str) -> torch.Tensor:
+    """[(raw deflate stream, Adler-32)] of frames of one shape -> uint8 (n, height, width, channels) on the device: ONE upload (offsets and
+    streams), emo_png_inflate, emo_png_unfilter, ONE small read (both statuses, the byte counts, the rows' Adler pairs)"""
+    n, row = len(streams), 1 + width * channels
+    sizes = np.array([len(s) for s, _ in streams], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    pad = -int(offsets[-1]) % 4 or (4 if offsets[-1] == 0 else 0)
+    host = np.concatenate([offsets.view(np.uint8)] + [np.frombuffer(s, np.uint8) for s, _ in streams] + [np.zeros(pad, np.uint8)])
+    dev = torch.from_numpy(host).to(device)                                       # the one copy
+    filtered, produced, inflated = ops.png_inflate(dev[8 * (n + 1):], dev[:8 * (n + 1)].view(torch.int64), height, width, channels)
+    frames, adler, unfiltered = ops.png_unfilter(filtered, channels)
+    back = torch.cat([inflated, unfiltered, produced, adler.reshape(-1)]).cpu().numpy()                       # the one read
+    for i in range(n):
+        for entry, st in (("emo_png_inflate", int(back[i])), ("emo_png_unfilter", int(back[n + i]))):
+            if st:
+                at = f" after {int(back[2 * n + i])} of {height * row} bytes" if entry == "emo_png_inflate" else ""
+                raise ValueError(f"{who}: frame {i} does not decode: {ops.PNG_STATUS.get(st, f'status {st}')}{at} ({entry} status {st})")
+        got = adler32_combine(back[3 * n + 2 * height * i:3 * n + 2 * height * (i + 1)].view(np.uint32), row)
+        if got != streams[i][1]:
+            raise ValueError(f"{who}: frame {i}: the Adler-32 of the decoded scanlines is {got:08x}, the zlib stream ends with {streams[i][1]:08x}")
+    return frames
+
+
+def decode_png(files, device=None) -> torch.Tensor:
+    """PNG files of one size and colour type (bytes each; what encode_png, Pillow or libpng write: bit depth 8, grey, grey + alpha, RGB
+    or RGBA, no interlace) -> packed uint8 frames (n, H, W, C) on the device, byte for byte `np.asarray(Image.open(f))`.  The host walks
+    the chunks only (parse_png); all streams go up in ONE copy and through two launches - emo_png_inflate, one wavefront per frame, and
+    emo_png_unfilter - followed by one small read: the statuses and the scanlines' Adler-32 pairs, which the host combines and compares
+    with every stream's trailer.  Of an APNG file the IDAT image is taken (decode_apng reads the animation).  ValueError naming the
+    frame for a file parse_png refuses, a frame of another size or colour type, a stream that does not inflate (with the status), a
+    filter type above 4, or a checksum that does not match.  There is no host decoder behind this."""
+    files = list(files)
+    if not files:
+        raise ValueError("decode_png: no frames")
+    device = _png_device(device, "decode_png")
+    parsed = []
+    for i, f in enumerate(files):
+        try:
+            parsed.append(parse_png(f))
+        except ValueError as e:
+            raise ValueError(f"decode_png: frame {i}: {e}") from None
+    shape = (parsed[0].height, parsed[0].width, parsed[0].channels)
+    for i, p in enumerate(parsed):
+        if (p.height, p.width, p.channels) != shape:
+            raise ValueError(f"decode_png: frame {i} is {p.height} x {p.width} x {p.channels}, frame 0 is {shape[0]} x {shape[1]} x {shape[2]}: "
+                             "the frames of a clip share one size and colour type")
+    return _decode_png_streams([(p.still, p.still_adler) for p in parsed], *shape, device, "decode_png")
+
+
+def decode_apng(data, device=None, select=None):
+    """An APNG file's bytes -> (uint8 frames (n, H, W, C) on the device, the delays as exact Fractions of a second, loop: acTL's
+    num_plays, 0 forever).  The frames of the animation: the IDAT image is left out when no fcTL stands in front of it.  A PNG without
+    acTL gives its one image, no delays and loop 0.  select= (a slice) picks frames before anything is decoded."""
+    device = _png_device(device, "decode_apng")
+    try:
+        p = parse_png(data)
+    except ValueError as e:
+        raise ValueError(f"decode_apng: {e}") from None
+    frames, delays = list(p.frames), list(p.delays)
+    if select is not None:
+        frames, delays = frames[select], delays[select]
+        if not frames:
+            raise ValueError(f"decode_apng: the file holds {len(p.frames)} frames; {select} selects none")
+    return _decode_png_streams(frames, p.height, p.width, p.channels, device, "decode_apng"), delays, p.loop
+
+
+def _png_rgb(frames: torch.Tensor) -> torch.Tensor:
+    """(n, H, W, C) -> (n, H, W, 3) as Pillow's `.convert("RGB")`: grey in all three channels, alpha dropped"""
+    c = int(frames.shape[-1])
+    if c == 3:
+        return frames
+    return (frames[..., :1].expand(*frames.shape[:-1], 3) if c < 3 else frames[..., :3]).contiguous()
+
+
+def _numbered_pngs(path, who) -> list:
+    """the files a numbered pattern names: consecutive numbers from the first that exists, 0 or 1"""
+    first = next((k for k in (0, 1) if os.path.exists(path % k)), None)
+    if first is None:
+        raise ValueError(f"{who}: neither {path % 0!r} nor {path % 1!r} exists")
+    paths, k = [], first
+    while os.path.exists(path % k):
+        paths.append(path % k)
+        k += 1
+    return paths
+
+
+def _read_png_clip(path, step, length, start, who):
+    """read_video for `.apng`, an animated or still `.png` and a numbered pattern -> (RGB frames on the device, fps or None)"""
+    path = os.fspath(path)
+    if path.lower().endswith(".png") and _png_pattern(path, who)[1]:
+        paths = _numbered_pngs(path, who)
+        picked = paths[start::step][:length]
+        if not picked:
+            raise ValueError(f"{who}: {path!r} names {len(paths)} files; [{start}::{step}][:{length}] selects none")
+        files = []
+        for p in picked:
+            with open(p, "rb") as f:
+                files.append(f.read())
+        return _png_rgb(decode_png(files)), None
+    with open(path, "rb") as f:
+        data = f.read()
+    try:
+        p = parse_png(data)
+    except ValueError as e:
+        raise ValueError(f"{who}: {path!r}: {e}") from None
+    picked = list(p.frames)[start::step][:length]
+    if not picked:
+        raise ValueError(f"{who}: {path!r} holds {len(p.frames)} frames; [{start}::{step}][:{length}] selects none")
+    delays = set(p.delays)
+    fps = 1 / p.delays[0] if len(delays) == 1 and p.delays[0] > 0 else None
+    return _png_rgb(_decode_png_streams(picked, p.height, p.width, p.channels, _png_device(None, who), f"{who}: {path!r}")), fps
+
+
 def save_images_grid(images: torch.Tensor, path: str, quality: int = 90):
     """magicanimate/utils/util.py:35-41: (b, c, 1, h, w) in [0, 1] -> one image file of the grid `torchvision.utils.make_grid(images)`
     lays out with its defaults (8 per row, 2 pixels of padding; make_grid_u8), `* 255` truncated to uint8 as :39 does.  `.png` is written
@@ -2033,7 +2295,10 @@ def decode_jpeg(data: bytes) -> np.ndarray:
 
 
 def video2images(path, step=4, length=16, start=0):
-    """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays"""
+    """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays; of an `.apng` /
+    `.png` file or a numbered `.png` pattern (read_video, decoded on the device) the same frames, copied to the host"""
+    if not os.fspath(path).lower().endswith(".avi"):
+        return list(read_video(path, step, length, start)[0].cpu().numpy())
     jpegs, _, _ = read_avi(path)
     return [decode_jpeg(j) for j in jpegs[start::step][:length]]
 
@@ -2045,7 +2310,9 @@ def read_image(path_or_bytes, size=None, resample="bicubic", progressive: bool =
     from parse_jpeg for a file it refuses (progressive, arithmetic-coded, 4:1:1, RGB, ...): Pillow reads those.
     progressive=True also decodes a Huffman-coded progressive file (SOF2) with a complete progression on the device, scan by scan
     (decode_mjpeg(progressive=True)): the same bytes, since libjpeg reads such a file to the coefficients of the baseline one; a
-    progression that stops early, which libjpeg smooths, stays refused."""
+    progression that stops early, which libjpeg smooths, stays refused.
+    A PNG file (recognised by its signature; what parse_png takes: 8 bits, grey, grey + alpha, RGB or RGBA, no interlace) is decoded by
+    decode_png and brought to RGB as `.convert("RGB")` does - grey in all three channels, alpha dropped - by indexing on the device."""
     if size is not None:
         size, resample = _resize_size(size, "read_image"), _resize_filter(resample)
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
@@ -2054,10 +2321,13 @@ def read_image(path_or_bytes, size=None, resample="bicubic", progressive: bool =
         with open(path_or_bytes, "rb") as f:
             data = f.read()
     try:
-        parse_jpeg(data, restart=True, layouts=True, progressive=progressive)
+        if data[:8] == PNG_SIGNATURE:
+            parse_png(data)
+        else:
+            parse_jpeg(data, restart=True, layouts=True, progressive=progressive)
     except ValueError as e:
         raise ValueError(f"read_image: {e}") from None
-    frames = decode_mjpeg([data], progressive=progressive)
+    frames = _png_rgb(decode_png([data])) if data[:8] == PNG_SIGNATURE else decode_mjpeg([data], progressive=progressive)
     if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
         frames = resize_frames(frames, size, resample)
     return frames[0]
@@ -2068,9 +2338,18 @@ def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"
     frames [start::step][:length], decoded by decode_mjpeg.  What `VideoReader(path).read()` gives magicanimate/pipelines/animation.py:174-185,
     without the frames passing through a host decoder.  size=(width, height) resizes the decoded frames as animation.py:177 does
     (resize_frames with `resample`), still on the device; None returns them as stored.  progressive=True takes progressive frames
-    too, mixed with baseline ones (decode_mjpeg(progressive=True))."""
+    too, mixed with baseline ones (decode_mjpeg(progressive=True)).
+    An `.apng` file, an animated (or still) `.png` file and a numbered pattern as write_png takes it (`frames/f_%04d.png`: consecutive
+    numbers from the first file that exists, 0 or 1) are read too, inflated and unfiltered on the device (decode_png, decode_apng) and
+    brought to RGB as read_image does; only the selected frames are decoded.  fps is then 1 / delay where all the file's delays are
+    equal, else None - None for stills -, and audio is None."""
     if size is not None:
         size, resample = _resize_size(size, "read_video"), _resize_filter(resample)
+    if os.fspath(path).lower().endswith((".png", ".apng")):
+        frames, fps = _read_png_clip(path, step, length, start, "read_video")
+        if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
+            frames = resize_frames(frames, size, resample)
+        return frames, fps, None
     jpegs, fps, audio = read_avi(path)
     picked = jpegs[start::step][:length]
     if not picked:

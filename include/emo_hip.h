@@ -613,6 +613,50 @@ int emo_png_deflate_bits(const uint32_t* tokens, const int32_t* n_tokens, const 
 int emo_png_deflate_emit(const uint32_t* tokens, const int32_t* n_tokens, const uint32_t* codes, const int64_t* bit_offsets, uint8_t* out,
                          int64_t out_bytes, int n, int H, int W, int C, int strip_rows, void* stream);
 
+/* ---- PNG / APNG input: the device half of the reader of what the block above writes and of what Pillow and libpng write: the numbered
+ * stills of ExtractFrames.py:51, the portrait `Image.open` reads (EMOAnimationPipeline.py:688, animation.py:185, inference.py:41), lossless
+ * pose / depth / mask clips.  PNG is ISO/IEC 15948: section 7 the scanline serialisation, section 9 filtering (9.2 the filter types, 9.3
+ * Average, 9.4 Paeth), section 10 the image data as a zlib stream (RFC 1950) of deflate blocks (RFC 1951).  The host half (signature,
+ * chunks and CRCs, IHDR / acTL / fcTL / fdAT, the zlib header, the Adler-32 trailer) is emote_hack_amd/video_io.py.  The kernels live in
+ * csrc/png_in.hip.  Shapes common to both entries: n, H, W >= 1, C in {1, 2, 3, 4} (grey, grey + alpha, RGB, RGBA at bit depth 8, no
+ * interlace), a filtered scanline has R = 1 + W * C bytes, and H * R <= 2^31 - 1; anything else is EMO_ERR_BAD_SHAPE before any launch.
+ * emo_png_inflate (RFC 1951): the RAW deflate streams of n frames - the host has taken off and checked the two zlib header bytes (RFC
+ *   1950 2.2) and the four of the Adler-32 - lie in `streams` (stream_bytes bytes, a multiple of 4, 4-byte aligned; bytes behind the last
+ *   frame are never used), frame i in bytes offsets[i] .. offsets[i + 1] (int64 [n + 1], 8-byte aligned).  Output: filtered uint8
+ *   [n][H * R], produced int32 [n] (the bytes the frame gave, at most H * R) and status int32 [n].  All three block types (3.2.4 stored,
+ *   3.2.6 fixed, 3.2.7 dynamic), any number of blocks, a stored block from any bit position.  Status:
+ *     EMO_PNG_OK            the final block ended with exactly H * R bytes produced (bytes behind it in the frame are not looked at)
+ *     EMO_PNG_BAD_BLOCK     block type 3
+ *     EMO_PNG_BAD_STORED    a stored block's NLEN is not the complement of its LEN
+ *     EMO_PNG_BAD_LENGTHS   a dynamic block's code lengths, decided as zlib's inflate decides: HLIT above 286 or HDIST above 30; an
+ *                           over-subscribed set; an incomplete set - other than a set of one single code of one bit (a distance set of
+ *                           one code), or no distance code at all, which are accepted, never for the code-length code -; a repeat (16)
+ *                           with no length in front of it; a repeat that runs past HLIT + HDIST (one that crosses from the literal /
+ *                           length lengths into the distance lengths is allowed); no code for the end-of-block symbol
+ *     EMO_PNG_BAD_SYMBOL    literal / length symbol 286 or 287, distance symbol 30 or 31, or 15 bits that begin no code of the set
+ *     EMO_PNG_BAD_DISTANCE  a distance that reaches in front of the frame's first byte
+ *     EMO_PNG_PAST_END      the frame's bytes end inside a block (a cut file, an empty frame; offsets that run backwards or leave the
+ *                           buffer are taken as an empty frame)
+ *     EMO_PNG_OVERFLOW      a literal, a match or a stored block would carry the output past H * R (none of it is written)
+ *     EMO_PNG_SHORT         the final block ended before H * R bytes
+ *   A frame with an error stops there: what it produced up to then is in filtered, produced says how much; other frames are not
+ *   touched.  One wavefront per frame.  Bounds: every read of the streams is masked to the frame's own bytes (past them the reader sees
+ *   zeros and the frame ends with EMO_PNG_PAST_END), every write to filtered is masked to the frame's own H * R, every table index to
+ *   its table; every loop is counted by input bits or output bytes - each turn takes at least one bit or ends the frame.  A damaged
+ *   file gives a status, never a hang or an access outside the buffers.
+ * emo_png_unfilter (PNG 9.2 - 9.4): filtered [n][H][R] -> packed uint8 frames [n][H][W][C]: per scanline, t its first byte, byte j of
+ *   the raw row is (filtered[1 + j] + pred_t) mod 256 with the pred_t of emo_png_filter over the RECONSTRUCTED a, b, c (a = raw[y][j - C],
+ *   b = raw[y - 1][j], c = raw[y - 1][j - C], 0 where there is none).  adler uint32 [n][H][2]: per row the Adler-32 pair of its R
+ *   filtered bytes in exactly the form emo_png_filter writes, for the host to combine and compare with the stream's trailer.  status
+ *   int32 [n]: EMO_PNG_OK, or EMO_PNG_BAD_FILTER for a type byte above 4 - the frame stops at the band of 64 rows that holds it (rows
+ *   in front of the band are written, their Adler pairs too).  A row holds at most 98304 bytes (W * C), more is EMO_ERR_BAD_SHAPE.
+ *   One wavefront per frame; reads and writes stay inside the frame's own rows whatever the bytes say. */
+enum { EMO_PNG_OK = 0, EMO_PNG_BAD_BLOCK = 1, EMO_PNG_BAD_STORED = 2, EMO_PNG_BAD_LENGTHS = 3, EMO_PNG_BAD_SYMBOL = 4, EMO_PNG_BAD_DISTANCE = 5,
+       EMO_PNG_PAST_END = 6, EMO_PNG_OVERFLOW = 7, EMO_PNG_SHORT = 8, EMO_PNG_BAD_FILTER = 9 };
+int emo_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, uint8_t* filtered, int32_t* produced,
+                    int32_t* status, int n, int H, int W, int C, void* stream);
+int emo_png_unfilter(const uint8_t* filtered, uint8_t* frames, uint32_t* adler, int32_t* status, int n, int H, int W, int C, void* stream);
+
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
  * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, one scan; the host half (marker segments of Annex B, the
