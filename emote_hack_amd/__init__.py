@@ -31,7 +31,7 @@ def __getattr__(name):  # heavy modules on demand
         from . import clip_vision
         return getattr(clip_vision, name)
     if name in ("save_videos_grid", "images2video", "video2images", "encode_mjpeg", "write_avi", "read_avi", "jpeg_tables",
-                "save_images_grid", "encode_png", "encode_apng", "write_png", "write_apng", "parse_png", "decode_png", "decode_apng",
+                "save_images_grid", "encode_png", "encode_apng", "write_png", "write_apng", "parse_png", "decode_png", "decode_apng", "parse_gif", "decode_gif",
                 "read_image", "read_video"):
         from . import video_io
         return getattr(video_io, name)

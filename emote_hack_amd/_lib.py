@@ -157,6 +157,8 @@ SIGNATURES = {
     "emo_png_deflate_emit": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _p]),
     "emo_png_inflate": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "emo_png_unfilter": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "emo_gif_lzw_decode": (_i, [_p, _i64, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "emo_gif_compose": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_bits": (_i, [_p, _i64, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "emo_jpeg_decode_segments": (_i, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i, _i, _i, _i, _p]),
     "emo_jpeg_idct": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),

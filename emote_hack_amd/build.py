@@ -16,7 +16,8 @@ LIB = os.path.join(LIBDIR, "libemo_hip.so")
 # the GEMM and the halo-conv kernels are instantiated per element type in their own translation units (parallel compile)
 SOURCES = ["elementwise.hip", "norm.hip", "gemm.hip", "gemm_f32.hip", "gemm_bf16.hip", "gemm_f16.hip", "conv_halo_f32.hip", "conv_halo_bf16.hip",
            "conv_halo_f16.hip", "attention.hip", "temporal.hip", "conditioning.hip", "frontend.hip", "vision.hip", "video_out.hip", "video_in.hip",
-           "video_in_progressive.hip", "image_resize.hip", "gif_out.hip", "png_out.hip", "png_in.hip"]
+           "video_in_progressive.hip", "image_resize.hip", "gif_out.hip", "png_out.hip", "png_in.hip",
+           "gif_in.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-pass-failed"]

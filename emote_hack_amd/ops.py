@@ -1087,6 +1087,93 @@ def png_unfilter(filtered: torch.Tensor, channels: int, out=None, adler=None, st
     return frames, adler, status
 
 
+GIF_FRAME_INTS = 11                              # EMO_GIF_FRAME_INTS: left, top, w, h, transparent | -1, disposal, fill, interlace, table row, entries, slot | -1
+GIF_STATUS = {0: "ok", 1: "a code the table does not define yet, or a code above Clear as the first of a table",
+              2: "the image data ends before the frame's last pixel and before an End of Information",
+              3: "End of Information before the frame's last pixel", 4: "a colour index at or beyond the frame's colour table",
+              8: "a frame descriptor that does not fit its canvas, its indices or the tables"}
+#                                                  EMO_GIF_OK / _BAD_CODE / _PAST_END / _SHORT / _BAD_INDEX / _BAD_FRAME (the last two are bits)
+
+
+def gif_status_words(status: int) -> str:
+    """a status of gif_lzw_decode or gif_compose in words (gif_compose ORs its two)"""
+    status = int(status)
+    if status in GIF_STATUS:
+        return GIF_STATUS[status]
+    words = [GIF_STATUS[b] for b in (4, 8) if status & b]
+    return " and ".join(words) if words and not status & ~12 else f"status {status}"
+
+
+def gif_layout_check(offsets, code_size, out_offsets, stream_bytes: int) -> int:
+    """What emo_gif_lzw_decode cannot read before its launch, checked on HOST copies (sequences or numpy arrays) of its three device
+    arrays: offsets (n + 1) ascending from >= 0 and inside the stream_bytes of the stream buffer, code_size (n) in 2 .. 8,
+    out_offsets (n + 1) ascending from 0 with a sum of at most 2^31 - 1.  -> out_offsets[n], the bytes of `indices`.  EmoHipError
+    (EMO_ERR_BAD_SHAPE in words) before any launch otherwise."""
+    offsets, code_size, out_offsets = [[int(v) for v in a] for a in (offsets, code_size, out_offsets)]
+    n = len(code_size)
+    bad = None
+    if n < 1 or len(offsets) != n + 1 or len(out_offsets) != n + 1:
+        bad = f"n={n} frames with {len(offsets)} offsets and {len(out_offsets)} out_offsets (n >= 1, n + 1 each)"
+    elif offsets[0] < 0 or offsets[-1] > int(stream_bytes) or any(b < a for a, b in zip(offsets, offsets[1:])):
+        bad = f"offsets must ascend inside the {int(stream_bytes)} bytes of the streams, got {offsets[:4]} .. {offsets[-1]}"
+    elif any(not 2 <= c <= 8 for c in code_size):
+        bad = f"an LZW minimum code size of {next(c for c in code_size if not 2 <= c <= 8)}: GIF takes 2 .. 8"
+    elif out_offsets[0] != 0 or any(b < a for a, b in zip(out_offsets, out_offsets[1:])):
+        bad = f"out_offsets must ascend from 0, got {out_offsets[:4]} .. {out_offsets[-1]}"
+    elif out_offsets[-1] > 2 ** 31 - 1 or out_offsets[-1] < 1:
+        bad = f"{out_offsets[-1]} colour indices in all: the frames' pixels are counted in 31 bits, at least 1"
+    if bad:
+        raise _lib.EmoHipError(f"emo_gif_lzw_decode: bad shape: {bad}")
+    return out_offsets[-1]
+
+
+def gif_lzw_decode(streams: torch.Tensor, offsets: torch.Tensor, code_size: torch.Tensor, out_offsets: torch.Tensor, total: int, layout=None,
+                   out=None, produced=None, status=None):
+    """the LZW image data of n GIF frames (uint8, a multiple of 4 bytes; frame i in bytes offsets[i] .. offsets[i + 1], int64 (n + 1);
+    sub-blocks joined), their minimum code sizes (int32 (n)) and where each frame's w * h colour indices go (out_offsets int64 (n + 1),
+    from 0 to total) -> (indices uint8 (total), in stream order, produced int32 (n), status int32 (n): a key of GIF_STATUS)
+    (emo_gif_lzw_decode; GIF89a Appendix F).  layout=(offsets, code_size, out_offsets) as host sequences - the same values - is checked
+    by gif_layout_check before the launch; a caller that leaves it out has checked them itself."""
+    _need_cuda(streams, offsets, code_size, out_offsets)
+    assert streams.dtype == torch.uint8 and streams.dim() == 1 and streams.is_contiguous(), (streams.dtype, streams.shape)
+    assert offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 2 and offsets.is_contiguous(), (offsets.dtype, offsets.shape)
+    n, total = offsets.numel() - 1, int(total)
+    assert code_size.dtype == torch.int32 and tuple(code_size.shape) == (n,) and code_size.is_contiguous(), (code_size.dtype, code_size.shape)
+    assert out_offsets.dtype == torch.int64 and tuple(out_offsets.shape) == (n + 1,) and out_offsets.is_contiguous(), (out_offsets.dtype, out_offsets.shape)
+    if layout is not None and gif_layout_check(*layout, streams.numel()) != total:
+        raise _lib.EmoHipError(f"emo_gif_lzw_decode: bad shape: out_offsets end at {int(layout[2][-1])}, total={total}")
+    if not 1 <= total <= 2 ** 31 - 1:
+        raise _lib.EmoHipError(f"emo_gif_lzw_decode: bad shape: total={total} colour indices (1 .. 2^31 - 1)")
+    indices = _jpeg_out(out, (total,), torch.uint8, streams.device, "indices")
+    produced = _jpeg_out(produced, (n,), torch.int32, streams.device, "produced")
+    status = _jpeg_out(status, (n,), torch.int32, streams.device, "status")
+    _launch("gif_lzw_decode", 0.0, float(streams.numel() + 2 * total),
+            lambda: check(_lib.load().emo_gif_lzw_decode(_ptr(streams), streams.numel(), _ptr(offsets), _ptr(code_size), _ptr(out_offsets),
+                                                         _ptr(indices), _ptr(produced), _ptr(status), n, _stream()), "emo_gif_lzw_decode"),
+            tag=f"{n}x{total}")
+    return indices, produced, status
+
+
+def gif_compose(indices: torch.Tensor, out_offsets: torch.Tensor, frames: torch.Tensor, tables: torch.Tensor, n_out: int, H: int, W: int,
+                out=None, status=None):
+    """colour indices in stream order as gif_lzw_decode leaves them, the frames' descriptors (int32 (n, GIF_FRAME_INTS)) and the colour
+    tables (uint8 (n_tables, 256, 3)) -> (rgb uint8 (n_out, H, W, 3): the canvas right after each frame whose slot is 0 .. n_out - 1,
+    status int32 (n): 0, or bits 4 / 8 of GIF_STATUS) (emo_gif_compose; GIF89a sections 18 - 23, Appendix E)."""
+    _need_cuda(indices, out_offsets, frames, tables)
+    assert indices.dtype == torch.uint8 and indices.dim() == 1 and indices.is_contiguous(), (indices.dtype, indices.shape)
+    assert frames.dtype == torch.int32 and frames.dim() == 2 and frames.shape[1] == GIF_FRAME_INTS and frames.is_contiguous(), (frames.dtype, frames.shape)
+    n = int(frames.shape[0])
+    assert out_offsets.dtype == torch.int64 and tuple(out_offsets.shape) == (n + 1,) and out_offsets.is_contiguous(), (out_offsets.dtype, out_offsets.shape)
+    assert tables.dtype == torch.uint8 and tables.dim() == 3 and tuple(tables.shape[1:]) == (256, 3) and tables.is_contiguous(), (tables.dtype, tables.shape)
+    n_out, H, W = int(n_out), int(H), int(W)
+    rgb = _jpeg_out(out, (max(n_out, 0), max(H, 0), max(W, 0), 3), torch.uint8, indices.device, "rgb")
+    status = _jpeg_out(status, (n,), torch.int32, indices.device, "status")
+    _launch("gif_compose", 0.0, float(indices.numel() + rgb.numel()),
+            lambda: check(_lib.load().emo_gif_compose(_ptr(indices), _ptr(out_offsets), _ptr(frames), _ptr(tables), _ptr(rgb), _ptr(status), n,
+                                                      int(tables.shape[0]), n_out, H, W, _stream()), "emo_gif_compose"), tag=f"{n}x{H}x{W}")
+    return rgb, status
+
+
 JPEG_DECODE_TABLE_INTS = 320                     # EMO_JPEG_DECODE_TABLE_INTS
 JPEG_STATUS = {0: "ok", 1: "a code the Huffman table does not define", 2: "the scan ends before the frame's last block",
                3: "a zero run leaves its block"}   # EMO_JPEG_OK / _BAD_CODE / _PAST_END / _BAD_RUN

@@ -191,8 +191,8 @@ class EMOAnimationPipeline(DenoiseLoop):
 
     @staticmethod
     def _clip_frames(path, n_frames, width, height, who, resample=None, progressive=False):
-        """the first n_frames frames of a Motion-JPEG `.avi` file - or of an `.apng` file, an animated `.png` or a numbered `.png` pattern
-        such as `pose/%04d.png` - as uint8 (n_frames, height, width, 3) on the device (video_io.read_video).
+        """the first n_frames frames of a Motion-JPEG `.avi` file - or of an `.apng` file, an animated `.png`, a numbered `.png` pattern
+        such as `pose/%04d.png` or a `.gif` file - as uint8 (n_frames, height, width, 3) on the device (video_io.read_video).
         The reference resizes what it reads through PIL (animation.py:174-185): with resample= (a filter of video_io.RESIZE_FILTERS; PIL's
         own default is "bicubic") frames of another size are resized on the device as PIL would (video_io.resize_frames); with None
         another size is refused.  progressive=True takes progressive frames in the clip too (video_io.decode_mjpeg)."""
@@ -216,7 +216,8 @@ class EMOAnimationPipeline(DenoiseLoop):
         _clip_frames does - and encoded from there.  A baseline `.jpg` / `.jpeg` path is decoded and resized to (width, height) on the
         device as well (video_io.read_image, byte for byte the pixels PIL's open + resize give); what parse_jpeg refuses is PIL's - a
         progressive file too, unless progressive=True sends a complete progression down the same device path.  A `.png` path is PIL's
-        too; video_io.read_image decodes one on the device for a caller that wants the pixels there."""
+        too; video_io.read_image decodes one on the device for a caller that wants the pixels there.  So is a `.gif` path: PIL opens its
+        first frame, and video_io.read_image gives the same pixels on the device."""
         rgb = self._source_image_rgb(source_image, width, height, resample, progressive)
         if torch.is_tensor(rgb):          # a still JPEG or the first frame of a clip, on the device
             if self.vae is None:

@@ -42,6 +42,12 @@
                     blocks, the 32 KiB window a ring in LDS) and emo_png_unfilter (a skewed wavefront over bands of 64 rows;
                     csrc/png_in.hip), one small read of the statuses and the rows' Adler-32 pairs - the bytes Pillow gives.  read_image
                     takes a `.png`, read_video an `.apng`, an animated `.png` and a numbered pattern through them
+  parse_gif, decode_gif      the GIF reader: header, screen descriptor, colour tables, NETSCAPE2.0, graphic control extensions, image
+                    descriptors and joined sub-blocks on the host, with the sticky disposal, the fill index and the table row of every
+                    frame resolved there; then ONE copy of all frames' LZW data, descriptors and tables, emo_gif_lzw_decode (one
+                    wavefront per frame) and emo_gif_compose (the frames replayed per pixel: transparency, disposal, sub-rectangles,
+                    interlace; csrc/gif_in.hip), one small read of the statuses - the bytes Pillow's seek + convert("RGB") give.
+                    read_image and read_video take a `.gif` through them
   FORMATS           the one table of the files a clip is written as - avi, gif, apng, numbered png stills: per format its extension,
                     the keywords it owns, whether it plays and holds sound, the checks of its options and of its rate, its encoder.
                     Every writer of a clip runs one sequence over its record (_write_clip), and save_plan does for the pipeline's
@@ -2080,6 +2086,267 @@ def _read_png_clip(path, step, length, start, who):
     return _png_rgb(_decode_png_streams(picked, p.height, p.width, p.channels, _png_device(None, who), f"{who}: {path!r}")), fps
 
 
+# ---------------------------------------------------------------------------------------------------------------------- reading GIF
+GIF_SIGNATURES = (b"GIF87a", b"GIF89a")
+_GIF_ONLY = ("decode_gif reads GIF87a / GIF89a files whose frames have a colour table, global or local, and lie inside the logical screen, "
+             "with LZW minimum code sizes 2 .. 8")
+
+
+@dataclasses.dataclass(frozen=True)
+class GifFrame:
+    """One image of a GIF file as parse_gif finds it, with what the host resolves for the device."""
+    left: int
+    top: int
+    width: int
+    height: int
+    interlace: bool
+    transparent: object        # the transparent index of the frame's graphic control extension, or None
+    delay: Fraction            # seconds; 0 without a graphic control extension
+    disposal_bits: int         # the frame's own disposal bits (0 without a graphic control extension)
+    disposal: int              # the EFFECTIVE disposal 0 .. 3: the most recent non-zero bits among the frames up to this one
+    fill: int                  # the index a disposal 2 fills with: transparent, else the background index (0 where the table has no such entry)
+    table_row: int             # the row of ParsedGif.tables the frame reads: 0 the global table where there is one
+    table_entries: int         # that table's entries, 2 .. 256
+    code_size: int             # the LZW minimum code size, 2 .. 8
+    data: bytes                # the image data, sub-blocks joined
+
+
+@dataclasses.dataclass(frozen=True)
+class ParsedGif:
+    """What parse_gif takes from a GIF file: everything but the pixels."""
+    version: bytes             # b"GIF87a" or b"GIF89a"
+    width: int                 # the logical screen
+    height: int
+    background: int            # the header's background index where there is a global table, else 0
+    global_entries: int        # entries of the global colour table, 0 without one
+    tables: np.ndarray         # uint8 (n_tables, 256, 3): the global table (if any) first, then the local ones in file order; unused entries zero
+    frames: tuple              # GifFrame each
+    loop: object               # the NETSCAPE2.0 loop count (0: forever), None without the extension (the clip plays once)
+    trailer: bool              # the file ends with the trailer byte
+
+    @property
+    def delays(self):
+        return tuple(f.delay for f in self.frames)
+
+
+def parse_gif(data) -> ParsedGif:
+    """A GIF87a / GIF89a file's bytes -> ParsedGif; no pixel is touched.  Read: the header, the logical screen descriptor (section 18),
+    the global colour table and the background index (19), the NETSCAPE2.0 application extension (loop), and per frame the graphic
+    control extension (23: the delay as an exact Fraction of a second, the transparent index or None, the disposal bits), the image
+    descriptor (20: left, top, width, height, interlace flag, local colour table 21), the LZW minimum code size and the image data
+    with its sub-blocks joined.  Comment, plain-text and other application extensions are skipped; a file without trailer is taken
+    when it holds at least one complete frame, as Pillow takes it.
+    Resolved here, as Pillow's GifImagePlugin resolves them: the EFFECTIVE disposal of a frame is sticky - the most recent non-zero
+    disposal bits among frames 0 .. k (bits 4 .. 7 count as 3), so a frame with bits 0 or without a control extension inherits -; the
+    index a disposal 2 fills with is the frame's transparent index, else the background index looked up in the FRAME's table; the row of
+    `tables` and the entry count of the table the frame reads.  A background index at or beyond the table it is looked up in has no
+    single rule in Pillow - frame 0 is disposed as a palette image and turns black, later frames go through `_rgb`, which takes entry
+    0 (both pinned by the host tests) - so a file in which such a fill would be carried out is refused by name; where it is never
+    carried out (the frame has a transparent index, another disposal, or is the last) the file is taken and `fill` is 0.
+    ValueError, naming what the file has, for: a frame with no colour table, neither global nor local (Pillow's mode L path); a frame
+    that reaches outside the logical screen (Pillow grows the canvas); an LZW minimum code size outside 2 .. 8; a transparent index
+    at or beyond its frame's table; a disposal to a background index its frame's table does not hold; a zero-sized frame or screen; a file with no image; a sub-block, table or block that runs past
+    the end of the file; a block that is no extension, image or trailer."""
+    data = bytes(data)
+    if data[:6] not in GIF_SIGNATURES:
+        raise ValueError("not a GIF file: neither a GIF87a nor a GIF89a header")
+    if len(data) < 13:
+        raise ValueError("the logical screen descriptor runs past the end of the file")
+    width, height, flags, background, _ = struct.unpack_from("<HHBBB", data, 6)
+    if not width or not height:
+        raise ValueError(f"a zero-sized logical screen ({width} x {height})")
+    pos, tables, global_entries = 13, [], 0
+
+    def table(pos, bits, what):
+        k = 2 << bits
+        if pos + 3 * k > len(data):
+            raise ValueError(f"{what} of {k} entries runs past the end of the file")
+        t = np.zeros((256, 3), np.uint8)
+        t[:k] = np.frombuffer(data, np.uint8, 3 * k, pos).reshape(k, 3)
+        tables.append(t)
+        return pos + 3 * k, k
+
+    def sub_blocks(pos, what):
+        parts = []
+        while True:
+            if pos >= len(data):
+                raise ValueError(f"a sub-block of {what} runs past the end of the file: no block terminator")
+            size = data[pos]
+            pos += 1
+            if size == 0:
+                return b"".join(parts), pos
+            if pos + size > len(data):
+                raise ValueError(f"a sub-block of {what} runs past the end of the file")
+            parts.append(data[pos:pos + size])
+            pos += size
+
+    if flags & 0x80:
+        pos, global_entries = table(pos, flags & 7, "the global colour table")
+    else:
+        background = 0
+    frames, loop, trailer, sticky = [], None, False, 0
+    delay, transparent, bits = Fraction(0), None, 0                              # of the graphic control extension in front of the next image
+    while pos < len(data):
+        kind = data[pos]
+        pos += 1
+        if kind == 0x3B:
+            trailer = True
+            break
+        if kind == 0x21:
+            if pos >= len(data):
+                raise ValueError("an extension block runs past the end of the file")
+            label = data[pos]
+            if label == 0xFF and data[pos + 1:pos + 2] == b"\x0b" and data[pos + 2:pos + 13] == b"NETSCAPE2.0":
+                body, pos = sub_blocks(pos + 13, "the NETSCAPE2.0 extension")
+                if loop is None and len(body) >= 3 and body[0] == 1:
+                    loop = struct.unpack_from("<H", body, 1)[0]
+                continue
+            body, pos = sub_blocks(pos + 1, f"extension {label:#04x}")
+            if label == 0xF9 and len(body) >= 4:
+                packed, cs, index = struct.unpack_from("<BHB", body)
+                delay, transparent, bits = Fraction(cs, 100), (index if packed & 1 else None), (packed >> 2) & 7
+                if bits:
+                    sticky = min(bits, 3)
+        elif kind == 0x2C:
+            if pos + 9 > len(data):
+                raise ValueError("an image descriptor runs past the end of the file")
+            left, top, w, h, packed = struct.unpack_from("<HHHHB", data, pos)
+            pos += 9
+            k = len(frames)
+            if not w or not h:
+                raise ValueError(f"frame {k} is zero-sized ({w} x {h})")
+            if left + w > width or top + h > height:
+                raise ValueError(f"frame {k} ({w} x {h} at ({left}, {top})) reaches outside the logical screen of {width} x {height}: {_GIF_ONLY}")
+            if packed & 0x80:
+                pos, entries = table(pos, packed & 7, f"the local colour table of frame {k}")
+                row = len(tables) - 1
+            elif global_entries:
+                row, entries = 0, global_entries
+            else:
+                raise ValueError(f"frame {k} has no colour table, neither a global nor a local one: {_GIF_ONLY}")
+            if pos >= len(data):
+                raise ValueError(f"the image data of frame {k} runs past the end of the file")
+            code_size = data[pos]
+            if not 2 <= code_size <= 8:
+                raise ValueError(f"frame {k} has an LZW minimum code size of {code_size}: {_GIF_ONLY}")
+            body, pos = sub_blocks(pos + 1, f"the image data of frame {k}")
+            if transparent is not None and transparent >= entries:
+                raise ValueError(f"frame {k} has the transparent index {transparent} and a colour table of {entries} entries")
+            fill = transparent if transparent is not None else (background if background < entries else 0)
+            frames.append(GifFrame(left, top, w, h, bool(packed & 0x40), transparent, delay, bits, sticky, fill, row, entries, code_size, body))
+            delay, transparent, bits = Fraction(0), None, 0
+        else:
+            raise ValueError(f"block {kind:#04x} at byte {pos - 1} is no extension, image descriptor or trailer")
+    if not frames:
+        raise ValueError("the file holds no image")
+    for k, f in enumerate(frames[:-1]):                                          # the last frame's disposal is never carried out
+        if f.disposal == 2 and f.transparent is None and background >= f.table_entries:
+            raise ValueError(f"frame {k} is disposed to the background index {background}, which its colour table of {f.table_entries} entries "
+                             "does not hold (Pillow has no single colour for that)")
+    return ParsedGif(data[:6], width, height, background, global_entries, np.stack(tables), tuple(frames), loop, trailer)
+
+
+def gif_fps(delays):
+    """the rate of a GIF's delays (Fractions of a second, whole centiseconds): 100 n / the sum of the centiseconds when every delay is
+    positive and the largest and the smallest differ by at most one centisecond - the spread gif_delays gives a constant rate -, else
+    None"""
+    cs = [d * 100 for d in delays]
+    if not cs or min(cs) <= 0 or max(cs) - min(cs) > 1:
+        return None
+    return Fraction(100 * len(cs)) / sum(cs)
+
+
+def gif_descriptors(frames, slot) -> np.ndarray:
+    """GifFrames in file order from frame 0 on, slot: {frame index: output slot} -> int32 (n, ops.GIF_FRAME_INTS), what emo_gif_compose
+    reads per frame: left, top, w, h, the transparent index or -1, the effective disposal, the fill index, the interlace flag, the table
+    row, the table's entries, the output slot or -1.  Nothing lies under frame 0, so a disposal 3 there becomes what Pillow does: a
+    fill with the frame's transparent index, or nothing."""
+    desc = np.zeros((len(frames), ops.GIF_FRAME_INTS), np.int32)
+    for k, f in enumerate(frames):
+        disposal, fill = f.disposal, f.fill
+        if k == 0 and disposal == 3:
+            disposal, fill = (2, f.transparent) if f.transparent is not None else (1, fill)
+        desc[k] = (f.left, f.top, f.width, f.height, -1 if f.transparent is None else f.transparent, disposal, fill, int(f.interlace),
+                   f.table_row, f.table_entries, slot.get(k, -1))
+    return desc
+
+
+def _decode_parsed_gif(p: ParsedGif, picked, device, who: str) -> torch.Tensor:
+    """the frames `picked` (indices into p.frames, each at most once) -> uint8 (len(picked), H, W, 3) on the device, in that order: ONE
+    upload (offsets, code sizes, descriptors, tables, streams), emo_gif_lzw_decode and emo_gif_compose over the frames up to the last
+    picked one, ONE small read (both statuses and the counts)"""
+    n = max(picked) + 1
+    fr = p.frames[:n]
+    slot = {k: i for i, k in enumerate(picked)}
+    offsets = np.concatenate([[0], np.cumsum([len(f.data) for f in fr])]).astype(np.int64)
+    out_offsets = np.concatenate([[0], np.cumsum([f.width * f.height for f in fr])]).astype(np.int64)
+    code_size = np.array([f.code_size for f in fr], np.int32)
+    desc = gif_descriptors(fr, slot)
+    pad = -int(offsets[-1]) % 4 or (4 if offsets[-1] == 0 else 0)
+    total = ops.gif_layout_check(offsets, code_size, out_offsets, int(offsets[-1]) + pad)      # before any launch
+    parts = [offsets.view(np.uint8), out_offsets.view(np.uint8), code_size.view(np.uint8), desc.reshape(-1).view(np.uint8),
+             np.ascontiguousarray(p.tables).reshape(-1)] + [np.frombuffer(f.data, np.uint8) for f in fr] + [np.zeros(pad, np.uint8)]
+    dev = torch.from_numpy(np.concatenate(parts)).to(device)                      # the one copy
+    at = np.cumsum([0] + [len(a) for a in parts[:5]])
+    d_offsets, d_out = dev[at[0]:at[1]].view(torch.int64), dev[at[1]:at[2]].view(torch.int64)
+    d_code, d_desc = dev[at[2]:at[3]].view(torch.int32), dev[at[3]:at[4]].view(torch.int32).view(n, ops.GIF_FRAME_INTS)
+    d_tables = dev[at[4]:at[5]].view(-1, 256, 3)
+    indices, produced, decoded = ops.gif_lzw_decode(dev[at[5]:], d_offsets, d_code, d_out, total)
+    rgb, composed = ops.gif_compose(indices, d_out, d_desc, d_tables, len(picked), p.height, p.width)
+    back = torch.cat([decoded, composed, produced]).cpu().numpy()                 # the one read
+    for k, f in enumerate(fr):
+        for entry, st in (("emo_gif_lzw_decode", int(back[k])), ("emo_gif_compose", int(back[n + k]))):
+            if st:
+                got = f" after {int(back[2 * n + k])} of {f.width * f.height} colour indices" if entry == "emo_gif_lzw_decode" else ""
+                raise ValueError(f"{who}: frame {k} does not decode: {ops.gif_status_words(st)}{got} ({entry} status {st})")
+    return rgb
+
+
+def _gif_device(device, who):
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ops._lib.EmoHipError(f"{who} decodes on the HIP device, got device {device} (there is no host decoder here)")
+    return device
+
+
+def decode_gif(data, device=None, select=None):
+    """A GIF file's bytes -> (uint8 frames (n, H, W, 3) on the device at the size of the logical screen, the delays as exact Fractions of
+    a second, loop: the NETSCAPE2.0 count, 0 forever, None without the extension).  Frame k is, byte for byte, what Pillow's
+    `im.seek(k); im.convert("RGB")` gives (at its default LoadingStrategy.RGB_AFTER_FIRST): the canvas after frame k, with the
+    transparency, the disposal of the frames before, sub-rectangles, local tables and interlace applied.  The host walks the blocks
+    only (parse_gif); the LZW data, descriptors and tables of all frames go up in ONE copy and through two launches -
+    emo_gif_lzw_decode, one wavefront per frame, and emo_gif_compose - followed by one small read of the statuses.  select= (a slice)
+    picks the frames returned; every frame up to the last selected one is still decoded and composited, because the canvas depends
+    on them, later ones are not.  ValueError for a file parse_gif refuses, and - naming the frame, the status in words and how far
+    it got - for image data that does not decode or a colour index beyond its table.  There is no host decoder behind this."""
+    device = _gif_device(device, "decode_gif")
+    try:
+        p = parse_gif(data)
+    except ValueError as e:
+        raise ValueError(f"decode_gif: {e}") from None
+    picked = list(range(len(p.frames)))
+    if select is not None:
+        picked = picked[select]
+        if not picked:
+            raise ValueError(f"decode_gif: the file holds {len(p.frames)} frames; {select} selects none")
+    return _decode_parsed_gif(p, picked, device, "decode_gif"), [p.frames[k].delay for k in picked], p.loop
+
+
+def _read_gif_clip(path, step, length, start, who):
+    """read_video for a `.gif` -> (RGB frames on the device, fps or None)"""
+    path = os.fspath(path)
+    with open(path, "rb") as f:
+        data = f.read()
+    try:
+        p = parse_gif(data)
+    except ValueError as e:
+        raise ValueError(f"{who}: {path!r}: {e}") from None
+    picked = list(range(len(p.frames)))[start::step][:length]
+    if not picked:
+        raise ValueError(f"{who}: {path!r} holds {len(p.frames)} frames; [{start}::{step}][:{length}] selects none")
+    return _decode_parsed_gif(p, picked, _gif_device(None, who), f"{who}: {path!r}"), gif_fps(p.delays)
+
+
 def save_images_grid(images: torch.Tensor, path: str, quality: int = 90):
     """magicanimate/utils/util.py:35-41: (b, c, 1, h, w) in [0, 1] -> one image file of the grid `torchvision.utils.make_grid(images)`
     lays out with its defaults (8 per row, 2 pixels of padding; make_grid_u8), `* 255` truncated to uint8 as :39 does.  `.png` is written
@@ -2296,7 +2563,7 @@ def decode_jpeg(data: bytes) -> np.ndarray:
 
 def video2images(path, step=4, length=16, start=0):
     """util.py:102-108: the frames [start::step][:length] of an `.avi` file this module wrote, as (H, W, 3) uint8 arrays; of an `.apng` /
-    `.png` file or a numbered `.png` pattern (read_video, decoded on the device) the same frames, copied to the host"""
+    `.png` / `.gif` file or a numbered `.png` pattern (read_video, decoded on the device) the same frames, copied to the host"""
     if not os.fspath(path).lower().endswith(".avi"):
         return list(read_video(path, step, length, start)[0].cpu().numpy())
     jpegs, _, _ = read_avi(path)
@@ -2312,7 +2579,9 @@ def read_image(path_or_bytes, size=None, resample="bicubic", progressive: bool =
     (decode_mjpeg(progressive=True)): the same bytes, since libjpeg reads such a file to the coefficients of the baseline one; a
     progression that stops early, which libjpeg smooths, stays refused.
     A PNG file (recognised by its signature; what parse_png takes: 8 bits, grey, grey + alpha, RGB or RGBA, no interlace) is decoded by
-    decode_png and brought to RGB as `.convert("RGB")` does - grey in all three channels, alpha dropped - by indexing on the device."""
+    decode_png and brought to RGB as `.convert("RGB")` does - grey in all three channels, alpha dropped - by indexing on the device.
+    A GIF file (recognised by its signature, `GIF87a` or `GIF89a`; what parse_gif takes) gives its first frame, decoded by decode_gif:
+    what `Image.open(path).convert("RGB")` gives."""
     if size is not None:
         size, resample = _resize_size(size, "read_image"), _resize_filter(resample)
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
@@ -2323,11 +2592,16 @@ def read_image(path_or_bytes, size=None, resample="bicubic", progressive: bool =
     try:
         if data[:8] == PNG_SIGNATURE:
             parse_png(data)
+        elif data[:6] in GIF_SIGNATURES:
+            parse_gif(data)
         else:
             parse_jpeg(data, restart=True, layouts=True, progressive=progressive)
     except ValueError as e:
         raise ValueError(f"read_image: {e}") from None
-    frames = _png_rgb(decode_png([data])) if data[:8] == PNG_SIGNATURE else decode_mjpeg([data], progressive=progressive)
+    if data[:6] in GIF_SIGNATURES:
+        frames = decode_gif(data, select=slice(0, 1))[0]
+    else:
+        frames = _png_rgb(decode_png([data])) if data[:8] == PNG_SIGNATURE else decode_mjpeg([data], progressive=progressive)
     if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
         frames = resize_frames(frames, size, resample)
     return frames[0]
@@ -2342,9 +2616,18 @@ def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"
     An `.apng` file, an animated (or still) `.png` file and a numbered pattern as write_png takes it (`frames/f_%04d.png`: consecutive
     numbers from the first file that exists, 0 or 1) are read too, inflated and unfiltered on the device (decode_png, decode_apng) and
     brought to RGB as read_image does; only the selected frames are decoded.  fps is then 1 / delay where all the file's delays are
-    equal, else None - None for stills -, and audio is None."""
+    equal, else None - None for stills -, and audio is None.
+    A `.gif` file is read too (decode_gif: LZW decoding and the compositing of the frames on the device; every frame up to the last
+    selected one is decoded, since a GIF frame is a patch on the canvas the frames before it left).  fps is then 100 n / the sum of the
+    file's n delays in centiseconds when every delay is positive and the largest and the smallest differ by at most one centisecond
+    (what gif_delays writes for a constant rate: 30 fps comes back as 30), else None; audio is None."""
     if size is not None:
         size, resample = _resize_size(size, "read_video"), _resize_filter(resample)
+    if os.fspath(path).lower().endswith(".gif"):
+        frames, fps = _read_gif_clip(path, step, length, start, "read_video")
+        if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
+            frames = resize_frames(frames, size, resample)
+        return frames, fps, None
     if os.fspath(path).lower().endswith((".png", ".apng")):
         frames, fps = _read_png_clip(path, step, length, start, "read_video")
         if size is not None and (int(frames.shape[2]), int(frames.shape[1])) != size:
@@ -2361,7 +2644,7 @@ def read_video(path, step=1, length=None, start=0, size=None, resample="bicubic"
 
 
 def load_control_clip(path, size, window, offset=0, max_length=None, resample="bicubic", progressive: bool = False):
-    """magicanimate/pipelines/animation.py:174-194 for a Motion-JPEG `.avi` file -> (control frames uint8 (t, height, width, 3) on the
+    """magicanimate/pipelines/animation.py:174-194 for a Motion-JPEG `.avi` file (or an `.apng`, `.png` or `.gif` clip, as read_video takes them) -> (control frames uint8 (t, height, width, 3) on the
     device, original_length): every frame is read (:175), resized to size=(width, height) when the clip has another size (:176-177; the
     reference compares the height alone, having square frames on both sides), cut to [offset : offset + max_length] when max_length is
     given (:178-179) and, when what is left is no multiple of `window` (config.L, the context length), followed by copies of its last

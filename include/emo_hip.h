@@ -657,6 +657,66 @@ int emo_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t*
                     int32_t* status, int n, int H, int W, int C, void* stream);
 int emo_png_unfilter(const uint8_t* filtered, uint8_t* frames, uint32_t* adler, int32_t* status, int n, int H, int W, int C, void* stream);
 
+/* ---- GIF input: the device half of the reader of what the GIF output block writes (`imageio.mimsave(path.gif)`, magicanimate/utils/
+ * util.py:33) and of what Pillow, imageio and browsers' tools write: pose, depth and mask clips handed round as GIFs, which the
+ * reference would read through `VideoReader(path).read()` (magicanimate/pipelines/animation.py:174-185).  GIF89a: section 18 the logical
+ * screen descriptor, 19 the global colour table, 20 the image descriptor (sub-rectangle, interlace flag), 21 the local colour table, 22
+ * the table-based image data, 23 the graphic control extension (delay, transparent index, disposal), Appendix E interlacing, Appendix F
+ * the variable-length-code LZW.  The host half (header, blocks and sub-blocks, the extensions, the sticky disposal, the refusals) is
+ * emote_hack_amd/video_io.py parse_gif.  The kernels live in csrc/gif_in.hip.
+ * emo_gif_lzw_decode (Appendix F): the image data of n frames, sub-blocks joined by the host, lie in `streams` (stream_bytes bytes, a
+ *   multiple of 4, 4-byte aligned; bytes behind the last frame are never used), frame i in bytes offsets[i] .. offsets[i + 1] (int64
+ *   [n + 1], 8-byte aligned) with LZW minimum code size code_size[i] (int32 [n], 2 .. 8).  Frame i writes its colour indices in STREAM
+ *   order (an interlaced frame's rows stay in pass order) to indices[out_offsets[i] .. out_offsets[i + 1]) (int64 [n + 1], 8-byte
+ *   aligned): exactly w * h of them.  produced int32 [n]: how many the frame gave; status int32 [n].  With c the code size: Clear is
+ *   1 << c, End of Information Clear + 1, the first free code Clear + 2; codes have c + 1 .. 12 bits, least significant bit first, and
+ *   widen when the next free code reaches 1 << width.  Taken, as Pillow 12.2 takes them: a stream that does not open with a Clear; a
+ *   full table (4096) with no Clear behind it - decoding goes on at 12 bits and adds no entries; several Clears in a row; the code equal
+ *   to the next free one (KwKwK); no End of Information once w * h indices are out; data behind the w * h-th index (decoding stops
+ *   there, a last string is cut, nothing further is looked at).  Status:
+ *     EMO_GIF_OK         w * h indices decoded
+ *     EMO_GIF_BAD_CODE   a code above the next free code; a code above Clear as the first code of a table (at the start, right behind
+ *                        a Clear); the next free code when the table is full (no 12-bit code is); a code size outside 2 .. 8
+ *     EMO_GIF_PAST_END   the frame's bytes end before w * h indices and before an End of Information (a cut file, an empty frame;
+ *                        offsets that run backwards or leave the buffer are taken as an empty frame)
+ *     EMO_GIF_SHORT      End of Information before w * h indices
+ *   A frame with an error stops there: what it produced up to then is in indices, produced says how much; other frames are not
+ *   touched.  One wavefront per frame.  Bounds: every read of the streams is masked to the frame's own bytes (past them the reader sees
+ *   zeros and the frame ends with EMO_GIF_PAST_END), every write and every read of indices is masked to the frame's own w * h, every
+ *   table index to 4096; the loop is counted by input bits - each turn takes at least 3 - and ends at w * h indices.  A damaged file
+ *   gives a status, never a hang or an access outside the buffers.  n < 1, null or misaligned pointers and a stream_bytes that is no
+ *   positive multiple of 4 are EMO_ERR_BAD_SHAPE / EMO_ERR_NULL before any launch.  offsets, code_size and out_offsets live on the
+ *   device, where this entry cannot read them before a launch: the caller checks them on the host (emote_hack_amd/ops.py
+ *   gif_layout_check: ascending offsets inside the stream buffer, code sizes 2 .. 8, ascending out_offsets from 0 whose sum stays at or
+ *   below 2^31 - 1; the indices buffer holds out_offsets[n] bytes) - the kernel itself treats out_offsets that run backwards as a frame
+ *   of no pixels and a code size out of range as EMO_GIF_BAD_CODE with nothing produced.
+ * emo_gif_compose (sections 18 - 23, Appendix E): replays the n frames in file order on a canvas of H x W pixels and stores the frames
+ *   asked for as packed RGB, rgb uint8 [n_out][H][W][3] (4-byte aligned).  frames int32 [n][EMO_GIF_FRAME_INTS]: left, top, w, h (the
+ *   rectangle, inside the canvas), the transparent index or -1, the effective disposal 0 .. 3, the index a disposal 2 fills with, the
+ *   interlace flag, the row of `tables` the frame reads, that table's entry count (1 .. 256), the output slot 0 .. n_out - 1 or -1 for a
+ *   frame that is composited but not returned.  tables uint8 [n_tables][256][3], unused entries zero.  indices and out_offsets as
+ *   emo_gif_lzw_decode leaves them (out_offsets[k + 1] - out_offsets[k] = w * h of frame k).  With pal_k the frame's table and t_k its
+ *   transparent index: the canvas starts as pal_0[t_0], or pal_0[0] without t_0; frame 0 draws EVERY pixel of its rectangle, the
+ *   transparent index too; frame k >= 1 draws pal_k[index] where index != t_k.  Immediately before frame k + 1 is drawn, frame k's
+ *   rectangle is filled with pal_k[fill index] when its disposal is 2, or set back to what it held right before frame k was drawn
+ *   when it is 3; 0 and 1 leave it.  (THE HOST resolves what GIF leaves open, as Pillow's GifImagePlugin does: a frame without
+ *   disposal bits inherits the last non-zero ones; the fill index is t_k, else the background index, else 0; disposal 3 on frame 0
+ *   becomes a fill with t_0 or nothing.)  The frame returned for k is the canvas right after frame k is drawn.  An interlaced frame of
+ *   h rows reads, for its canvas row y, stream row y / 8 (y % 8 == 0), a + (y - 4) / 8 (y % 8 == 4), a + b + (y - 2) / 4 (y % 4 == 2),
+ *   else a + b + c + (y - 1) / 2, with a = ceil(h / 8), b = ceil((h - 4) / 8), c = ceil((h - 2) / 4), a negative h - k counting as 0.
+ *   status int32 [n], zeroed by the entry, then ORed: EMO_GIF_BAD_INDEX for a frame that draws an index at or beyond its table's entry
+ *   count (the pixel takes the zero entry behind the table; one atomic per offending wavefront), EMO_GIF_BAD_FRAME for a descriptor
+ *   that does not fit - a rectangle outside the canvas, w * h other than the frame's room in indices, a table row or a slot out of
+ *   range: such a frame is left out, so no read or write leaves the buffers.  n, n_tables, n_out, H, W < 1, n_out > n, H or W above
+ *   65535 and n_out * H * W * 3 above 2^31 - 1 are EMO_ERR_BAD_SHAPE before any launch.  One thread per 4 neighbouring pixels; no
+ *   canvas goes to memory except the frames asked for. */
+#define EMO_GIF_FRAME_INTS 11
+enum { EMO_GIF_OK = 0, EMO_GIF_BAD_CODE = 1, EMO_GIF_PAST_END = 2, EMO_GIF_SHORT = 3, EMO_GIF_BAD_INDEX = 4, EMO_GIF_BAD_FRAME = 8 };
+int emo_gif_lzw_decode(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* code_size,
+                       const int64_t* out_offsets, uint8_t* indices, int32_t* produced, int32_t* status, int n, void* stream);
+int emo_gif_compose(const uint8_t* indices, const int64_t* out_offsets, const int32_t* frames, const uint8_t* tables, uint8_t* rgb,
+                    int32_t* status, int n, int n_tables, int n_out, int H, int W, void* stream);
+
 /* ---- Motion-JPEG input: the device half of the reader that stands in for `VideoReader(path).read()`
  * (magicanimate/utils/videoreader.py; magicanimate/pipelines/animation.py:174-180 the control sequence, :182-185 the source image taken
  * from a video's first frame).  Baseline sequential JPEG, ITU-T T.81, 8-bit, one scan; the host half (marker segments of Annex B, the
